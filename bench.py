@@ -16,7 +16,6 @@ from __future__ import annotations
 import argparse
 import json
 import os
-import socket
 import subprocess
 import sys
 import time
@@ -178,6 +177,55 @@ def emit(detail):
     print(compact_line(detail), flush=True)
 
 
+DUMP_LIMIT_BYTES = 64 << 20     # --dump-outputs: at most this much in all; above it every array keeps the same seeded sample of its rows
+DUMP_SAMPLE_SEED = 0
+
+
+def output_arrays(outs, gathered, limit=DUMP_LIMIT_BYTES):
+    """What one sampling call hands its caller, as host arrays for --dump-outputs: the gathered packed SMPL parameters and every tensor of the
+    S result dicts (sample, pred_xstart, other_outputs...), named by their key path ('s<k>.' in front when S > 1).  float64 stays float64,
+    everything else becomes float32.  If the whole exceeds `limit` bytes, every array with more than one row keeps a fixed, seeded, sorted
+    sample of its rows (axis 0), the same rows for arrays of the same length, so that the files of two runs compare element for element;
+    the cap is hard (ValueError if single-row arrays alone exceed it)."""
+    arrays = {}
+
+    def add(name, v):
+        if isinstance(v, dict):
+            for k, vv in v.items():
+                add(f"{name}.{k}" if name else k, vv)
+        elif torch.is_tensor(v):
+            t = v.detach()
+            arrays[name] = t.cpu().numpy() if t.dtype == torch.float64 else t.float().cpu().numpy()
+
+    add("gathered_smpl_params", gathered)
+    for k, o in enumerate(outs):
+        add(f"s{k}" if len(outs) > 1 else "", o)
+    total = sum(a.nbytes for a in arrays.values())
+    if total > limit:
+        scale = limit / total
+        rows = {}
+        for name, a in arrays.items():
+            if a.ndim and a.shape[0] > 1:
+                n = a.shape[0]
+                if n not in rows:
+                    keep = max(1, int(n * scale))
+                    rows[n] = np.sort(np.random.Generator(np.random.PCG64(DUMP_SAMPLE_SEED)).choice(n, keep, replace=False))
+                arrays[name] = np.ascontiguousarray(a[rows[n]])
+        # only arrays of one row (none of today's outputs: they are all batch-major) are kept whole: they must not break the cap
+        total = sum(a.nbytes for a in arrays.values())
+        if total > limit:
+            raise ValueError(f"--dump-outputs: {total} bytes after sampling rows, more than the {limit} allowed")
+    return arrays
+
+
+def dump_outputs(out_dir, arrays):
+    """--dump-outputs: one <name>.npy per array under out_dir."""
+    os.makedirs(out_dir, exist_ok=True)
+    for name, a in arrays.items():
+        np.save(os.path.join(out_dir, name + ".npy"), a)
+    print(f"bench.py: {len(arrays)} output arrays ({sum(a.nbytes for a in arrays.values())} bytes) written to {out_dir}", file=sys.stderr, flush=True)
+
+
 def self_launch(argv):
     """`python bench.py --gpus N` with N > 1 and no torchrun environment: start the N ranks ourselves (one process per GPU,
     RCCL over xGMI), exactly as the driver would: python -m torch.distributed.run --nnodes=1 --nproc-per-node N ... bench.py <argv>.
@@ -187,13 +235,12 @@ def self_launch(argv):
     n = ap.parse_known_args(argv)[0].gpus
     if n <= 1 or "WORLD_SIZE" in os.environ:
         return None
-    with socket.socket() as sk:
-        sk.bind(("127.0.0.1", 0))
-        port = sk.getsockname()[1]
     env = dict(os.environ)
     env.setdefault("HSA_ENABLE_IPC_MODE_LEGACY", "0")      # dmabuf IPC only on this host driver (RCCL needs it)
-    cmd = [sys.executable, "-m", "torch.distributed.run", "--nnodes=1", f"--nproc-per-node={n}", "--master-addr", "127.0.0.1",
-           "--master-port", str(port), os.path.abspath(__file__), *argv]
+    # the rendezvous store binds port 0 itself and hands the port it got to the ranks: no free port is looked up here and bound again later,
+    # which another process of a busy machine can take in between (the launch then fails)
+    cmd = [sys.executable, "-m", "torch.distributed.run", "--nnodes=1", f"--nproc-per-node={n}", "--rdzv-backend=c10d", "--rdzv-endpoint=127.0.0.1:0",
+           f"--rdzv-id=bench-{os.getpid()}", "--local-addr=127.0.0.1", os.path.abspath(__file__), *argv]
     print(f"bench.py: --gpus {n} without a torchrun environment: launching {n} ranks: {' '.join(cmd)}", file=sys.stderr, flush=True)
     return subprocess.call(cmd, env=env)
 
@@ -263,8 +310,9 @@ def cpu_baseline(n, rs, num_scene_points, budget_s, faithful=True):
                       f"{done} of {T} steps timed ({dt:.1f} s)" + (f", extrapolated linearly to {T} steps" if faithful and done < T else "")}
 
 
-def measure(args, workload, steps, warmup, legs_on, cpu_seconds, dev, rank, world, tier_compare=True):
-    """One workload end to end (model, inputs, calibration, warm-up, the timed region, the profiled call, the legs): the JSON object of rank 0."""
+def measure(args, workload, steps, warmup, legs_on, cpu_seconds, dev, rank, world, tier_compare=True, dump_dir=None):
+    """One workload end to end (model, inputs, calibration, warm-up, the timed region, the profiled call, the legs): the JSON object of rank 0.
+    dump_dir: rank 0 writes what the last timed call returned there (output_arrays)."""
     if args.precision_given is None and workload in WORKLOAD_PRECISION:
         args = argparse.Namespace(**{**vars(args), "precision": WORKLOAD_PRECISION[workload]})
     from egohmr_amd import _lib
@@ -309,7 +357,7 @@ def measure(args, workload, steps, warmup, legs_on, cpu_seconds, dev, rank, worl
     # the build's proxy loss (docs/EXPERIMENTS.md 3.5), so C5 is timed at the weight its tight goldens use (0.5) - the kernels' work does not depend on it
     w_guid = (0.5 if volsmpl else 2.0) if guided else 1.0
 
-    def one_step(m=model):
+    def one_call(m=model):
         f = m.fused_sampler
         f.invalidate()                                                               # conditioning is part of the job: re-encode
         # the S samples of an item share its conditioning and are independent given it: one fused loop over S*B bodies
@@ -318,7 +366,11 @@ def measure(args, workload, steps, warmup, legs_on, cpu_seconds, dev, rank, worl
         # region) instead of with a host wait at the end of every call
         outs = f.run_samples(diffusion, batch, noises[:S], ddim=ddim, guided=guided, cond_grad_weight=w_guid, defer_status=True)
         packs = [edist.pack_params(o["other_outputs"]["pred_smpl_params"]) for o in outs]
-        return edist.gather_packed(torch.cat(packs, 0)), outs[-1]
+        return edist.gather_packed(torch.cat(packs, 0)), outs
+
+    def one_step(m=model):
+        gathered, outs = one_call(m)
+        return gathered, outs[-1]
 
     # the precision schedule of the default path is CALIBRATED on the loaded weights (FusedSampler.calibrate_schedule) - here, before the
     # warm-up, on the first items of this batch; it is a one-off per (checkpoint, sampler) and not part of a steady-state sampling call
@@ -336,12 +388,17 @@ def measure(args, workload, steps, warmup, legs_on, cpu_seconds, dev, rank, worl
     torch.cuda.synchronize()
     t0 = time.perf_counter()
     for _ in range(steps):
-        gathered, res = one_step()
+        gathered, outs = one_call()
+        if not dump_dir:
+            outs = outs[-1:]                                                         # (only the last sample's dict is held across the next call)
     torch.cuda.synchronize()
     fs.check_status()                                                                # (inside the timed region: the last call's status word)
     edist.barrier()
     torch.cuda.synchronize()
     dt_rank = time.perf_counter() - t0
+    res = outs[-1]
+    if dump_dir and rank == 0:                                                       # (behind the timed region, before any other call)
+        dump_outputs(dump_dir, output_arrays(outs, gathered))
     dt = edist.max_over_ranks(dt_rank, dev)
     per_rank = edist.gather_floats(B * S * steps / dt_rank, dev)                   # bodies/s of every rank (its own clock)
     gather_ms = None
@@ -663,9 +720,6 @@ def measure(args, workload, steps, warmup, legs_on, cpu_seconds, dev, rank, worl
 
 
 def main():
-    rc = self_launch(sys.argv[1:])
-    if rc is not None:
-        sys.exit(rc)
     ap = argparse.ArgumentParser()
     ap.add_argument("--gpus", type=int, default=1)
     ap.add_argument("--steps", type=int, default=3)
@@ -687,7 +741,15 @@ def main():
     ap.add_argument("--no-legs", action="store_true", help="skip the comparison legs (all-f16x3, f32, f16, other weight set)")
     ap.add_argument("--no-configs", action="store_true", help="default workload only: do not append BASELINE configs 2 and 3 (configs.c2_ddim10 / configs.c3_guided)")
     ap.add_argument("--launch-check", action="store_true", help="only initialise the ranks, report the world size, exit (works without a GPU: gloo)")
+    ap.add_argument("--dump-outputs", metavar="DIR", default=None,
+                    help="write what the last timed call of the headline workload returned to DIR/<name>.npy (float32 / float64, at most 64 MB: a fixed "
+                         "seeded sample of the rows above that); the inputs are seeded, so two builds can be compared output for output")
     args = ap.parse_args()
+    if args.steps < 1:
+        ap.error("--steps must be at least 1")        # (here, before self_launch: rejected once, not by every rank it would start)
+    rc = self_launch(sys.argv[1:])
+    if rc is not None:
+        sys.exit(rc)
     args.precision_given = args.precision or os.environ.get("EGOHMR_GCN_PRECISION")
     args.precision = args.precision_given or "f16x3"
 
@@ -698,11 +760,26 @@ def main():
         raise SystemExit(f"bench.py: --gpus {args.gpus} but {world} rank(s) were started (WORLD_SIZE={os.environ.get('WORLD_SIZE')}); "
                          "start it as `python bench.py --gpus N` (it launches the ranks) or under torch.distributed.run with --nproc-per-node N")
     if args.launch_check:
-        seen = int(torch.distributed.get_world_size()) if world > 1 else 1
-        edist.barrier()
+        # over gloo the ranks meet in all-reduces of a CPU tensor, not in barrier(): torch's barrier() looks up the accelerator, which starts the
+        # HIP runtime (and opens the GPU) in every rank of a check that is meant to run without one
+        gloo = world > 1 and torch.distributed.get_backend() == "gloo"
+
+        def meet():
+            if not gloo:
+                edist.barrier()
+                return int(torch.distributed.get_world_size()) if world > 1 else 1
+            t = torch.ones(1)
+            torch.distributed.all_reduce(t)
+            return int(t.item())
+
+        seen = meet()
         if rank == 0:
             print(json.dumps({"launch_check": True, "n_gpus": world, "n_ranks_seen": seen, "backend": torch.distributed.get_backend() if world > 1 else None}))
-        edist.barrier()
+        meet()
+        if world > 1:
+            # tear the group down before the interpreter does: a gloo group left to the exit handlers aborted ranks now and then
+            # ("terminate called without an active exception", SIGABRT after the line was printed)
+            torch.distributed.destroy_process_group()
         return
     assert torch.cuda.is_available(), "bench.py needs a HIP device; there is no CPU fallback"
     ndev = torch.cuda.device_count()
@@ -713,7 +790,7 @@ def main():
     dev = torch.device("cuda", local)
     assert torch.cuda.current_device() == local, (torch.cuda.current_device(), local)   # every native call launches on the CURRENT device's stream
 
-    out = measure(args, args.workload, args.steps, args.warmup, not args.no_legs, args.cpu_seconds, dev, rank, world)
+    out = measure(args, args.workload, args.steps, args.warmup, not args.no_legs, args.cpu_seconds, dev, rank, world, dump_dir=args.dump_outputs)
     # BASELINE configs 2 and 3 inside the default line, so that the driver's ONE run observes them (3 timed calls each, no legs)
     if args.workload == "ddpm100" and world == 1 and not args.no_configs:
         keep = ("metric", "value", "unit", "steps", "warmup", "ms_per_step", "dtype", "config", "schedule", "roofline", "roofline_hbm", "roofline_guidance", "breakdown_ms",

@@ -25,11 +25,14 @@ def test_bench_gpus_2_self_launches_two_ranks():
 
 
 def test_bench_gpus_8_launch_check():
-    """the shape of the driver's SCALE run: eight ranks rendezvous over 127.0.0.1 and agree on the world size"""
-    r = _run(["--gpus", "8", "--launch-check"])
+    """the shape of the driver's SCALE run: eight ranks rendezvous over 127.0.0.1 and agree on the world size - without starting the HIP
+    runtime in the ranks (on a GPU machine each of them would hold the GPU open: eight at once is more than a shared box allows).  The
+    runtime's own log (AMD_LOG_LEVEL) prints its version once in every process that starts it: the torch.distributed launcher does."""
+    r = _run(["--gpus", "8", "--launch-check"], env_extra={"AMD_LOG_LEVEL": "3"})
     assert r.returncode == 0, r.stderr[-2000:]
     out = json.loads([l for l in r.stdout.splitlines() if l.startswith("{")][-1])
     assert out["n_gpus"] == 8 and out["n_ranks_seen"] == 8
+    assert r.stderr.count("ROCclr version") <= 1, r.stderr[-6000:]
 
 
 def test_bench_refuses_mismatched_world_size():

@@ -8,7 +8,9 @@ import math
 import os
 import sys
 
+import numpy as np
 import pytest
+import torch
 
 REPO = os.path.dirname(os.path.dirname(os.path.abspath(__file__)))
 if REPO not in sys.path:
@@ -89,3 +91,63 @@ def test_every_committed_round5_line_is_compact():
         assert len(txt) < 4096, p
         o = _strict(txt)
         assert o["roofline"] and math.isfinite(o["value"]), p
+
+
+def _fake_outs(S, B, V=50):
+    """result dicts shaped like FusedSampler.run_samples' (CPU tensors stand in for the device ones)"""
+    g = torch.Generator().manual_seed(1)
+    outs = []
+    for _ in range(S):
+        outs.append({"sample": torch.randn(B, 144, generator=g), "pred_xstart": torch.randn(B, 144, generator=g),
+                     "other_outputs": {"pred_vertices": torch.randn(B, V, 3, generator=g),
+                                       "pred_smpl_params": {"betas": torch.randn(B, 10, generator=g).double(), "body_pose": torch.randn(B, 23, 3, 3, generator=g)},
+                                       "vis": torch.ones(B, 24, dtype=torch.bool), "note": "not an array"}})
+    return outs, torch.randn(S * B, 226, generator=g)
+
+
+def test_output_arrays_names_and_dtypes():
+    outs, gathered = _fake_outs(1, 6)
+    a = bench.output_arrays(outs, gathered)
+    assert set(a) == {"gathered_smpl_params", "sample", "pred_xstart", "other_outputs.pred_vertices", "other_outputs.pred_smpl_params.betas",
+                      "other_outputs.pred_smpl_params.body_pose", "other_outputs.vis"}
+    assert a["other_outputs.pred_smpl_params.betas"].dtype == np.float64 and a["other_outputs.vis"].dtype == np.float32
+    np.testing.assert_array_equal(a["other_outputs.pred_vertices"], outs[0]["other_outputs"]["pred_vertices"].numpy())
+    np.testing.assert_array_equal(a["gathered_smpl_params"], gathered.numpy())
+    outs, gathered = _fake_outs(3, 6)
+    a = bench.output_arrays(outs, gathered)
+    assert {"s0.sample", "s2.other_outputs.pred_vertices"} <= set(a) and "sample" not in a
+
+
+def test_output_arrays_above_the_limit_keep_the_same_seeded_rows(tmp_path):
+    outs, gathered = _fake_outs(2, 40)
+    full = bench.output_arrays(outs, gathered, limit=1 << 30)
+    limit = sum(x.nbytes for x in full.values()) // 4
+    a = bench.output_arrays(outs, gathered, limit=limit)
+    b = bench.output_arrays(outs, gathered, limit=limit)
+    assert sum(x.nbytes for x in a.values()) <= limit
+    assert a.keys() == full.keys()
+    for k in a:
+        np.testing.assert_array_equal(a[k], b[k])
+        assert a[k].shape[1:] == full[k].shape[1:] and 1 <= a[k].shape[0] < full[k].shape[0]
+    # rows are a sorted subset of the full output, the same ones for every array of the same length
+    rows = [i for i in range(40) if any((full["s0.sample"][i] == r).all() for r in a["s0.sample"])]
+    np.testing.assert_array_equal(a["s1.other_outputs.pred_vertices"], full["s1.other_outputs.pred_vertices"][rows])
+    bench.dump_outputs(str(tmp_path / "d"), a)
+    for k, v in a.items():
+        np.testing.assert_array_equal(np.load(tmp_path / "d" / f"{k}.npy"), v)
+
+
+def test_bench_rejects_zero_steps():
+    """once, in the process it was given to: `--gpus 8 --steps 0` starts no ranks"""
+    import subprocess
+    for extra in ([], ["--gpus", "8"]):
+        r = subprocess.run([sys.executable, os.path.join(REPO, "bench.py"), "--steps", "0", *extra], capture_output=True, text=True, timeout=300)
+        assert r.returncode != 0 and r.stderr.count("--steps must be at least 1") == 1, r.stderr[-2000:]
+        assert "launching" not in r.stderr
+
+
+def test_output_arrays_cap_is_hard():
+    """single-row arrays are never sampled: if they alone exceed the cap, output_arrays refuses instead of writing more"""
+    big = {"sample": torch.zeros(1, 1000)}
+    with pytest.raises(ValueError):
+        bench.output_arrays([big], torch.zeros(1, 226), limit=2000)

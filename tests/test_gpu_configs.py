@@ -295,6 +295,31 @@ def test_bench_self_launches_two_ranks_on_this_box(dev):
     assert detail["n_ranks_seen"] == 2 and detail["schedule"]["calibrated"] and abs(detail["value"] - out["value"]) < 1e-3 * out["value"]
 
 
+def test_bench_dump_outputs_are_the_same_on_every_run(dev, tmp_path):
+    """`bench.py --dump-outputs DIR` writes what the last timed call returned; the inputs are seeded, so two runs write the same arrays, and
+    --steps is the number of timed calls the line reports ms_per_step over."""
+    import json
+    repo = os.path.dirname(os.path.dirname(os.path.abspath(__file__)))
+    env = {k: v for k, v in os.environ.items() if k not in ("WORLD_SIZE", "RANK", "LOCAL_RANK", "MASTER_ADDR", "MASTER_PORT")}
+    dumps = []
+    for run in ("a", "b"):
+        r = subprocess.run([sys.executable, os.path.join(repo, "bench.py"), "--gpus", "1", "--steps", "2", "--warmup", "1", "--batch", "8", "--scene-points", "512",
+                            "--workload", "c1_ddim5", "--cpu-seconds", "0", "--no-legs", "--dump-outputs", str(tmp_path / run)],
+                           capture_output=True, text=True, env=env, timeout=900)
+        assert r.returncode == 0, (r.stdout[-1500:], r.stderr[-3000:])
+        out = json.loads(r.stdout.strip().splitlines()[-1])
+        assert out["steps"] == 2 and out["ms_per_step"] > 0
+        dumps.append({f[:-4]: np.load(tmp_path / run / f) for f in sorted(os.listdir(tmp_path / run))})
+    a, b = dumps
+    assert a.keys() == b.keys() and {"gathered_smpl_params", "sample", "other_outputs.pred_vertices", "other_outputs.pred_keypoints_3d"} <= set(a)
+    assert a["other_outputs.pred_vertices"].shape == (8, 6890, 3) and a["gathered_smpl_params"].shape[0] == 8
+    assert sum(v.nbytes for v in a.values()) <= 64 << 20
+    for k in a:
+        assert a[k].dtype in (np.float32, np.float64), k
+        np.testing.assert_array_equal(a[k], b[k], err_msg=k)
+    assert np.isfinite(a["other_outputs.pred_vertices"]).all()
+
+
 def test_driver_two_stage_conditions_on_stage1_translation(dev, model, synth_weights, smpl_asset, tmp_path):
     """--two_stage (test_egohmr.py:243-246, :302-303, :691-692): the sampler is conditioned on the stage-1 translation read from the stage-1
     results.pkl (egohmr_amd.io.load_stage1_cam), the ground truth keeps its own, `pred_cam_full_list` lands in the results pkl; against
