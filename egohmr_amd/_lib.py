@@ -3,6 +3,11 @@
 The library is the product: there is no eager / CPU fallback.  If it is missing or cannot be
 loaded this module raises - loudly - at first use.
 
+``lib()`` is the raw C contract: every entry point returns its rc / size / string and never throws.  ``api()`` is the package's
+convention: a ``torch.Tensor`` in any argument position is validated by ``ptr()`` (HIP device, contiguous) and passed as its address;
+a status function raises on a nonzero rc, one of ``VALUE_FUNCTIONS`` on a negative one and otherwise returns it (``EgoHMRRangeError``
+for rc -34, ``EgoHMRHipError`` else).  Opaque native objects (the denoiser, the SMPL model) are owned by a ``Handle``.
+
 ``import torch`` happens before the dlopen on purpose: PyTorch-ROCm ships its own
 ``libamdhip64.so`` (SONAME libamdhip64.so.7, same as /opt/rocm's) and the dynamic loader then
 binds our library to that already-loaded runtime, so device pointers / streams handed over
@@ -11,9 +16,11 @@ from torch tensors are valid inside the kernels' launches.
 from __future__ import annotations
 
 import ctypes as C
+import itertools
 import os
 import subprocess
 import sys
+from types import SimpleNamespace
 
 import torch  # noqa: F401  (must precede the dlopen, see module docstring)
 
@@ -25,7 +32,9 @@ SOURCES = ["gcn.hip", "gcn_tile.hip", "linear.hip", "conv.hip", "stem.hip", "met
 
 
 class EgoHMRHipError(RuntimeError):
-    pass
+    def __init__(self, msg="", rc=None, function=None):        # rc, function: the failed entry point's (None: not a native call's error)
+        super().__init__(msg)
+        self.rc, self.function = rc, function
 
 
 class EgoHMRRangeError(EgoHMRHipError):
@@ -241,13 +250,17 @@ PROTOTYPES = {
 }
 PROF_CLASSES = ("input", "chain_f16x3", "chain_f16", "hidden_f32", "out_dot", "step_body", "skin_input", "guidance", "reserved_8", "reserved_9",
                 "guid_nearest", "guid_skin_bwd", "guid_posefeat_bwd", "step_fused", "guid_nearest_evals")   # EHM_PROF_* of the header (the last one is a COUNT in `launches`)
+# the entry points that return a value (a size, a tile, a mode) rather than a status: negative = error.  Every other int-returning one is a status
+VALUE_FUNCTIONS = frozenset({"ehm_gcn_row_tile", "ehm_gcn_get_precision", "ehm_gcn_activation_group", "ehm_conv_x2_rows", "ehm_conv_x2_workspace_bytes",
+                             "ehm_sample_workspace_bytes", "ehm_resnet_stem_scratch_bytes"})
 
 _lib = None
+_api = None
 
 
 def lib() -> C.CDLL:
     """The loaded library.  Raises EgoHMRHipError when it is absent - never falls back."""
-    global _lib
+    global _lib, _api
     if _lib is None:
         if not os.path.exists(LIB_PATH):
             raise EgoHMRHipError(
@@ -266,16 +279,65 @@ def lib() -> C.CDLL:
             fn.argtypes = args
         if handle.ehm_target_arch() != b"gfx950":
             raise EgoHMRHipError("libegohmr_hip.so was not built for gfx950")
+        _api = SimpleNamespace(**{name: _checked(name, getattr(handle, name)) for name in PROTOTYPES})
         _lib = handle
     return _lib
 
 
+def api() -> SimpleNamespace:
+    """The checked view of the library (module docstring): one callable per PROTOTYPES entry."""
+    lib()
+    return _api
+
+
+def _error(rc: int, function: str) -> EgoHMRHipError:
+    msg = lib().ehm_last_error()
+    cls = EgoHMRRangeError if rc == -34 else EgoHMRHipError
+    return cls(f"{function} failed (rc={rc}): {msg.decode() if msg else ''}", rc=rc, function=function)
+
+
+def _checked(name, fn):
+    unchecked, value = PROTOTYPES[name][0] in (None, C.c_char_p), name in VALUE_FUNCTIONS
+
+    def call(*args):
+        # (the tensors are converted here, not in an argtype's from_param: an exception raised there reaches the caller as ctypes.ArgumentError)
+        rc = fn(*[ptr(a) if isinstance(a, torch.Tensor) else a for a in args])
+        if not unchecked and (rc < 0 if value else rc != 0):
+            raise _error(rc, name)
+        return rc
+    call.__name__ = name
+    return call
+
+
 def check(rc: int, what: str = "") -> None:
     if rc != 0:
-        msg = lib().ehm_last_error()
-        if rc == -34:
-            raise EgoHMRRangeError(f"{what or 'libegohmr_hip'} (rc={rc}): {msg.decode() if msg else ''}")
-        raise EgoHMRHipError(f"{what or 'libegohmr_hip'} failed (rc={rc}): {msg.decode() if msg else ''}")
+        raise _error(rc, what or "libegohmr_hip")
+
+
+class Handle:
+    """Owner of an opaque native object: pointer, destroy function, the tensors that must outlive it; passes as the pointer (NULL once closed).
+    `serial` is unique in the process - unlike the host address, which a handle created after a destroy can reuse - for cache keys."""
+    _serials = itertools.count(1)
+
+    def __init__(self, ptr, destroy, keep=()):
+        self.ptr, self._destroy, self.keep = ptr, destroy, list(keep)
+        self.serial = next(Handle._serials)
+
+    @property
+    def _as_parameter_(self):
+        return self.ptr
+
+    def close(self):
+        p, self.ptr = self.ptr, None
+        if p is not None:
+            self._destroy(p)
+        self.keep = []
+
+    def __del__(self):
+        try:
+            self.close()
+        except Exception:                 # (interpreter teardown: the library may be gone already)
+            pass
 
 
 def ptr(t) -> int:
@@ -329,7 +391,11 @@ def f32(t, device=None):
 
 
 def stream_ptr() -> int:
-    return torch.cuda.current_stream().cuda_stream
+    """The current stream (evaluated before a native call validates its tensors: without a HIP device, the package's error is raised here)."""
+    try:
+        return torch.cuda.current_stream().cuda_stream
+    except RuntimeError as e:
+        raise EgoHMRHipError(f"egohmr_amd kernels need a HIP device; there is no CPU path ({e})") from e
 
 
 def on_device(dev):

@@ -206,13 +206,11 @@ class GaussianDiffusion:
             mo = dict(mo)
             mo["pred_x_start_guided"] = x0
         out = th.empty_like(xc)
-        L, n, st = _lib.lib(), xc.numel(), _lib.stream_ptr()
+        A, n, st = _lib.api(), xc.numel(), _lib.stream_ptr()
         if ddim:
-            _lib.check(L.ehm_ddim_step(_lib.ptr(xc), _lib.ptr(x0), _lib.ptr(noise), _lib.ptr(out), c.sqrt_recip_ac, c.sqrt_recipm1_ac,
-                                       c.sqrt_ac_prev, c.dir_coef, c.sigma, c.nonzero, n, st), "ehm_ddim_step")
+            A.ehm_ddim_step(xc, x0, noise, out, c.sqrt_recip_ac, c.sqrt_recipm1_ac, c.sqrt_ac_prev, c.dir_coef, c.sigma, c.nonzero, n, st)
         else:
-            _lib.check(L.ehm_ddpm_step(_lib.ptr(xc), _lib.ptr(x0), _lib.ptr(noise), _lib.ptr(grad), _lib.ptr(out), c.coef1, c.coef2,
-                                       c.log_variance, c.nonzero, c.grad_scale, n, st), "ehm_ddpm_step")
+            A.ehm_ddpm_step(xc, x0, noise, grad, out, c.coef1, c.coef2, c.log_variance, c.nonzero, c.grad_scale, n, st)
         return {"sample": out, "pred_xstart": mo.get("pred_x_start_guided", mo["pred_x_start"]), "other_outputs": mo}
 
     def p_sample(self, model, batch, x, t, clip_denoised=True, denoised_fn=None, cond_grad_weight=0.0, noise=None):

@@ -82,7 +82,7 @@ class ResNet50Features(nn.Module):
             self.check_status()
         if getattr(self, "_sk_host", None) is None:
             self._sk_host = torch.zeros(1, dtype=torch.int32).pin_memory()
-        _lib.check(_lib.lib().ehm_conv_x2_workspace_status(ws.data_ptr(), self._sk_host.data_ptr(), _lib.stream_ptr()), "ehm_conv_x2_workspace_status")
+        _lib.api().ehm_conv_x2_workspace_status(ws, self._sk_host.data_ptr(), _lib.stream_ptr())
         self._sk_event = torch.cuda.Event()
         self._sk_event.record()
         self._sk_ws_checked = ws
@@ -99,7 +99,7 @@ class ResNet50Features(nn.Module):
             self._sk_host.zero_()
             ws = self._sk_ws_checked
             with torch.cuda.device(ws.device):
-                _lib.check(_lib.lib().ehm_conv_x2_workspace_status(ws.data_ptr(), None, _lib.stream_ptr()), "ehm_conv_x2_workspace_status")
+                _lib.api().ehm_conv_x2_workspace_status(ws, None, _lib.stream_ptr())
 
     # ------------------------------------------------------------------ inference form: BatchNorm folded into the convolutions
     @torch.no_grad()
@@ -112,7 +112,7 @@ class ResNet50Features(nn.Module):
         import ctypes as C
         import math
 
-        from . import _lib
+        A, P = _lib.api(), _lib.ptr
 
         def fold(conv, bn):
             scale = (bn.weight.double() / torch.sqrt(bn.running_var.double() + bn.eps))
@@ -142,7 +142,7 @@ class ResNet50Features(nn.Module):
             amax = float(w2.abs().max())
             scale = 2.0 ** math.floor(math.log2(2048.0 / amax)) if amax > 0 else 1.0
             buf = torch.empty(Co_pad, K, device=w.device)              # X2 rows have the byte size of float rows
-            _lib.check(_lib.lib().ehm_split_pack(w2.data_ptr(), buf.data_ptr(), Co_pad, K, K, scale, _lib.stream_ptr()), "ehm_split_pack")
+            A.ehm_split_pack(w2, buf, Co_pad, K, K, scale, _lib.stream_ptr())
             packed[id(w)] = (buf, scale, p[1].contiguous(), (Co, Ci, KH, KW), p[2][0], p[3][0])
             return packed[id(w)]
 
@@ -151,9 +151,8 @@ class ResNet50Features(nn.Module):
             N, H, W, _ = x.shape
             Ho, Wo = (H + 2 * pad - KH) // stride + 1, (W + 2 * pad - KW) // stride + 1
             y = torch.empty(N, Ho, Wo, Co, device=x.device)
-            d = _lib.ConvDesc(x.data_ptr(), buf.data_ptr(), bias.data_ptr(), res.data_ptr() if res is not None else None, y.data_ptr(),
-                              N, H, W, Ci, Co, KH, KW, stride, pad, 1 if relu else 0, scale)
-            _lib.check(_lib.lib().ehm_conv_nhwc_split(C.byref(d), _lib.stream_ptr()), "ehm_conv_nhwc_split")
+            d = _lib.ConvDesc(P(x), P(buf), P(bias), P(res), P(y), N, H, W, Ci, Co, KH, KW, stride, pad, 1 if relu else 0, scale)
+            A.ehm_conv_nhwc_split(C.byref(d), _lib.stream_ptr())
             return y
 
         stem_wt = stem[0].reshape(64, 147).t().contiguous()                        # [147][64], k = (ci*7 + kh)*7 + kw
@@ -162,7 +161,7 @@ class ResNet50Features(nn.Module):
         def x2_buffer(pixels, ch, dev, clear_last=False):
             """X2 activation matrix for ehm_conv_x2: pixels rounded up to the row tile + one all-zero row (out-of-image taps read it;
             ehm_conv_x2 clears it in its output, the stem's buffer is cleared here)"""
-            rows = int(_lib.lib().ehm_conv_x2_rows(pixels))
+            rows = int(A.ehm_conv_x2_rows(pixels))
             buf = torch.empty(rows, ch, device=dev)                                 # X2 rows have the byte size of float rows
             if clear_last:
                 buf[rows - 1].zero_()
@@ -171,13 +170,11 @@ class ResNet50Features(nn.Module):
         def stem_mc(x, x2=False):
             """conv1 + bn1 + relu + maxpool in one pass, NCHW in -> NHWC out (csrc/stem.hip); x2: output in the X2 split format"""
             N, _, H, W = x.shape
-            lib = _lib.lib()
             if stem_wt.device != x.device:
                 raise _lib.EgoHMRHipError("ResNet50Features.folded(): weights and input live on different devices")
-            scratch = torch.empty(lib.ehm_resnet_stem_scratch_bytes(N, H, W) // 4, device=x.device)
+            scratch = torch.empty(A.ehm_resnet_stem_scratch_bytes(N, H, W) // 4, device=x.device)
             y = x2_buffer(N * (H // 4) * (W // 4), 64, x.device, clear_last=True) if x2 else torch.empty(N, H // 4, W // 4, 64, device=x.device)
-            _lib.check(lib.ehm_resnet_stem(x.data_ptr(), stem_wt.data_ptr(), stem_b.data_ptr(), scratch.data_ptr(), y.data_ptr(), N, H, W,
-                                           1 if x2 else 0, _lib.stream_ptr()), "ehm_resnet_stem")
+            A.ehm_resnet_stem(x, stem_wt, stem_b, scratch, y, N, H, W, 1 if x2 else 0, _lib.stream_ptr())
             if x2 and _x2_debug_hook is not None:
                 _x2_debug_hook(y, 64)
             return y
@@ -195,7 +192,7 @@ class ResNet50Features(nn.Module):
             amax = float(w2.abs().max())
             scale = 2.0 ** math.floor(math.log2(2048.0 / amax)) if amax > 0 else 1.0
             buf = torch.empty(Co, K, device=w.device)
-            _lib.check(_lib.lib().ehm_split_pack(w2.data_ptr(), buf.data_ptr(), Co, K, K, scale, _lib.stream_ptr()), "ehm_split_pack")
+            A.ehm_split_pack(w2, buf, Co, K, K, scale, _lib.stream_ptr())
             packed[key] = (buf, scale, (p[1].double() + ds[1].double()).float().contiguous(), (Co, Ci, 1, 1), p[2][0], p[3][0], wd.shape[1], ds[2][0])
             return packed[key]
 
@@ -209,19 +206,18 @@ class ResNet50Features(nn.Module):
                 buf, scale, bias, (Co, Ci, KH, KW), stride, pad = pack(p)
             Ho, Wo = (H + 2 * pad - KH) // stride + 1, (W + 2 * pad - KW) // stride + 1
             y = x2_buffer(N * Ho * Wo, Co, x.device)
-            d = _lib.ConvX2Desc(x.data_ptr(), x.shape[0], buf.data_ptr(), bias.data_ptr(), res.data_ptr() if res is not None else None, y.data_ptr(),
-                                N, H, W, Ci, Co, KH, KW, stride, pad, 1 if relu else 0, scale, None, 0)
+            d = _lib.ConvX2Desc(P(x), x.shape[0], P(buf), P(bias), P(res), P(y), N, H, W, Ci, Co, KH, KW, stride, pad, 1 if relu else 0, scale, None, 0)
             d.hi_only = int(bool(self.hi_only))                                  # the plain-f16 tier (EgoHMR.encoder_precision = 'f16'): NOT parity grade
             if shortcut is not None:
                 x_in, (_, H2, W2) = shortcut[0], shortcut[1]
-                d.x2, d.x2_rows, d.H2, d.W2, d.Ci2, d.stride2 = x_in.data_ptr(), x_in.shape[0], H2, W2, Ci2, stride2
-            need = int(_lib.lib().ehm_conv_x2_workspace_bytes(C.byref(d)))      # stream-K scratch (layers 3 / 4: tile counts that straddle the block slots)
+                d.x2, d.x2_rows, d.H2, d.W2, d.Ci2, d.stride2 = P(x_in), x_in.shape[0], H2, W2, Ci2, stride2
+            need = int(A.ehm_conv_x2_workspace_bytes(C.byref(d)))      # stream-K scratch (layers 3 / 4: tile counts that straddle the block slots)
             if need:
                 ws = sk_ws.get(str(x.device))
                 if ws is None or ws.numel() < need:
                     ws = sk_ws[str(x.device)] = torch.zeros(need, dtype=torch.uint8, device=x.device)   # zeroed ONCE: the convs leave their counters zeroed
-                d.workspace, d.workspace_bytes, d.workspace_clean = ws.data_ptr(), ws.numel(), 1
-            _lib.check(_lib.lib().ehm_conv_x2(C.byref(d), _lib.stream_ptr()), "ehm_conv_x2")
+                d.workspace, d.workspace_bytes, d.workspace_clean = P(ws), ws.numel(), 1
+            A.ehm_conv_x2(C.byref(d), _lib.stream_ptr())
             if _x2_debug_hook is not None:
                 _x2_debug_hook(y, Co)
             return y, (N, Ho, Wo)
@@ -241,8 +237,7 @@ class ResNet50Features(nn.Module):
                 else:
                     x, shp = conv_x2(y, s2, c3, res=conv_x2(x, shp, ds, relu=False)[0])
             out = torch.empty(N, x.shape[1], device=x.device)
-            _lib.check(_lib.lib().ehm_x2_group_mean(x.data_ptr(), out.data_ptr(), N, shp[1] * shp[2], x.shape[1], int(bool(self.hi_only)), _lib.stream_ptr()),
-                       "ehm_x2_group_mean")
+            A.ehm_x2_group_mean(x, out, N, shp[1] * shp[2], x.shape[1], int(bool(self.hi_only)), _lib.stream_ptr())
             self._sk_status_async(sk_ws.get(str(x.device)))
             return out
 
@@ -298,19 +293,17 @@ class ResnetPointnet(nn.Module):
     @staticmethod
     def _pack(w64: torch.Tensor, device):
         """float64 [N,K] -> (X2 buffer, power-of-two scale); K padded to a multiple of 32."""
-        from . import _lib
         w = w64.float().contiguous().to(device)
         N, K = w.shape
         Kp = (K + 31) // 32 * 32
         amax = float(w.abs().max())
         scale = 2.0 ** (12 - int(np.floor(np.log2(amax)) + 1)) if amax > 0 else 1.0
         buf = torch.empty(N, Kp, dtype=torch.float32, device=device)         # X2 has the byte size of float32 [N,Kp]
-        _lib.check(_lib.lib().ehm_split_pack(w.data_ptr(), buf.data_ptr(), N, K, Kp, scale, _lib.stream_ptr()), "ehm_split_pack")
+        _lib.api().ehm_split_pack(w, buf, N, K, Kp, scale, _lib.stream_ptr())
         return buf, scale, w
 
     def _prepare(self, device):
         if getattr(self, "_tkey", None) is None:
-            from . import _lib
             self._tkey = _lib.TensorKey(self)
         key = self._tkey() + (str(device),)
         if self._packed is not None and self._packed_key == key:
@@ -340,15 +333,13 @@ class ResnetPointnet(nn.Module):
 
     @torch.no_grad()
     def forward(self, p):
-        from . import _lib
         if not p.is_cuda:
             raise _lib.EgoHMRHipError("ResnetPointnet runs on the HIP kernels only (got a CPU tensor); there is no CPU path")
         with _lib.on_device(p.device):                                                   # the library launches on the CURRENT device's stream
             return self._forward_on_device(p)
 
     def _forward_on_device(self, p):
-        from . import _lib
-        L, dev, H = _lib.lib(), p.device, self.hidden_dim
+        A, P_, dev, H = _lib.api(), _lib.ptr, p.device, self.hidden_dim
         P = self._prepare(dev)
         p = _lib.f32(p)
         B, N, _ = p.shape
@@ -358,17 +349,15 @@ class ResnetPointnet(nn.Module):
         f32buf = lambda cols: torch.empty(M, cols, dtype=torch.float32, device=dev)      # X2 buffers (same bytes as float32)
         P32, Hb, netA, netB = f32buf(32), f32buf(H), f32buf(H), f32buf(H)
         p = p.contiguous()
-        _lib.check(L.ehm_pointnet_lift(p.data_ptr(), None, None, None, P32.data_ptr(), B, N, Np, 2 * H, st), "ehm_pointnet_lift")
+        A.ehm_pointnet_lift(p, None, None, None, P32, B, N, Np, 2 * H, st)
 
-        def gemm(A0, K0, A1, K1, W, bias, gbias, Y, colmax, relu_in0, relu_out, lift=False, gstride=0):
-            d = _lib.LinearDesc(A0=A0.data_ptr() if A0 is not None else None, A1=A1.data_ptr() if A1 is not None else None, W=W[0].data_ptr(),
-                                lift_points=p.data_ptr() if lift else None, lift_W4=P["pos_w4"].data_ptr() if lift else None,
-                                bias=bias.data_ptr() if bias is not None else None,
-                                group_bias=gbias.data_ptr() if gbias is not None else None,
-                                Y=Y.data_ptr() if Y is not None else None, colmax=colmax.data_ptr() if colmax is not None else None,
+        def gemm(A0, K0, A1, K1, W, bias, gbias, Y, colmax, relu_in0, relu_out, lift=False):
+            """gbias: (per-body bias matrix [B, 2H], first column of this GEMM's H columns) or None"""
+            d = _lib.LinearDesc(A0=P_(A0), A1=P_(A1), W=P_(W[0]), lift_points=P_(p) if lift else None, lift_W4=P_(P["pos_w4"]) if lift else None,
+                                bias=P_(bias), group_bias=P_(gbias[0]) + 4 * gbias[1] if gbias else None, Y=P_(Y), colmax=P_(colmax),
                                 M=M, N=H, K0=K0, K1=K1, rows_per_group=Np, valid_rows_per_group=N, relu_in0=int(relu_in0),
-                                relu_out=int(relu_out), w_scale=W[1], hi_only=int(bool(self.hi_only)), group_bias_stride=gstride)
-            _lib.check(L.ehm_linear_split(d, st), "ehm_linear_split")
+                                relu_out=int(relu_out), w_scale=W[1], hi_only=int(bool(self.hi_only)), group_bias_stride=gbias[0].shape[1] if gbias else 0)
+            A.ehm_linear_split(d, st)
             if Y is not None and _x2_debug_hook is not None:
                 _x2_debug_hook(Y, H)
 
@@ -377,8 +366,7 @@ class ResnetPointnet(nn.Module):
             256 x 256 x 256 products as one 256 x 256 workgroup (170 - 450 us, on the PointNet's critical path).
             relu_in_cols: the first that many output columns see relu(x)."""
             y = torch.empty(x.shape[0], Wt.shape[1], device=dev)
-            _lib.check(L.ehm_skinny_gemm_f32(x.data_ptr(), Wt.data_ptr(), bias.data_ptr() if bias is not None else None, y.data_ptr(),
-                                             x.shape[0], Wt.shape[0], Wt.shape[1], relu_in_cols << 1, st), "ehm_skinny_gemm_f32")
+            A.ehm_skinny_gemm_f32(x, Wt, bias, y, x.shape[0], Wt.shape[0], Wt.shape[1], relu_in_cols << 1, st)
             return y
 
         neg_inf = float("-inf")
@@ -392,10 +380,9 @@ class ResnetPointnet(nn.Module):
         for i in (1, 2, 3):
             # pooled halves of fc_0(relu(cat[net, pooled])) and of shortcut(cat[net, pooled]): one launch, [B, 2H]
             vs = small(pooled, P[f"wvsT_{i}"], P[f"bvs_{i}"], relu_in_cols=H)
-            v, s = vs[:, :H], vs[:, H:]
-            gemm(cur, H, None, 0, P[f"g1_{i}"], None, v, Hb, None, True, True, gstride=2 * H)
+            gemm(cur, H, None, 0, P[f"g1_{i}"], None, (vs, 0), Hb, None, True, True)
             pooled = pooled_all[i]
-            gemm(Hb, H, cur, H, P[f"g3_{i}"], P[f"g3_{i}"][3], s, nxt if i < 3 else None, pooled, False, False, gstride=2 * H)
+            gemm(Hb, H, cur, H, P[f"g3_{i}"], P[f"g3_{i}"][3], (vs, H), nxt if i < 3 else None, pooled, False, False)
             cur, nxt = nxt, cur
         return small(pooled, P["fc_cT"], P["fc_cb"], relu_in_cols=P["fc_cT"].shape[1])
 

@@ -52,12 +52,13 @@ class FusedSampler:
     def gcn(self):
         key = self._param_key()
         if self._gcn is None or key != self._gcn_key:
-            self._free()
+            if self._gcn is not None:
+                self._gcn.close()
             m = self.model
             dm = m.diffusion_model
             gi = dm.gconv_input[0]
-            h, self._gcn_keep = dm.create_native_handle(m.device)             # (ModulatedGCN owns the parameter marshalling: ehm_gcn_create)
-            self._gcn, self._gcn_key = h, key
+            h, keep = dm.create_native_handle(m.device)                        # (ModulatedGCN owns the parameter marshalling: ehm_gcn_create)
+            self._gcn, self._gcn_key = _lib.Handle(h, _lib.api().ehm_gcn_destroy, keep), key
             # fold InputProcess (Linear 6->512) into the x_t slice of the input conv: x @ (Wp^T W_k[2694:3206]) + bp W_k[...]
             W = gi.gconv.W.detach().double()                                            # [2, 3718, hid]
             Wp, bp = m.input_process.poseEmbedding.weight.detach().double(), m.input_process.poseEmbedding.bias.detach().double()
@@ -75,29 +76,18 @@ class FusedSampler:
             self._folded = SimpleNamespace(Wx=Wx.float().contiguous(), bx=bx, W_img=gi.gconv.W.detach()[:, :a, :],
                                            W_oth=gi.gconv.W.detach()[:, a:b, :], W_t=W[:, c:d, :], W_img_cat=W_img_cat, W_oth_cat=W_oth_cat,
                                            k_oth=k_oth)
-        _lib.check(_lib.lib().ehm_gcn_set_uncond_mode(self._gcn, 0 if self.model.only_mask_img_cond else 1), "ehm_gcn_set_uncond_mode")
+        A = _lib.api()
+        A.ehm_gcn_set_uncond_mode(self._gcn, 0 if self.model.only_mask_img_cond else 1)
         mode = PRECISIONS[self.model.gcn_precision]
-        if _lib.lib().ehm_gcn_get_precision(self._gcn) != mode:
-            _lib.check(_lib.lib().ehm_gcn_set_precision(self._gcn, mode), "ehm_gcn_set_precision")
+        if A.ehm_gcn_get_precision(self._gcn) != mode:
+            A.ehm_gcn_set_precision(self._gcn, mode)
         if self.model.diffusion_model.nonlocal_layer:       # the one-call loop runs the block natively (ehm_gcn_set_nonlocal)
             (wq, sq, bq), (wo, so, bo) = self._nonlocal_packed()
-            if getattr(self, "_nl_set", None) != (self._nl_key, self._gcn.value):
-                p = _lib.NonlocalParams(wq.data_ptr(), bq.data_ptr(), sq, wo.data_ptr(), bo.data_ptr(), so, self.model.diffusion_model.non_local.inter_channels)
-                _lib.check(_lib.lib().ehm_gcn_set_nonlocal(self._gcn, C.byref(p)), "ehm_gcn_set_nonlocal")
-                self._nl_set = (self._nl_key, self._gcn.value)
+            if getattr(self, "_nl_set", None) != (self._nl_key, self._gcn.serial):
+                p = _lib.NonlocalParams(_lib.ptr(wq), _lib.ptr(bq), sq, _lib.ptr(wo), _lib.ptr(bo), so, self.model.diffusion_model.non_local.inter_channels)
+                A.ehm_gcn_set_nonlocal(self._gcn, C.byref(p))
+                self._nl_set = (self._nl_key, self._gcn.serial)
         return self._gcn
-
-    def _free(self):
-        if self._gcn is not None:
-            try:
-                _lib.lib().ehm_gcn_destroy(self._gcn)
-            except Exception:
-                pass
-            self._gcn = None
-            self._nl_set = None          # a new handle may reuse the freed one's address: the non-local block must be installed again
-
-    def __del__(self):
-        self._free()
 
     def _backbone_fn(self):
         """ResNet-50 with BatchNorm folded into the convolutions, rebuilt when the backbone weights change."""
@@ -111,7 +101,7 @@ class FusedSampler:
             return self._prepare_on_device(batch)
 
     def _prepare_on_device(self, batch) -> _Prepared:
-        m, L = self.model, _lib.lib()
+        m = self.model
         # Cache key = identity AND version of every tensor the conditioning is computed from, and of every weight it passes
         # through.  The cached entry keeps strong references to those input tensors, so neither their id() nor their storage can be
         # recycled for a different batch while the entry is alive; in-place edits bump _version.
@@ -165,14 +155,15 @@ class FusedSampler:
         flags = torch.empty(2, B, dtype=torch.uint8, device=dev)                       # finite | need (scratch)
         maps = torch.empty(2 * B + 1, dtype=torch.int32, device=dev)                   # mask_slot | mask_items | count
         sums = (img.reshape(B, -1).sum(dim=1), scene.reshape(B, -1).sum(dim=1))
-        d = _lib.ItemPrepDesc(keypoints_2d=kp.data_ptr(), joint_map=jm[1].data_ptr(), NK=kp.shape[1], force_visible=8, fx=fx.data_ptr(), cx=cx.data_ptr(),
-                              cy=cy.data_ptr(), box_center=bc.data_ptr(), box_size=bs.data_ptr(), transl=transl.data_ptr(), fx_norm=m.cfg.CAM.FX_NORM_COEFF,
-                              with_bbox=int(m.with_bbox_info), with_cam_center=int(m.with_cam_center), tW1=tw[0].data_ptr(), tb1=tw[1].data_ptr(),
-                              tW2=tw[2].data_ptr(), tb2=tw[3].data_ptr(), t_hidden=te[0].out_features, t_out=n_tr, img_rowsum=sums[0].data_ptr(),
-                              scene_rowsum=sums[1].data_ptr(), other=oth.data_ptr(), other_ld=f.k_oth, other_col0=n_scene, vis=vis.data_ptr(),
-                              mask_slot=maps.data_ptr(), mask_items=maps[B:].data_ptr(), count=maps[2 * B:].data_ptr(), finite=flags.data_ptr(),
-                              need_scratch=flags[1].data_ptr(), pass_group=int(getattr(m, "pass_group", 1)), B=B)
-        _lib.check(L.ehm_item_prep(C.byref(d), st), "ehm_item_prep")
+        P = _lib.ptr
+        d = _lib.ItemPrepDesc(keypoints_2d=P(kp), joint_map=P(jm[1]), NK=kp.shape[1], force_visible=8, fx=P(fx), cx=P(cx),
+                              cy=P(cy), box_center=P(bc), box_size=P(bs), transl=P(transl), fx_norm=m.cfg.CAM.FX_NORM_COEFF,
+                              with_bbox=int(m.with_bbox_info), with_cam_center=int(m.with_cam_center), tW1=P(tw[0]), tb1=P(tw[1]),
+                              tW2=P(tw[2]), tb2=P(tw[3]), t_hidden=te[0].out_features, t_out=n_tr, img_rowsum=P(sums[0]),
+                              scene_rowsum=P(sums[1]), other=P(oth), other_ld=f.k_oth, other_col0=n_scene, vis=P(vis),
+                              mask_slot=P(maps), mask_items=P(maps[B:]), count=P(maps[2 * B:]), finite=P(flags),
+                              need_scratch=P(flags[1]), pass_group=int(getattr(m, "pass_group", 1)), B=B)
+        _lib.api().ehm_item_prep(C.byref(d), st)
         if getattr(self, "_count_host", None) is None:
             self._count_host = torch.zeros(1, dtype=torch.int32).pin_memory()
         self._count_host.copy_(maps[2 * B:], non_blocking=True)
@@ -217,7 +208,7 @@ class FusedSampler:
         """The step-invariant slices of the input graph conv ([B,2,hid] each: image features, scene + translation + camera features)
         and the beta head (egohmr.py:263-265, Linear -> ReLU -> Linear + init_betas) as exact-float32 matrix-core GEMMs built for M = B
         rows (ehm_skinny_gemm_f32).  oth = [scene | transl | cam] zero-padded to a multiple of 32 columns, n_other of them live."""
-        m, f, L = self.model, self._folded, _lib.lib()
+        m, f, A = self.model, self._folded, _lib.api()
         B, dev, hid = img_feats.shape[0], img_feats.device, m.diffusion_model.hid_dim
         st = _lib.stream_ptr()
         a = img_feats.shape[1]
@@ -227,8 +218,8 @@ class FusedSampler:
                                       f"{l1.in_features} -> {l1.out_features} -> {l2.out_features}, other features {n_other}")
         h_img = torch.empty(B, 2, hid, device=dev)
         h_oth = torch.empty(B, 2, hid, device=dev)
-        _lib.check(L.ehm_skinny_gemm_f32(_lib.ptr(img_feats), _lib.ptr(f.W_img_cat), None, _lib.ptr(h_img), B, a, 2 * hid, 0, st), "ehm_skinny_gemm_f32")
-        _lib.check(L.ehm_skinny_gemm_f32(_lib.ptr(oth), _lib.ptr(f.W_oth_cat), None, _lib.ptr(h_oth), B, f.k_oth, 2 * hid, 0, st), "ehm_skinny_gemm_f32")
+        A.ehm_skinny_gemm_f32(img_feats, f.W_img_cat, None, h_img, B, a, 2 * hid, 0, st)
+        A.ehm_skinny_gemm_f32(oth, f.W_oth_cat, None, h_oth, B, f.k_oth, 2 * hid, 0, st)
         # beta head: both layers on the same kernel (weights transposed and zero-padded once per weight version; init_betas folded into
         # the second bias)
         ib = m.beta_layer.init_betas
@@ -247,9 +238,9 @@ class FusedSampler:
         W1, b1, W2, b2 = self._beta_w
         xb = torch.cat([img_feats, oth], dim=1)
         hb = torch.empty(B, l1.out_features, device=dev)
-        _lib.check(L.ehm_skinny_gemm_f32(_lib.ptr(xb), _lib.ptr(W1), _lib.ptr(b1), _lib.ptr(hb), B, xb.shape[1], l1.out_features, 1, st), "ehm_skinny_gemm_f32")
+        A.ehm_skinny_gemm_f32(xb, W1, b1, hb, B, xb.shape[1], l1.out_features, 1, st)
         b32 = torch.empty(B, 32, device=dev)
-        _lib.check(L.ehm_skinny_gemm_f32(_lib.ptr(hb), _lib.ptr(W2), _lib.ptr(b2), _lib.ptr(b32), B, l1.out_features, 32, 0, st), "ehm_skinny_gemm_f32")
+        A.ehm_skinny_gemm_f32(hb, W2, b2, b32, B, l1.out_features, 32, 0, st)
         return h_img, h_oth, b32[:, :l2.out_features].contiguous()
 
     def _cond_param_key(self):
@@ -260,12 +251,12 @@ class FusedSampler:
 
     def _apply_pass_map(self, st, passes):
         """(virtual bodies, num_masked for the descriptor) after telling the handle which items still need the second pass."""
-        m, L = self.model, _lib.lib()
+        m, A = self.model, _lib.api()
         h = self.gcn()
         if passes == 2 and m.prune_passes:
-            _lib.check(L.ehm_gcn_set_pass_map(h, _lib.ptr(st.mask_items) if st.num_masked else None, _lib.ptr(st.mask_slot), st.num_masked), "ehm_gcn_set_pass_map")
+            A.ehm_gcn_set_pass_map(h, st.mask_items if st.num_masked else None, st.mask_slot, st.num_masked)
             return st.B + st.num_masked, st.num_masked
-        _lib.check(L.ehm_gcn_set_pass_map(h, None, None, -1), "ehm_gcn_set_pass_map")
+        A.ehm_gcn_set_pass_map(h, None, None, -1)
         return passes * st.B, -1
 
     def invalidate(self, structure: bool = False):
@@ -319,19 +310,18 @@ class FusedSampler:
 
     @torch.no_grad()
     def denoise_once(self, st, x_t, tvec, passes):
-        m, L = self.model, _lib.lib()
+        m, A = self.model, _lib.api()
         hid, B = m.diffusion_model.hid_dim, st.B
-        tile = L.ehm_gcn_row_tile()
+        tile = A.ehm_gcn_row_tile()
         rows = self._apply_pass_map(st, passes)[0] * 24
         rows_pad = (rows + tile - 1) // tile * tile
         X = [torch.zeros(rows_pad, hid, device=m.device) for _ in range(3)]
         s = _lib.stream_ptr()
         h = self.gcn()
-        _lib.check(L.ehm_gcn_input_layer(h, _lib.ptr(st.h_img), _lib.ptr(st.h_oth), _lib.ptr(st.vis), _lib.ptr(x_t), _lib.ptr(self._folded.Wx),
-                                         _lib.ptr(tvec), _lib.ptr(X[0]), B, passes, s), "ehm_gcn_input_layer")
-        bufs = (C.c_void_p * 3)(*[x.data_ptr() for x in X])
+        A.ehm_gcn_input_layer(h, st.h_img, st.h_oth, st.vis, x_t, self._folded.Wx, tvec, X[0], B, passes, s)
+        bufs = (C.c_void_p * 3)(*map(_lib.ptr, X))
         res = C.c_int(0)
-        _lib.check(L.ehm_gcn_hidden_stack(h, bufs, rows_pad, C.byref(res), s), "ehm_gcn_hidden_stack")
+        A.ehm_gcn_hidden_stack(h, bufs, rows_pad, C.byref(res), s)
         cur = res.value
         feat = X[cur]
         if m.diffusion_model.nonlocal_layer:
@@ -339,7 +329,7 @@ class FusedSampler:
                 raise _lib.EgoHMRHipError("the optional non-local GCN block runs on float32 features; use gcn_precision 'f16x3' or 'f32' with it")
             feat = self._non_local(feat, rows, rows_pad)
         x0 = torch.empty(B, 144, device=m.device)
-        _lib.check(L.ehm_gcn_output_layer(h, _lib.ptr(feat), _lib.ptr(st.vis), _lib.ptr(x0), B, passes, s), "ehm_gcn_output_layer")
+        A.ehm_gcn_output_layer(h, feat, st.vis, x0, B, passes, s)
         self.last_hidden = feat[:rows]
         return x0
 
@@ -357,7 +347,7 @@ class FusedSampler:
     @torch.no_grad()
     def collision(self, verts, scene, want_grad=True, want_hits=False, all_points=None):
         """The collision proxy for a batch of bodies: (loss [B], d loss / d verts [B,V,3] or None, hits [B] int32 or None)."""
-        m, L = self.model, _lib.lib()
+        m = self.model
         verts, scene = _lib.f32(verts, m.device), _lib.f32(scene, m.device)
         B, V, N = verts.shape[0], verts.shape[1], scene.shape[1]
         loss = torch.empty(B, device=m.device)
@@ -365,27 +355,24 @@ class FusedSampler:
         hits = torch.empty(B, device=m.device, dtype=torch.int32) if want_hits else None
         allp = m.guide_all_points if all_points is None else all_points
         with torch.cuda.device(m.device):
-            _lib.check(L.ehm_collision_query(_lib.ptr(verts), _lib.ptr(scene), _lib.ptr(loss), _lib.ptr(gverts), _lib.ptr(hits), B, V, N,
-                                             m.collision_tau, int(bool(allp)), _lib.stream_ptr()), "ehm_collision_query")
+            _lib.api().ehm_collision_query(verts, scene, loss, gverts, hits, B, V, N, m.collision_tau, int(bool(allp)), _lib.stream_ptr())
         return loss, gverts, hits
 
     @torch.no_grad()
     def guidance_gradient(self, st, x, betas):
-        m, L = self.model, _lib.lib()
+        m, A = self.model, _lib.api()
         B = x.shape[0]
         mean, std = m._std_mean()
         verts = torch.empty(B, m.smpl.num_verts, 3, device=m.device)
         joints = torch.empty(B, m.smpl.num_joints_out, 3, device=m.device)
         s = _lib.stream_ptr()
-        _lib.check(L.ehm_smpl_forward_rot6d(m.smpl.handle(), _lib.ptr(betas), _lib.ptr(x), _lib.ptr(mean), _lib.ptr(std), _lib.ptr(verts),
-                                            _lib.ptr(joints), None, None, None, B, s), "ehm_smpl_forward_rot6d")
+        A.ehm_smpl_forward_rot6d(m.smpl.handle(), betas, x, mean, std, verts, joints, None, None, None, B, s)
         loss, gverts, _ = self.collision(verts, st.scene)
         gpose = torch.empty(B, 144, device=m.device)
-        _lib.check(L.ehm_smpl_backward_rot6d(m.smpl.handle(), _lib.ptr(betas), _lib.ptr(x), _lib.ptr(mean), _lib.ptr(std), _lib.ptr(gverts),
-                                             _lib.ptr(gpose), B, s), "ehm_smpl_backward_rot6d")
+        A.ehm_smpl_backward_rot6d(m.smpl.handle(), betas, x, mean, std, gverts, gpose, B, s)
         grad = torch.empty(B, 144, device=m.device)
         denom = self.guide_denom(B)
-        _lib.check(L.ehm_guidance_grad_finish(_lib.ptr(gpose), _lib.ptr(loss), _lib.ptr(grad), B, denom, s), "ehm_guidance_grad_finish")
+        A.ehm_guidance_grad_finish(gpose, loss, grad, B, denom, s)
         return grad
 
     def guide_denom(self, B: int) -> float:
@@ -656,7 +643,7 @@ class FusedSampler:
                 return self._run_on_device(diffusion, batch, noise_stack, ddim, guided, cond_grad_weight, trace, prepared, denom_items, False, None)
 
     def _run_on_device(self, diffusion, batch, noise_stack, ddim, guided, cond_grad_weight, trace, prepared, denom_items, defer_status, lowprec):
-        m, L = self.model, _lib.lib()
+        m, A = self.model, _lib.api()
         nonlocal_ci = m.diffusion_model.non_local.inter_channels if m.diffusion_model.nonlocal_layer else 0
         if nonlocal_ci and m.gcn_precision == "f16":
             raise _lib.EgoHMRHipError("the optional non-local GCN block runs on float32 features; use gcn_precision 'f16x3' or 'f32' with it")
@@ -691,19 +678,15 @@ class FusedSampler:
                                lbs_every_step=int(m.lbs_every_step), num_scene_points=st.scene.shape[1] if any_guided else 0,
                                guide_denom=self.guide_denom(denom_items or B), tau=m.collision_tau, num_masked=num_masked,
                                guide_all_points=int(bool(m.guide_all_points)), lowprec_steps=int(lowprec), nonlocal_ci=int(nonlocal_ci))
-        nbytes = L.ehm_sample_workspace_bytes(C.byref(desc), hid, V)
-        if nbytes < 0:
-            raise _lib.EgoHMRHipError(f"ehm_sample_workspace_bytes rejected the descriptor (rc={nbytes})")
+        nbytes = A.ehm_sample_workspace_bytes(C.byref(desc), hid, V)
         dev = m.device
         mean, std = m._std_mean()
         gcn, smpl_h = self.gcn(), m.smpl.handle()
 
         def launch(bufs, ws, tr):
-            _lib.check(L.ehm_sample_loop(gcn, smpl_h, C.byref(desc), steps, _lib.ptr(bufs.h_img), _lib.ptr(bufs.h_oth), _lib.ptr(bufs.vis),
-                                         _lib.ptr(self._folded.Wx), _lib.ptr(bufs.tvecs), _lib.ptr(bufs.noise),
-                                         _lib.ptr(bufs.scene) if any_guided else None, _lib.ptr(bufs.betas), _lib.ptr(mean), _lib.ptr(std),
-                                         _lib.ptr(bufs.x_final), _lib.ptr(bufs.x0), _lib.ptr(bufs.verts), _lib.ptr(bufs.joints), _lib.ptr(bufs.R),
-                                         _lib.ptr(bufs.pose6d), _lib.ptr(tr), _lib.ptr(ws), nbytes, _lib.stream_ptr()), "ehm_sample_loop")
+            A.ehm_sample_loop(gcn, smpl_h, C.byref(desc), steps, bufs.h_img, bufs.h_oth, bufs.vis, self._folded.Wx, bufs.tvecs, bufs.noise,
+                              bufs.scene if any_guided else None, bufs.betas, mean, std, bufs.x_final, bufs.x0, bufs.verts, bufs.joints, bufs.R,
+                              bufs.pose6d, tr, ws, nbytes, _lib.stream_ptr())
 
         def out_bufs():
             return dict(x_final=torch.empty(B, 144, device=dev), x0=torch.empty(B, 144, device=dev), verts=torch.empty(B, V, 3, device=dev),
@@ -717,9 +700,10 @@ class FusedSampler:
             if graph and not any_guided and not trace:
                 # hipGraph route: the loop's launches are captured once per (shape, schedule) with every pointer inside persistent
                 # buffers; a call copies its inputs in, replays, and copies the results out.
-                # (every pointer the captured launches bake in that is not inside `bufs`: the two native handles and the mean / std buffers)
-                key = (B, T, int(ddim), desc.passes, desc.lbs_every_step, desc.lowprec_steps, m.gcn_precision, self._gcn_key,
-                       bytes(steps), st.scene.shape[1], num_masked, smpl_h.value if hasattr(smpl_h, "value") else int(smpl_h or 0),
+                # (every pointer the captured launches bake in that is not inside `bufs`: the two native handles - by serial, a recreated handle
+                # can reuse a destroyed one's address - and the mean / std buffers)
+                key = (B, T, int(ddim), desc.passes, desc.lbs_every_step, desc.lowprec_steps, m.gcn_precision, gcn.serial,
+                       bytes(steps), st.scene.shape[1], num_masked, smpl_h.serial,
                        mean.data_ptr(), std.data_ptr(), self._folded.Wx.data_ptr(), getattr(self, '_nl_set', None))
                 ent = self._graphs.get(key)
                 if ent is None:
@@ -733,7 +717,7 @@ class FusedSampler:
                     bufs.mask_items.copy_(st.mask_items)
                     bufs.mask_slot.copy_(st.mask_slot)
                     if num_masked >= 0:      # the captured kernels read the pass map through these persistent arrays
-                        _lib.check(L.ehm_gcn_set_pass_map(gcn, _lib.ptr(bufs.mask_items) if num_masked else None, _lib.ptr(bufs.mask_slot), num_masked))
+                        A.ehm_gcn_set_pass_map(gcn, bufs.mask_items if num_masked else None, bufs.mask_slot, num_masked)
                     launch(bufs, ws, None)                       # eager once: every lazy allocation inside the library happens here
                     torch.cuda.synchronize(dev)
                     g = torch.cuda.CUDAGraph()
@@ -767,11 +751,11 @@ class FusedSampler:
             if defer_status:
                 if getattr(self, "_status_host", None) is None:
                     self._status_host = torch.zeros(1, dtype=torch.int32).pin_memory()
-                _lib.check(L.ehm_gcn_stack_status_async(gcn, self._status_host.data_ptr(), _lib.stream_ptr()), "ehm_gcn_stack_status_async")
+                A.ehm_gcn_stack_status_async(gcn, self._status_host.data_ptr(), _lib.stream_ptr())
                 self._status_event = torch.cuda.Event()
                 self._status_event.record()
             else:
-                _lib.check(L.ehm_gcn_stack_status(gcn, _lib.stream_ptr()), "ehm_gcn_stack_status")
+                A.ehm_gcn_stack_status(gcn, _lib.stream_ptr())
                 m.backbone.check_status()                 # (the stream has been waited for: the trunk's stream-K time-out word is there)
         # ddim_sample_with_grad hands out the GUIDED x0 of its last step as pred_xstart (gaussian_diffusion.py:587-592) while other_outputs keep the model's own;
         # that step has alpha_bar_prev = 1, so its sample IS the guided x0 (x0g * 1 + 0 * eps)
@@ -789,4 +773,4 @@ class FusedSampler:
         if int(self._status_host[0]) != 0:
             self._status_host.zero_()
             with torch.cuda.device(self.model.device):
-                _lib.check(_lib.lib().ehm_gcn_stack_status(self.gcn(), _lib.stream_ptr()), "ehm_gcn_stack_status")
+                _lib.api().ehm_gcn_stack_status(self.gcn(), _lib.stream_ptr())

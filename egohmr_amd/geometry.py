@@ -22,7 +22,7 @@ class _Rot6dToRotmat(torch.autograd.Function):
         n = x.shape[0]
         R = torch.empty(n, 3, 3, device=x.device, dtype=torch.float32)
         with _lib.on_device(x.device):
-            _lib.check(_lib.lib().ehm_rot6d_to_rotmat(_lib.ptr(x), _lib.ptr(R), n, mode, _lib.stream_ptr()), "ehm_rot6d_to_rotmat")
+            _lib.api().ehm_rot6d_to_rotmat(x, R, n, mode, _lib.stream_ptr())
         ctx.save_for_backward(x)
         ctx.mode = mode
         return R
@@ -33,8 +33,7 @@ class _Rot6dToRotmat(torch.autograd.Function):
         gR = _lib.f32(gR)
         gx = torch.empty_like(x)
         with _lib.on_device(x.device):
-            _lib.check(_lib.lib().ehm_rot6d_to_rotmat_bwd(_lib.ptr(x), _lib.ptr(gR), _lib.ptr(gx), x.shape[0], ctx.mode,
-                                                          _lib.stream_ptr()), "ehm_rot6d_to_rotmat_bwd")
+            _lib.api().ehm_rot6d_to_rotmat_bwd(x, gR, gx, x.shape[0], ctx.mode, _lib.stream_ptr())
         return gx, None
 
 
@@ -84,7 +83,7 @@ class _RotmatToAngleAxis(torch.autograd.Function):
         n = R.shape[0]
         aa = torch.empty(n, 3, device=R.device, dtype=torch.float32)
         with _lib.on_device(R.device):
-            _lib.check(_lib.lib().ehm_rotmat_to_angle_axis(_lib.ptr(R), _lib.ptr(aa), n, _lib.stream_ptr()), "ehm_rotmat_to_angle_axis")
+            _lib.api().ehm_rotmat_to_angle_axis(R, aa, n, _lib.stream_ptr())
         ctx.save_for_backward(R)
         return aa
 
@@ -94,7 +93,7 @@ class _RotmatToAngleAxis(torch.autograd.Function):
         gaa = _lib.f32(gaa)
         gR = torch.empty_like(R)
         with _lib.on_device(R.device):
-            _lib.check(_lib.lib().ehm_rotmat_to_angle_axis_bwd(_lib.ptr(R), _lib.ptr(gaa), _lib.ptr(gR), R.shape[0], _lib.stream_ptr()), "ehm_rotmat_to_angle_axis_bwd")
+            _lib.api().ehm_rotmat_to_angle_axis_bwd(R, gaa, gR, R.shape[0], _lib.stream_ptr())
         return gR
 
 

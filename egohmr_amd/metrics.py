@@ -25,7 +25,7 @@ def nn_dist2(x: torch.Tensor, y: torch.Tensor, return_idx: bool = False):
     d = torch.empty(B, P1, device=x.device, dtype=torch.float32)
     idx = torch.empty(B, P1, device=x.device, dtype=torch.int32) if return_idx else None
     with torch.cuda.device(x.device):
-        _lib.check(_lib.lib().ehm_nn_dist2(_lib.ptr(x), _lib.ptr(y), _lib.ptr(d), _lib.ptr(idx), B, P1, P2, _lib.stream_ptr()), "ehm_nn_dist2")
+        _lib.api().ehm_nn_dist2(x, y, d, idx, B, P1, P2, _lib.stream_ptr())
     return (d, idx) if return_idx else d
 
 
@@ -97,7 +97,7 @@ def point_errors(pred: torch.Tensor, gt: torch.Tensor, points: int | None = None
                             B, S, P, pred.shape[2], gt.shape[1], int(origin_point))
     import ctypes as C
     with _lib.on_device(dev):
-        _lib.check(_lib.lib().ehm_eval_point_errors(C.byref(d), _lib.stream_ptr()), "ehm_eval_point_errors")
+        _lib.api().ehm_eval_point_errors(C.byref(d), _lib.stream_ptr())
     return {"mean": mean, "vis_sum": vis, "invis_sum": invis, "per_point": pp}
 
 
@@ -135,8 +135,7 @@ def procrustes(pred: torch.Tensor, gt: torch.Tensor, mask=None, aligned: bool = 
     mean, vis, invis = torch.empty(B, S, device=dev), torch.empty(B, S, device=dev), torch.empty(B, S, device=dev)
     m = _mask_u8(mask, B, J, dev)
     with _lib.on_device(dev):
-        _lib.check(_lib.lib().ehm_eval_procrustes(_lib.ptr(pred), _lib.ptr(gt), _lib.ptr(m), _lib.ptr(al), _lib.ptr(pj), _lib.ptr(mean), _lib.ptr(vis), _lib.ptr(invis),
-                                                  B, S, J, _lib.stream_ptr()), "ehm_eval_procrustes")
+        _lib.api().ehm_eval_procrustes(pred, gt, m, al, pj, mean, vis, invis, B, S, J, _lib.stream_ptr())
     return {"aligned": al, "per_joint": pj, "mean": mean, "vis_sum": vis, "invis_sum": invis}
 
 
@@ -159,7 +158,7 @@ def diversity(pred_joints_aligned: torch.Tensor, joint_mask=None, invert: bool =
     sd, apd = torch.empty(B, device=a.device), torch.empty(B, device=a.device)
     m = _mask_u8(joint_mask, B, J, a.device)
     with _lib.on_device(a.device):
-        _lib.check(_lib.lib().ehm_eval_diversity(_lib.ptr(a), _lib.ptr(m), int(bool(invert)), _lib.ptr(sd), _lib.ptr(apd), B, S, J, _lib.stream_ptr()), "ehm_eval_diversity")
+        _lib.api().ehm_eval_diversity(a, m, int(bool(invert)), sd, apd, B, S, J, _lib.stream_ptr())
     return sd, apd
 
 

@@ -15,6 +15,7 @@ denoiser, rot6d->rotmat, SMPL LBS and the sampler update are hand-written HIP ke
 """
 from __future__ import annotations
 
+import ctypes as C
 from types import SimpleNamespace
 
 import numpy as np
@@ -114,14 +115,13 @@ class ModulatedGCN(nn.Module):
     # ------------------------------------------------------------------ native handle (ehm_gcn_create) - shared with FusedSampler.gcn()
     def create_native_handle(self, device):
         """ehm_gcn_create on this module's parameters -> (handle, tensors that must stay alive while it lives).  The caller destroys it."""
-        import ctypes as C
         keep = []
 
         def params(gc, bn):
             def t(x):
                 x = _lib.f32(x, device)
                 keep.append(x)
-                return x.data_ptr()
+                return _lib.ptr(x)
             p = _lib.GConvParams()
             p.W, p.M, p.adj2, p.bias = t(gc.W), t(gc.M), t(gc.adj2), t(gc.bias)
             if bn is not None:
@@ -140,8 +140,7 @@ class ModulatedGCN(nn.Module):
         keep.append(adj)
         h = C.c_void_p()
         with torch.cuda.device(device):
-            _lib.check(_lib.lib().ehm_gcn_create(C.byref(h), _lib.ptr(adj), C.byref(inp), arr, len(hidden), C.byref(outp), self.hid_dim,
-                                                 _lib.stream_ptr()), "ehm_gcn_create")
+            _lib.api().ehm_gcn_create(C.byref(h), adj, C.byref(inp), arr, len(hidden), C.byref(outp), self.hid_dim, _lib.stream_ptr())
         return h, keep
 
     # ------------------------------------------------------------------ the optional non-local block (modulated_gcn.py:93-94, :104-110)
@@ -149,7 +148,6 @@ class ModulatedGCN(nn.Module):
         """The non-local block's two 1x1-conv GEMMs in ehm_conv_nhwc_split's operand format: ([theta | phi | g] weights, scale, bias),
         (W.0 with BatchNorm(eval) folded, scale, bias); re-packed when a parameter of the block changes."""
         import math
-        L = _lib.lib()
         nl = self.non_local
         device = nl.theta.weight.device
         key = tuple((p.data_ptr(), p._version) for p in list(nl.parameters()) + list(nl.buffers()))
@@ -163,7 +161,7 @@ class ModulatedGCN(nn.Module):
                 scale = 2.0 ** math.floor(math.log2(2048.0 / amax)) if amax > 0 else 1.0
                 buf = torch.empty(Co_pad, K, device=device)
                 with torch.cuda.device(device):
-                    _lib.check(L.ehm_split_pack(wp.data_ptr(), buf.data_ptr(), Co_pad, K, K, scale, _lib.stream_ptr()), "ehm_split_pack")
+                    _lib.api().ehm_split_pack(wp, buf, Co_pad, K, K, scale, _lib.stream_ptr())
                 return buf, scale, bias.float().contiguous()
             wqkv = torch.cat([nl.theta.weight, nl.phi.weight, nl.g.weight], 0).flatten(1).float()
             bqkv = torch.cat([nl.theta.bias, nl.phi.bias, nl.g.bias], 0)
@@ -179,20 +177,19 @@ class ModulatedGCN(nn.Module):
         """NONLocalBlock2D on the joint axis (modulated_gcn.py:104-110): [theta|phi|g] as ONE 1x1-conv GEMM and W + BatchNorm(eval,
         folded) + residual as another, both on ehm_conv_nhwc_split (rows = N, H = W = 1); the 24 x 24 softmax attention per body
         in ehm_nonlocal_attention.  X: float32 [rows_pad, hid] -> the same."""
-        import ctypes as C
-        L = _lib.lib()
+        A, P = _lib.api(), _lib.ptr
         nl = self.non_local
         hid, ci = self.hid_dim, nl.inter_channels
         (wq, sq, bq), (wo, so, bo) = self.nonlocal_packed()
         s = _lib.stream_ptr()
         qkv = torch.empty(rows, 3 * ci, device=X.device)
-        d = _lib.ConvDesc(X.data_ptr(), wq.data_ptr(), bq.data_ptr(), None, qkv.data_ptr(), rows, 1, 1, hid, 3 * ci, 1, 1, 1, 0, 0, sq)
-        _lib.check(L.ehm_conv_nhwc_split(C.byref(d), s), "ehm_conv_nhwc_split")
+        d = _lib.ConvDesc(P(X), P(wq), P(bq), None, P(qkv), rows, 1, 1, hid, 3 * ci, 1, 1, 1, 0, 0, sq)
+        A.ehm_conv_nhwc_split(C.byref(d), s)
         y = torch.empty(rows, ci, device=X.device)
-        _lib.check(L.ehm_nonlocal_attention(qkv.data_ptr(), y.data_ptr(), rows // 24, ci, s), "ehm_nonlocal_attention")
+        A.ehm_nonlocal_attention(qkv, y, rows // 24, ci, s)
         Z = torch.zeros(rows_pad, hid, device=X.device)
-        d = _lib.ConvDesc(y.data_ptr(), wo.data_ptr(), bo.data_ptr(), X.data_ptr(), Z.data_ptr(), rows, 1, 1, ci, hid, 1, 1, 1, 0, 0, so)
-        _lib.check(L.ehm_conv_nhwc_split(C.byref(d), s), "ehm_conv_nhwc_split")
+        d = _lib.ConvDesc(P(y), P(wo), P(bo), P(X), P(Z), rows, 1, 1, ci, hid, 1, 1, 1, 0, 0, so)
+        A.ehm_conv_nhwc_split(C.byref(d), s)
         return Z
 
     # ------------------------------------------------------------------ ModulatedGCN.forward on its own (modulated_gcn.py:99-116)
@@ -206,8 +203,10 @@ class ModulatedGCN(nn.Module):
             self._sa_keyfn = _lib.TensorKey(self)
         key = (self._sa_keyfn(), str(device))
         if getattr(self, "_sa_key", None) != key:
-            self._free_standalone()
+            if getattr(self, "_sa", None) is not None:
+                self._sa[0].close()
             h, keep = self.create_native_handle(device)
+            h = _lib.Handle(h, _lib.api().ehm_gcn_destroy, keep)
             W = _lib.f32(self.gconv_input[0].gconv.W.detach(), device)                       # [2, in_dim, hid]
             K = W.shape[1]
             Kp = (K + 31) // 32 * 32
@@ -219,21 +218,9 @@ class ModulatedGCN(nn.Module):
             scale = 2.0 ** math.floor(math.log2(2048.0 / amax)) if amax > 0 else 1.0
             buf = torch.empty(Cop, Kp, device=device)
             with torch.cuda.device(device):
-                _lib.check(_lib.lib().ehm_split_pack(w2.data_ptr(), buf.data_ptr(), Cop, Kp, Kp, scale, _lib.stream_ptr()), "ehm_split_pack")
-            self._sa, self._sa_key = (h, keep, buf, scale, K, Kp), key
+                _lib.api().ehm_split_pack(w2, buf, Cop, Kp, Kp, scale, _lib.stream_ptr())
+            self._sa, self._sa_key = (h, buf, scale, K, Kp), key
         return self._sa
-
-    def _free_standalone(self):
-        sa = getattr(self, "_sa", None)
-        if sa is not None:
-            try:
-                _lib.lib().ehm_gcn_destroy(sa[0])
-            except Exception:
-                pass
-            self._sa = self._sa_key = None
-
-    def __del__(self):
-        self._free_standalone()
 
     @torch.no_grad()
     def forward(self, x):
@@ -243,7 +230,6 @@ class ModulatedGCN(nn.Module):
         BatchNorm, ReLU), the residual blocks as ONE chained launch (ehm_gcn_hidden_stack), the optional non-local block, gconv_output
         (ehm_gcn_output_layer).  EgoHMR.forward / the sampler do NOT come through here: they hoist the step-invariant slices of the input feature
         (FusedSampler.prepare) - this is the module's own call surface for a user who feeds it a full feature tensor, as the reference allows."""
-        import ctypes as C
         if self.training:
             raise NotImplementedError("ModulatedGCN.forward: inference only (BatchNorm in eval mode, no dropout); training is out of scope (SURVEY.md section 2)")
         if not x.is_cuda:
@@ -253,35 +239,35 @@ class ModulatedGCN(nn.Module):
         if self.out_dim != 6:
             raise NotImplementedError("the output-conv kernels are built for out_dim = 6 (the 6-D rotation head, egohmr.py:132)")
         from .fused import PRECISIONS
-        L = _lib.lib()
+        A = _lib.api()
         dev = x.device
         B, hid = x.shape[0], self.hid_dim
         with _lib.on_device(dev):
-            h, _, wbuf, scale, K, Kp = self._standalone(dev)
-            if L.ehm_gcn_get_precision(h) != PRECISIONS[self.precision]:
-                _lib.check(L.ehm_gcn_set_precision(h, PRECISIONS[self.precision]), "ehm_gcn_set_precision")
+            h, wbuf, scale, K, Kp = self._standalone(dev)
+            if A.ehm_gcn_get_precision(h) != PRECISIONS[self.precision]:
+                A.ehm_gcn_set_precision(h, PRECISIONS[self.precision])
             s = _lib.stream_ptr()
             rows = B * 24
             xp = torch.zeros(rows, Kp, device=dev)
             xp[:, :K] = _lib.f32(x).reshape(rows, K)
             pre = torch.empty(rows, 2 * hid, device=dev)
-            d = _lib.ConvDesc(xp.data_ptr(), wbuf.data_ptr(), None, None, pre.data_ptr(), rows, 1, 1, Kp, 2 * hid, 1, 1, 1, 0, 0, scale)
-            _lib.check(L.ehm_conv_nhwc_split(C.byref(d), s), "ehm_conv_nhwc_split")
-            tile = L.ehm_gcn_row_tile()
+            d = _lib.ConvDesc(_lib.ptr(xp), _lib.ptr(wbuf), None, None, _lib.ptr(pre), rows, 1, 1, Kp, 2 * hid, 1, 1, 1, 0, 0, scale)
+            A.ehm_conv_nhwc_split(C.byref(d), s)
+            tile = A.ehm_gcn_row_tile()
             rows_pad = (rows + tile - 1) // tile * tile
             X = [torch.zeros(rows_pad, hid, device=dev) for _ in range(3)]
-            _lib.check(L.ehm_gcn_input_layer_rows(h, pre.data_ptr(), X[0].data_ptr(), B, s), "ehm_gcn_input_layer_rows")
-            bufs = (C.c_void_p * 3)(*[t.data_ptr() for t in X])
+            A.ehm_gcn_input_layer_rows(h, pre, X[0], B, s)
+            bufs = (C.c_void_p * 3)(*map(_lib.ptr, X))
             res = C.c_int(0)
-            _lib.check(L.ehm_gcn_hidden_stack(h, bufs, rows_pad, C.byref(res), s), "ehm_gcn_hidden_stack")
+            A.ehm_gcn_hidden_stack(h, bufs, rows_pad, C.byref(res), s)
             feat = X[res.value]
             if self.nonlocal_layer:
                 if self.precision == "f16":
                     raise _lib.EgoHMRHipError("the optional non-local GCN block runs on float32 features; use precision 'f16x3' or 'f32' with it")
                 feat = self.non_local_native(feat, rows, rows_pad)
             out = torch.empty(B, 144, device=dev)
-            _lib.check(L.ehm_gcn_output_layer(h, feat.data_ptr(), None, out.data_ptr(), B, 1, s), "ehm_gcn_output_layer")
-            _lib.check(L.ehm_gcn_stack_status(h, s), "ehm_gcn_stack_status")
+            A.ehm_gcn_output_layer(h, feat, None, out, B, 1, s)
+            A.ehm_gcn_stack_status(h, s)
         return out.view(B, 24, 6)
 
 
@@ -458,16 +444,13 @@ class EgoHMR(nn.Module):
         joints = torch.empty(B, self.smpl.num_joints_out, 3, device=self.device)
         R = torch.empty(B, 24, 3, 3, device=self.device)
         pose6d = torch.empty(B, 144, device=self.device)
-        _lib.check(_lib.lib().ehm_smpl_forward_rot6d(self.smpl.handle(), _lib.ptr(st.betas), _lib.ptr(x0), _lib.ptr(mean), _lib.ptr(std),
-                                                     _lib.ptr(verts), _lib.ptr(joints), _lib.ptr(R), _lib.ptr(pose6d), None, B,
-                                                     _lib.stream_ptr()), "ehm_smpl_forward_rot6d")
+        _lib.api().ehm_smpl_forward_rot6d(self.smpl.handle(), st.betas, x0, mean, std, verts, joints, R, pose6d, None, B, _lib.stream_ptr())
         batch["vis_mask_smpl"] = st.vis_bool
         return self._pack_output(batch, st, x0, pose6d, R, verts, joints, chk=x_t.contiguous(), chk_rows=1)
 
     def _pack_output(self, batch, st, x0, pose6d, R, verts, joints, chk=None, chk_rows=0, last_noise=None, x_final=None):
         """The output dict of EgoHMR.forward (egohmr.py:283-303) in one launch (ehm_pack_outputs): items with a NaN / Inf in their inputs
         (st.finite) or in a row of `chk` come out as NaN, like the reference's float32 graph gives them."""
-        import ctypes as C
         B, J, dev = x0.shape[0], joints.shape[1], x0.device
         buf = torch.empty(B * (10 + 216 + 5 * J + 4), device=dev)
         cuts, off = [], 0
@@ -475,16 +458,13 @@ class EgoHMR(nn.Module):
             cuts.append(buf[off:off + B * n].view(B, n))
             off += B * n
         betas, go, bp, kp3d, kp2d, focal, center = cuts
-        d = _lib.PackDesc(B=B, J=J, V=verts.shape[1], finite=st.finite.data_ptr(), chk=chk.data_ptr() if chk is not None else None, chk_rows=int(chk_rows),
-                          last_noise=last_noise.data_ptr() if last_noise is not None else None, x_final=x_final.data_ptr() if x_final is not None else None,
-                          x0=x0.data_ptr(), pose6d=pose6d.data_ptr(), R=R.data_ptr(), verts=verts.data_ptr(), joints=joints.data_ptr(),
-                          betas_in=st.betas.data_ptr(), betas_out=betas.data_ptr(), transl=st.transl.data_ptr(), fx=st.fx.data_ptr(), cx=st.cam_cx.data_ptr(),
-                          cy=st.cam_cy.data_ptr(), fx_norm=self.cfg.CAM.FX_NORM_COEFF, global_orient=go.data_ptr(), body_pose=bp.data_ptr(),
-                          kp3d_full=kp3d.data_ptr(), kp2d_full=kp2d.data_ptr(), focal=focal.data_ptr(), center=center.data_ptr(), finite_out=None)
-        for t in (x0, pose6d, R, verts, joints, st.betas, st.transl, st.fx, st.cam_cx, st.cam_cy, st.finite):
-            assert t.is_contiguous()
+        P = _lib.ptr
+        d = _lib.PackDesc(B=B, J=J, V=verts.shape[1], finite=P(st.finite), chk=P(chk), chk_rows=int(chk_rows), last_noise=P(last_noise), x_final=P(x_final),
+                          x0=P(x0), pose6d=P(pose6d), R=P(R), verts=P(verts), joints=P(joints), betas_in=P(st.betas), betas_out=P(betas),
+                          transl=P(st.transl), fx=P(st.fx), cx=P(st.cam_cx), cy=P(st.cam_cy), fx_norm=self.cfg.CAM.FX_NORM_COEFF, global_orient=P(go),
+                          body_pose=P(bp), kp3d_full=P(kp3d), kp2d_full=P(kp2d), focal=P(focal), center=P(center), finite_out=None)
         with _lib.on_device(dev):
-            _lib.check(_lib.lib().ehm_pack_outputs(C.byref(d), _lib.stream_ptr()), "ehm_pack_outputs")
+            _lib.api().ehm_pack_outputs(C.byref(d), _lib.stream_ptr())
         self.scene_pcd_verts = st.scene
         self.input_transl = st.transl
         self.smpl_output = smpl_mod.SMPLOutput(vertices=verts, joints=joints, full_pose=R)

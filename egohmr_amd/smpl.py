@@ -74,8 +74,8 @@ class SMPL(nn.Module):
         bufs = (self.v_template, self.shapedirs, self.posedirs, self.J_regressor, self.lbs_weights)
         key = tuple((b.data_ptr(), b._version) for b in bufs) + (str(self.v_template.device),)   # in-place loads (load_state_dict) re-pack too
         if self._handle is None or self._handle_key != key:
-            self._free()
-            L = _lib.lib()
+            if self._handle is not None:
+                self._handle.close()
             if not self.v_template.is_cuda:
                 raise _lib.EgoHMRHipError("SMPL buffers are on the CPU: move the module to a HIP device (.to('cuda'))")
             par = (C.c_int32 * 24)(*[int(p) for p in self.parents.tolist()])
@@ -83,22 +83,10 @@ class SMPL(nn.Module):
             ext = (C.c_int32 * max(len(idx), 1))(*idx)
             h = C.c_void_p()
             with torch.cuda.device(self.v_template.device):
-                _lib.check(L.ehm_smpl_create(C.byref(h), _lib.ptr(self.v_template), _lib.ptr(self.shapedirs), _lib.ptr(self.posedirs),
-                                             _lib.ptr(self.J_regressor), _lib.ptr(self.lbs_weights), par, ext, self.num_verts,
-                                             len(idx), _lib.stream_ptr()), "ehm_smpl_create")
-            self._handle, self._handle_key = h, key
+                _lib.api().ehm_smpl_create(C.byref(h), self.v_template, self.shapedirs, self.posedirs, self.J_regressor, self.lbs_weights, par, ext,
+                                           self.num_verts, len(idx), _lib.stream_ptr())
+            self._handle, self._handle_key = _lib.Handle(h, _lib.api().ehm_smpl_destroy), key
         return self._handle
-
-    def _free(self):
-        if self._handle is not None:
-            try:
-                _lib.lib().ehm_smpl_destroy(self._handle)
-            except Exception:
-                pass
-            self._handle = None
-
-    def __del__(self):
-        self._free()
 
     # ------------------------------------------------------------------ forward
     def forward(self, betas=None, body_pose=None, global_orient=None, transl=None, return_verts=True,
@@ -119,8 +107,7 @@ class SMPL(nn.Module):
         verts = torch.empty(B, self.num_verts, 3, device=dev, dtype=torch.float32)
         joints = torch.empty(B, self.num_joints_out, 3, device=dev, dtype=torch.float32)
         with torch.cuda.device(dev):
-            _lib.check(_lib.lib().ehm_smpl_forward(self.handle(), _lib.ptr(betas), _lib.ptr(full), _lib.ptr(verts), _lib.ptr(joints),
-                                                   None, B, _lib.stream_ptr()), "ehm_smpl_forward")
+            _lib.api().ehm_smpl_forward(self.handle(), betas, full, verts, joints, None, B, _lib.stream_ptr())
         if transl is not None:
             joints = joints + transl.unsqueeze(1)
             verts = verts + transl.unsqueeze(1)

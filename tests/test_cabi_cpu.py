@@ -76,6 +76,59 @@ def test_cabi_rejects_bad_arguments_without_a_gpu():
     assert L.ehm_sample_workspace_bytes(None, 1024, 6890) == -22
 
 
+def test_checked_view_covers_every_entry_point():
+    """_lib.api(): one checked callable per prototype; the entry points that return a value (not a status) are named once, and a new one has to be
+    classified here."""
+    from egohmr_amd import _lib
+    A = _lib.api()
+    for name in _lib.PROTOTYPES:
+        assert callable(getattr(A, name)), name
+    assert _lib.VALUE_FUNCTIONS == {"ehm_gcn_row_tile", "ehm_gcn_get_precision", "ehm_gcn_activation_group", "ehm_conv_x2_rows",
+                                    "ehm_conv_x2_workspace_bytes", "ehm_sample_workspace_bytes", "ehm_resnet_stem_scratch_bytes"}
+    assert _lib.VALUE_FUNCTIONS <= set(_lib.PROTOTYPES)
+
+
+def test_checked_view_raises_where_the_raw_view_returns():
+    import torch
+    from egohmr_amd import _lib
+    A, L = _lib.api(), _lib.lib()
+    for call, name in ((lambda: A.ehm_gcn_hidden_layer(None, 0, None, None, None, 192, None), "ehm_gcn_hidden_layer"),
+                       (lambda: A.ehm_sample_workspace_bytes(None, 1024, 6890), "ehm_sample_workspace_bytes")):
+        with pytest.raises(_lib.EgoHMRHipError, match=name) as e:
+            call()
+        assert e.value.rc == -22 and e.value.function == name and not isinstance(e.value, _lib.EgoHMRRangeError)
+    assert L.ehm_gcn_hidden_layer(None, 0, None, None, None, 192, None) == -22     # the raw view is unchanged: an rc, never an exception
+    assert A.ehm_gcn_row_tile() == 192
+    # a CPU tensor is refused before the foreign call, as the package's own error (not ctypes.ArgumentError)
+    with pytest.raises(_lib.EgoHMRHipError, match="HIP device"):
+        A.ehm_rot6d_to_rotmat(torch.zeros(4, 6), None, 4, 1, None)
+
+
+def test_handle_destroys_once_and_has_a_unique_serial():
+    import gc
+    from egohmr_amd import _lib
+    destroyed = []
+    h = _lib.Handle(0x1000, destroyed.append, keep=[object()])
+    h.close()
+    h.close()
+    assert destroyed == [0x1000] and h.ptr is None and h.keep == []
+    del h
+    gc.collect()
+    assert destroyed == [0x1000]
+    a, b = _lib.Handle(0x2000, destroyed.append), _lib.Handle(0x2000, destroyed.append)     # same address, two objects
+    assert a.serial != b.serial and b.serial > a.serial
+    del a
+    gc.collect()
+    assert destroyed == [0x1000, 0x2000]                # __del__ closes an open handle
+    b.close()
+
+    def failing(_):
+        raise RuntimeError("library already unloaded")
+    c = _lib.Handle(0x3000, failing)
+    c.__del__()                                         # teardown swallows a failing destroy
+    assert c.ptr is None
+
+
 def test_product_path_fails_loudly_on_cpu_tensors():
     import torch
     from egohmr_amd import _lib

@@ -519,6 +519,15 @@ def test_hip_graph_replay_equals_eager_enqueue():
         for v, x in runs[1:]:
             assert torch.equal(v, runs[0][0]) and torch.equal(x, runs[0][1]), seed
     assert not torch.equal(outs[3][0][0], outs[4][0][0])
+    # an in-place SMPL edit recreates the SMPL handle (its host address may be the destroyed one's): the graph route must capture again
+    model.smpl.v_template.add_(1e-3)
+    verts = {}
+    for mode in (True, False):
+        model.use_hip_graph = mode
+        verts[mode] = model.fused_sampler.run(d, b, noise, ddim=True)["other_outputs"]["pred_vertices"].clone()
+        if mode:
+            assert len(model.fused_sampler._graphs) == 2
+    assert torch.equal(verts[True], verts[False]) and not torch.equal(verts[False], outs[4][0][0])
 
 
 @pytest.mark.gpu
