@@ -16,6 +16,7 @@ _LAZY = {
     "rot6d_to_rotmat": ("geometry", "rot6d_to_rotmat"),
     "rotmat_to_rot6d": ("geometry", "rotmat_to_rot6d"),
     "EgoHMRHipError": ("_lib", "EgoHMRHipError"),
+    "ProHMRSceneTransl": ("stage1", "ProHMRSceneTransl"),
 }
 
 
@@ -24,7 +25,7 @@ def __getattr__(name):
         import importlib
         mod, attr = _LAZY[name]
         return getattr(importlib.import_module(f"{__name__}.{mod}"), attr)
-    if name in ("smpl", "synthetic", "diffusion", "model", "geometry", "dist", "_lib", "encoders"):
+    if name in ("smpl", "synthetic", "diffusion", "model", "geometry", "dist", "_lib", "encoders", "stage1"):
         import importlib
         return importlib.import_module(f"{__name__}.{name}")
     raise AttributeError(name)

@@ -28,7 +28,7 @@ _HERE = os.path.dirname(os.path.abspath(__file__))
 LIB_PATH = os.environ.get("EHM_LIB_PATH") or os.path.join(_HERE, "libegohmr_hip.so")   # EHM_LIB_PATH: A/B a second build (experiments)
 CSRC = os.path.join(_HERE, "csrc")
 INCLUDE = os.path.join(os.path.dirname(_HERE), "include")
-SOURCES = ["gcn.hip", "gcn_tile.hip", "linear.hip", "conv.hip", "stem.hip", "metrics.hip", "smpl.hip", "sampler.hip", "guidance.hip", "prep.hip", "step.hip", "eval.hip"]
+SOURCES = ["gcn.hip", "gcn_tile.hip", "linear.hip", "conv.hip", "stem.hip", "metrics.hip", "smpl.hip", "sampler.hip", "guidance.hip", "prep.hip", "step.hip", "eval.hip", "stage1.hip"]
 
 
 class EgoHMRHipError(RuntimeError):
@@ -183,6 +183,15 @@ class SampleDesc(C.Structure):
                 ("num_scene_points", C.c_int), ("guide_denom", C.c_float), ("tau", C.c_float), ("num_masked", C.c_int), ("guide_all_points", C.c_int), ("lowprec_steps", C.c_int), ("nonlocal_ci", C.c_int), ("per_step_launches", C.c_int)]
 
 
+class Stage1Desc(C.Structure):
+    """ehm_stage1_desc"""
+    _fields_ = [("img_feats", C.c_void_p), ("scene_feats", C.c_void_p), ("fx", C.c_void_p), ("cam_cx", C.c_void_p), ("cam_cy", C.c_void_p),
+                ("box_center", C.c_void_p), ("box_size", C.c_void_p), ("W1t", C.c_void_p), ("b1", C.c_void_p), ("W2", C.c_void_p), ("b2", C.c_void_p),
+                ("init_cam", C.c_void_p), ("init_betas", C.c_void_p), ("pred_cam", C.c_void_p), ("pred_cam_full", C.c_void_p), ("pred_betas", C.c_void_p),
+                ("fx_norm", C.c_float), ("crop_res", C.c_float), ("with_cam_center", C.c_int), ("with_bbox_info", C.c_int), ("with_focal_length", C.c_int),
+                ("img_dim", C.c_int), ("scene_dim", C.c_int), ("hidden", C.c_int), ("B", C.c_int)]
+
+
 _P, _I, _L, _F = C.c_void_p, C.c_int, C.c_int64, C.c_float
 
 # name -> (restype, argtypes); every symbol include/egohmr_hip.h declares
@@ -240,7 +249,9 @@ PROTOTYPES = {
     "ehm_nn_dist2": (_I, [_P, _P, _P, _P, _I, _I, _I, _P]),
     "ehm_eval_point_errors": (_I, [C.POINTER(EvalPointsDesc), _P]),
     "ehm_eval_procrustes": (_I, [_P, _P, _P, _P, _P, _P, _P, _P, _I, _I, _I, _P]),
+    "ehm_eval_procrustes_vis": (_I, [_P, _P, _P, _P, _P, _P, _P, _P, _I, _I, _I, _P]),
     "ehm_eval_diversity": (_I, [_P, _P, _I, _P, _P, _I, _I, _I, _P]),
+    "ehm_stage1_head": (_I, [C.POINTER(Stage1Desc), _P]),
     "ehm_sample_workspace_bytes": (_L, [C.POINTER(SampleDesc), _I, _I]),
     "ehm_sample_loop": (_I, [_P, _P, C.POINTER(SampleDesc), C.POINTER(StepCoefs)] + [_P] * 18 + [_L, _P]),
     "ehm_item_prep": (_I, [C.POINTER(ItemPrepDesc), _P]),

@@ -7,6 +7,7 @@
 //                                  sums over the visible / invisible points (G-MPJPE :399-407, MPJPE :409-417, V2V :441-449)
 //   procrustes                     one thread per (item, sample), float64 in registers as the reference's numpy loop (utils/pose_utils.py:10-66): centred
 //                                  24 x 3 clouds, K = X1^T X2, 3 x 3 SVD by one-sided Jacobi, R = V Z U^T, scale, translation -> per-joint error :419-437
+//   procrustes_vis                 the same solve on clouds whose invisible joints are zeroed (pose_utils.py:75-107, --eval_with_vis_mask_pa), any J
 //   diversity                      one wave per item, lane = joint: unbiased std over the samples and the pairwise-distance sum (:453-494), masked means
 //
 // These are latency-bound reductions over a few MB (the largest, V2V at B x S = 1280 bodies, reads 106 MB once: HBM-bound, ~25 us at 5 TB/s); what the
@@ -282,6 +283,69 @@ __global__ __launch_bounds__(64) void procrustes_kernel(const float* __restrict_
   if (invis_sum) invis_sum[i] = (float)(mask ? s_all - s_vis : 0.0);
 }
 
+// The --eval_with_vis_mask_pa alignment (utils/pose_utils.py:75-107): the same float64 solve as procrustes_kernel on MASKED copies of both clouds - an
+// invisible joint is multiplied by 0, i.e. it stays in the means over all J as a point at the origin - and the similarity applied to the unmasked
+// prediction.  Three passes over the J joints in global memory (means, K / var1, errors): no per-joint arrays, so J is not bounded.
+__global__ __launch_bounds__(64) void procrustes_vis_kernel(const float* __restrict__ pred, const float* __restrict__ gt, const uint8_t* __restrict__ amask,
+                                                            float* __restrict__ aligned, float* __restrict__ per_joint, float* __restrict__ mean,
+                                                            float* __restrict__ vis_sum, float* __restrict__ invis_sum, int n, int S, int J) {
+  const int i = blockIdx.x * 64 + threadIdx.x;
+  if (i >= n) return;
+  const int b = i / S;
+  const float* p = pred + (size_t)i * J * 3;
+  const float* g = gt + (size_t)b * J * 3;
+  const uint8_t* m = amask + (size_t)b * J;
+  double mu1[3] = {0, 0, 0}, mu2[3] = {0, 0, 0};
+  for (int j = 0; j < J; ++j) {
+    const double w = m[j] ? 1.0 : 0.0;
+    for (int c = 0; c < 3; ++c) { mu1[c] += w * (double)p[3 * j + c]; mu2[c] += w * (double)g[3 * j + c]; }
+  }
+  for (int c = 0; c < 3; ++c) { mu1[c] /= J; mu2[c] /= J; }
+  double K[3][3] = {{0, 0, 0}, {0, 0, 0}, {0, 0, 0}}, var1 = 0.0;
+  for (int j = 0; j < J; ++j) {
+    const double w = m[j] ? 1.0 : 0.0;
+    double x1[3], x2[3];
+    for (int c = 0; c < 3; ++c) { x1[c] = w * (double)p[3 * j + c] - mu1[c]; x2[c] = w * (double)g[3 * j + c] - mu2[c]; var1 += x1[c] * x1[c]; }
+    for (int r = 0; r < 3; ++r)
+      for (int c = 0; c < 3; ++c) K[r][c] += x1[r] * x2[c];
+  }
+  double U[3][3], s[3], V[3][3];
+  svd3(K, U, s, V);
+  int mn = 0;                                                                // Z acts on the smallest singular value (see procrustes_kernel)
+  if (s[1] < s[mn]) mn = 1;
+  if (s[2] < s[mn]) mn = 2;
+  const double dsign = det3(U) * det3(V) >= 0.0 ? 1.0 : -1.0;
+  double Rm[3][3], tr = 0.0;
+  for (int r = 0; r < 3; ++r)
+    for (int c = 0; c < 3; ++c) {
+      double acc = 0.0;
+      for (int k = 0; k < 3; ++k) acc += (k == mn ? dsign : 1.0) * V[r][k] * U[c][k];
+      Rm[r][c] = acc;
+    }
+  for (int k = 0; k < 3; ++k) tr += (k == mn ? dsign : 1.0) * s[k];
+  const double scale = tr / var1;                                            // no visible joint: 0 / 0 = NaN, as the reference
+  double t[3];
+  for (int r = 0; r < 3; ++r) t[r] = mu2[r] - scale * (Rm[r][0] * mu1[0] + Rm[r][1] * mu1[1] + Rm[r][2] * mu1[2]);
+  double s_all = 0.0, s_vis = 0.0, s_inv = 0.0;
+  for (int j = 0; j < J; ++j) {
+    double e2 = 0.0;
+    for (int r = 0; r < 3; ++r) {
+      const double h = scale * (Rm[r][0] * (double)p[3 * j] + Rm[r][1] * (double)p[3 * j + 1] + Rm[r][2] * (double)p[3 * j + 2]) + t[r];
+      if (aligned) aligned[((size_t)i * J + j) * 3 + r] = (float)h;
+      const double d = h - (double)g[3 * j + r];
+      e2 += d * d;
+    }
+    const double e = sqrt(e2), w = m[j] ? 1.0 : 0.0;
+    if (per_joint) per_joint[(size_t)i * J + j] = (float)e;
+    s_all += e;
+    s_vis += e * w;                                                          // products, not a branch: a NaN error reaches both sums (test_egohmr.py:433-436)
+    s_inv += e * (1.0 - w);
+  }
+  if (mean) mean[i] = (float)(s_all / J);
+  if (vis_sum) vis_sum[i] = (float)s_vis;
+  if (invis_sum) invis_sum[i] = (float)s_inv;
+}
+
 // ------------------------------------------------------------------------------------------------ diversity
 __global__ __launch_bounds__(64) void diversity_kernel(const float* __restrict__ joints, const uint8_t* __restrict__ mask, int invert, float* __restrict__ std_out,
                                                        float* __restrict__ apd_out, int S, int J) {
@@ -352,6 +416,17 @@ extern "C" int ehm_eval_procrustes(const float* pred, const float* gt, const uin
   const int n = B * S;
   hipLaunchKernelGGL(procrustes_kernel, dim3((unsigned)ceil_div(n, 64)), dim3(64), 0, (hipStream_t)stream, pred, gt, mask, aligned, per_joint, mean, vis_sum,
                      invis_sum, n, S, J);
+  EHM_LAUNCH_CHECK();
+  return 0;
+}
+
+extern "C" int ehm_eval_procrustes_vis(const float* pred, const float* gt, const uint8_t* align_mask, float* aligned, float* per_joint, float* mean,
+                                       float* vis_sum, float* invis_sum, int B, int S, int J, void* stream) {
+  EHM_CHECK_ARG(pred && gt && align_mask && B > 0 && S > 0 && J >= 1 && (aligned || per_joint || mean));
+  EHM_CHECK_ARG((int64_t)B * S <= INT32_MAX);
+  const int n = B * S;
+  hipLaunchKernelGGL(procrustes_vis_kernel, dim3((unsigned)ceil_div(n, 64)), dim3(64), 0, (hipStream_t)stream, pred, gt, align_mask, aligned, per_joint, mean,
+                     vis_sum, invis_sum, n, S, J);
   EHM_LAUNCH_CHECK();
   return 0;
 }

@@ -8,6 +8,8 @@ What it stands in for (test_egohmr.py; argparse, the EgoBody dataloader, open3d 
     :374-505   G-MPJPE / MPJPE / PA-MPJPE / V2V with their visible / invisible splits, std / APD diversity, contact score
     :507-560   the running means the script prints (`error_dict`, `diversity_dict`)
     :672-695   ``results_seed_{seed}.pkl``
+``Stage1Driver`` is the counterpart for the stage-1 script (test_prohmr_scene.py:160-217, 417-426): the body translation of every image into
+``output_prohmr_scene_{model_id}/results.pkl``, which ``--two_stage`` stage-2 runs read.
 Everything stays on the device until ``summary()`` / ``results()``; the reference moves every metric to numpy per batch and runs
 the Procrustes alignment as a CPU loop of numpy SVDs (utils/pose_utils.py).  The S samples of a batch share one conditioning pass
 (``FusedSampler.prepare`` caches it per batch), the reference re-runs ResNet-50 and the PointNet in every denoising step.
@@ -27,8 +29,6 @@ class Stage2Driver:
                  with_coap_grad: bool = False, cond_grad_weight: float = 2.0, eval_coll_loss: bool = False,
                  eval_contact_score: bool = True, eval_with_vis_mask_pa: bool = False, fx_norm_coeff: float = 1500.0,
                  batch_samples: bool = True, two_stage: bool = False):
-        if eval_with_vis_mask_pa:
-            raise NotImplementedError("reconstruction_error_with_vis_mask (utils/pose_utils.py) is not on the default path (test_egohmr.py:76)")
         self.model, self.diffusion = model, diffusion
         self.smpl_neutral, self.smpl_male, self.smpl_female = smpl_neutral, smpl_male, smpl_female
         self.S, self.respacing = int(num_samples), timestep_respacing
@@ -40,6 +40,9 @@ class Stage2Driver:
         # camera-frame translation, results.pkl['pred_cam_full_list'] read by egohmr_amd.io.load_stage1_cam - and the sampler is
         # conditioned on it instead of the ground-truth translation (:243-245)
         self.two_stage = bool(two_stage)
+        # --eval_with_vis_mask_pa (test_egohmr.py:73, default True in the reference's script; False here so that existing results do not change):
+        # PA-MPJPE aligns on the visible joints only (reconstruction_error_with_vis_mask, utils/pose_utils.py:75-126; ehm_eval_procrustes_vis)
+        self.eval_with_vis_mask_pa = bool(eval_with_vis_mask_pa)
         self._acc = {}
         self._lists = {k: [] for k in ("pred_betas", "pred_global_orient", "pred_body_pose", "gt_cam_full", "pred_cam_full", "coll", "contact")}
         self._vis_counts = dict(joint_vis=0, joint_invis=0, vertex_vis=0, vertex_invis=0)
@@ -128,7 +131,8 @@ class Stage2Driver:
         for k, r in (("g_mpjpe", M.point_errors(p["joints_full"], g["joints"], points=24, mask=jvis)),                       # :399
                      ("mpjpe", M.point_errors(p["joints_align"], g["joints_align"], points=24, mask=jvis)),                  # :409
                      ("v2v", M.point_errors(p["vertices_align"], g["vertices_align"], mask=vvis)),                           # :441
-                     ("pa_mpjpe", M.procrustes(p["joints_align"][:, :, :24].contiguous(), g["joints_align"][:, :24].contiguous(), mask=jvis))):   # :418-431
+                     ("pa_mpjpe", M.procrustes(p["joints_align"][:, :, :24].contiguous(), g["joints_align"][:, :24].contiguous(), mask=jvis,       # :418-437
+                                               align_mask=jvis if self.eval_with_vis_mask_pa else None))):
             res[k], res[k + "_vis_sum"], res[k + "_invis_sum"] = r["mean"], r["vis_sum"], r["invis_sum"]                     # [B,S] each
         if S > 1:                                                                               # :453-494: (std, apd) per joint selection, one launch each
             ja = p["joints_align"][:, :, :24].contiguous()
@@ -181,3 +185,26 @@ class Stage2Driver:
 
     def save(self, save_root: str, model_id: str, seed: int) -> str:
         return eio.save_results(save_root, model_id, seed, self.results())
+
+
+class Stage1Driver:
+    """The translation half of test_prohmr_scene.py: run egohmr_amd.stage1.ProHMRSceneTransl over the stage-1 batches (whole-scene clouds),
+    collect pred_cam_full (:209-217) and write results.pkl (:417-426).  Stage-1 metrics and rendering are out of scope."""
+
+    def __init__(self, model):
+        self.model = model
+        self._cams = []
+
+    @torch.no_grad()
+    def step(self, batch) -> dict:
+        out = self.model(batch)
+        self._cams.append(out["pred_cam_full"])
+        return out
+
+    def results(self) -> dict:
+        """{'pred_cam_full_list': float32 numpy [n, 3]}, n = the images stepped so far, in order."""
+        cam = torch.cat(self._cams, 0) if self._cams else torch.zeros(0, 3)
+        return {"pred_cam_full_list": cam.detach().float().cpu().numpy()}
+
+    def save(self, save_root: str, model_id: str) -> str:
+        return eio.save_stage1_results(save_root, model_id, self.results()["pred_cam_full_list"])

@@ -5,6 +5,7 @@
 * mpjpe / g_mpjpe / v2v                test_egohmr.py:399-443           -> ehm_eval_point_errors (csrc/eval.hip)
 * pa_mpjpe (batched Procrustes)        utils/pose_utils.py:10-66, :109-126 (the reference loops numpy SVDs per sample on the CPU)
                                        -> ehm_eval_procrustes: float64 in registers, 3 x 3 SVD by one-sided Jacobi, one thread per sample
+  (visible-joint alignment)            utils/pose_utils.py:75-107       -> ehm_eval_procrustes_vis (align_mask=)
 * std_diversity / apd                  test_egohmr.py:453-494           -> ehm_eval_diversity (one wave per item)
 Every function here is a launch of a hand-written kernel; CPU tensors raise (the CPU restatement is oracle/metrics.py, test infrastructure).
 """
@@ -124,18 +125,25 @@ def v2v(pred_vertices: torch.Tensor, pred_pelvis, gt_vertices: torch.Tensor, gt_
     return point_errors(p, g, pred_origin=po, gt_origin=go)["mean"].reshape(lead)
 
 
-def procrustes(pred: torch.Tensor, gt: torch.Tensor, mask=None, aligned: bool = False, per_joint: bool = False) -> dict:
-    """ehm_eval_procrustes (csrc/eval.hip): utils/pose_utils.py:10-66 batched - pred [B,S,J,3] against gt [B,J,3], float64 inside the kernel."""
+def procrustes(pred: torch.Tensor, gt: torch.Tensor, mask=None, aligned: bool = False, per_joint: bool = False, align_mask=None) -> dict:
+    """ehm_eval_procrustes (csrc/eval.hip): utils/pose_utils.py:10-66 batched - pred [B,S,J,3] against gt [B,J,3], float64 inside the kernel.
+    align_mask [B,J]: the visible-joint alignment of --eval_with_vis_mask_pa instead (ehm_eval_procrustes_vis, pose_utils.py:75-107): invisible
+    joints of both clouds enter the solve as points at the origin, the error is taken over all J, and the same mask splits vis_sum / invis_sum
+    (test_egohmr.py:427-437) - `mask` must then be None or that same tensor.  An item without a visible joint gives NaN, as the reference."""
     pred, gt = _f32c(pred), _f32c(gt)
     B, S, J = pred.shape[0], pred.shape[1], pred.shape[2]
     assert gt.shape == (B, J, 3), (tuple(pred.shape), tuple(gt.shape))
+    if align_mask is not None and mask is not None and mask is not align_mask:
+        raise ValueError("procrustes(align_mask=...) splits the sums by the alignment mask: pass mask=None or the same tensor")
     dev = pred.device
     al = torch.empty(B, S, J, 3, device=dev) if aligned else None
     pj = torch.empty(B, S, J, device=dev) if per_joint else None
     mean, vis, invis = torch.empty(B, S, device=dev), torch.empty(B, S, device=dev), torch.empty(B, S, device=dev)
-    m = _mask_u8(mask, B, J, dev)
     with _lib.on_device(dev):
-        _lib.api().ehm_eval_procrustes(pred, gt, m, al, pj, mean, vis, invis, B, S, J, _lib.stream_ptr())
+        if align_mask is not None:
+            _lib.api().ehm_eval_procrustes_vis(pred, gt, _mask_u8(align_mask, B, J, dev), al, pj, mean, vis, invis, B, S, J, _lib.stream_ptr())
+        else:
+            _lib.api().ehm_eval_procrustes(pred, gt, _mask_u8(mask, B, J, dev), al, pj, mean, vis, invis, B, S, J, _lib.stream_ptr())
     return {"aligned": al, "per_joint": pj, "mean": mean, "vis_sum": vis, "invis_sum": invis}
 
 

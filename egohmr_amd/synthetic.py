@@ -218,6 +218,35 @@ def egohmr_manifest(hid_dim: int = 1024, num_blocks: int = 4, scene_feat_dim: in
     return m
 
 
+def stage1_context_dim(with_focal_length: bool = True, with_bbox_info: bool = True, with_cam_center: bool = True, img_feat_dim: int = 2048,
+                       scene_feat_dim: int = 512) -> int:
+    """Width of the stage-1 context (models/prohmr/prohmr_scene.py:36-45): 2048 + 512 + 1 (fx) + 3 (bbox) + 2 (centre) with every flag on."""
+    return img_feat_dim + scene_feat_dim + (1 if with_focal_length else 0) + (3 if with_bbox_info else 0) + (2 if with_cam_center else 0)
+
+
+def stage1_manifest(with_focal_length: bool = True, with_bbox_info: bool = True, with_cam_center: bool = True, scene_feat_dim: int = 512) -> list:
+    """(name, shape) of what the stage-1 translation reads from a ProHMR-scene checkpoint: ``backbone.*`` and ``scene_enc.*`` (the names of
+    egohmr_manifest) and the FCHead of the flow, ``flow.fc_head.*`` (models/prohmr/fc_head.py:19-29)."""
+    ctx = stage1_context_dim(with_focal_length, with_bbox_info, with_cam_center, scene_feat_dim=scene_feat_dim)
+    m = [e for e in egohmr_manifest(scene_feat_dim=scene_feat_dim) if e[0].startswith(("backbone.", "scene_enc."))]
+    return m + [("flow.fc_head.layers.0.weight", (1024, ctx)), ("flow.fc_head.layers.0.bias", (1024,)),
+                ("flow.fc_head.layers.2.weight", (13, 1024)), ("flow.fc_head.layers.2.bias", (13,)),
+                ("flow.fc_head.init_cam", (1, 1, 3)), ("flow.fc_head.init_betas", (1, 1, 10))]
+
+
+def make_stage1_state_dict(seed: int = 0, head_gain: float = 0.04, **flags) -> dict:
+    """Seeded weights for every name of :func:`stage1_manifest`.  The head's last layer is N(0, head_gain / sqrt(1024)) - about 1.4 x the std of
+    the reference's xavier init with gain 0.02 (fc_head.py:23) - so that it moves the camera by a tenth or two of the scale s on these features
+    (s stays near 0.7 - 0.9), and init_cam = [0.9, 0, 0] + small noise like a smpl_mean_params.npz 'cam'."""
+    man = stage1_manifest(**flags)
+    sd = make_state_dict(seed, manifest=[e for e in man if not e[0].endswith("init_cam")])
+    g = _rng(6000 + seed)
+    sd["flow.fc_head.layers.2.weight"] = g.normal(scale=head_gain / np.sqrt(1024), size=(13, 1024)).astype(np.float32)
+    sd["flow.fc_head.layers.2.bias"] = g.normal(scale=0.01, size=(13,)).astype(np.float32)
+    sd["flow.fc_head.init_cam"] = (np.array([0.9, 0.0, 0.0]) + g.normal(scale=0.02, size=3)).reshape(1, 1, 3).astype(np.float32)
+    return {k: sd[k] for k, _ in man}
+
+
 def positional_table(max_len: int = 5000, d_model: int = 512) -> np.ndarray:
     """sin/cos table of models/egohmr/egohmr.py:614-619, float32 arithmetic like torch's."""
     position = np.arange(max_len, dtype=np.float32)[:, None]

@@ -387,10 +387,40 @@ int ehm_eval_point_errors(const ehm_eval_points_desc* d, void* stream);
  * each may be NULL (one of aligned / per_joint / mean must not be).  3 <= J <= 32. */
 int ehm_eval_procrustes(const float* pred, const float* gt, const uint8_t* mask, float* aligned, float* per_joint, float* mean, float* vis_sum,
                         float* invis_sum, int B, int S, int J, void* stream);
+/* utils/pose_utils.py:75-107 (compute_similarity_transform_with_vis_mask) + :119-126 as test_egohmr.py:427-437 runs it with --eval_with_vis_mask_pa:
+ * the joints of BOTH clouds that align_mask [B,J] marks invisible are multiplied by 0, not dropped - they stay in the means over all J as points at the
+ * origin, and the centred masked copies give K and var1; the similarity is then applied to the UNMASKED pred[b,s] and the error is taken over all J
+ * against the unmasked gt[b].  align_mask also splits vis_sum / invis_sum (sum of error * mask, error * (1 - mask): a NaN error reaches both, as in the
+ * reference).  No visible joint: var1 = 0 and every output of that item is NaN.  Outputs as ehm_eval_procrustes; any J >= 1 (no per-joint arrays). */
+int ehm_eval_procrustes_vis(const float* pred, const float* gt, const uint8_t* align_mask, float* aligned, float* per_joint, float* mean, float* vis_sum,
+                            float* invis_sum, int B, int S, int J, void* stream);
 /* test_egohmr.py:453-494: sample diversity of joints [B,S,J,3] over the joints selected by mask [B,J] (NULL: all; invert != 0: the unselected ones) -
  * std_out [B] = mean over the selected joints and the 3 coordinates of the unbiased std over the samples; apd_out [B] = sum over ordered sample pairs and
  * selected joints of the joint distance / n_selected / S / (S - 1) / 2 (the reference's normalisation).  No selected joint -> NaN, as the reference. */
 int ehm_eval_diversity(const float* joints, const uint8_t* mask, int invert, float* std_out, float* apd_out, int B, int S, int J, void* stream);
+
+/* ------------------------------------------------------------------ stage 1 (ProHMR-scene) translation ---------- */
+/* The deterministic half of the stage-1 model (models/prohmr/prohmr_scene.py:111-130, fc_head.py:46-50) and the camera conversion of
+ * test_prohmr_scene.py:175-213 (utils/geometry.py:119-131), per item, in one launch:
+ *   ctx = [cam_cx/ofx, cam_cy/ofx | box_center_x/ofx, box_center_y/ofx, box_size/ofx | fx | img_feats | scene_feats],  ofx = fx * fx_norm,
+ *         each of the three leading groups present only with its flag; read in place (no concatenated copy), K = its length
+ *   h = relu(W1 ctx + b1) (hidden = 1024),  off = W2 h + b2 (13),  pred_betas = off[0:10] + init_betas,  pred_cam = off[10:13] + init_cam
+ *   pred_cam_full = convert_pare_to_full_img_cam(pred_cam, box_size, box_center, 2 cam_cx, 2 cam_cy, fx * fx_norm, crop_res)   (s is not clamped)
+ * W1t is nn.Linear's weight TRANSPOSED, [K, hidden] row-major; W2 is [13, hidden] as nn.Linear keeps it.  f32 FMA throughout.
+ * pred_betas may be NULL. */
+typedef struct ehm_stage1_desc {
+  const float* img_feats;    /* [B, img_dim]   */
+  const float* scene_feats;  /* [B, scene_dim] */
+  const float* fx; const float* cam_cx; const float* cam_cy; const float* box_center /* [B,2] */; const float* box_size;   /* [B] each */
+  const float* W1t; const float* b1; const float* W2; const float* b2; const float* init_cam; const float* init_betas;
+  float* pred_cam;           /* [B,3]  */
+  float* pred_cam_full;      /* [B,3]  */
+  float* pred_betas;         /* [B,10] */
+  float fx_norm, crop_res;
+  int with_cam_center, with_bbox_info, with_focal_length;
+  int img_dim, scene_dim, hidden, B;
+} ehm_stage1_desc;
+int ehm_stage1_head(const ehm_stage1_desc* d, void* stream);
 
 /* ------------------------------------------------------------------ per-item scalars ---------- */
 /* The per-item scalar work of EgoHMR.forward in front of the encoders, in two launches:
