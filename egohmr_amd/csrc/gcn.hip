@@ -472,34 +472,51 @@ extern "C" void ehm_gcn_destroy(ehm_gcn* h) {
   delete h;
 }
 
-// fills the launch arguments of the input conv for the handle's current precision / pass map (shared with smpl.hip's fused launch)
-int ehm_gcn_input_args(ehm_gcn* h, const float* h_img, const float* h_oth, const uint8_t* vis, const float* x, const float* Wx, const float* tvec,
-                       float* out, int B, int passes, GcnInputArgs* a) {
+// fills the launch arguments of the input conv for the pass map of `r` (shared with smpl.hip's and step.hip's fused launches)
+int ehm_gcn_input_args(const ehm_gcn* h, const GcnRun& r, const float* h_img, const float* h_oth, const uint8_t* vis, const float* x, const float* Wx,
+                       const float* tvec, float* out, int B, int passes, GcnInputArgs* a) {
   EHM_CHECK_ARG(h && h_img && h_oth && vis && x && Wx && tvec && out && a);
   EHM_CHECK_ARG(B > 0 && (passes == 1 || passes == 2));
   a->h_img = h_img; a->h_oth = h_oth; a->vis = vis; a->x = x; a->Wx = Wx; a->tvec = tvec;
   a->L = h->input;
   a->Y = out;
-  a->B = B; a->passes = passes; a->mask_all = h->uncond_masks_all;
-  a->mask_items = (passes == 2 && h->num_masked >= 0) ? h->mask_items : nullptr;
+  a->B = B; a->passes = passes; a->mask_all = r.uncond_masks_all;
+  a->mask_items = r.items(passes);
   a->sticky = h->chain_sticky;
-  a->total_vb = ehm_gcn_virtual_bodies(h, B, passes);
-  h->valid_rows = (int64_t)a->total_vb * kJ;
+  a->total_vb = r.virtual_bodies(B, passes);
   a->ny = (int)ceil_div(h->hid, 256);
   return 0;
 }
 
-extern "C" int ehm_gcn_input_layer(ehm_gcn* h, const float* h_img, const float* h_oth, const uint8_t* vis, const float* x,
-                                   const float* Wx, const float* tvec, float* out, int B, int passes, void* stream) {
-  GcnInputArgs a;
-  const int rc = ehm_gcn_input_args(h, h_img, h_oth, vis, x, Wx, tvec, out, B, passes, &a);
-  if (rc != 0) return rc;
-  dim3 grid((unsigned)a.total_vb, (unsigned)a.ny);
-  if (h->precision == EHM_PREC_F32) hipLaunchKernelGGL(gcn_input_kernel<0>, grid, dim3(256), 0, (hipStream_t)stream, a);
-  else if (h->precision == EHM_PREC_F16X3) hipLaunchKernelGGL(gcn_input_kernel<1>, grid, dim3(256), 0, (hipStream_t)stream, a);   // X2 split rows
-  else hipLaunchKernelGGL(gcn_input_kernel<2>, grid, dim3(256), 0, (hipStream_t)stream, a);                                        // plain f16 rows
+template <bool PRE, int OUT>
+static void launch_input_conv(const GcnInputArgs& a, hipStream_t st) {
+  const dim3 grid((unsigned)a.total_vb, (unsigned)a.ny);
+  if constexpr (PRE) hipLaunchKernelGGL(gcn_input_rows_kernel<OUT>, grid, dim3(256), 0, st, a);
+  else hipLaunchKernelGGL(gcn_input_kernel<OUT>, grid, dim3(256), 0, st, a);
+}
+// the input conv (PRE: on the pre-activations a.pre), its rows in the activation format of `prec`
+template <bool PRE>
+static int input_conv(const GcnInputArgs& a, int prec, hipStream_t st) {
+  if (prec == EHM_PREC_F32) launch_input_conv<PRE, 0>(a, st);
+  else if (prec == EHM_PREC_F16X3) launch_input_conv<PRE, 1>(a, st);   // X2 split rows
+  else launch_input_conv<PRE, 2>(a, st);                                // plain f16 rows
   EHM_LAUNCH_CHECK();
   return 0;
+}
+
+int ehm_gcn_input_impl(const ehm_gcn* h, const GcnRun& r, const float* h_img, const float* h_oth, const uint8_t* vis, const float* x,
+                       const float* Wx, const float* tvec, float* out, int B, int passes, hipStream_t st) {
+  GcnInputArgs a;
+  const int rc = ehm_gcn_input_args(h, r, h_img, h_oth, vis, x, Wx, tvec, out, B, passes, &a);
+  return rc != 0 ? rc : input_conv<false>(a, r.precision, st);
+}
+
+extern "C" int ehm_gcn_input_layer(ehm_gcn* h, const float* h_img, const float* h_oth, const uint8_t* vis, const float* x,
+                                   const float* Wx, const float* tvec, float* out, int B, int passes, void* stream) {
+  EHM_CHECK_ARG(h);
+  const int rc = ehm_gcn_input_impl(h, h->run, h_img, h_oth, vis, x, Wx, tvec, out, B, passes, (hipStream_t)stream);
+  if (rc == 0) h->run.valid_rows = (int64_t)h->run.virtual_bodies(B, passes) * kJ;
+  return rc;
 }
 
 extern "C" int ehm_gcn_input_layer_rows(ehm_gcn* h, const float* pre, float* out, int bodies, void* stream) {
@@ -512,52 +529,56 @@ extern "C" int ehm_gcn_input_layer_rows(ehm_gcn* h, const float* pre, float* out
   a.total_vb = bodies;
   a.ny = (int)ceil_div(h->hid, 256);
   a.sticky = h->chain_sticky;
-  h->valid_rows = (int64_t)bodies * kJ;
+  h->run.valid_rows = (int64_t)bodies * kJ;
   a.pre = pre;
-  dim3 grid((unsigned)a.total_vb, (unsigned)a.ny);
-  if (h->precision == EHM_PREC_F32) hipLaunchKernelGGL(gcn_input_rows_kernel<0>, grid, dim3(256), 0, (hipStream_t)stream, a);
-  else if (h->precision == EHM_PREC_F16X3) hipLaunchKernelGGL(gcn_input_rows_kernel<1>, grid, dim3(256), 0, (hipStream_t)stream, a);
-  else hipLaunchKernelGGL(gcn_input_rows_kernel<2>, grid, dim3(256), 0, (hipStream_t)stream, a);
+  return input_conv<true>(a, h->run.precision, (hipStream_t)stream);
+}
+
+static int hidden_layer(const ehm_gcn* h, const GcnRun& r, int layer, const float* X, const float* residual, float* out, int64_t rows_pad,
+                        hipStream_t st) {
+  EHM_CHECK_ARG(X && out);
+  EHM_CHECK_ARG(layer >= 0 && layer < h->num_hidden);
+  EHM_CHECK_ARG(rows_pad > 0 && rows_pad % BM == 0);
+  EHM_CHECK_ARG(X != out);
+  if (r.precision != EHM_PREC_F32)   // X / residual / out in the mode's activation format, except that in mode 1 the last hidden conv writes float32 for the output conv
+    return ehm_gcn_tile_layer_impl(h, r, layer, X, residual, out, rows_pad, layer == h->num_hidden - 1, st);
+  const int m_tiles = (int)(rows_pad / BM);
+  const int blocks = m_tiles * (h->hid / BNH);
+  if (residual)
+    hipLaunchKernelGGL(gcn_hidden_kernel<true>, dim3(blocks), dim3(256), 0, st, X, h->hidden[layer], residual, out, m_tiles);
+  else
+    hipLaunchKernelGGL(gcn_hidden_kernel<false>, dim3(blocks), dim3(256), 0, st, X, h->hidden[layer], (const float*)nullptr, out, m_tiles);
   EHM_LAUNCH_CHECK();
   return 0;
 }
 
 extern "C" int ehm_gcn_hidden_layer(ehm_gcn* h, int layer, const float* X, const float* residual, float* out,
                                     int64_t rows_pad, void* stream) {
-  EHM_CHECK_ARG(h && X && out);
-  EHM_CHECK_ARG(layer >= 0 && layer < h->num_hidden);
-  EHM_CHECK_ARG(rows_pad > 0 && rows_pad % BM == 0);
-  EHM_CHECK_ARG(X != out);
-  if (h->precision != EHM_PREC_F32)   // X / residual / out in the mode's activation format, except that in mode 1 the last hidden conv writes float32 for the output conv
-    return ehm_gcn_tile_layer_impl(h, layer, X, residual, out, rows_pad, layer == h->num_hidden - 1, (hipStream_t)stream);
-  const int m_tiles = (int)(rows_pad / BM);
-  const int blocks = m_tiles * (h->hid / BNH);
-  if (residual)
-    hipLaunchKernelGGL(gcn_hidden_kernel<true>, dim3(blocks), dim3(256), 0, (hipStream_t)stream, X, h->hidden[layer], residual,
-                       out, m_tiles);
-  else
-    hipLaunchKernelGGL(gcn_hidden_kernel<false>, dim3(blocks), dim3(256), 0, (hipStream_t)stream, X, h->hidden[layer],
-                       (const float*)nullptr, out, m_tiles);
-  EHM_LAUNCH_CHECK();
-  return 0;
+  EHM_CHECK_ARG(h);
+  return hidden_layer(h, h->run, layer, X, residual, out, rows_pad, (hipStream_t)stream);
 }
 
-extern "C" int ehm_gcn_hidden_stack(ehm_gcn* h, float* const bufs[3], int64_t rows_pad, int* result_index, void* stream) {
+int ehm_gcn_hidden_stack_impl(ehm_gcn* h, const GcnRun& r, float* const bufs[3], int64_t rows_pad, int* result_index, hipStream_t st) {
   EHM_CHECK_ARG(h && bufs && bufs[0] && bufs[1] && bufs[2] && result_index && rows_pad > 0 && rows_pad % BM == 0);
   EHM_CHECK_ARG(h->num_hidden % 2 == 0);
   const int nblk = h->num_hidden / 2;
   *result_index = (nblk & 1) ? 2 : 0;
   if (nblk == 0) return 0;
-  if (h->chain && h->precision != EHM_PREC_F32) return ehm_gcn_tile_chain_impl(h, (void* const*)bufs, rows_pad, (hipStream_t)stream);
+  if (h->chain && r.precision != EHM_PREC_F32) return ehm_gcn_tile_chain_impl(h, r, (void* const*)bufs, rows_pad, st);
   int in = 0;
   for (int blk = 0; blk < nblk; ++blk) {     // the same buffer rotation, one launch per conv
     const int y2 = in == 0 ? 2 : 0;
-    int rc = ehm_gcn_hidden_layer(h, 2 * blk, bufs[in], nullptr, bufs[1], rows_pad, stream);
-    if (rc == 0) rc = ehm_gcn_hidden_layer(h, 2 * blk + 1, bufs[1], bufs[in], bufs[y2], rows_pad, stream);
+    int rc = hidden_layer(h, r, 2 * blk, bufs[in], nullptr, bufs[1], rows_pad, st);
+    if (rc == 0) rc = hidden_layer(h, r, 2 * blk + 1, bufs[1], bufs[in], bufs[y2], rows_pad, st);
     if (rc != 0) return rc;
     in = y2;
   }
   return 0;
+}
+
+extern "C" int ehm_gcn_hidden_stack(ehm_gcn* h, float* const bufs[3], int64_t rows_pad, int* result_index, void* stream) {
+  EHM_CHECK_ARG(h);
+  return ehm_gcn_hidden_stack_impl(h, h->run, bufs, rows_pad, result_index, (hipStream_t)stream);
 }
 
 extern "C" int ehm_gcn_stack_status(ehm_gcn* h, void* stream) {
@@ -615,37 +636,38 @@ extern "C" int ehm_gcn_reserve(ehm_gcn* h, int max_bodies, int passes) {
   return ehm_gcn_reserve_rows(h, round_up((int64_t)max_bodies * passes * kJ, BM));
 }
 
-extern "C" int ehm_gcn_output_layer(ehm_gcn* h, const float* X, const uint8_t* vis, float* x0, int B, int passes,
-                                    void* stream) {
-  EHM_CHECK_ARG(h && X && x0);
-  EHM_CHECK_ARG(B > 0 && (passes == 1 || (passes == 2 && vis)));
-  const int64_t rows = (int64_t)ehm_gcn_virtual_bodies(h, B, passes) * kJ;
+int ehm_gcn_output_dot_impl(ehm_gcn* h, const GcnRun& r, const float* X, int B, int passes, const float** hs, hipStream_t st) {
+  const int64_t rows = (int64_t)r.virtual_bodies(B, passes) * kJ;
   if (rows > h->hs_rows) {      // [rows,12] scratch of the two-kernel output conv: sized by ehm_gcn_create / ehm_gcn_reserve, grown here only
     const int rc = ehm_gcn_reserve_rows(h, round_up(rows, BM));   // for a batch larger than reserved (allocates: call ehm_gcn_reserve before a capture)
     if (rc != 0) return rc;
   }
-  if (h->precision == EHM_PREC_F16)
-    hipLaunchKernelGGL(gcn_out_dot_kernel<true>, dim3((unsigned)ceil_div(rows, OUT_ROWS_PER_BLOCK)), dim3(256), 0, (hipStream_t)stream, X, h->out,
-                       h->hs, rows);
+  if (r.precision == EHM_PREC_F16)
+    hipLaunchKernelGGL(gcn_out_dot_kernel<true>, dim3((unsigned)ceil_div(rows, OUT_ROWS_PER_BLOCK)), dim3(256), 0, st, X, h->out, h->hs, rows);
   else
-    hipLaunchKernelGGL(gcn_out_dot_kernel<false>, dim3((unsigned)ceil_div(rows, OUT_ROWS_PER_BLOCK)), dim3(256), 0, (hipStream_t)stream, X, h->out,
-                       h->hs, rows);
-  hipLaunchKernelGGL(gcn_out_mix_kernel, dim3(B), dim3(192), 0, (hipStream_t)stream, h->hs, h->out, vis, x0, B, passes,
-                     (passes == 2 && h->num_masked >= 0) ? h->mask_slot : nullptr);
+    hipLaunchKernelGGL(gcn_out_dot_kernel<false>, dim3((unsigned)ceil_div(rows, OUT_ROWS_PER_BLOCK)), dim3(256), 0, st, X, h->out, h->hs, rows);
+  EHM_LAUNCH_CHECK();
+  *hs = h->hs;
+  return 0;
+}
+
+extern "C" int ehm_gcn_output_layer(ehm_gcn* h, const float* X, const uint8_t* vis, float* x0, int B, int passes,
+                                    void* stream) {
+  EHM_CHECK_ARG(h && X && x0);
+  EHM_CHECK_ARG(B > 0 && (passes == 1 || (passes == 2 && vis)));
+  const float* hs;
+  const int rc = ehm_gcn_output_dot_impl(h, h->run, X, B, passes, &hs, (hipStream_t)stream);
+  if (rc != 0) return rc;
+  hipLaunchKernelGGL(gcn_out_mix_kernel, dim3(B), dim3(192), 0, (hipStream_t)stream, hs, h->out, vis, x0, B, passes, h->run.slots(passes));
   EHM_LAUNCH_CHECK();
   return 0;
 }
 
-int ehm_gcn_virtual_bodies(const ehm_gcn* h, int B, int passes) {
-  return passes == 2 ? B + (h->num_masked >= 0 ? h->num_masked : B) : B;
-}
-const int32_t* ehm_gcn_mask_slot(const ehm_gcn* h, int passes) { return (passes == 2 && h->num_masked >= 0) ? h->mask_slot : nullptr; }
-
 extern "C" int ehm_gcn_set_pass_map(ehm_gcn* h, const int32_t* mask_items, const int32_t* mask_slot, int num_masked) {
   EHM_CHECK_ARG(h && (num_masked < 0 || (mask_slot && (num_masked == 0 || mask_items))));
-  h->mask_items = num_masked >= 0 ? mask_items : nullptr;
-  h->mask_slot = num_masked >= 0 ? mask_slot : nullptr;
-  h->num_masked = num_masked < 0 ? -1 : num_masked;
+  h->run.mask_items = num_masked >= 0 ? mask_items : nullptr;
+  h->run.mask_slot = num_masked >= 0 ? mask_slot : nullptr;
+  h->run.num_masked = num_masked < 0 ? -1 : num_masked;
   return 0;
 }
 
@@ -656,39 +678,16 @@ extern "C" int ehm_gcn_set_nonlocal(ehm_gcn* h, const ehm_nonlocal_params* p) {
   h->nonlocal = *p;
   return 0;
 }
-int ehm_gcn_nonlocal_ci(const ehm_gcn* h) { return h->nonlocal.Ci; }
-const ehm_nonlocal_params* ehm_gcn_nonlocal(const ehm_gcn* h) { return &h->nonlocal; }
-
-int ehm_gcn_output_dot_impl(ehm_gcn* h, const float* X, int B, int passes, const float** hs, const void** out_dev, hipStream_t st) {
-  const int64_t rows = (int64_t)ehm_gcn_virtual_bodies(h, B, passes) * kJ;
-  if (rows > h->hs_rows) {
-    const int rc = ehm_gcn_reserve_rows(h, round_up(rows, BM));
-    if (rc != 0) return rc;
-  }
-  if (h->precision == EHM_PREC_F16)
-    hipLaunchKernelGGL(gcn_out_dot_kernel<true>, dim3((unsigned)ceil_div(rows, OUT_ROWS_PER_BLOCK)), dim3(256), 0, st, X, h->out, h->hs, rows);
-  else
-    hipLaunchKernelGGL(gcn_out_dot_kernel<false>, dim3((unsigned)ceil_div(rows, OUT_ROWS_PER_BLOCK)), dim3(256), 0, st, X, h->out, h->hs, rows);
-  EHM_LAUNCH_CHECK();
-  *hs = h->hs;
-  *out_dev = &h->out;
-  return 0;
-}
-
-const void* ehm_gcn_out_dev(const ehm_gcn* h) { return &h->out; }
-int ehm_gcn_hid(const ehm_gcn* h) { return h->hid; }
-int ehm_gcn_num_hidden(const ehm_gcn* h) { return h->num_hidden; }
-int ehm_gcn_chain_enabled(const ehm_gcn* h) { return h->chain != 0 && h->precision != EHM_PREC_F32; }
 
 extern "C" int ehm_gcn_set_precision(ehm_gcn* h, int mode) {
   EHM_CHECK_ARG(h && (mode == EHM_PREC_F32 || mode == EHM_PREC_F16X3 || mode == EHM_PREC_F16));
-  h->precision = mode;
+  h->run.precision = mode;
   return 0;
 }
-extern "C" int ehm_gcn_get_precision(const ehm_gcn* h) { return h ? h->precision : EHM_EINVAL; }
+extern "C" int ehm_gcn_get_precision(const ehm_gcn* h) { return h ? h->run.precision : EHM_EINVAL; }
 extern "C" int ehm_gcn_set_uncond_mode(ehm_gcn* h, int masks_whole_condition) {
   EHM_CHECK_ARG(h && (masks_whole_condition == 0 || masks_whole_condition == 1));
-  h->uncond_masks_all = masks_whole_condition;
+  h->run.uncond_masks_all = masks_whole_condition;
   return 0;
 }
-extern "C" int ehm_gcn_activation_group(const ehm_gcn* h) { return h ? (h->precision == EHM_PREC_F16 ? 0 : 32) : EHM_EINVAL; }
+extern "C" int ehm_gcn_activation_group(const ehm_gcn* h) { return h ? (h->run.precision == EHM_PREC_F16 ? 0 : 32) : EHM_EINVAL; }

@@ -41,20 +41,31 @@ struct OutDev {
 
 enum { EHM_PREC_F32 = 0, EHM_PREC_F16X3 = 1, EHM_PREC_F16 = 2 };
 
-struct ehm_gcn {
-  int hid = 0;
-  int num_hidden = 0;
+// What a GCN call runs with besides the weights, an argument of every internal function: the extern "C" entry points pass the handle's
+// ehm_gcn::run (ehm_gcn_set_precision / _set_pass_map / _set_uncond_mode), the sampling loop a copy per step.
+struct GcnRun {
   int precision = EHM_PREC_F32;
   const int32_t* mask_items = nullptr;   // exact pass pruning (ehm_gcn_set_pass_map): items that need the second pass, [num_masked] ...
   const int32_t* mask_slot = nullptr;    // ... and for every item its slot in that list or -1, [B]; nullptr = every item has a second pass
   int num_masked = -1;
   int uncond_masks_all = 0;              // second ("unconditional") pass of diffuse_fuse: 0 = image features masked, 1 = whole condition masked
+  int64_t valid_rows = 0;                // rows the input conv / checked pack produced (0: unknown = all): what the epilogues' range guard looks at - the
+                                         // tile padding behind them holds don't-care values (float32 rows of a last conv re-read as X2 halves, uninitialised scratch)
+  int virtual_bodies(int B, int passes) const { return passes == 2 ? B + (num_masked >= 0 ? num_masked : B) : B; }   // B + second passes after pruning
+  const int32_t* items(int passes) const { return (passes == 2 && num_masked >= 0) ? mask_items : nullptr; }
+  const int32_t* slots(int passes) const { return (passes == 2 && num_masked >= 0) ? mask_slot : nullptr; }
+  unsigned int guarded_rows(int64_t rows_pad) const { return (unsigned int)(valid_rows > 0 && valid_rows < rows_pad ? valid_rows : rows_pad); }
+};
+
+struct ehm_gcn {
+  int hid = 0;
+  int num_hidden = 0;
+  GcnRun run{};                          // run.valid_rows is written by the public input_layer / _rows / pack_activations_checked only: the separate
+                                         // calls input_layer -> hidden_stack have no argument to carry it
   LayerDev input{};
   LayerDev hidden[16]{};
   LayerDev* hidden_dev = nullptr;        // device copy of hidden[] for the chained kernel (gcn_tile.hip)
   unsigned int* chain_sync = nullptr;    // tickets[8] | done[nl][m_tiles] | err | finished, zeroed before every chained launch
-  int64_t valid_rows = 0;                // rows the last input conv / checked pack produced (0: unknown = all): what the epilogues' range guard looks at - the
-                                         // tile padding behind them holds don't-care values (float32 rows of a last conv re-read as X2 halves, uninitialised scratch)
   unsigned int* chain_sticky = nullptr;  // one word, zeroed at create / by ehm_gcn_stack_status: accumulates the launches' err flags
   size_t chain_sync_words = 0;
   int chain_sync_clean = 0;              // 1: the last chained launch zeroed tickets / done / finished itself (its last block does)

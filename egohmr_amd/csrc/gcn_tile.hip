@@ -1046,8 +1046,8 @@ __global__ void unpack_x2_kernel(const half_t* __restrict__ X, float* __restrict
   Y[i] = split_load<G>(X, i / K, (int)(i % K), K);
 }
 
-bool shape_ok(const ehm_gcn* h, int64_t rows_pad) {
-  const int P = h->precision == EHM_PREC_F16X3 ? 3 : 1;
+bool shape_ok(const ehm_gcn* h, int prec, int64_t rows_pad) {
+  const int P = prec == EHM_PREC_F16X3 ? 3 : 1;
   const int kt = P == 3 ? h->hid / 32 : h->hid / 64;
   if (h->hid % 64 != 0 || kt < 2 || rows_pad % 192 != 0) {
     ehm_set_error("f16 matrix-core convs need hid %% 64 == 0, hid >= %d and rows_pad %% 192 == 0 (hid = %d, rows_pad = %lld)", P == 3 ? 64 : 128,
@@ -1068,9 +1068,9 @@ void ehm_pack_half(const float* X, void* Y, size_t n, float scale, hipStream_t s
 }
 
 // One conv per launch (ehm_gcn_hidden_layer in the f16 modes).
-int ehm_gcn_tile_layer_impl(const ehm_gcn* h, int layer, const void* X, const void* residual, void* out, int64_t rows_pad, bool out_f32,
-                            hipStream_t st) {
-  if (!shape_ok(h, rows_pad)) return EHM_EINVAL;
+int ehm_gcn_tile_layer_impl(const ehm_gcn* h, const GcnRun& r, int layer, const void* X, const void* residual, void* out, int64_t rows_pad,
+                            bool out_f32, hipStream_t st) {
+  if (!shape_ok(h, r.precision, rows_pad)) return EHM_EINVAL;
   OneArgs a;
   a.L = h->hidden[layer];
   a.X = X;
@@ -1079,9 +1079,9 @@ int ehm_gcn_tile_layer_impl(const ehm_gcn* h, int layer, const void* X, const vo
   a.m_tiles = (int)(rows_pad / 192);
   a.out_f32 = out_f32 ? 1 : 0;
   a.sticky = h->chain_sticky;
-  a.rows_valid = (unsigned int)(h->valid_rows > 0 && h->valid_rows < rows_pad ? h->valid_rows : rows_pad);
+  a.rows_valid = r.guarded_rows(rows_pad);
   const int blocks = a.m_tiles * (h->hid / 64);
-  if (h->precision == EHM_PREC_F16X3) hipLaunchKernelGGL(gcn_hidden_tile_kernel<3>, dim3(blocks), dim3(256), 0, st, a);
+  if (r.precision == EHM_PREC_F16X3) hipLaunchKernelGGL(gcn_hidden_tile_kernel<3>, dim3(blocks), dim3(256), 0, st, a);
   else hipLaunchKernelGGL(gcn_hidden_tile_kernel<1>, dim3(blocks), dim3(256), 0, st, a);
   EHM_LAUNCH_CHECK();
   return 0;
@@ -1098,14 +1098,14 @@ int ehm_gcn_tile_layer_impl(const ehm_gcn* h, int layer, const void* X, const vo
 //     done[layer][m]; consume = done[layer-1][m] == n_tiles seen by one lane, barrier, then agent-scope (sc1) activation loads,
 //     which never hit in the CU's L1.
 // The sync words live in the handle (sized at ehm_gcn_create for max_rows; ehm_gcn_reserve grows them outside any capture).
-int ehm_gcn_tile_chain_impl(ehm_gcn* h, void* const bufs[3], int64_t rows_pad, hipStream_t st) {
+int ehm_gcn_tile_chain_impl(ehm_gcn* h, const GcnRun& r, void* const bufs[3], int64_t rows_pad, hipStream_t st) {
   const int nl = h->num_hidden;
-  if (!shape_ok(h, rows_pad)) return EHM_EINVAL;
+  if (!shape_ok(h, r.precision, rows_pad)) return EHM_EINVAL;
   if (nl < 2 || (nl & 1)) {
     ehm_set_error("chained hidden convs need an even number (>= 2) of them");
     return EHM_EINVAL;
   }
-  const bool wide = h->precision != EHM_PREC_F16X3 && h->hid % 128 == 0;   // f16 mode: one 8-wave block per CU, 128-channel tiles
+  const bool wide = r.precision != EHM_PREC_F16X3 && h->hid % 128 == 0;   // f16 mode: one 8-wave block per CU, 128-channel tiles
   const int m_tiles = (int)(rows_pad / 192), n_tiles = h->hid / (wide ? 128 : 64);
   const size_t need = 8 + (size_t)nl * m_tiles + 8;   // tickets | done | err, finished
   if (h->chain_sync_words < need) {
@@ -1129,7 +1129,7 @@ int ehm_gcn_tile_chain_impl(ehm_gcn* h, void* const bufs[3], int64_t rows_pad, h
   a.err = h->chain_sync + h->chain_err_off;
   a.finished = a.err + 1;
   a.sticky = h->chain_sticky;
-  a.rows_valid = (unsigned int)(h->valid_rows > 0 && h->valid_rows < rows_pad ? h->valid_rows : rows_pad);
+  a.rows_valid = r.guarded_rows(rows_pad);
   const int total = nl * m_tiles * n_tiles;
   int blocks = (wide ? 1 : 2) * ehm_num_cus();         // what is co-resident (80 KiB LDS per 4-wave block, 112 KiB per 8-wave block)
 #ifdef EHM_STAMPS
@@ -1139,7 +1139,7 @@ int ehm_gcn_tile_chain_impl(ehm_gcn* h, void* const bufs[3], int64_t rows_pad, h
   a.nq = ehm_num_cus() / 32;
   if (a.nq < 1) a.nq = 1;
   if (a.nq > 8) a.nq = 8;
-  if (h->precision == EHM_PREC_F16X3) hipLaunchKernelGGL((gcn_hidden_chain_kernel<3, 4>), dim3(blocks), dim3(256), 0, st, a);
+  if (r.precision == EHM_PREC_F16X3) hipLaunchKernelGGL((gcn_hidden_chain_kernel<3, 4>), dim3(blocks), dim3(256), 0, st, a);
   else if (wide) hipLaunchKernelGGL((gcn_hidden_chain_kernel<1, 8>), dim3(blocks), dim3(512), 0, st, a);
   else hipLaunchKernelGGL((gcn_hidden_chain_kernel<1, 4>), dim3(blocks), dim3(256), 0, st, a);
   EHM_LAUNCH_CHECK();
@@ -1156,11 +1156,11 @@ extern "C" int ehm_gcn_pack_activations(const float* X, void* X2, int64_t rows, 
 }
 
 extern "C" int ehm_gcn_pack_activations_checked(ehm_gcn* h, const float* X, void* X2, int64_t rows, void* stream) {
-  EHM_CHECK_ARG(h && X && X2 && rows > 0 && h->precision != EHM_PREC_F32);
-  h->valid_rows = rows;
+  EHM_CHECK_ARG(h && X && X2 && rows > 0 && h->run.precision != EHM_PREC_F32);
+  h->run.valid_rows = rows;
   const int K = h->hid;
   const dim3 grid((unsigned)ceil_div(rows * K, 256));
-  if (h->precision == EHM_PREC_F16) hipLaunchKernelGGL(pack_half_kernel, grid, dim3(256), 0, (hipStream_t)stream, X, (half_t*)X2, (size_t)rows * K, 1.f, h->chain_sticky);
+  if (h->run.precision == EHM_PREC_F16) hipLaunchKernelGGL(pack_half_kernel, grid, dim3(256), 0, (hipStream_t)stream, X, (half_t*)X2, (size_t)rows * K, 1.f, h->chain_sticky);
   else hipLaunchKernelGGL(pack_x2_kernel<32>, grid, dim3(256), 0, (hipStream_t)stream, X, (half_t*)X2, rows, K, h->chain_sticky);
   EHM_LAUNCH_CHECK();
   return 0;

@@ -33,26 +33,22 @@ void ehm_smpl_dev(const ehm_smpl* h, void* out);   // copies the handle's SmplDe
 size_t ehm_smpl_dev_size();
 int ehm_smpl_num_verts(const ehm_smpl* h);
 int ehm_smpl_num_extra(const ehm_smpl* h);
-// gcn.hip
+// gcn.hip (GcnRun: gcn_dev.h)
 struct GcnInputArgs;
-int ehm_gcn_input_args(ehm_gcn* h, const float* h_img, const float* h_oth, const uint8_t* vis, const float* x, const float* Wx, const float* tvec,
-                       float* out, int B, int passes, GcnInputArgs* a);
-int ehm_gcn_hid(const ehm_gcn* h);
-int ehm_gcn_nonlocal_ci(const ehm_gcn* h);
-const ehm_nonlocal_params* ehm_gcn_nonlocal(const ehm_gcn* h);
-int ehm_gcn_num_hidden(const ehm_gcn* h);
-int ehm_gcn_chain_enabled(const ehm_gcn* h);   // the hidden convs run as chained launches in the handle's precision (f16 modes, EHM_F16_CHAIN != 0)
-int ehm_gcn_virtual_bodies(const ehm_gcn* h, int B, int passes);   // B + second passes after pruning (ehm_gcn_set_pass_map)
-const int32_t* ehm_gcn_mask_slot(const ehm_gcn* h, int passes);
-// output conv, first half only: responses hs [passes*B*24, 12] = X . [W0 | W1] (scratch owned by the handle); *out_dev = the OutDev block
-int ehm_gcn_output_dot_impl(ehm_gcn* h, const float* X, int B, int passes, const float** hs, const void** out_dev, hipStream_t st);
-const void* ehm_gcn_out_dev(const ehm_gcn* h);   // the OutDev block (gcn_dev.h) of the output conv
+struct GcnRun;
+int ehm_gcn_input_args(const ehm_gcn* h, const GcnRun& r, const float* h_img, const float* h_oth, const uint8_t* vis, const float* x, const float* Wx,
+                       const float* tvec, float* out, int B, int passes, GcnInputArgs* a);
+int ehm_gcn_input_impl(const ehm_gcn* h, const GcnRun& r, const float* h_img, const float* h_oth, const uint8_t* vis, const float* x,
+                       const float* Wx, const float* tvec, float* out, int B, int passes, hipStream_t st);   // input conv, rows in r.precision's format
+int ehm_gcn_hidden_stack_impl(ehm_gcn* h, const GcnRun& r, float* const bufs[3], int64_t rows_pad, int* result_index, hipStream_t st);
+// output conv, first half only: responses *hs [virtual bodies*24, 12] = X . [W0 | W1] (scratch owned by the handle)
+int ehm_gcn_output_dot_impl(ehm_gcn* h, const GcnRun& r, const float* X, int B, int passes, const float** hs, hipStream_t st);
 // sampler.hip
 int ehm_num_cus();   // multiProcessorCount of the current device (cached)
 // gcn_tile.hip (f16 matrix-core hidden convs: 'f16x3' split operands and plain 'f16')
-int ehm_gcn_tile_layer_impl(const ehm_gcn* h, int layer, const void* X, const void* residual, void* out, int64_t rows_pad, bool out_f32,
-                            hipStream_t st);
-int ehm_gcn_tile_chain_impl(ehm_gcn* h, void* const bufs[3], int64_t rows_pad, hipStream_t st);
+int ehm_gcn_tile_layer_impl(const ehm_gcn* h, const GcnRun& r, int layer, const void* X, const void* residual, void* out, int64_t rows_pad,
+                            bool out_f32, hipStream_t st);
+int ehm_gcn_tile_chain_impl(ehm_gcn* h, const GcnRun& r, void* const bufs[3], int64_t rows_pad, hipStream_t st);
 void ehm_pack_half(const float* X, void* Y, size_t n, float scale, hipStream_t st);
 // gcn.hip
 int ehm_gcn_reserve_rows(ehm_gcn* h, int64_t rows_pad);   // sync words + output-conv scratch for up to rows_pad rows (allocates: not inside a capture)

@@ -234,15 +234,16 @@ extern "C" int ehm_sample_loop(ehm_gcn* gcn, ehm_smpl* smpl, const ehm_sample_de
   EHM_CHECK_ARG(gcn && smpl && d && steps && h_img && h_oth && vis && Wx && tvecs && noise && betas && mean && std_);
   EHM_CHECK_ARG(x_final && x0_final && verts && joints && R && pose6d && workspace);
   EHM_CHECK_ARG(d->B > 0 && d->num_steps > 0 && (d->passes == 1 || d->passes == 2));
-  EHM_CHECK_ARG(d->passes == 1 || ehm_gcn_virtual_bodies(gcn, d->B, 2) == d->B + (d->num_masked >= 0 ? d->num_masked : d->B));   // desc and ehm_gcn_set_pass_map agree
-  const int hid = ehm_gcn_hid(gcn), nh = ehm_gcn_num_hidden(gcn), V = ehm_smpl_num_verts(smpl);
+  GcnRun base = gcn->run;      // the handle's settings at entry: every step runs on a copy of them, the handle is left as it is
+  EHM_CHECK_ARG(d->passes == 1 || base.virtual_bodies(d->B, 2) == d->B + (d->num_masked >= 0 ? d->num_masked : d->B));   // desc and ehm_gcn_set_pass_map agree
+  const int hid = gcn->hid, nh = gcn->num_hidden, V = ehm_smpl_num_verts(smpl);
   EHM_CHECK_ARG(nh % 2 == 0);
   bool any_guided = false;
   for (int k = 0; k < d->num_steps; ++k) any_guided |= steps[k].grad_scale != 0.f;
   EHM_CHECK_ARG(!any_guided || (scene && d->num_scene_points > 0));      // (ddim rows with grad_scale != 0: ddim_sample_with_grad, gaussian_diffusion.py:559-614)
-  const ehm_nonlocal_params* nlp = ehm_gcn_nonlocal(gcn);
+  const ehm_nonlocal_params* nlp = &gcn->nonlocal;
   EHM_CHECK_ARG(d->nonlocal_ci == nlp->Ci);                                            // the descriptor sized the workspace for the block that is set
-  EHM_CHECK_ARG(nlp->Ci == 0 || (ehm_gcn_get_precision(gcn) != 2 && d->lowprec_steps == 0));   // the block reads float32 features
+  EHM_CHECK_ARG(nlp->Ci == 0 || (base.precision != EHM_PREC_F16 && d->lowprec_steps == 0));   // the block reads float32 features
   Workspace w = carve(d, hid, V, 64 + kJ, (char*)workspace);
   EHM_CHECK_ARG(workspace_bytes >= w.total_bytes);
   hipStream_t st = (hipStream_t)stream;
@@ -255,15 +256,9 @@ extern "C" int ehm_sample_loop(ehm_gcn* gcn, ehm_smpl* smpl, const ehm_sample_de
   EHM_HIP(hipMemcpyAsync(w.x_cur, noise, n * sizeof(float), hipMemcpyDeviceToDevice, st));   // x_T, :476-478
 
   int rc = 0;
-  const int base_prec = ehm_gcn_get_precision(gcn);
-  const int lowprec = base_prec == 1 /* f16x3 */ ? d->lowprec_steps : 0;
-  struct PrecisionGuard {      // the per-step kernel choice is host-side state of the handle: put it back on EVERY exit path (EHM_HIP returns early)
-    ehm_gcn* g;
-    int prec;
-    bool armed;
-    ~PrecisionGuard() { if (armed) ehm_gcn_set_precision(g, prec); }
-  } guard{gcn, base_prec, lowprec > 0};
-  auto prec_of = [&](int k) { return (lowprec > 0 && k < lowprec) ? 2 : base_prec; };
+  base.valid_rows = w.rows;     // what every step's input conv produces
+  const int lowprec = base.precision == EHM_PREC_F16X3 ? d->lowprec_steps : 0;
+  auto prec_of = [&](int k) { return (lowprec > 0 && k < lowprec) ? (int)EHM_PREC_F16 : base.precision; };   // (the same X2 buffers)
   // ---- deferred skinning of the per-step launches (see carve): slots filled since the last skinning launch
   // (a body model with dense skinning weights has no MFMA fragments: its steps keep the VALU skinning launch of ehm_step_body_impl - the workspace
   //  was sized without looking at the handle, the slots simply stay unused)
@@ -292,7 +287,8 @@ extern "C" int ehm_sample_loop(ehm_gcn* gcn, ehm_smpl* smpl, const ehm_sample_de
   bool input_done = false;          // step k's input conv already ran inside step k-1's skinning launch
   for (int k = 0; k < d->num_steps && rc == 0; ++k) {
     const ehm_step_coefs& c = steps[k];
-    if (lowprec > 0) ehm_gcn_set_precision(gcn, prec_of(k));   // host-side kernel choice only; same X2 buffers
+    GcnRun run = base;
+    run.precision = prec_of(k);
     const bool last = k == d->num_steps - 1;
     if (trace) EHM_HIP(hipMemcpyAsync(trace + (int64_t)k * n, w.x_cur, n * sizeof(float), hipMemcpyDeviceToDevice, st));
     // ---- collision guidance on x_t (gaussian_diffusion.py:378-385, egohmr.py:517-570): depends on x_t and betas only, so it runs first
@@ -306,17 +302,17 @@ extern "C" int ehm_sample_loop(ehm_gcn* gcn, ehm_smpl* smpl, const ehm_sample_de
     // ---- denoiser: EgoHMR.forward's per-step part (egohmr.py:232-257): input conv, chained hidden convs, output conv responses ----
     if (rc == 0 && !input_done) {
       EhmProfScope ps(EHM_PROF_INPUT, st);
-      rc = ehm_gcn_input_layer(gcn, h_img, h_oth, vis, w.x_cur, Wx, tvecs + (int64_t)k * 2 * hid, w.X[0], B, d->passes, st);
+      rc = ehm_gcn_input_impl(gcn, run, h_img, h_oth, vis, w.x_cur, Wx, tvecs + (int64_t)k * 2 * hid, w.X[0], B, d->passes, st);
     }
     input_done = false;
     int in = 0;
     if (rc == 0) {
-      const int p = prec_of(k);
-      EhmProfScope ps(p == 1 ? EHM_PROF_CHAIN_F16X3 : p == 2 ? EHM_PROF_CHAIN_F16 : EHM_PROF_HIDDEN_F32, st);
-      rc = ehm_gcn_hidden_stack(gcn, w.X, w.rows_pad, &in, st);
+      const int p = run.precision;
+      EhmProfScope ps(p == EHM_PREC_F16X3 ? EHM_PROF_CHAIN_F16X3 : p == EHM_PREC_F16 ? EHM_PROF_CHAIN_F16 : EHM_PROF_HIDDEN_F32, st);
+      rc = ehm_gcn_hidden_stack_impl(gcn, run, w.X, w.rows_pad, &in, st);
     }
     const float* hs = nullptr;
-    const void* out_dev = nullptr;
+    const void* out_dev = &gcn->out;
     const float* feat = w.X[in];
     if (rc == 0 && nlp->Ci > 0) {
       // optional non-local block (modulated_gcn.py:104-110): z = BN(W (softmax(theta phi^T) g)) + x over the 24 joints of a body; float32 features in X[in]
@@ -332,15 +328,15 @@ extern "C" int ehm_sample_loop(ehm_gcn* gcn, ehm_smpl* smpl, const ehm_sample_de
     // ---- fused: responses + x0 + x_{t-1} + the next step's input conv in one launch (the same arithmetic as the launches below).  Not for a
     //      step whose successor reads another activation format (the next rows would land on other bodies' rows of `feat`), nor - without
     //      deferred skinning - for the last step (its pose and skinning follow at once).
-    if (rc == 0 && fused_steps && (last ? defer_skin : prec_of(k) == prec_of(k + 1))) {
+    if (rc == 0 && fused_steps && (last ? defer_skin : run.precision == prec_of(k + 1))) {
       if (defer_skin && pending > 0 && !pending_poses) rc = flush_skin(false);      // (slots filled by per-step launches carry their poses already)
       const float* eps = noise + (int64_t)(1 + k) * n;
       float* dst = last ? x_final : w.x_cur;
       GcnInputArgs nin;
-      if (rc == 0 && !last) rc = ehm_gcn_input_args(gcn, h_img, h_oth, vis, dst, Wx, tvecs + (int64_t)(k + 1) * 2 * hid, w.X[0], B, d->passes, &nin);
+      if (rc == 0 && !last) rc = ehm_gcn_input_args(gcn, run, h_img, h_oth, vis, dst, Wx, tvecs + (int64_t)(k + 1) * 2 * hid, w.X[0], B, d->passes, &nin);
       if (rc == 0)
-        rc = ehm_step_fused_impl(ehm_gcn_out_dev(gcn), feat, prec_of(k), vis, w.x_cur, eps, grad, dst, defer_skin ? w.loop_x0 + (int64_t)pending * n : x0_final,
-                                 &c, d->ddim, d->passes, ehm_gcn_mask_slot(gcn, d->passes), B, last ? nullptr : &nin, prec_of(k + 1), st);
+        rc = ehm_step_fused_impl(out_dev, feat, run.precision, vis, w.x_cur, eps, grad, dst, defer_skin ? w.loop_x0 + (int64_t)pending * n : x0_final,
+                                 &c, d->ddim, d->passes, run.slots(d->passes), B, last ? nullptr : &nin, prec_of(k + 1), st);
       input_done = !last;
       if (rc == 0 && defer_skin) {
         pending_poses = true;
@@ -352,7 +348,7 @@ extern "C" int ehm_sample_loop(ehm_gcn* gcn, ehm_smpl* smpl, const ehm_sample_de
     if (rc == 0 && pending_poses) rc = flush_skin(false);        // this step fills its slot WITH its pose
     if (rc == 0) {
       EhmProfScope ps(EHM_PROF_OUT_DOT, st);
-      rc = ehm_gcn_output_dot_impl(gcn, feat, B, d->passes, &hs, &out_dev, st);
+      rc = ehm_gcn_output_dot_impl(gcn, run, feat, B, d->passes, &hs, st);
     }
     // ---- per body, one launch: output-conv mix + visibility fuse -> x0 (egohmr.py:247-256), x_{t-1} (gaussian_diffusion.py:298-337 /
     //      :511-556), de-normalise + rot6d + kinematic chain (egohmr.py:258-260); then the skinning launch (egohmr.py:276) ----
@@ -363,26 +359,24 @@ extern "C" int ehm_sample_loop(ehm_gcn* gcn, ehm_smpl* smpl, const ehm_sample_de
       GcnInputArgs nin;
       const GcnInputArgs* pnin = nullptr;
       if (!last && d->lbs_every_step && !defer_skin) {   // X[0] is free: the chain has consumed it and, if its result landed there, so has the output conv
-        if (lowprec > 0) ehm_gcn_set_precision(gcn, prec_of(k + 1));   // the activation format the next step's convs will read
-        rc = ehm_gcn_input_args(gcn, h_img, h_oth, vis, dst, Wx, tvecs + (int64_t)(k + 1) * 2 * hid, w.X[0], B, d->passes, &nin);
-        if (lowprec > 0) ehm_gcn_set_precision(gcn, prec_of(k));
+        rc = ehm_gcn_input_args(gcn, run, h_img, h_oth, vis, dst, Wx, tvecs + (int64_t)(k + 1) * 2 * hid, w.X[0], B, d->passes, &nin);
         pnin = &nin;
       }
       int fused = 0;
       if (rc == 0 && defer_skin) {
         // the step leaves its transforms and fragments in slot `pending`; no skinning (and no fused input conv) launch now
-        rc = ehm_step_body_impl(smpl, hs, out_dev, vis, w.x_cur, eps, grad, dst, x0_final, &c, d->ddim, d->passes, ehm_gcn_mask_slot(gcn, d->passes), 1,
+        rc = ehm_step_body_impl(smpl, hs, out_dev, vis, w.x_cur, eps, grad, dst, x0_final, &c, d->ddim, d->passes, run.slots(d->passes), 1,
                                 betas, mean, std_, verts, joints, R, w.loop_A + (int64_t)pending * B * kJ * 12, pose6d, B, st, nullptr, 0, nullptr,
                                 (char*)w.loop_pf + (int64_t)pending * pf_bytes_step);
         ++pending;
         if (rc == 0 && (pending == w.skin_seg || last)) rc = flush_skin(last);
       } else if (rc == 0) {
-        rc = ehm_step_body_impl(smpl, hs, out_dev, vis, w.x_cur, eps, grad, dst, x0_final, &c, d->ddim, d->passes, ehm_gcn_mask_slot(gcn, d->passes),
+        rc = ehm_step_body_impl(smpl, hs, out_dev, vis, w.x_cur, eps, grad, dst, x0_final, &c, d->ddim, d->passes, run.slots(d->passes),
                                 (d->lbs_every_step || last) ? 1 : 0,
                                 betas, mean, std_, verts, joints, R, w.A, pose6d, B, st, pnin, prec_of(k + 1), &fused);
       }
       input_done = fused != 0;
     }
   }
-  return rc;      // (PrecisionGuard restores base_prec)
+  return rc;
 }

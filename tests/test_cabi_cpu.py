@@ -221,6 +221,14 @@ def test_default_library_has_no_experiment_and_no_env_switch_on_the_launch_path(
     assert not os.path.exists(os.path.join(REPO, "tools", "jobs"))
 
 
+def test_sample_loop_does_not_change_the_gcn_handle():
+    """ehm_sample_loop runs every step on its own copy of the handle's settings (GcnRun, csrc/gcn_dev.h): a precision schedule passes the step's
+    precision down instead of switching the handle, so no setter of the GCN handle is called from the loop."""
+    src = open(os.path.join(REPO, "egohmr_amd", "csrc", "sampler.hip")).read()
+    assert "ehm_sample_loop" in src
+    assert re.findall(r"\behm_gcn_set_\w*\s*\(", src) == []
+
+
 def test_conv_x2_stream_k_plans_at_the_benchmark_batch():
     """Host logic of csrc/conv.hip::sk_plan, no GPU needed (ehm_conv_x2_workspace_bytes only plans; without a device the library assumes an MI355X: 256 CUs = 512
     block slots).  At N = 256 images ResNet-50's layers 2 - 4 land just above a multiple of the slots; which convs are cut into K runs, and how much scratch that takes:

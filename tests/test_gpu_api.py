@@ -190,6 +190,34 @@ def test_run_samples_equals_sequential_runs(dev, model, guided):
     assert float((seq[0]["sample"] - seq[1]["sample"]).abs().max()) > 1e-3              # different noise, different samples
 
 
+def test_precision_schedule_leaves_the_gcn_handle_as_it_was(dev, model):
+    """A sampling call with a precision schedule (plain f16 on the leading steps, split-f16 on the rest) runs every step on its own copy of the
+    handle's settings: afterwards the handle reports the precision set before the call, and a granular denoiser evaluation is bit-equal to the
+    same evaluation made before it."""
+    from egohmr_amd import _lib
+    from egohmr_amd.diffusion import create_gaussian_diffusion
+    from egohmr_amd.model import PRECISIONS
+    d = create_gaussian_diffusion(num_diffusion_timesteps=20, timestep_respacing="")
+    B, lowprec = 4, 12
+    b = _batch(dev, B)
+    noise = torch.from_numpy(syn.make_noise_stack(d.num_timesteps, B, seed=51)).to(dev)
+    fs, L = model.fused_sampler, _lib.lib()
+    old = model.gcn_precision
+    model.gcn_precision = "f16x3"
+    try:
+        st = fs.prepare(b)
+        tv = fs.timestep_vectors(torch.tensor([7], device=dev))[0]
+        x_t = noise[0].contiguous()
+        before = fs.denoise_once(st, x_t, tv, 2).clone()
+        fs.run(d, b, noise, ddim=False, lowprec=lowprec)
+        assert fs.last_lowprec == lowprec
+        assert L.ehm_gcn_get_precision(fs._gcn) == PRECISIONS["f16x3"]          # the raw handle: fs.gcn() would set the model's precision again
+        after = fs.denoise_once(st, x_t, tv, 2)
+    finally:
+        model.gcn_precision = old
+    assert torch.equal(after, before)
+
+
 def test_deferred_status_pipeline(dev, model):
     """run(..., defer_status=True): no host wait at the end of the call; the chain-status word is looked at by the next call or by
     check_status().  Same results as the synchronous route."""
