@@ -822,8 +822,13 @@ extern "C" int ehm_linear_split(const ehm_linear_desc* d, void* stream) {
   EHM_CHECK_ARG(d->M > 0 && d->M % LBM == 0 && d->N > 0 && d->N % LBN == 0);
   EHM_CHECK_ARG(d->K0 > 0 && d->K0 % BK == 0 && d->K1 >= 0 && d->K1 % BK == 0 && (d->K1 == 0 || d->A1) && d->K0 + d->K1 >= 2 * BK);
   EHM_CHECK_ARG(d->rows_per_group > 0 && d->rows_per_group % LBM == 0 && d->M % d->rows_per_group == 0);
+  EHM_CHECK_ARG(d->valid_rows_per_group <= d->rows_per_group);
   EHM_CHECK_ARG(d->w_scale > 0.f);
   EHM_CHECK_ARG(d->M < (int64_t)1 << 31 && (int64_t)LBM * d->N * 4 < ((int64_t)1 << 31));
+  if (d->relu_in0 && d->K1 != 0) {
+    ehm_set_error("ehm_linear_split: relu_in0 needs K1 == 0 (the ReLU'd operand must be the only K segment)");
+    return EHM_EINVAL;
+  }
   LinArgs a;
   a.A0 = (const float*)d->A0; a.A1 = (const float*)d->A1; a.W = (const float*)d->W;
   a.bias = d->bias; a.gbias = d->group_bias; a.Y = (char*)d->Y; a.colmax = d->colmax;
@@ -837,10 +842,6 @@ extern "C" int ehm_linear_split(const ehm_linear_desc* d, void* stream) {
   const int64_t tiles = (d->M / LBM) * (d->N / LBN);
   int64_t blocks = 2 * (int64_t)ehm_num_cus();            // what is co-resident (80 KiB of LDS per block)
   if (blocks > tiles) blocks = tiles;
-  if (d->relu_in0 && d->K1 != 0) {
-    ehm_set_error("ehm_linear_split: relu_in0 needs K1 == 0 (the ReLU'd operand must be the only K segment)");
-    return EHM_EINVAL;
-  }
   if (d->hi_only) {
     if (lift) hipLaunchKernelGGL((linear_tile_kernel<false, true, true>), dim3((unsigned)blocks), dim3(256), 0, (hipStream_t)stream, a);
     else if (d->relu_in0) hipLaunchKernelGGL((linear_tile_kernel<true, false, true>), dim3((unsigned)blocks), dim3(256), 0, (hipStream_t)stream, a);
@@ -856,6 +857,10 @@ extern "C" int ehm_skinny_gemm_f32(const float* X, const float* W, const float* 
   EHM_CHECK_ARG(X && W && Y && M > 0 && K > 0 && N > 0);
   if (K % 32 != 0 || N % 32 != 0 || ((uintptr_t)X % 16) != 0) {
     ehm_set_error("ehm_skinny_gemm_f32 needs K %% 32 == 0, N %% 32 == 0 and a 16-byte aligned X (K = %d, N = %d)", K, N);
+    return EHM_EINVAL;
+  }
+  if ((relu >> 1) % 32 != 0) {   // relu_in is decided per 32-column block
+    ehm_set_error("ehm_skinny_gemm_f32: relu >> 1 (the rectified leading columns) must be a multiple of 32 (relu = %d)", relu);
     return EHM_EINVAL;
   }
   const dim3 grid((unsigned)(N / 32), (unsigned)ceil_div(M, 32));

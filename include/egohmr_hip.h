@@ -217,8 +217,8 @@ typedef struct {
   int64_t M;               /* rows, multiple of 192 (the row tile)                                  */
   int N, K0, K1;           /* N multiple of 128; K0, K1 multiples of 32, K0 + K1 >= 64              */
   int rows_per_group;      /* padded points per body, multiple of 192                               */
-  int valid_rows_per_group;/* real points per body (<= rows_per_group); 0 = all                     */
-  int relu_in0;            /* apply ReLU to A0 on load (ResnetBlockFC's actvn before fc_0); needs K1 == 0 */
+  int valid_rows_per_group;/* real points per body, <= rows_per_group (a larger value is refused); 0 = all */
+  int relu_in0;            /* apply ReLU to A0 on load (ResnetBlockFC's actvn before fc_0); needs K1 == 0 (else refused) */
   int relu_out;            /* apply ReLU before storing                                             */
   float w_scale;           /* the power-of-two scale baked into W                                   */
   const float* lift_points;/* NULL, or [M/rows_per_group, valid_rows_per_group, 3] float32: A0 is not read but generated on
@@ -240,8 +240,8 @@ int ehm_pointnet_lift(const float* pts, const float* Wpos, const float* bpos, vo
 /* Y[M,N] = act(X[M,K] . W[K,N] + bias[N]) in exact float32 on the matrix cores, for short M (batches of feature vectors): the
  * step-invariant slices of the input graph conv (models/egohmr/modulated_gcn/modulated_gcn_conv.py:39-50 on the image / scene
  * features) and the beta head's first layer (models/egohmr/egohmr.py:263-265, fc_head_beta).  K % 32 == 0, N % 32 == 0, any M;
- * X 16-byte aligned; bias may be NULL.  relu: bit 0 applies max(., 0) to the output; relu >> 1 = number of leading output columns (a multiple of 32)
- * whose INPUT row is rectified first - [relu(x) . Wa | x . Wb] in one launch (the pooled halves of a ResnetBlockFC's fc_0 and shortcut,
+ * X 16-byte aligned; bias may be NULL.  relu: bit 0 applies max(., 0) to the output; relu >> 1 = number of leading output columns (a multiple of 32:
+ * other counts are refused) whose INPUT row is rectified first - [relu(x) . Wa | x . Wb] in one launch (the pooled halves of a ResnetBlockFC's fc_0 and shortcut,
  * models/respointnet.py:41-51).  Deterministic (no atomics). */
 int ehm_skinny_gemm_f32(const float* X, const float* W, const float* bias, float* Y, int M, int K, int N, int relu, void* stream);
 

@@ -74,6 +74,37 @@ def test_cabi_rejects_bad_arguments_without_a_gpu():
     assert b"bad argument" in L.ehm_last_error()
     assert L.ehm_ddpm_step(None, None, None, None, None, 0, 0, 0, 0, 0, 10, None) == -22
     assert L.ehm_sample_workspace_bytes(None, 1024, 6890) == -22
+    # ehm_linear_split: every refusal runs before the library asks for the device (ehm_num_cus) or launches anything
+    for bad in (dict(valid_rows_per_group=577),                  # more valid rows than rows: padding would reach colmax, lift would read the next group
+                dict(relu_in0=1, K1=32, A1=0x40000),             # the ReLU'd operand must be the only K segment
+                dict(relu_in0=1, K1=32, A1=0x40000, hi_only=1),
+                dict(M=577, rows_per_group=577, valid_rows_per_group=0),   # M % 192
+                dict(N=192),                                     # N % 128
+                dict(K0=48),                                     # K0 % 32
+                dict(K1=16, A1=0x40000),                         # K1 % 32
+                dict(K0=32),                                     # K0 + K1 < 64 (one K tile)
+                dict(lift_points=0x50000, lift_W4=0x60000),      # lift mode with an A0
+                dict(A0=None, lift_points=0x50000, lift_W4=0x60000, relu_in0=1),
+                dict(rows_per_group=384),                        # M % rows_per_group
+                dict(Y=None),                                    # neither Y nor colmax
+                dict(group_bias=0x70000, group_bias_stride=128)):   # a group-bias row shorter than N
+        assert L.ehm_linear_split(_dummy_linear_desc(**bad), None) == -22, bad
+        assert b"bad argument" in L.ehm_last_error() or b"relu_in0 needs K1 == 0" in L.ehm_last_error(), bad
+    # ehm_skinny_gemm_f32: relu >> 1 (the leading columns whose input is rectified) is applied per 32-column block
+    for relu in (2 * 16 + 1, 2 * 16, 2 * 48, 2 * 1):
+        assert L.ehm_skinny_gemm_f32(0x10000, 0x20000, None, 0x30000, 1, 64, 64, relu, None) == -22, relu
+        assert b"multiple of 32" in L.ehm_last_error()
+
+
+def _dummy_linear_desc(**kw):
+    """An ehm_linear_desc that every check of ehm_linear_split accepts, on dummy (never dereferenced) addresses.  Each use breaks one rule, so
+    no call reaches a launch."""
+    from egohmr_amd import _lib
+    f = dict(A0=0x10000, A1=None, W=0x20000, bias=None, group_bias=None, Y=0x30000, colmax=None, M=576, N=256, K0=64, K1=0,
+             rows_per_group=576, valid_rows_per_group=500, relu_in0=0, relu_out=0, w_scale=1.0, lift_points=None, lift_W4=None, hi_only=0,
+             group_bias_stride=0)
+    f.update(kw)
+    return _lib.LinearDesc(**f)
 
 
 def test_checked_view_covers_every_entry_point():
