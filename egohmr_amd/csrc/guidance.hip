@@ -600,9 +600,9 @@ __device__ __forceinline__ void rot6d_bwd(float a1x, float a1y, float a1z, float
   // b3 = b1 x b2
   g1[0] += b2[1] * g3[2] - b2[2] * g3[1]; g1[1] += b2[2] * g3[0] - b2[0] * g3[2]; g1[2] += b2[0] * g3[1] - b2[1] * g3[0];
   g2[0] += g3[1] * b1[2] - g3[2] * b1[1]; g2[1] += g3[2] * b1[0] - g3[0] * b1[2]; g2[2] += g3[0] * b1[1] - g3[1] * b1[0];
-  // b2 = u / max(|u|, eps)
+  // b2 = u / max(|u|, eps); like clamp_min's backward, the gradient takes the |u| path where |u| >= eps (ties included)
   float gu[3];
-  if (n2r > 1e-12f) {
+  if (n2r >= 1e-12f) {
     const float t = b2[0] * g2[0] + b2[1] * g2[1] + b2[2] * g2[2];
 #pragma unroll
     for (int c = 0; c < 3; ++c) gu[c] = (g2[c] - b2[c] * t) / n2;
@@ -617,8 +617,8 @@ __device__ __forceinline__ void rot6d_bwd(float a1x, float a1y, float a1z, float
     ga2[c] = gu[c] - gub1 * b1[c];
     g1[c] += -d * gu[c] - gub1 * a2[c];
   }
-  // b1 = a1 / max(|a1|, eps)
-  if (n1r > 1e-12f) {
+  // b1 = a1 / max(|a1|, eps), the same tie rule
+  if (n1r >= 1e-12f) {
     const float t = b1[0] * g1[0] + b1[1] * g1[1] + b1[2] * g1[2];
 #pragma unroll
     for (int c = 0; c < 3; ++c) ga1[c] = (g1[c] - b1[c] * t) / n1;
@@ -795,8 +795,19 @@ int own_scratch(int64_t bytes, void** out) {
   return 0;
 }
 
+// The brute-force search keeps the body's vertices in LDS (3 Vp floats): larger bodies are refused before anything is allocated or written
+constexpr int kMaxCollisionVerts = (160 * 1024 - 256) / 12;
+int check_collision_verts(int V) {
+  if (V > kMaxCollisionVerts) {
+    ehm_set_error("collision proxy: %d vertices do not fit the 160 KiB LDS (at most %d)", V, kMaxCollisionVerts);
+    return EHM_EINVAL;
+  }
+  return 0;
+}
+
 int collision_impl(const float* verts, const float* scene, float* loss, float* gverts, int* hits, int B, int V, int N, float tau,
                    float margin, const Scratch& s, hipStream_t st) {
+  if (int rc = check_collision_verts(V)) return rc;
   if (gverts) EHM_HIP(hipMemsetAsync(gverts, 0, (size_t)B * V * 3 * sizeof(float), st));
   if (hits) EHM_HIP(hipMemsetAsync(hits, 0, (size_t)B * sizeof(int), st));
   EHM_HIP(hipMemsetAsync(loss, 0, (size_t)B * sizeof(float), st));
@@ -806,10 +817,6 @@ int collision_impl(const float* verts, const float* scene, float* loss, float* g
   const size_t lds = (size_t)3 * Vp * sizeof(float);
   // (per device, and cheap: set unconditionally rather than once per process)
   EHM_HIP(hipFuncSetAttribute((const void*)nearest_kernel, hipFuncAttributeMaxDynamicSharedMemorySize, 160 * 1024 - 256));
-  if (lds > 160 * 1024 - 256) {
-    ehm_set_error("collision proxy: %d vertices do not fit the 160 KiB LDS", V);
-    return EHM_EINVAL;
-  }
   const size_t lds_grid = (size_t)4 * Vp * sizeof(float) + (size_t)(2 * kMaxCells + 1) * sizeof(int) + 16;   // 16-byte slots (x, y, z, id) + the cell offsets
   if (V <= 8192 && lds_grid <= 160 * 1024 - 4608) {          // (the grid kernel keeps 8 vertices per thread in registers)
     EHM_HIP(hipFuncSetAttribute((const void*)nearest_grid_kernel, hipFuncAttributeMaxDynamicSharedMemorySize, 160 * 1024 - 4608));
@@ -875,6 +882,7 @@ int ehm_guidance_impl(ehm_smpl* smpl, const float* betas, const float* x, const 
 extern "C" int ehm_collision_proxy(const float* verts, const float* scene, float* loss, float* gverts, int B, int V, int N, float tau,
                                    void* stream) {
   EHM_CHECK_ARG(verts && scene && loss && gverts && B > 0 && V > 0 && N > 0 && tau > 0.f);
+  if (int rc = check_collision_verts(V)) return rc;
   void* sc = nullptr;
   int rc = own_scratch(ehm_guidance_scratch_bytes(B, N), &sc);
   if (rc) return rc;
@@ -884,6 +892,7 @@ extern "C" int ehm_collision_proxy(const float* verts, const float* scene, float
 extern "C" int ehm_collision_query(const float* verts, const float* scene, float* loss, float* gverts, int32_t* hits, int B, int V, int N,
                                    float tau, int all_points, void* stream) {
   EHM_CHECK_ARG(verts && scene && loss && B > 0 && V > 0 && N > 0 && tau > 0.f);
+  if (int rc = check_collision_verts(V)) return rc;
   void* sc = nullptr;
   int rc = own_scratch(ehm_guidance_scratch_bytes(B, N), &sc);
   if (rc) return rc;

@@ -339,7 +339,8 @@ int ehm_ddim_step(const float* x, const float* x0, const float* noise, float* x_
  * see DESIGN.md): with the bbox selection of egohmr.py:550-552,
  *   loss[b] = sum over scene points p inside bbox(verts[b]) of relu(tau - min_v |p - v|)^2
  * and gverts[b,v,:] = d(loss[b])/d(verts[b,v,:]).  scene [B,N,3] (already canonicalised,
- * egohmr.py:211); loss [B]; gverts [B,V,3] (overwritten). */
+ * egohmr.py:211); loss [B]; gverts [B,V,3] (overwritten).  V <= 13632 (the vertices live in
+ * LDS): a larger V is refused with EINVAL before anything is allocated, launched or written. */
 int ehm_collision_proxy(const float* verts, const float* scene, float* loss, float* gverts, int B, int V, int N,
                         float tau, void* stream);
 

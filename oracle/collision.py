@@ -56,3 +56,52 @@ def proxy_occupancy(points, verts, tau: float = TAU):
 def proxy_sdf(points, verts, tau: float = TAU):
     """Stand-in for `volume.query_fast(points [1,n,3], smpl_output) -> sdf [1,n]` (egohmr_volsmpl.py:574, `< 0` = inside)."""
     return (proxy_min_dist(points[0], verts[0]) - tau).unsqueeze(0)
+
+
+def exact_proxy(verts, scene, tau: float = TAU, all_points: bool = False, chunk: int | None = None):
+    """The proxy of a batch in float64, by brute force over every vertex, on whatever device the inputs are: the reference for the
+    native search (ehm_collision_query).  verts [B,V,3], scene [B,N,3] (float32 or float64; computed in float64 from exactly these values).
+
+    all_points=False selects the scene points inside the vertex bounding box, faces included (egohmr.py:550-552); True takes every point
+    (egohmr_volsmpl.py:609-612).  The nearest vertex of a point is the lowest-index one among equally near vertices, like torch.min.
+    Returns a dict of float64 / int64 tensors:
+      loss [B], gverts [B,V,3] (d loss / d verts), hits [B] (selected points with d < tau),
+      selected [B,N] bool, d [B,N] (sqrt(min d2 + 1e-12)), nearest [B,N] (vertex index), gap [B,N] (second-nearest minus nearest
+      squared distance, where vertices at the very position of the nearest one do not count as second: exact duplicates tie on purpose),
+      ncontrib [B,V] (hit points whose nearest vertex is v), gabs [B,V,3] (sum of |d loss_p / d v| over those points)."""
+    v64, p64 = verts.double(), scene.double()
+    B, V, N = v64.shape[0], v64.shape[1], p64.shape[1]
+    tau = float(tau)
+    chunk = chunk or max(1, (1 << 24) // (B * V))                            # ~0.4 GB of float64 differences per step
+    if all_points:
+        selected = torch.ones(B, N, dtype=torch.bool, device=p64.device)
+    else:
+        lo, hi = v64.min(1, keepdim=True).values, v64.max(1, keepdim=True).values
+        selected = ((p64 >= lo) & (p64 <= hi)).all(-1)
+    d = torch.empty(B, N, dtype=torch.float64, device=p64.device)
+    nearest = torch.empty(B, N, dtype=torch.long, device=p64.device)
+    gap = torch.empty(B, N, dtype=torch.float64, device=p64.device)
+    for s in range(0, N, chunk):
+        diff = p64[:, s:s + chunk, None, :] - v64[:, None, :, :]
+        d2 = (diff * diff).sum(-1)                                             # [B,c,V]
+        bi = torch.argmin(d2, -1)                                              # the first minimum (documented for argmin)
+        best = torch.gather(d2, -1, bi.unsqueeze(-1)).squeeze(-1)
+        bv = torch.gather(v64, 1, bi.unsqueeze(-1).expand(-1, -1, 3))          # [B,c,3]
+        same = (v64[:, None, :, :] == bv[:, :, None, :]).all(-1)               # exact duplicates of the nearest vertex
+        second = torch.where(same, torch.full_like(d2, float("inf")), d2).min(-1).values
+        d[:, s:s + chunk] = torch.sqrt(best + 1e-12)
+        nearest[:, s:s + chunk] = bi
+        gap[:, s:s + chunk] = second - best
+    h = torch.where(selected, tau - d, torch.zeros_like(d))
+    hit = h > 0
+    hz = torch.where(hit, h, torch.zeros_like(h))
+    loss = (hz * hz).sum(1)
+    bv = torch.gather(v64, 1, nearest.unsqueeze(-1).expand(-1, -1, 3))
+    c = (2.0 * hz / d).unsqueeze(-1) * (p64 - bv)                              # d (tau - d)^2 / d v = 2 h (p - v) / d
+    gverts = torch.zeros(B, V, 3, dtype=torch.float64, device=p64.device)
+    gabs = torch.zeros_like(gverts)
+    idx = nearest.unsqueeze(-1).expand(-1, -1, 3)
+    gverts.scatter_add_(1, idx, c)
+    gabs.scatter_add_(1, idx, c.abs())
+    ncontrib = torch.zeros(B, V, dtype=torch.float64, device=p64.device).scatter_add_(1, nearest, hit.double())
+    return dict(loss=loss, gverts=gverts, hits=hit.sum(1), selected=selected, d=d, nearest=nearest, gap=gap, ncontrib=ncontrib, gabs=gabs)

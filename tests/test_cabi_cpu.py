@@ -90,6 +90,13 @@ def test_cabi_rejects_bad_arguments_without_a_gpu():
                 dict(group_bias=0x70000, group_bias_stride=128)):   # a group-bias row shorter than N
         assert L.ehm_linear_split(_dummy_linear_desc(**bad), None) == -22, bad
         assert b"bad argument" in L.ehm_last_error() or b"relu_in0 needs K1 == 0" in L.ehm_last_error(), bad
+    # ehm_collision_proxy / _query: a body whose vertices do not fit the LDS is refused among the argument checks, before the scratch is
+    # allocated or the caller's loss / gverts / hits are cleared (dummy addresses: nothing may be written through them)
+    for V in (13633, 13636, 50000):
+        assert L.ehm_collision_query(0x10000, 0x20000, 0x30000, 0x40000, 0x50000, 2, V, 64, 0.05, 1, None) == -22, V
+        assert b"do not fit" in L.ehm_last_error(), V
+        assert L.ehm_collision_proxy(0x10000, 0x20000, 0x30000, 0x40000, 2, V, 64, 0.05, None) == -22, V
+        assert b"do not fit" in L.ehm_last_error(), V
     # ehm_skinny_gemm_f32: relu >> 1 (the leading columns whose input is rectified) is applied per 32-column block
     for relu in (2 * 16 + 1, 2 * 16, 2 * 48, 2 * 1):
         assert L.ehm_skinny_gemm_f32(0x10000, 0x20000, None, 0x30000, 1, 64, 64, relu, None) == -22, relu
