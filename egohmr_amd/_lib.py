@@ -28,7 +28,7 @@ _HERE = os.path.dirname(os.path.abspath(__file__))
 LIB_PATH = os.environ.get("EHM_LIB_PATH") or os.path.join(_HERE, "libegohmr_hip.so")   # EHM_LIB_PATH: A/B a second build (experiments)
 CSRC = os.path.join(_HERE, "csrc")
 INCLUDE = os.path.join(os.path.dirname(_HERE), "include")
-SOURCES = ["gcn.hip", "gcn_tile.hip", "linear.hip", "conv.hip", "stem.hip", "metrics.hip", "smpl.hip", "sampler.hip", "guidance.hip", "prep.hip", "step.hip", "eval.hip", "stage1.hip"]
+SOURCES = ["gcn.hip", "gcn_tile.hip", "linear.hip", "conv.hip", "stem.hip", "metrics.hip", "smpl.hip", "sampler.hip", "guidance.hip", "prep.hip", "step.hip", "eval.hip", "stage1.hip", "scene.hip"]
 
 
 class EgoHMRHipError(RuntimeError):
@@ -192,6 +192,14 @@ class Stage1Desc(C.Structure):
                 ("img_dim", C.c_int), ("scene_dim", C.c_int), ("hidden", C.c_int), ("B", C.c_int)]
 
 
+class SceneDesc(C.Structure):
+    """ehm_scene_desc"""
+    _fields_ = [("verts", C.c_void_p), ("total_verts", C.c_int64), ("mesh_offsets", C.c_void_p), ("num_meshes", C.c_int), ("max_mesh_verts", C.c_int64),
+                ("groups", C.c_void_p), ("num_groups", C.c_int), ("params", C.c_void_p), ("mode", C.c_int), ("chain_len", C.c_int), ("B", C.c_int),
+                ("target", C.c_int), ("stride", C.c_int), ("points", C.c_void_p), ("index", C.c_void_p), ("n_selected", C.c_void_p),
+                ("status", C.c_void_p), ("workspace", C.c_void_p), ("workspace_bytes", C.c_int64)]
+
+
 _P, _I, _L, _F = C.c_void_p, C.c_int, C.c_int64, C.c_float
 
 # name -> (restype, argtypes); every symbol include/egohmr_hip.h declares
@@ -252,6 +260,8 @@ PROTOTYPES = {
     "ehm_eval_procrustes_vis": (_I, [_P, _P, _P, _P, _P, _P, _P, _P, _I, _I, _I, _P]),
     "ehm_eval_diversity": (_I, [_P, _P, _I, _P, _P, _I, _I, _I, _P]),
     "ehm_stage1_head": (_I, [C.POINTER(Stage1Desc), _P]),
+    "ehm_scene_workspace_bytes": (_I, [C.POINTER(SceneDesc), C.POINTER(C.c_int64)]),
+    "ehm_scene_select": (_I, [C.POINTER(SceneDesc), _P]),
     "ehm_sample_workspace_bytes": (_L, [C.POINTER(SampleDesc), _I, _I]),
     "ehm_sample_loop": (_I, [_P, _P, C.POINTER(SampleDesc), C.POINTER(StepCoefs)] + [_P] * 18 + [_L, _P]),
     "ehm_item_prep": (_I, [C.POINTER(ItemPrepDesc), _P]),

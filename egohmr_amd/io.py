@@ -5,6 +5,7 @@
 * `load_stage1_cam`: `results.pkl['pred_cam_full_list']` written by the stage-1 script (test_prohmr_scene.py:417-426) and
   consumed by `--two_stage` runs; `save_stage1_results` writes that file from egohmr_amd.stage1's translations.
 * `load_stage1_checkpoint`: a ProHMR-scene checkpoint into egohmr_amd.stage1.ProHMRSceneTransl (test_prohmr_scene.py:81-85).
+* `read_obj_vertices`: the vertex array of a scene mesh OBJ (scene_mesh/{scene}/{scene}.obj), for egohmr_amd.scene.SceneClouds.
 * `load_preprocess_stats`, `load_smpl_mean_params`, `load_checkpoint`: test_egohmr.py:109-111, models/egohmr/egohmr.py:669-671,
   test_egohmr.py:125-127.
 
@@ -134,3 +135,22 @@ def load_checkpoint(model: torch.nn.Module, path_or_state, strict: bool = False)
     w = torch.load(path_or_state, map_location="cpu") if isinstance(path_or_state, (str, os.PathLike)) else path_or_state
     sd = w["state_dict"] if isinstance(w, Mapping) and "state_dict" in w else w
     return model.load_state_dict(sd, strict=strict)
+
+
+def read_obj_vertices(path: str) -> np.ndarray:
+    """The vertices of an OBJ file, [V, 3] float64 in file order: the ``v x y z`` lines (a fourth weight or trailing vertex colours are
+    ignored), what ``np.asarray(o3d.io.read_triangle_mesh(path).vertices)`` holds in preprocess_scene_s1.py / preprocess_scene_s2_for_test.py.
+
+    open3d reads OBJ files through tinyobjloader, whose default ``real_t`` is float: each coordinate is parsed, rounded to float32 and widened to
+    float64 in open3d's vertex array.  So here: parsed as a double, rounded to float32, widened.  That is believed from the libraries' sources
+    and defaults, not checked against open3d itself (not a dependency of this package).  Faces, normals and texture coordinates are not
+    read."""
+    rows = []
+    with open(path, "r") as f:
+        for line in f:
+            if line.startswith("v ") or line.startswith("v\t"):
+                tok = line.split()
+                if len(tok) < 4:
+                    raise ValueError(f"{path}: vertex line with fewer than 3 coordinates: {line.strip()!r}")
+                rows.append((float(tok[1]), float(tok[2]), float(tok[3])))
+    return np.asarray(rows, np.float64).reshape(-1, 3).astype(np.float32).astype(np.float64)

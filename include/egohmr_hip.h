@@ -423,6 +423,62 @@ typedef struct ehm_stage1_desc {
 } ehm_stage1_desc;
 int ehm_stage1_head(const ehm_stage1_desc* d, void* stream);
 
+/* ------------------------------------------------------------------ scene clouds -------------- */
+/* The scene point cloud each stage reads, per item, from scene meshes resident on the device (csrc/scene.hip).  It replaces the offline
+ * preprocessing plus the loader's transform:
+ *   EHM_SCENE_WHOLE  stage 1: preprocess_scene_s1.py:94-118 (the chain of mesh.transform, z > 0, uniform_down_sample, first `target`) and
+ *                    dataloaders/egobody_dataset.py:205-212 (points_coord_trans into the PV camera)
+ *   EHM_SCENE_CUBE   stage 2: preprocess_scene_s2_for_test.py:176-208 (rotation about y through the centre, inclusive xz bounds,
+ *                    y <= min(y) + cube_size, uniform_down_sample, first `target`) and egobody_dataset.py:213-225
+ * then [::stride] and the float32 cast of egobody_dataset.py:272-273.  select(pred, target): the n vertices where pred holds, in mesh order;
+ * k = n / target; rows r / k of the ranks r with r % k == 0 and r / k < target.  The predicates are float64 with every operation rounded in the
+ * reference's order; the output row is T_out v of the ORIGINAL mesh vertex, ((T0 x + T1 y) + T2 z) + T3 in float64, rounded once to float32.
+ *
+ * Meshes: one float64 SoA buffer verts = [x[total_verts] | y[total_verts] | z[total_verts]], mesh m is [mesh_offsets[m], mesh_offsets[m+1]).
+ * Items go in groups of up to EHM_SCENE_GROUP items of the same mesh (groups [num_groups, 1 + EHM_SCENE_GROUP] int32: the mesh, then the items,
+ * -1 after the last): a vertex load serves the whole group.  params [B, EHM_SCENE_PARAMS] float64 per item, at the EHM_SCENE_P_* slots: the
+ * chain (chain_len 3x4 matrices, rows of 4) or the cube's cos a, sin a, centre x, z, bounds and cube_size; T_out (3x4) in both modes.
+ * Per item, written: status (EHM_SCENE_OK, _TOO_FEW: n < target, _EMPTY_CROP: no vertex passes the xz test) and n_selected; points
+ * [B, ceil(target/stride), 3] f32 and index [B, ceil(target/stride)] int64 (the source vertex within its mesh; may be NULL) of the OK items
+ * only.  At most five launches; the workspace (ehm_scene_workspace_bytes) needs no initialisation. */
+#define EHM_SCENE_GROUP 8
+#define EHM_SCENE_PARAMS 64
+#define EHM_SCENE_MAX_CHAIN 4
+#define EHM_SCENE_P_CHAIN 0   /* whole scene: chain_len x 12 */
+#define EHM_SCENE_P_COS 0     /* cube: cos a, sin a, cx, cz, x_min, x_max, z_min, z_max, cube_size */
+#define EHM_SCENE_P_SIN 1
+#define EHM_SCENE_P_CX 2
+#define EHM_SCENE_P_CZ 3
+#define EHM_SCENE_P_XMIN 4
+#define EHM_SCENE_P_XMAX 5
+#define EHM_SCENE_P_ZMIN 6
+#define EHM_SCENE_P_ZMAX 7
+#define EHM_SCENE_P_CUBE 8
+#define EHM_SCENE_P_OUT 48    /* both: T_out, 12 */
+enum { EHM_SCENE_WHOLE = 0, EHM_SCENE_CUBE = 1 };
+enum { EHM_SCENE_OK = 0, EHM_SCENE_TOO_FEW = 1, EHM_SCENE_EMPTY_CROP = 2 };
+typedef struct ehm_scene_desc {
+  const double* verts;          /* [3, total_verts] */
+  int64_t total_verts;
+  const int64_t* mesh_offsets;  /* [num_meshes + 1] */
+  int num_meshes;
+  int64_t max_mesh_verts;       /* the largest mesh's vertex count (sizes the grid and the workspace) */
+  const int32_t* groups;        /* [num_groups, 1 + EHM_SCENE_GROUP] */
+  int num_groups;
+  const double* params;         /* [B, EHM_SCENE_PARAMS] */
+  int mode, chain_len, B, target, stride;
+  float* points;                /* [B, ceil(target/stride), 3] */
+  int64_t* index;               /* [B, ceil(target/stride)] or NULL */
+  int64_t* n_selected;          /* [B] */
+  int32_t* status;              /* [B] */
+  void* workspace;
+  int64_t workspace_bytes;
+} ehm_scene_desc;
+/* *bytes = the workspace ehm_scene_select needs for this descriptor (its workspace fields are not read); a status, like every entry point whose
+ * result is not a value of its own */
+int ehm_scene_workspace_bytes(const ehm_scene_desc* d, int64_t* bytes);
+int ehm_scene_select(const ehm_scene_desc* d, void* stream);
+
 /* ------------------------------------------------------------------ per-item scalars ---------- */
 /* The per-item scalar work of EgoHMR.forward in front of the encoders, in two launches:
  *   vis [B,24] u8       models/egohmr/egohmr.py:186-188: confidence > 0, OpenPose joint `force_visible` (8) always on, gathered by joint_map
