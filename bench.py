@@ -9,7 +9,9 @@ conditioning encoders (ResNet-50, scene PointNet, heads) once, then T denoising 
 two passes with diffuse_fuse, rot6d->rotmat + SMPL LBS in every step, sampler update), final decode, and
 at N > 1 the single RCCL all-gather of the packed SMPL parameters.  The default workload is the one
 BASELINE.json's metric is quoted on: 100-step DDPM, batch 256 per GPU, 1 sample/item, 4096 scene points.
-Rank 0 prints ONE JSON line (contract in the task statement) with `roofline` and `cpu_baseline` objects.
+Rank 0 prints ONE JSON line (contract in the task statement).  A plain run measures the headline alone (its `roofline` and `cpu_baseline`
+are null); `--full` adds everything else: comparison legs, roofline and per-kernel figures from a profiled call, the CPU baselines,
+BASELINE configs 2-5 and the evaluation block.
 """
 from __future__ import annotations
 
@@ -310,8 +312,9 @@ def cpu_baseline(n, rs, num_scene_points, budget_s, faithful=True):
                       f"{done} of {T} steps timed ({dt:.1f} s)" + (f", extrapolated linearly to {T} steps" if faithful and done < T else "")}
 
 
-def measure(args, workload, steps, warmup, legs_on, cpu_seconds, dev, rank, world, tier_compare=True, dump_dir=None):
-    """One workload end to end (model, inputs, calibration, warm-up, the timed region, the profiled call, the legs): the JSON object of rank 0.
+def measure(args, workload, steps, warmup, legs_on, cpu_seconds, dev, rank, world, tier_compare=True, dump_dir=None, full=False):
+    """One workload end to end (model, inputs, calibration, warm-up, the timed region): the JSON object of rank 0.
+    full: also the collective timing, the legs, the profiled call, the encoder split and the CPU baselines, behind the timed region.
     dump_dir: rank 0 writes what the last timed call returned there (output_arrays)."""
     if args.precision_given is None and workload in WORKLOAD_PRECISION:
         args = argparse.Namespace(**{**vars(args), "precision": WORKLOAD_PRECISION[workload]})
@@ -401,7 +404,65 @@ def measure(args, workload, steps, warmup, legs_on, cpu_seconds, dev, rank, worl
         dump_outputs(dump_dir, output_arrays(outs, gathered))
     dt = edist.max_over_ranks(dt_rank, dev)
     per_rank = edist.gather_floats(B * S * steps / dt_rank, dev)                   # bodies/s of every rank (its own clock)
-    gather_ms = None
+    assert torch.isfinite(res["other_outputs"]["pred_vertices"]).all()
+    assert gathered.shape == (world * B * S, edist.PACKED_WIDTH)
+    lowprec = fs.last_lowprec                                                        # leading steps on plain f16 operands in the timed calls
+    sched = fs.schedule_info
+    value = world * B * S * steps / dt
+    k_last = T - lowprec
+    passes = 2
+
+    # the headline object: what the timed calls and the calibration before them measured, nothing that takes a launch of its own
+    out = None
+    if rank == 0:
+        num_masked = fs.prepare(batch).num_masked                                   # (the last timed call's conditioning, still cached: no launch)
+        out = {
+            "metric": "sampled bodies/sec (100-step DDPM, batch 256)" if workload == "ddpm100" else f"sampled bodies/sec ({workload})",
+            "value": value,
+            "unit": "bodies/s",
+            "n_gpus": world,
+            "n_ranks_seen": world if world == 1 else int(torch.distributed.get_world_size()),
+            "per_rank_bodies_per_s": per_rank, "all_gather_ms": None,
+            "multi_gpu_note": None if world == 1 else ("weak scaling: every rank runs the whole N = 1 job on its own items, value = all items / the slowest rank's time; expect a "
+                                                       "few percent below N x the one-GPU number: N sockets at their own 1400 W caps clock independently (box-to-box spread "
+                                                       "was +-3 %), and each rank's Python thread enqueues ~200 launches per call"),
+            "steps": steps,
+            "warmup": warmup,
+            "ms_per_step": dt / steps * 1e3,
+            "higher_is_better": True,
+            "scaling": "weak",
+            "vs_baseline": None,
+            "dtype": {"f32": "f32",
+                      "f16x3": "f32 results: denoiser GEMMs as 3x f16 MFMA on hi/lo-split operands (f32 accumulate) on the last "
+                               f"{k_last} of {T} steps, plain f16 operands on the first {lowprec}; k = {k_last} is " +
+                               ("given on the command line" if args.f16x3_last_steps is not None else "CALIBRATED on the loaded weights") +
+                               f" to a {model.schedule_tol:g} m bar (final bodies vs the all-split loop; the contract bar is 1e-4 m: leg schedule_at_contract_tol; docs/EXPERIMENTS.md 3.6)",
+                      "f16": "f16 denoiser GEMMs and activations (f32 accumulate) + f32 everything else"}[args.precision],
+            "data": "synthetic",
+            "full": bool(full),
+            "config": {"workload": desc, "name": workload, "items_per_gpu": B, "samples_per_item": S, "samples_in_one_loop": bool(S > 1), "collision_guided": guided, "denoising_steps": T,
+                       "scene_points": N, "gcn_passes_per_step": passes, "lbs_every_step": bool(model.lbs_every_step),
+                       "gcn_precision": args.precision, "encoder_precision": model.encoder_precision, "guidance_weight": w_guid if guided else None, "f16x3_last_steps": k_last if args.precision == "f16x3" else None,
+                       "f16x3_last_steps_policy": str(model.f16x3_last_steps),
+                       "pass_pruning": {"items_without_second_pass": int(B - num_masked) if model.prune_passes else 0, "of": B,
+                                        "note": "exact (egohmr.py:249-254): all-visible items skip the image-masked pass; the synthetic "
+                                                "visibility draw (Bernoulli 0.6 per OpenPose joint, SURVEY 8d) almost never produces one"},
+                       "weights": ("seeded synthetic, x_t-SENSITIVE (trained-like: d x0 / d x_t follows the MMSE gain of a Gaussian prior; synthetic.make_sensitive_state_dict)"
+                                   if args.weights == "sensitive" else "seeded synthetic, plain random network (ignores x_t; rounds 1-2)") + " - no checkpoint offline",
+                       "smpl": "synthetic SMPL-shaped asset",
+                       "parallelism": f"items sharded x{world}, one RCCL all-gather of [B,226] at the end"},
+            "schedule": None if args.precision != "f16x3" else {
+                "f16x3_last_steps": k_last, "f16_steps": lowprec, "calibrated": sched is not None and args.f16x3_last_steps is None,
+                "explicit_k_from_command_line": args.f16x3_last_steps,
+                "schedule_calibrated_on": None if sched is None else f"the loaded ({args.weights}) weights, {sched['bodies']} items of this batch, 2 private noise draws, tol {sched['tol_m']:g} m",
+                "calibration_seconds_once_per_checkpoint_and_sampler": t_cal, "calibration_trials": None if sched is None else sched["trials"]},
+            "bodies_per_step": B * S,
+            "body_denoising_steps_per_s": value * T,                      # makes loops of different length comparable (C5: 1000 steps per body)
+        }
+    if not full:
+        return out
+
+    # --full: everything else this workload reports, each with launches of its own behind the timed region
     if world > 1:                                                                    # the one collective of a call, timed apart (5 calls, barriers outside)
         pk = torch.cat([edist.pack_params(res["other_outputs"]["pred_smpl_params"])] * S, 0)
         edist.gather_packed(pk)
@@ -412,10 +473,8 @@ def measure(args, workload, steps, warmup, legs_on, cpu_seconds, dev, rank, worl
             edist.gather_packed(pk)
         torch.cuda.synchronize()
         gather_ms = edist.max_over_ranks((time.perf_counter() - t1) / 5 * 1e3, dev)
-    assert torch.isfinite(res["other_outputs"]["pred_vertices"]).all()
-    assert gathered.shape == (world * B * S, edist.PACKED_WIDTH)
-    lowprec = fs.last_lowprec                                                        # leading steps on plain f16 operands in the timed calls
-    sched = fs.schedule_info
+        if rank == 0:
+            out["all_gather_ms"] = gather_ms
 
     # comparison legs (rank-local, N=1 only): the same job, same noise, (a) WITHOUT the precision schedule (every step split-f16: f32-grade
     # for ANY weights), (b) with the hidden convs on the f32-input MFMA (exact f32 products), (c) on plain f16 operands in every step (the
@@ -538,7 +597,6 @@ def measure(args, workload, steps, warmup, legs_on, cpu_seconds, dev, rank, worl
     t_enc = time.perf_counter() - t1
 
     if rank == 0:
-        passes = 2
         hid = model.diffusion_model.hid_dim
         # samples of an item run in groups of loop_bodies // B per fused loop (FusedSampler.run_samples): a LAUNCH works on S_l samples' bodies
         lb = int(getattr(model, "loop_bodies", 0) or 0)
@@ -643,51 +701,13 @@ def measure(args, workload, steps, warmup, legs_on, cpu_seconds, dev, rank, worl
                     "mfma", nb * 2.0 * 20670 * 207, PEAK_F32_MFMA_TFLOPS, "TFLOP/s",
                     "2 x bodies x 20670 x 207 flop, exact-f32 MFMA (v_mfma_f32_32x32x2_f32; 224 of 207 columns issued)")
             guid["guided_step_total_us"] = prof["guidance"]["ms_per_call"] / prof["guidance"]["launches_per_call"] * 1e3
-        value = world * B * S * steps / dt
         flops_per_body = {"ddpm100": 183.8e9, "c2_ddim10": 35.5e9}.get(workload)  # SURVEY 8d, hoisted, with diffuse_fuse
         guid_steps = prof["guidance"]["launches_per_call"]
-        k_last = T - lowprec
-        out = {
-            "metric": "sampled bodies/sec (100-step DDPM, batch 256)" if workload == "ddpm100" else f"sampled bodies/sec ({workload})",
-            "value": value,
-            "unit": "bodies/s",
-            "n_gpus": world,
-            "n_ranks_seen": world if world == 1 else int(torch.distributed.get_world_size()),
-            "per_rank_bodies_per_s": per_rank, "all_gather_ms": gather_ms,
-            "multi_gpu_note": None if world == 1 else ("weak scaling: every rank runs the whole N = 1 job on its own items, value = all items / the slowest rank's time; expect a "
-                                                       "few percent below N x the one-GPU number: N sockets at their own 1400 W caps clock independently (box-to-box spread "
-                                                       "was +-3 %), and each rank's Python thread enqueues ~200 launches per call"),
-            "steps": steps,
-            "warmup": warmup,
-            "ms_per_step": dt / steps * 1e3,
-            "higher_is_better": True,
-            "scaling": "weak",
-            "vs_baseline": None,
-            "dtype": {"f32": "f32",
-                      "f16x3": "f32 results: denoiser GEMMs as 3x f16 MFMA on hi/lo-split operands (f32 accumulate) on the last "
-                               f"{k_last} of {T} steps, plain f16 operands on the first {lowprec}; k = {k_last} is " +
-                               ("given on the command line" if args.f16x3_last_steps is not None else "CALIBRATED on the loaded weights") +
-                               f" to a {model.schedule_tol:g} m bar (final bodies vs the all-split loop; the contract bar is 1e-4 m: leg schedule_at_contract_tol; docs/EXPERIMENTS.md 3.6)",
-                      "f16": "f16 denoiser GEMMs and activations (f32 accumulate) + f32 everything else"}[args.precision],
-            "data": "synthetic",
-            "config": {"workload": desc, "name": workload, "items_per_gpu": B, "samples_per_item": S, "samples_in_one_loop": bool(S > 1), "collision_guided": guided, "denoising_steps": T,
-                       "scene_points": N, "gcn_passes_per_step": passes, "lbs_every_step": bool(model.lbs_every_step),
-                       "gcn_precision": args.precision, "encoder_precision": model.encoder_precision, "guidance_weight": w_guid if guided else None, "f16x3_last_steps": k_last if args.precision == "f16x3" else None,
-                       "f16x3_last_steps_policy": str(model.f16x3_last_steps),
-                       "pass_pruning": {"items_without_second_pass": int(B - st.num_masked) if model.prune_passes else 0, "of": B,
-                                        "note": "exact (egohmr.py:249-254): all-visible items skip the image-masked pass; the synthetic "
-                                                "visibility draw (Bernoulli 0.6 per OpenPose joint, SURVEY 8d) almost never produces one"},
-                       "weights": ("seeded synthetic, x_t-SENSITIVE (trained-like: d x0 / d x_t follows the MMSE gain of a Gaussian prior; synthetic.make_sensitive_state_dict)"
-                                   if args.weights == "sensitive" else "seeded synthetic, plain random network (ignores x_t; rounds 1-2)") + " - no checkpoint offline",
-                       "smpl": "synthetic SMPL-shaped asset",
-                       "parallelism": f"items sharded x{world}, one RCCL all-gather of [B,226] at the end"},
-            "schedule": None if args.precision != "f16x3" else {
-                "f16x3_last_steps": k_last, "f16_steps": lowprec, "calibrated": sched is not None and args.f16x3_last_steps is None,
-                "explicit_k_from_command_line": args.f16x3_last_steps,
-                "schedule_calibrated_on": None if sched is None else f"the loaded ({args.weights}) weights, {sched['bodies']} items of this batch, 2 private noise draws, tol {sched['tol_m']:g} m",
-                "calibration_seconds_once_per_checkpoint_and_sampler": t_cal, "calibration_trials": None if sched is None else sched["trials"],
+        if out["schedule"] is not None:
+            out["schedule"].update({
                 "measured_gain_dx0_dxt": fs.measure_gain(batch, timesteps=sorted({diffusion.timestep_map[-1], diffusion.timestep_map[T // 2], diffusion.timestep_map[T // 10], 0}, reverse=True)),
-                "gain_note": "directional || x0(x_t + d) - x0(x_t) || / || d || through the product's denoiser, per ORIGINAL timestep; ~1 at low noise = early rounding errors are carried"},
+                "gain_note": "directional || x0(x_t + d) - x0(x_t) || / || d || through the product's denoiser, per ORIGINAL timestep; ~1 at low noise = early rounding errors are carried"})
+        out.update({
             "roofline": kernels[dominant],
             "roofline_other_kernel": {k: v for k, v in kernels.items() if k != dominant} or None,
             "roofline_hbm": hbm,
@@ -700,15 +720,13 @@ def measure(args, workload, steps, warmup, legs_on, cpu_seconds, dev, rank, worl
                        "parity_ceiling_bodies_per_s": (PEAK_F16_MFMA_TFLOPS / 3) * 1e12 / flops_per_body if flops_per_body else None,
                        "note": "with every product as 3 MFMA the dense f16 peak allows 833 TFLOP/s algorithmic = the ceiling above, so >= 10k bodies/s is out of "
                                "reach at f32-grade arithmetic on every step"},
-        }
+        })
         out.update(legs)
         if cpu_seconds > 0 and world == 1:
             out["cpu_baseline"] = cpu_baseline(n, rs, N, cpu_seconds * 0.6)
             out["cpu_baseline_hoisted"] = cpu_baseline(n, rs, N, cpu_seconds * 0.4, faithful=False) if T <= 100 else None
         else:
             out["cpu_baseline"] = None
-        out["bodies_per_step"] = B * S
-        out["body_denoising_steps_per_s"] = value * T                      # makes loops of different length comparable (C5: 1000 steps per body)
         if guid_steps:
             out["guided_step_us"] = prof["guidance"]["ms_per_call"] / guid_steps * 1e3
         if "f32_grade_path_of_this_job" in legs:
@@ -727,7 +745,11 @@ def main():
     ap.add_argument("--workload", default="ddpm100", choices=sorted(WORKLOADS))
     ap.add_argument("--batch", type=int, default=256, help="items per GPU")
     ap.add_argument("--scene-points", type=int, default=4096)
-    ap.add_argument("--cpu-seconds", type=float, default=15.0, help="time budget of the CPU baseline leg (0 = skip)")
+    ap.add_argument("--full", action="store_true",
+                    help="measure everything beyond the headline too: comparison legs, the profiled call behind the roofline and per-kernel figures, "
+                         "the encoder split, the CPU baselines, BASELINE configs 2-5 and the evaluation block.  Without it a run sets up, warms up, "
+                         "times --steps calls, writes --dump-outputs and prints the line (roofline and cpu_baseline null)")
+    ap.add_argument("--cpu-seconds", type=float, default=15.0, help="with --full: time budget of the CPU baseline leg (0 = skip)")
     ap.add_argument("--no-lbs-every-step", action="store_true")
     ap.add_argument("--precision", default=None, choices=["f32", "f16x3", "f16"],
                     help="arithmetic of the hidden GCN convs (docs/EXPERIMENTS.md 3.2): f32 MFMA | split-f16 MFMA (f32-grade) | plain f16 (not parity-grade)")
@@ -738,8 +760,8 @@ def main():
                     help="explicit k instead of the calibration (e.g. the k a previous run printed): no calibration launches, so that under rocprofv3 "
                          "every launch of a chain kernel is a full-size one and the kernel-stats average equals roofline.avg_launch_ms * 8")
     ap.add_argument("--loop-bodies", type=int, default=None, help="EgoHMR.loop_bodies for this run (bodies per fused loop of a multi-sample batch)")
-    ap.add_argument("--no-legs", action="store_true", help="skip the comparison legs (all-f16x3, f32, f16, other weight set)")
-    ap.add_argument("--no-configs", action="store_true", help="default workload only: do not append BASELINE configs 2 and 3 (configs.c2_ddim10 / configs.c3_guided)")
+    ap.add_argument("--no-legs", action="store_true", help="with --full: skip the comparison legs (all-f16x3, f32, f16, other weight set)")
+    ap.add_argument("--no-configs", action="store_true", help="with --full, default workload only: do not append BASELINE configs 2-5 (configs.c2_ddim10 ... configs.c5_volsmpl_ddpm1000)")
     ap.add_argument("--launch-check", action="store_true", help="only initialise the ranks, report the world size, exit (works without a GPU: gloo)")
     ap.add_argument("--dump-outputs", metavar="DIR", default=None,
                     help="write what the last timed call of the headline workload returned to DIR/<name>.npy (float32 / float64, at most 64 MB: a fixed "
@@ -790,14 +812,14 @@ def main():
     dev = torch.device("cuda", local)
     assert torch.cuda.current_device() == local, (torch.cuda.current_device(), local)   # every native call launches on the CURRENT device's stream
 
-    out = measure(args, args.workload, args.steps, args.warmup, not args.no_legs, args.cpu_seconds, dev, rank, world, dump_dir=args.dump_outputs)
-    # BASELINE configs 2 and 3 inside the default line, so that the driver's ONE run observes them (3 timed calls each, no legs)
-    if args.workload == "ddpm100" and world == 1 and not args.no_configs:
+    out = measure(args, args.workload, args.steps, args.warmup, not args.no_legs, args.cpu_seconds, dev, rank, world, dump_dir=args.dump_outputs, full=args.full)
+    # --full: BASELINE configs 2-5 inside the same line (3 timed calls each, 2 for config 5, no legs)
+    if args.full and args.workload == "ddpm100" and world == 1 and not args.no_configs:
         keep = ("metric", "value", "unit", "steps", "warmup", "ms_per_step", "dtype", "config", "schedule", "roofline", "roofline_hbm", "roofline_guidance", "breakdown_ms",
                 "bodies_per_step", "body_denoising_steps_per_s", "guided_step_us", "mpjpe_vs_f32_path_mm", "f32_grade_path_of_this_job")
         subs = {}
         for wl, nsteps in (("c2_ddim10", 3), ("c3_guided", 3), ("c4_ddim50_s5", 3), ("c5_volsmpl_ddpm1000", 2)):
-            sub = measure(args, wl, nsteps, 1, False, 0.0, dev, rank, world)
+            sub = measure(args, wl, nsteps, 1, False, 0.0, dev, rank, world, full=True)
             subs[wl] = {k: sub[k] for k in keep if k in sub}
             subs[wl]["gcn_precision"] = sub["config"]["gcn_precision"]
             subs[wl]["encoder_precision"] = sub["config"]["encoder_precision"]          # (C5 names the fp16 tier: its encoders run hi-only too)

@@ -83,6 +83,23 @@ def test_compact_line_multi_gpu_keys():
     assert o["cpu_baseline"] is None and len(json.dumps(o)) < 4096
 
 
+def test_compact_line_of_a_plain_run():
+    """a run without --full measures the headline alone: its detail object has no roofline, legs, CPU baseline, breakdown or configs, and the
+    line still carries every contract key (roofline and cpu_baseline null) with the headline's figures unchanged"""
+    d = _canned()
+    plain = {k: d[k] for k in ("metric", "value", "unit", "n_gpus", "n_ranks_seen", "per_rank_bodies_per_s", "all_gather_ms", "multi_gpu_note", "steps",
+                               "warmup", "ms_per_step", "higher_is_better", "scaling", "vs_baseline", "dtype", "data", "config", "schedule")}
+    plain.update(full=False, bodies_per_step=256, body_denoising_steps_per_s=d["value"] * 100)
+    o = _strict(bench.compact_line(plain))
+    for k in CONTRACT_KEYS:
+        assert k in o, k
+    assert o["roofline"] is None and o["cpu_baseline"] is None
+    assert not {"configs", "legs", "roofline_hbm", "evaluation_block", "encoders_ms"} & set(o)
+    full = _strict(bench.compact_line(d))
+    for k in ("metric", "value", "unit", "higher_is_better", "dtype", "ms_per_step", "steps", "warmup", "config"):
+        assert o[k] == full[k], k
+
+
 def test_every_committed_round5_line_is_compact():
     """builder-run compact lines kept under profiles/ (r05*_line.json) obey the same bound"""
     for p in glob.glob(os.path.join(REPO, "profiles", "r05*_line.json")):
