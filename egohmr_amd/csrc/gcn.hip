@@ -494,12 +494,12 @@ static void launch_input_conv(const GcnInputArgs& a, hipStream_t st) {
   if constexpr (PRE) hipLaunchKernelGGL(gcn_input_rows_kernel<OUT>, grid, dim3(256), 0, st, a);
   else hipLaunchKernelGGL(gcn_input_kernel<OUT>, grid, dim3(256), 0, st, a);
 }
-// the input conv (PRE: on the pre-activations a.pre), its rows in the activation format of `prec`
+// the input conv (PRE: on the pre-activations a.pre), its rows in the activation format `fmt` (gcn_input_format)
 template <bool PRE>
-static int input_conv(const GcnInputArgs& a, int prec, hipStream_t st) {
-  if (prec == EHM_PREC_F32) launch_input_conv<PRE, 0>(a, st);
-  else if (prec == EHM_PREC_F16X3) launch_input_conv<PRE, 1>(a, st);   // X2 split rows
-  else launch_input_conv<PRE, 2>(a, st);                                // plain f16 rows
+static int input_conv(const GcnInputArgs& a, int fmt, hipStream_t st) {
+  if (fmt == EHM_PREC_F32) launch_input_conv<PRE, 0>(a, st);
+  else if (fmt == EHM_PREC_F16X3) launch_input_conv<PRE, 1>(a, st);   // X2 split rows
+  else launch_input_conv<PRE, 2>(a, st);                               // plain f16 rows
   EHM_LAUNCH_CHECK();
   return 0;
 }
@@ -508,7 +508,7 @@ int ehm_gcn_input_impl(const ehm_gcn* h, const GcnRun& r, const float* h_img, co
                        const float* Wx, const float* tvec, float* out, int B, int passes, hipStream_t st) {
   GcnInputArgs a;
   const int rc = ehm_gcn_input_args(h, r, h_img, h_oth, vis, x, Wx, tvec, out, B, passes, &a);
-  return rc != 0 ? rc : input_conv<false>(a, r.precision, st);
+  return rc != 0 ? rc : input_conv<false>(a, gcn_input_format(h, r.precision), st);
 }
 
 extern "C" int ehm_gcn_input_layer(ehm_gcn* h, const float* h_img, const float* h_oth, const uint8_t* vis, const float* x,
@@ -531,7 +531,7 @@ extern "C" int ehm_gcn_input_layer_rows(ehm_gcn* h, const float* pre, float* out
   a.sticky = h->chain_sticky;
   h->run.valid_rows = (int64_t)bodies * kJ;
   a.pre = pre;
-  return input_conv<true>(a, h->run.precision, (hipStream_t)stream);
+  return input_conv<true>(a, gcn_input_format(h, h->run.precision), (hipStream_t)stream);
 }
 
 static int hidden_layer(const ehm_gcn* h, const GcnRun& r, int layer, const float* X, const float* residual, float* out, int64_t rows_pad,

@@ -80,6 +80,13 @@ struct ehm_gcn {
   ehm_nonlocal_params nonlocal{};   // optional non-local block of the one-call loop (ehm_gcn_set_nonlocal); Ci == 0: none
 };
 
+// Activation format of the rows the input conv writes under precision `prec` (EHM_PREC_* values as formats: float32 / X2 / f16 rows).  The output
+// conv reads f16 rows in mode 2 and float32 rows otherwise, so in mode 1 the conv in front of it writes float32: the last hidden conv, or - with
+// no hidden conv at all - the input conv itself.
+static inline int gcn_input_format(const ehm_gcn* h, int prec) {
+  return (prec == EHM_PREC_F16X3 && h->num_hidden == 0) ? (int)EHM_PREC_F32 : prec;
+}
+
 // Split-f16 activation / weight format ("X2<G>"): row-major rows of K values, every group of G consecutive k stored as
 // G f16 "hi" followed by G f16 "lo" (value = hi + lo, hi = rn_f16(x), lo = rn_f16(x - hi)).  Same bytes per row as
 // float32.  G = 32: one 128-byte line per 32-k tile.

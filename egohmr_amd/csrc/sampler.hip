@@ -336,7 +336,7 @@ extern "C" int ehm_sample_loop(ehm_gcn* gcn, ehm_smpl* smpl, const ehm_sample_de
       if (rc == 0 && !last) rc = ehm_gcn_input_args(gcn, run, h_img, h_oth, vis, dst, Wx, tvecs + (int64_t)(k + 1) * 2 * hid, w.X[0], B, d->passes, &nin);
       if (rc == 0)
         rc = ehm_step_fused_impl(out_dev, feat, run.precision, vis, w.x_cur, eps, grad, dst, defer_skin ? w.loop_x0 + (int64_t)pending * n : x0_final,
-                                 &c, d->ddim, d->passes, run.slots(d->passes), B, last ? nullptr : &nin, prec_of(k + 1), st);
+                                 &c, d->ddim, d->passes, run.slots(d->passes), B, last ? nullptr : &nin, gcn_input_format(gcn, prec_of(k + 1)), st);
       input_done = !last;
       if (rc == 0 && defer_skin) {
         pending_poses = true;
@@ -373,7 +373,7 @@ extern "C" int ehm_sample_loop(ehm_gcn* gcn, ehm_smpl* smpl, const ehm_sample_de
       } else if (rc == 0) {
         rc = ehm_step_body_impl(smpl, hs, out_dev, vis, w.x_cur, eps, grad, dst, x0_final, &c, d->ddim, d->passes, run.slots(d->passes),
                                 (d->lbs_every_step || last) ? 1 : 0,
-                                betas, mean, std_, verts, joints, R, w.A, pose6d, B, st, pnin, prec_of(k + 1), &fused);
+                                betas, mean, std_, verts, joints, R, w.A, pose6d, B, st, pnin, gcn_input_format(gcn, prec_of(k + 1)), &fused);
       }
       input_done = fused != 0;
     }

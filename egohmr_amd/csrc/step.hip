@@ -134,7 +134,7 @@ void launch_fused(int next_prec, int B, hipStream_t st, const StepFusedArgs& a) 
 }  // namespace
 
 // The tail of a step + the head of the next one (next_input == nullptr: the loop's last step).  `X` = the step's last hidden conv's rows in
-// precision `prec` (f16 rows for EHM_PREC_F16, float32 rows otherwise); the next step's rows are written in `next_prec`'s format.
+// precision `prec` (f16 rows for EHM_PREC_F16, float32 rows otherwise); the next step's rows are written in the format `next_prec` (gcn_input_format).
 int ehm_step_fused_impl(const void* out_dev, const float* X, int prec, const uint8_t* vis, const float* x, const float* noise, const float* grad,
                         float* x_next, float* x0, const ehm_step_coefs* c, int ddim, int passes, const int32_t* mask_slot, int B,
                         const GcnInputArgs* next_input, int next_prec, hipStream_t st) {

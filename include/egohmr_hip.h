@@ -116,7 +116,7 @@ void ehm_gcn_destroy(ehm_gcn* h);
  * f32-grade results); 2 = plain f16 operands and f16 activation storage (NOT parity-grade on its own - BASELINE config 5's
  * fp16 denoiser, and the early steps of ehm_sample_desc.lowprec_steps).
  * Activation matrices exchanged between ehm_gcn_input_layer -> ehm_gcn_hidden_layer / _stack: mode 0 float32 [rows_pad,hid];
- * mode 1 the opaque "X2" split format (same byte size), except that the LAST hidden conv writes float32; mode 2 f16
+ * mode 1 the opaque "X2" split format (same byte size), except that the LAST hidden conv writes float32 (with no hidden conv: the input conv); mode 2 f16
  * [rows_pad,hid] throughout.  ehm_gcn_output_layer reads what the handle's mode produces.  ehm_gcn_pack/unpack_activations convert float32 <-> the mode's format (tests, interop). */
 int ehm_gcn_set_precision(ehm_gcn* h, int mode);
 int ehm_gcn_get_precision(const ehm_gcn* h);

@@ -99,7 +99,7 @@ def modulated_graph_conv(sd, p, x, adj):
     h1 = torch.matmul(x, W[1])
     a = adj + sd[p + ".adj2"]
     a = (a.T + a) / 2
-    E = torch.eye(a.size(0), dtype=a.dtype)
+    E = torch.eye(a.size(0), dtype=a.dtype, device=a.device)
     out = torch.matmul(a * E, M * h0) + torch.matmul(a * (1 - E), M * h1)
     return out + sd[p + ".bias"].view(1, 1, -1)
 
