@@ -57,13 +57,15 @@ class ResNet50Features(nn.Module):
                 blocks.append(_Bottleneck(cin, width, stride if b == 0 else 1, project=(b == 0)))
                 cin = width * 4
             setattr(self, f"layer{i}", nn.Sequential(*blocks))
+        self._fold_key_fn = self._fold_key = self._fold_fn = None      # current()
+        self._sk_host = self._sk_event = self._sk_ws_checked = None    # _sk_status_async / check_status
 
     def current(self):
         """folded() for the weights as they are now: rebuilt when a parameter / buffer changes (storage or version counter)."""
-        if getattr(self, "_fold_key_fn", None) is None:
+        if self._fold_key_fn is None:
             self._fold_key_fn = _lib.TensorKey(self)
         key = self._fold_key_fn()
-        if getattr(self, "_fold_key", None) != key:
+        if self._fold_key != key:
             self._fold_fn, self._fold_key = self.folded(), key
         return self._fold_fn
 
@@ -77,10 +79,9 @@ class ResNet50Features(nn.Module):
         that has arrived is looked at first (no host wait on the product path)."""
         if ws is None:                                     # (no conv of this pass had a stream-K plan)
             return
-        ev = getattr(self, "_sk_event", None)
-        if ev is not None and ev.query():
+        if self._sk_event is not None and self._sk_event.query():
             self.check_status()
-        if getattr(self, "_sk_host", None) is None:
+        if self._sk_host is None:
             self._sk_host = torch.zeros(1, dtype=torch.int32).pin_memory()
         _lib.api().ehm_conv_x2_workspace_status(ws, self._sk_host.data_ptr(), _lib.stream_ptr())
         self._sk_event = torch.cuda.Event()
@@ -90,10 +91,9 @@ class ResNet50Features(nn.Module):
     def check_status(self):
         """Raise if a stream-K conv of an earlier trunk pass timed out waiting for a partner block's partial sums (its tiles are NaN and the
         workspace's counters poisoned); the workspace is zeroed again by the call, so the next pass is clean.  Waits for that pass."""
-        ev = getattr(self, "_sk_event", None)
-        if ev is None:
+        if self._sk_event is None:
             return
-        ev.synchronize()
+        self._sk_event.synchronize()
         self._sk_event = None
         if int(self._sk_host[0]) != 0:
             self._sk_host.zero_()
@@ -286,8 +286,7 @@ class ResnetPointnet(nn.Module):
         for b in range(4):
             setattr(self, f"block_{b}", _ResBlockFC(2 * hidden_dim, hidden_dim, hidden_dim))
         self.fc_c = nn.Linear(hidden_dim, out_dim)
-        self._packed = None
-        self._packed_key = None
+        self._packed = self._packed_key = self._tkey = None
 
     # ------------------------------------------------------------------ weight preparation (once per weight version)
     @staticmethod
@@ -303,7 +302,7 @@ class ResnetPointnet(nn.Module):
         return buf, scale, w
 
     def _prepare(self, device):
-        if getattr(self, "_tkey", None) is None:
+        if self._tkey is None:
             self._tkey = _lib.TensorKey(self)
         key = self._tkey() + (str(device),)
         if self._packed is not None and self._packed_key == key:

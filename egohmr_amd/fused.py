@@ -8,6 +8,8 @@ models/egohmr/egohmr.py:173-303 (forward) and :517-570 (guide_coll); see DESIGN.
 from __future__ import annotations
 
 import ctypes as C
+import dataclasses
+from functools import partial
 from types import SimpleNamespace
 
 import torch
@@ -18,8 +20,62 @@ from . import smpl as smpl_mod
 PRECISIONS = {"f32": 0, "f16x3": 1, "f16": 2}
 
 # ---------------------------------------------------------------------------------------------- native engine
-class _Prepared(SimpleNamespace):
-    pass
+def pass_map(need):
+    """Per-item `need` [B] (True: an invisible joint, the item takes the image-masked pass too) -> (mask_items: ascending indices with need,
+    mask_slot [B]: rank of b among them or -1, num_masked: their count), int32 - as pass_map_kernel (csrc/prep.hip) writes it.  One host read-back."""
+    need = need.reshape(-1).bool()
+    rank = torch.cumsum(need, 0, dtype=torch.int32) - 1
+    mask_slot = torch.where(need, rank, torch.full_like(rank, -1)).contiguous()
+    mask_items = torch.nonzero(need).reshape(-1).to(torch.int32).contiguous()
+    return mask_items, mask_slot, int(mask_items.numel())
+
+
+@dataclasses.dataclass
+class _Prepared:
+    """The step-invariant conditioning of a batch (FusedSampler.prepare)."""
+    B: int
+    h_img: torch.Tensor                 # [B,2,hid] image slice of the input conv        } per item: PER_ITEM
+    h_oth: torch.Tensor                 # [B,2,hid] scene + translation + camera slice
+    vis: torch.Tensor                   # [B,24] uint8 joint visibility
+    vis_bool: torch.Tensor              # the same as bool
+    betas: torch.Tensor
+    scene: torch.Tensor
+    transl: torch.Tensor
+    fx: torch.Tensor
+    cam_cx: torch.Tensor
+    cam_cy: torch.Tensor
+    img_feats: torch.Tensor
+    scene_feats: torch.Tensor
+    finite: torch.Tensor                # [B] bool: the item's inputs are finite
+    mask_items: torch.Tensor            # the pass map (pass_map above); num_masked = -1: no map
+    mask_slot: torch.Tensor
+    num_masked: int
+    inputs: list = None                 # strong references to the batch tensors behind the cache key (prepare)
+
+    PER_ITEM = ("h_img", "h_oth", "vis", "vis_bool", "betas", "scene", "transl", "fx", "cam_cx", "cam_cy", "img_feats", "scene_feats", "finite")
+
+    def take(self, index):
+        """Some items as a prepared batch of their own: index = n (the first n; n >= B: self) or an index tensor (repeats allowed)."""
+        if isinstance(index, int):
+            if index >= self.B:
+                return self
+            index = torch.arange(index, device=self.vis.device)
+        index = index.to(self.vis.device, torch.long)
+        picked = {k: getattr(self, k).index_select(0, index).contiguous() for k in self.PER_ITEM}
+        mask_items, mask_slot, num_masked = pass_map(~picked["vis_bool"].all(dim=1))
+        return dataclasses.replace(self, B=int(index.numel()), mask_items=mask_items, mask_slot=mask_slot, num_masked=num_masked, **picked)
+
+    def tile(self, S):
+        """The batch S times, sample-major (body s * B + b); its pass map by offset arithmetic on the device (= pass_map(need.repeat(S)),
+        tests/test_prepared_cpu.py, without the host read-back).  num_masked = -1 (no map) stays -1."""
+        B, nm = self.B, max(self.num_masked, 0)
+        off = torch.arange(S, device=self.mask_slot.device, dtype=torch.int32).view(-1, 1)
+        slot = self.mask_slot.view(1, -1)
+        tiled = {k: getattr(self, k).repeat(S, *([1] * (getattr(self, k).dim() - 1))).contiguous() for k in self.PER_ITEM}
+        return dataclasses.replace(
+            self, B=S * B, mask_items=(self.mask_items.view(1, -1) + off * B).reshape(-1).contiguous(),
+            mask_slot=torch.where(slot >= 0, slot + off * nm, torch.full_like(slot, -1)).reshape(-1).contiguous(),
+            num_masked=S * self.num_masked if self.num_masked >= 0 else self.num_masked, **tiled)
 
 
 class FusedSampler:
@@ -27,13 +83,15 @@ class FusedSampler:
 
     def __init__(self, model):
         self._model_ref = [model]
-        self._gcn = None
-        self._gcn_key = None
-        self._folded = None
-        self._prep_key = None
-        self._prep = None
-        self._ws = None
-        self._graphs = {}
+        self._gcn = self._gcn_key = self._folded = None        # native denoiser handle, its weight key, the folded input-conv slices (gcn)
+        self._nl_set = None                                    # (non-local block's weight key, handle serial) the handle was last given
+        self._pk = self._ck = None                             # TensorKeys behind _param_key / _cond_param_key (built on first use: invalidate)
+        self._prep = self._prep_key = None                     # the cached conditioning (prepare)
+        self._joint_map = self._count_host = None              # prepare: openpose_to_smpl on the device; pinned word for the second-pass count
+        self._beta_key = self._beta_w = None                   # _project: the beta head's packed weights
+        self._tv_cache = None                                  # timestep_vectors: (key, vectors) of the last timestep sequence
+        self._ws, self._graphs = None, {}                      # eager workspace; hipGraph entries by shape / schedule key (_replay)
+        self._status_host = self._status_event = None          # defer_status: pinned status word + the event behind its copy
         self._sched_cache = {}          # schedule_key -> calibration info (calibrate_schedule)
         self.schedule_info = None       # the calibration the most recent 'auto' run used (None: ran all-f16x3 / explicit k)
         self.last_lowprec = 0
@@ -45,8 +103,7 @@ class FusedSampler:
 
     # ------------------------------------------------------------------ weights -> native handle
     def _param_key(self):
-        if getattr(self, "_pk", None) is None:
-            self._pk = _lib.TensorKey(self.model.diffusion_model, self.model.input_process)
+        self._pk = self._pk or _lib.TensorKey(self.model.diffusion_model, self.model.input_process)
         return self._pk()
 
     def gcn(self):
@@ -73,20 +130,18 @@ class FusedSampler:
             W_img_cat = Wd[:, :a, :].permute(1, 0, 2).reshape(a, 2 * hid).contiguous()
             W_oth_cat = torch.zeros(k_oth, 2 * hid, device=m.device)
             W_oth_cat[:b - a] = Wd[:, a:b, :].permute(1, 0, 2).reshape(b - a, 2 * hid)
-            self._folded = SimpleNamespace(Wx=Wx.float().contiguous(), bx=bx, W_img=gi.gconv.W.detach()[:, :a, :],
-                                           W_oth=gi.gconv.W.detach()[:, a:b, :], W_t=W[:, c:d, :], W_img_cat=W_img_cat, W_oth_cat=W_oth_cat,
-                                           k_oth=k_oth)
+            self._folded = SimpleNamespace(Wx=Wx.float().contiguous(), bx=bx, W_t=W[:, c:d, :], W_img_cat=W_img_cat, W_oth_cat=W_oth_cat, k_oth=k_oth)
         A = _lib.api()
         A.ehm_gcn_set_uncond_mode(self._gcn, 0 if self.model.only_mask_img_cond else 1)
         mode = PRECISIONS[self.model.gcn_precision]
         if A.ehm_gcn_get_precision(self._gcn) != mode:
             A.ehm_gcn_set_precision(self._gcn, mode)
         if self.model.diffusion_model.nonlocal_layer:       # the one-call loop runs the block natively (ehm_gcn_set_nonlocal)
-            (wq, sq, bq), (wo, so, bo) = self._nonlocal_packed()
-            if getattr(self, "_nl_set", None) != (self._nl_key, self._gcn.serial):
+            ((wq, sq, bq), (wo, so, bo)), nl_key = self.model.diffusion_model.nonlocal_packed()
+            if self._nl_set != (nl_key, self._gcn.serial):
                 p = _lib.NonlocalParams(_lib.ptr(wq), _lib.ptr(bq), sq, _lib.ptr(wo), _lib.ptr(bo), so, self.model.diffusion_model.non_local.inter_channels)
                 A.ehm_gcn_set_nonlocal(self._gcn, C.byref(p))
-                self._nl_set = (self._nl_key, self._gcn.serial)
+                self._nl_set = (nl_key, self._gcn.serial)
         return self._gcn
 
     def _backbone_fn(self):
@@ -109,13 +164,12 @@ class FusedSampler:
                batch["box_center"], batch["box_size"], batch["smpl_params"]["transl"]]
         if ins[0].shape[0] == 0:
             raise ValueError("empty batch (the reference fails on it too: egohmr.py:233 reshapes x_t [0, 144] to [0, 24, -1])")
-        # ... and of the model switches that ehm_item_prep bakes into the cached state (the pass map's grouping, the camera-feature columns, the
-        # scene frame, which OpenPose joints feed the visibility mask)
+        # ... and of the model switches that ehm_item_prep bakes into the cached state (the camera-feature columns, the scene frame, which
+        # OpenPose joints feed the visibility mask)
         if m.encoder_precision not in ("f16x3", "f16"):
             raise ValueError(f"EgoHMR.encoder_precision must be 'f16x3' or 'f16', not {m.encoder_precision!r}")
         m.backbone.hi_only = m.scene_enc.hi_only = m.encoder_precision == "f16"
-        switches = (int(getattr(m, "pass_group", 1)), bool(m.with_bbox_info), bool(m.with_cam_center), bool(m.scene_cano), tuple(m.openpose_to_smpl),
-                    m.encoder_precision)
+        switches = (bool(m.with_bbox_info), bool(m.with_cam_center), bool(m.scene_cano), tuple(m.openpose_to_smpl), m.encoder_precision)
         key = tuple((id(t), t._version, t.data_ptr()) for t in ins) + self._param_key() + self._cond_param_key() + (switches,)
         if self._prep is not None and self._prep_key == key:
             return self._prep
@@ -144,7 +198,7 @@ class FusedSampler:
         tw = [_lib.f32(te[0].weight, dev), _lib.f32(te[0].bias, dev), _lib.f32(te[2].weight, dev), _lib.f32(te[2].bias, dev)]
         n_scene, n_tr = m.scene_enc.fc_c.out_features, te[2].out_features
         n_other = n_scene + n_tr + 1 + (3 if m.with_bbox_info else 0) + (2 if m.with_cam_center else 0)
-        jm = getattr(self, "_joint_map", None)
+        jm = self._joint_map
         if kp.dim() != 3 or kp.shape[2] != 3 or not all(0 <= int(k) < kp.shape[1] for k in m.openpose_to_smpl):
             # (item_prep_kernel indexes keypoints_2d[b, joint_map[t], 2]: checked here, once per batch, instead of on the device)
             raise ValueError(f"orig_keypoints_2d must be [B, NK, 3] with NK > max(openpose_to_smpl) = {max(m.openpose_to_smpl)}; got {tuple(kp.shape)}")
@@ -162,29 +216,17 @@ class FusedSampler:
                               tW2=P(tw[2]), tb2=P(tw[3]), t_hidden=te[0].out_features, t_out=n_tr, img_rowsum=P(sums[0]),
                               scene_rowsum=P(sums[1]), other=P(oth), other_ld=f.k_oth, other_col0=n_scene, vis=P(vis),
                               mask_slot=P(maps), mask_items=P(maps[B:]), count=P(maps[2 * B:]), finite=P(flags),
-                              need_scratch=P(flags[1]), pass_group=int(getattr(m, "pass_group", 1)), B=B)
+                              need_scratch=P(flags[1]), pass_group=1, B=B)
         _lib.api().ehm_item_prep(C.byref(d), st)
-        if getattr(self, "_count_host", None) is None:
+        if self._count_host is None:
             self._count_host = torch.zeros(1, dtype=torch.int32).pin_memory()
         self._count_host.copy_(maps[2 * B:], non_blocking=True)
         count_ready = torch.cuda.Event()
         count_ready.record(torch.cuda.current_stream(dev))
-        # The two encoders are independent, but each fills the chip on its own: two HIP streams measured slower than one (model.overlap_encoders).
-        if m.overlap_encoders:
-            cur = torch.cuda.current_stream(dev)
-            if getattr(self, "_side_stream", None) is None or self._side_stream.device != dev:
-                self._side_stream = torch.cuda.Stream(device=dev)
-            side = self._side_stream
-            side.wait_stream(cur)
-            with torch.cuda.stream(side):
-                scene_feats = m.scene_enc(scene)                                       # :214
-            img_feats = self._backbone_fn()(img)                                       # :183 (BatchNorm folded into the convs)
-            cur.wait_stream(side)
-            scene_feats.record_stream(cur)
-            scene.record_stream(side)
-        else:
-            img_feats = self._backbone_fn()(img)
-            scene_feats = m.scene_enc(scene)
+        # The two encoders are independent, but each fills the chip on its own: one after the other on ONE stream (two streams measured
+        # slower, docs/EXPERIMENTS.md)
+        img_feats = self._backbone_fn()(img)                                           # :183 (BatchNorm folded into the convs)
+        scene_feats = m.scene_enc(scene)                                               # :214
         oth[:, :n_scene].copy_(scene_feats)                                            # :220-221 [scene | transl | cam] (the rest was written by ehm_item_prep)
         h_img, h_oth, betas = self._project(img_feats.contiguous(), oth, n_other)
         # items with a non-finite input (flags[0] == 0: their outputs are NaN by the packer's rule) get ZERO conditioning: the encoders' saturating f16 stores
@@ -195,12 +237,10 @@ class FusedSampler:
         h_oth.masked_fill_(bad, 0.0)
         count_ready.synchronize()
         num_masked = int(self._count_host[0])
-        mask_slot, mask_items = maps[:B], maps[B:B + num_masked]
         self._prep = _Prepared(B=B, h_img=h_img, h_oth=h_oth, vis=vis, vis_bool=vis.view(torch.bool),
                                betas=betas, scene=scene, transl=transl, fx=fx, cam_cx=cx, cam_cy=cy, img_feats=img_feats,
-                               scene_feats=scene_feats, finite=flags[0].view(torch.bool))
-        self._prep.inputs = ins                  # strong references (see the key above)
-        self._prep.mask_items, self._prep.mask_slot, self._prep.num_masked = mask_items, mask_slot, num_masked
+                               scene_feats=scene_feats, finite=flags[0].view(torch.bool), mask_items=maps[B:B + num_masked],
+                               mask_slot=maps[:B], num_masked=num_masked, inputs=ins)      # (inputs: strong references, see the key above)
         self._prep_key = key
         return self._prep
 
@@ -224,7 +264,7 @@ class FusedSampler:
         # the second bias)
         ib = m.beta_layer.init_betas
         key = tuple((t.data_ptr(), t._version) for t in (l1.weight, l1.bias, l2.weight, l2.bias, ib)) + (str(dev),)
-        if getattr(self, "_beta_key", None) != key:
+        if self._beta_key != key:
             Wt = torch.zeros(a + f.k_oth, l1.out_features, device=dev)
             w = l1.weight.detach().float().to(dev)
             Wt[:a] = w[:, :a].t()
@@ -245,8 +285,7 @@ class FusedSampler:
 
     def _cond_param_key(self):
         m = self.model
-        if getattr(self, "_ck", None) is None:
-            self._ck = _lib.TensorKey(m.backbone, m.scene_enc, m.transl_enc, m.beta_layer, m.embed_timestep)
+        self._ck = self._ck or _lib.TensorKey(m.backbone, m.scene_enc, m.transl_enc, m.beta_layer, m.embed_timestep)
         return self._ck()
 
     def _apply_pass_map(self, st, passes):
@@ -264,7 +303,7 @@ class FusedSampler:
         parameter slots behind the weight-version keys (needed only after sub-modules or parameters were ADDED to the model)."""
         self._prep, self._prep_key = None, None
         if structure:
-            self._pk = self._ck = self._bbk = None
+            self._pk = self._ck = None
 
     @torch.no_grad()
     def timestep_vectors(self, t_orig) -> torch.Tensor:
@@ -276,9 +315,8 @@ class FusedSampler:
         ckey = None
         if not torch.is_tensor(t_orig):
             ckey = (self._param_key(), self._cond_param_key(), tuple(int(t) for t in t_orig))
-            hit = getattr(self, "_tv_cache", None)
-            if hit is not None and hit[0] == ckey:
-                return hit[1]
+            if self._tv_cache is not None and self._tv_cache[0] == ckey:
+                return self._tv_cache[1]
             t_orig = torch.tensor(ckey[2], device=m.device, dtype=torch.long)
         temb = m.embed_timestep.time_embed(m.sequence_pos_encoder.pe[t_orig][:, 0])    # [n,512]
         tv = torch.einsum("ne,kef->nkf", temb.double(), self._folded.W_t) + self._folded.bx[None]
@@ -302,6 +340,11 @@ class FusedSampler:
             cache[key] = ((_lib.StepCoefs * T)(*rows), first_guided)
         return cache[key]
 
+    @staticmethod
+    def guided_steps(diffusion, ddim, cond_grad_weight, guided) -> int:
+        """The guided steps of a loop (a contiguous tail, gaussian_diffusion.py:378-385): schedule_key's ONE count, for run, calibration and install."""
+        return diffusion.num_timesteps - FusedSampler.step_table(diffusion, ddim, cond_grad_weight, guided)[1]
+
     # ------------------------------------------------------------------ granular denoiser (EgoHMR.forward)
     def _workspace(self, nbytes, device):
         if self._ws is None or self._ws.numel() < nbytes or self._ws.device != device:
@@ -311,37 +354,10 @@ class FusedSampler:
     @torch.no_grad()
     def denoise_once(self, st, x_t, tvec, passes):
         m, A = self.model, _lib.api()
-        hid, B = m.diffusion_model.hid_dim, st.B
-        tile = A.ehm_gcn_row_tile()
         rows = self._apply_pass_map(st, passes)[0] * 24
-        rows_pad = (rows + tile - 1) // tile * tile
-        X = [torch.zeros(rows_pad, hid, device=m.device) for _ in range(3)]
-        s = _lib.stream_ptr()
         h = self.gcn()
-        A.ehm_gcn_input_layer(h, st.h_img, st.h_oth, st.vis, x_t, self._folded.Wx, tvec, X[0], B, passes, s)
-        bufs = (C.c_void_p * 3)(*map(_lib.ptr, X))
-        res = C.c_int(0)
-        A.ehm_gcn_hidden_stack(h, bufs, rows_pad, C.byref(res), s)
-        cur = res.value
-        feat = X[cur]
-        if m.diffusion_model.nonlocal_layer:
-            if m.gcn_precision == "f16":
-                raise _lib.EgoHMRHipError("the optional non-local GCN block runs on float32 features; use gcn_precision 'f16x3' or 'f32' with it")
-            feat = self._non_local(feat, rows, rows_pad)
-        x0 = torch.empty(B, 144, device=m.device)
-        A.ehm_gcn_output_layer(h, feat, st.vis, x0, B, passes, s)
-        self.last_hidden = feat[:rows]
-        return x0
-
-    def _non_local(self, X, rows, rows_pad):
-        """NONLocalBlock2D on the joint axis (modulated_gcn.py:104-110): ModulatedGCN.non_local_native."""
-        return self.model.diffusion_model.non_local_native(X, rows, rows_pad)
-
-    def _nonlocal_packed(self):
-        dm = self.model.diffusion_model
-        self._nl_packed = dm.nonlocal_packed()
-        self._nl_key = dm._nl_key
-        return self._nl_packed
+        fill = lambda X0: A.ehm_gcn_input_layer(h, st.h_img, st.h_oth, st.vis, x_t, self._folded.Wx, tvec, X0, st.B, passes, _lib.stream_ptr())
+        return m.diffusion_model.denoiser_tail(h, fill, rows=rows, B=st.B, passes=passes, vis=st.vis, precision=m.gcn_precision, device=m.device)
 
     # ------------------------------------------------------------------ guidance pieces
     @torch.no_grad()
@@ -436,24 +452,6 @@ class FusedSampler:
             idx += 1
         return idx
 
-    def _subset(self, st, sel):
-        """Some items of a prepared batch as a prepared batch of their own (pass map recomputed): sel = n (the first n) or an index tensor."""
-        if isinstance(sel, int):
-            if sel >= st.B:
-                return st
-            sel = torch.arange(sel, device=st.vis.device)
-        sel = sel.to(st.vis.device, torch.long)
-        fields = {k: (v.index_select(0, sel).contiguous() if torch.is_tensor(v) and v.dim() >= 1 and v.shape[0] == st.B and k not in ("mask_items", "mask_slot") else v)
-                  for k, v in vars(st).items()}
-        r = _Prepared(**fields)
-        r.B = int(sel.numel())
-        need = ~r.vis_bool.all(dim=1)
-        order = torch.argsort((~need).to(torch.uint8), stable=True).to(torch.int32)
-        r.mask_slot = torch.where(need, torch.cumsum(need.to(torch.int32), 0) - 1, torch.full_like(need, -1, dtype=torch.int32)).to(torch.int32).contiguous()
-        r.num_masked = int(need.sum())
-        r.mask_items = order[: r.num_masked].contiguous()
-        return r
-
     @torch.no_grad()
     def calibrate_schedule(self, diffusion, batch=None, ddim=False, guided=False, cond_grad_weight=1.0, tol=None, bodies=64, prepared=None,
                            seeds=(20260929, 20260930), force=False, denom_items=None, n_guided=None):
@@ -475,7 +473,7 @@ class FusedSampler:
         st_full = prepared if prepared is not None else self.prepare(batch)
         T = diffusion.num_timesteps
         if n_guided is None:
-            n_guided = sum(1 for i in range(min(T, 16)) if diffusion.step_coefs(i, ddim, 0.0, cond_grad_weight, guided).grad_scale != 0.0)   # guided tail: t <= 10
+            n_guided = self.guided_steps(diffusion, ddim, cond_grad_weight, guided)
         denom_items = int(denom_items or st_full.B)
         old_tol, m.schedule_tol = m.schedule_tol, tol
         try:
@@ -491,7 +489,7 @@ class FusedSampler:
         if good.numel() == 0:
             return {"k": int(T), "T": int(T), "f16_steps": 0, "tol_m": tol, "criterion": "no item with finite inputs in the batch: not calibrated, not cached",
                     "bodies": 0, "ddim": bool(ddim), "guided_steps": int(n_guided), "trials": []}
-        st = self._subset(st_full, good[torch.arange(int(bodies), device=good.device) % good.numel()])
+        st = st_full.take(good[torch.arange(int(bodies), device=good.device) % good.numel()])
         nb, dev = st.B, m.device
         sub_batch = dict(batch) if batch is not None else {}
 
@@ -534,7 +532,7 @@ class FusedSampler:
     def install_schedule(self, diffusion, info, ddim=False, guided=False, cond_grad_weight=1.0, denom_items=1):
         """Adopt a calibration result measured elsewhere (another rank's: egohmr_amd.dist.agree_schedule) for THIS process's weights."""
         T = diffusion.num_timesteps
-        n_guided = sum(1 for i in range(min(T, 16)) if diffusion.step_coefs(i, ddim, 0.0, cond_grad_weight, guided).grad_scale != 0.0)
+        n_guided = self.guided_steps(diffusion, ddim, cond_grad_weight, guided)
         assert int(info["T"]) == T, (info["T"], T)
         self._sched_cache[self.schedule_key(diffusion, ddim, n_guided, cond_grad_weight, self.guide_denom(int(denom_items)))] = dict(info)
         self.schedule_info = dict(info)
@@ -545,7 +543,7 @@ class FusedSampler:
         averaged over `bodies` items, per ORIGINAL timestep - the J that decides whether early rounding errors are contracted
         (calibrate_schedule).  Evaluated through the product's own denoiser in its f32-grade arithmetic."""
         m = self.model
-        st = self._subset(prepared if prepared is not None else self.prepare(batch), bodies)
+        st = (prepared if prepared is not None else self.prepare(batch)).take(bodies)
         g = torch.Generator(device=m.device).manual_seed(seed)
         x = torch.randn(st.B, 144, device=m.device, generator=g)
         d = torch.randn(st.B, 144, device=m.device, generator=g)
@@ -591,26 +589,11 @@ class FusedSampler:
 
     def _run_sample_group(self, diffusion, batch, st, noise_stacks, ddim, guided, cond_grad_weight, defer_status):
         """S samples of the prepared batch `st` as ONE loop over S*B bodies -> S result dicts."""
-        S, B = len(noise_stacks), st.B
+        S, B, T = len(noise_stacks), st.B, diffusion.num_timesteps
+        run = partial(self.run, diffusion, dict(batch), ddim=ddim, guided=guided, cond_grad_weight=cond_grad_weight, denom_items=B, defer_status=defer_status)
         if S == 1:
-            return [self.run(diffusion, dict(batch), noise_stacks[0], ddim=ddim, guided=guided, cond_grad_weight=cond_grad_weight, prepared=st, denom_items=B,
-                             defer_status=defer_status)]
-        rep = lambda t: t.repeat(S, *([1] * (t.dim() - 1))).contiguous()
-        fields = {k: (rep(v) if torch.is_tensor(v) and v.dim() >= 1 and v.shape[0] == B and k not in ("mask_items", "mask_slot") else v)
-                  for k, v in vars(st).items()}
-        r = _Prepared(**fields)
-        r.B = S * B
-        off = torch.arange(S, device=st.mask_slot.device, dtype=torch.int32)
-        nm = max(st.num_masked, 0)
-        r.mask_items = (st.mask_items.view(1, -1) + off.view(-1, 1) * B).reshape(-1).contiguous()
-        r.mask_slot = torch.where(st.mask_slot.view(1, -1) >= 0, st.mask_slot.view(1, -1) + off.view(-1, 1) * nm,
-                                  torch.full((1, 1), -1, device=off.device, dtype=torch.int32)).reshape(-1).to(torch.int32).contiguous()
-        r.num_masked = S * st.num_masked if st.num_masked >= 0 else st.num_masked
-        r.inputs = st.inputs
-        T = diffusion.num_timesteps
-        noise = torch.cat([_lib.f32(n, self.model.device)[: T + 1] for n in noise_stacks], dim=1)
-        res = self.run(diffusion, dict(batch), noise, ddim=ddim, guided=guided, cond_grad_weight=cond_grad_weight, prepared=r, denom_items=B,
-                       defer_status=defer_status)
+            return [run(noise_stack=noise_stacks[0], prepared=st)]
+        res = run(noise_stack=torch.cat([_lib.f32(n, self.model.device)[: T + 1] for n in noise_stacks], dim=1), prepared=st.tile(S))
 
         def split(x):
             if torch.is_tensor(x):
@@ -628,9 +611,11 @@ class FusedSampler:
         """p_sample_loop / ddim_sample_loop (gaussian_diffusion.py:391-508 / :618-718) in one native call.
         Returns the reference's dict(sample, pred_xstart, other_outputs)."""
         m = self.model
+        call = dict(diffusion=diffusion, batch=batch, noise_stack=noise_stack, ddim=ddim, guided=guided, cond_grad_weight=cond_grad_weight, trace=trace,
+                    prepared=prepared, denom_items=denom_items)
         with _lib.on_device(m.device):
             try:
-                return self._run_on_device(diffusion, batch, noise_stack, ddim, guided, cond_grad_weight, trace, prepared, denom_items, defer_status, lowprec)
+                return self._run_on_device(**call, defer_status=defer_status, lowprec=lowprec)
             except _lib.EgoHMRRangeError:
                 # an activation left the f16 range and was clamped (status bit 2 of the handle, raised by the conv kernels' stores): never silent.
                 # on_saturation = 'f32': this checkpoint gets float32 activations from now on (exact-f32 MFMA path, ~3x slower) and the call runs again
@@ -640,116 +625,125 @@ class FusedSampler:
                 warnings.warn("egohmr_amd: a denoiser activation reached the f16 range (|x| >= 65504) and was clamped in the split-f16 / f16 path; "
                               "EgoHMR.on_saturation = 'f32': switching this model to gcn_precision = 'f32' and re-running the call", RuntimeWarning)
                 m.gcn_precision = "f32"
-                return self._run_on_device(diffusion, batch, noise_stack, ddim, guided, cond_grad_weight, trace, prepared, denom_items, False, None)
+                return self._run_on_device(**call, defer_status=False, lowprec=None)
 
-    def _run_on_device(self, diffusion, batch, noise_stack, ddim, guided, cond_grad_weight, trace, prepared, denom_items, defer_status, lowprec):
-        m, A = self.model, _lib.api()
+    def _run_on_device(self, *, diffusion, batch, noise_stack, ddim, guided, cond_grad_weight, trace, prepared, denom_items, defer_status, lowprec):
+        m = self.model
         nonlocal_ci = m.diffusion_model.non_local.inter_channels if m.diffusion_model.nonlocal_layer else 0
         if nonlocal_ci and m.gcn_precision == "f16":
-            raise _lib.EgoHMRHipError("the optional non-local GCN block runs on float32 features; use gcn_precision 'f16x3' or 'f32' with it")
-        ev = getattr(self, "_status_event", None)
-        if ev is not None and ev.query():                 # a deferred status word of an earlier call has arrived: look at it now
+            raise _lib.EgoHMRHipError(m.diffusion_model.NONLOCAL_F16)
+        if self._status_event is not None and self._status_event.query():   # a deferred status word of an earlier call has arrived: look at it now
             self.check_status()
         st = prepared if prepared is not None else self.prepare(batch)
-        B, T, hid, V = st.B, diffusion.num_timesteps, m.diffusion_model.hid_dim, m.smpl.num_verts
+        B, T = st.B, diffusion.num_timesteps
         noise = _lib.f32(noise_stack, m.device)
         assert noise.shape[0] >= T + 1 and noise.shape[1] == B and noise.shape[2] == 144, noise.shape
         steps, first_guided = self.step_table(diffusion, ddim, cond_grad_weight, guided)
         any_guided = first_guided < T
-        n_guided = T - first_guided                       # (the reference guides a contiguous tail: t < 10, gaussian_diffusion.py:378-385)
         tvecs = self.timestep_vectors([diffusion.timestep_map[i] for i in range(T - 1, -1, -1)])   # [T,2,hid]
-        passes = 2 if m.diffuse_fuse else 1
-        # precision schedule: an explicit `lowprec` (calibration runs), else EgoHMR.f16x3_last_steps; 'auto' = the k calibrated for THESE
-        # weights and THIS sampler - measured now, on this batch's first items, when it is not cached yet (auto_calibrate) - or no f16 step
         if nonlocal_ci:
             lowprec = 0                                   # the block reads float32 features: no plain-f16 steps
-        if lowprec is None:
-            skey = None
-            if m.f16x3_last_steps == "auto" and m.gcn_precision == "f16x3":
-                skey = self.schedule_key(diffusion, ddim, n_guided, cond_grad_weight, self.guide_denom(denom_items or B))
-                if skey not in self._sched_cache and m.auto_calibrate:
-                    self.calibrate_schedule(diffusion, batch, ddim=ddim, guided=guided, cond_grad_weight=cond_grad_weight, prepared=st,
-                                            denom_items=denom_items or B, n_guided=n_guided)
-                self.schedule_info = self._sched_cache.get(skey)
-            lowprec = self.lowprec_steps(T, n_guided, ddim, key=skey)
+        elif lowprec is None:
+            lowprec = self._scheduled_lowprec(diffusion=diffusion, batch=batch, st=st, ddim=ddim, guided=guided, cond_grad_weight=cond_grad_weight,
+                                              n_guided=T - first_guided, denom_items=denom_items or B)
         self.last_lowprec = int(lowprec)                  # leading steps of THIS call on plain f16 operands
-        _, num_masked = self._apply_pass_map(st, passes)
-        desc = _lib.SampleDesc(B=B, passes=passes, num_steps=T, ddim=int(ddim), per_step_launches=int(bool(m.per_step_launches)),
-                               lbs_every_step=int(m.lbs_every_step), num_scene_points=st.scene.shape[1] if any_guided else 0,
-                               guide_denom=self.guide_denom(denom_items or B), tau=m.collision_tau, num_masked=num_masked,
-                               guide_all_points=int(bool(m.guide_all_points)), lowprec_steps=int(lowprec), nonlocal_ci=int(nonlocal_ci))
-        nbytes = A.ehm_sample_workspace_bytes(C.byref(desc), hid, V)
-        dev = m.device
-        mean, std = m._std_mean()
+        desc, nbytes = self._describe(st=st, T=T, ddim=ddim, any_guided=any_guided, denom_items=denom_items or B, lowprec=lowprec, nonlocal_ci=nonlocal_ci)
         gcn, smpl_h = self.gcn(), m.smpl.handle()
-
-        def launch(bufs, ws, tr):
-            A.ehm_sample_loop(gcn, smpl_h, C.byref(desc), steps, bufs.h_img, bufs.h_oth, bufs.vis, self._folded.Wx, bufs.tvecs, bufs.noise,
-                              bufs.scene if any_guided else None, bufs.betas, mean, std, bufs.x_final, bufs.x0, bufs.verts, bufs.joints, bufs.R,
-                              bufs.pose6d, tr, ws, nbytes, _lib.stream_ptr())
-
-        def out_bufs():
-            return dict(x_final=torch.empty(B, 144, device=dev), x0=torch.empty(B, 144, device=dev), verts=torch.empty(B, V, 3, device=dev),
-                        joints=torch.empty(B, m.smpl.num_joints_out, 3, device=dev), R=torch.empty(B, 24, 3, 3, device=dev),
-                        pose6d=torch.empty(B, 144, device=dev))
-
+        launch = partial(self._launch, gcn=gcn, smpl_h=smpl_h, desc=desc, steps=steps, nbytes=nbytes, any_guided=any_guided)
         ins = dict(h_img=st.h_img, h_oth=st.h_oth, vis=st.vis, tvecs=tvecs, noise=noise[: T + 1].contiguous(), betas=st.betas, scene=st.scene)
         graph = m.use_hip_graph is True or (m.use_hip_graph == "auto" and desc.passes * B <= 64)
-        tr = None
-        with torch.cuda.device(dev):
+        tr = torch.empty(T, B, 144, device=m.device) if trace else None
+        with torch.cuda.device(m.device):
             if graph and not any_guided and not trace:
-                # hipGraph route: the loop's launches are captured once per (shape, schedule) with every pointer inside persistent
-                # buffers; a call copies its inputs in, replays, and copies the results out.
-                # (every pointer the captured launches bake in that is not inside `bufs`: the two native handles - by serial, a recreated handle
-                # can reuse a destroyed one's address - and the mean / std buffers)
-                key = (B, T, int(ddim), desc.passes, desc.lbs_every_step, desc.lowprec_steps, m.gcn_precision, gcn.serial,
-                       bytes(steps), st.scene.shape[1], num_masked, smpl_h.serial,
-                       mean.data_ptr(), std.data_ptr(), self._folded.Wx.data_ptr(), getattr(self, '_nl_set', None))
-                ent = self._graphs.get(key)
-                if ent is None:
-                    if len(self._graphs) >= 8:
-                        self._graphs.clear()
-                    bufs = SimpleNamespace(**{k: torch.empty_like(v) for k, v in ins.items()}, **out_bufs())
-                    bufs.mask_items, bufs.mask_slot = torch.empty_like(st.mask_items), torch.empty_like(st.mask_slot)
-                    ws = torch.empty(int(nbytes), dtype=torch.uint8, device=dev)
-                    for k, v in ins.items():
-                        getattr(bufs, k).copy_(v)
-                    bufs.mask_items.copy_(st.mask_items)
-                    bufs.mask_slot.copy_(st.mask_slot)
-                    if num_masked >= 0:      # the captured kernels read the pass map through these persistent arrays
-                        A.ehm_gcn_set_pass_map(gcn, bufs.mask_items if num_masked else None, bufs.mask_slot, num_masked)
-                    launch(bufs, ws, None)                       # eager once: every lazy allocation inside the library happens here
-                    torch.cuda.synchronize(dev)
-                    g = torch.cuda.CUDAGraph()
-                    with torch.cuda.graph(g):
-                        launch(bufs, ws, None)
-                    ent = self._graphs[key] = SimpleNamespace(graph=g, bufs=bufs, ws=ws)
-                for k, v in ins.items():
-                    getattr(ent.bufs, k).copy_(v)
-                ent.bufs.mask_items.copy_(st.mask_items)
-                ent.bufs.mask_slot.copy_(st.mask_slot)
-                ent.graph.replay()
-                o = SimpleNamespace(**{k: getattr(ent.bufs, k).clone() for k in ("x_final", "x0", "verts", "joints", "R", "pose6d")})
+                o = self._replay(launch=launch, gcn=gcn, smpl_h=smpl_h, desc=desc, steps=steps, nbytes=nbytes, st=st, ins=ins)
             else:
-                o = SimpleNamespace(**ins, **out_bufs())
-                tr = torch.empty(T, B, 144, device=dev) if trace else None
-                launch(o, self._workspace(nbytes, dev), tr)
-        x_final, x0, verts, joints, R, pose6d = o.x_final, o.x0, o.verts, o.joints, o.R, o.pose6d
+                o = SimpleNamespace(**ins, **self._out_bufs(B))
+                launch(bufs=o, ws=self._workspace(nbytes, m.device), tr=tr)
+        return self._finish(batch=batch, st=st, o=o, tr=tr, noise=noise, T=T, guided_ddim=ddim and any_guided, gcn=gcn, defer_status=defer_status)
+
+    def _scheduled_lowprec(self, *, diffusion, batch, st, ddim, guided, cond_grad_weight, n_guided, denom_items):
+        """Leading plain-f16 steps by EgoHMR.f16x3_last_steps; 'auto' = the k calibrated for THESE weights and THIS sampler, measured now if need be."""
+        m, skey = self.model, None
+        if m.f16x3_last_steps == "auto" and m.gcn_precision == "f16x3":
+            skey = self.schedule_key(diffusion, ddim, n_guided, cond_grad_weight, self.guide_denom(denom_items))
+            if skey not in self._sched_cache and m.auto_calibrate:
+                self.calibrate_schedule(diffusion, batch, ddim=ddim, guided=guided, cond_grad_weight=cond_grad_weight, prepared=st,
+                                        denom_items=denom_items, n_guided=n_guided)
+            self.schedule_info = self._sched_cache.get(skey)
+        return self.lowprec_steps(diffusion.num_timesteps, n_guided, ddim, key=skey)
+
+    def _describe(self, *, st, T, ddim, any_guided, denom_items, lowprec, nonlocal_ci):
+        """(the loop's descriptor, its workspace size) after giving the handle this batch's pass map."""
+        m = self.model
+        passes = 2 if m.diffuse_fuse else 1
+        _, num_masked = self._apply_pass_map(st, passes)
+        desc = _lib.SampleDesc(B=st.B, passes=passes, num_steps=T, ddim=int(ddim), per_step_launches=int(bool(m.per_step_launches)),
+                               lbs_every_step=int(m.lbs_every_step), num_scene_points=st.scene.shape[1] if any_guided else 0,
+                               guide_denom=self.guide_denom(denom_items), tau=m.collision_tau, num_masked=num_masked,
+                               guide_all_points=int(bool(m.guide_all_points)), lowprec_steps=int(lowprec), nonlocal_ci=int(nonlocal_ci))
+        return desc, _lib.api().ehm_sample_workspace_bytes(C.byref(desc), m.diffusion_model.hid_dim, m.smpl.num_verts)
+
+    def _out_bufs(self, B):
+        smpl = self.model.smpl
+        shapes = dict(x_final=(144,), x0=(144,), verts=(smpl.num_verts, 3), joints=(smpl.num_joints_out, 3), R=(24, 3, 3), pose6d=(144,))
+        return {k: torch.empty(B, *shape, device=self.model.device) for k, shape in shapes.items()}
+
+    def _launch(self, *, gcn, smpl_h, desc, steps, nbytes, any_guided, bufs, ws, tr):
+        mean, std = self.model._std_mean()
+        _lib.api().ehm_sample_loop(gcn, smpl_h, C.byref(desc), steps, bufs.h_img, bufs.h_oth, bufs.vis, self._folded.Wx, bufs.tvecs, bufs.noise,
+                                   bufs.scene if any_guided else None, bufs.betas, mean, std, bufs.x_final, bufs.x0, bufs.verts, bufs.joints, bufs.R,
+                                   bufs.pose6d, tr, ws, nbytes, _lib.stream_ptr())
+
+    def _replay(self, *, launch, gcn, smpl_h, desc, steps, nbytes, st, ins):
+        """hipGraph route: the loop's launches are captured once per (shape, schedule) with every pointer inside persistent buffers; a call
+        copies its inputs in, replays, and copies the results out."""
+        m, dev = self.model, self.model.device
+        ins = dict(ins, mask_items=st.mask_items, mask_slot=st.mask_slot)      # (the captured kernels read the pass map through persistent arrays too)
+        mean, std = m._std_mean()
+        # (every pointer the captured launches bake in that is not inside `bufs`: the two native handles - by serial, a recreated handle
+        # can reuse a destroyed one's address - and the mean / std buffers)
+        key = (st.B, desc.num_steps, desc.ddim, desc.passes, desc.lbs_every_step, desc.lowprec_steps, m.gcn_precision, gcn.serial,
+               bytes(steps), st.scene.shape[1], desc.num_masked, smpl_h.serial,
+               mean.data_ptr(), std.data_ptr(), self._folded.Wx.data_ptr(), self._nl_set)
+        ent = self._graphs.get(key)
+        if ent is None:
+            if len(self._graphs) >= 8:
+                self._graphs.clear()
+            bufs = SimpleNamespace(**{k: torch.empty_like(v) for k, v in ins.items()}, **self._out_bufs(st.B))
+            ws = torch.empty(int(nbytes), dtype=torch.uint8, device=dev)
+            for k, v in ins.items():
+                getattr(bufs, k).copy_(v)
+            if desc.num_masked >= 0:
+                _lib.api().ehm_gcn_set_pass_map(gcn, bufs.mask_items if desc.num_masked else None, bufs.mask_slot, desc.num_masked)
+            launch(bufs=bufs, ws=ws, tr=None)                # eager once: every lazy allocation inside the library happens here
+            torch.cuda.synchronize(dev)
+            g = torch.cuda.CUDAGraph()
+            with torch.cuda.graph(g):
+                launch(bufs=bufs, ws=ws, tr=None)
+            ent = self._graphs[key] = SimpleNamespace(graph=g, bufs=bufs, ws=ws)
+        for k, v in ins.items():
+            getattr(ent.bufs, k).copy_(v)
+        ent.graph.replay()
+        return SimpleNamespace(**{k: getattr(ent.bufs, k).clone() for k in ("x_final", "x0", "verts", "joints", "R", "pose6d")})
+
+    def _finish(self, *, batch, st, o, tr, noise, T, guided_ddim, gcn, defer_status):
+        """The call's result dict (ehm_pack_outputs) and its status read."""
+        m, A = self.model, _lib.api()
         # non-finite noise: x_T or a step's draw poisons the item from the next denoiser evaluation on; the LAST step's draw is multiplied by
         # nonzero_mask = 0 (DDIM: by sigma = 0 too) and 0 * NaN = NaN lands in that element of `sample` only (gaussian_diffusion.py:357-359, :575-580)
         self.last_trace = tr
         if tr is not None:
             batch["x_t"] = tr[-1]
         batch["vis_mask_smpl"] = st.vis_bool
-        out = m._pack_output(batch, st, x0, pose6d, R, verts, joints, chk=noise, chk_rows=T, last_noise=noise[T], x_final=x_final)
+        out = m._pack_output(batch, st, o.x0, o.pose6d, o.R, o.verts, o.joints, chk=noise, chk_rows=T, last_noise=noise[T], x_final=o.x_final)
         # a chained launch that gave up on a producer wait (GPU shared / preempted) flags the handle instead of hanging: one read-back
         # per sampling call (the call's only host wait, after everything has been enqueued) turns that into an exception rather than
         # silently wrong bodies
         # defer_status (throughput pipelines that keep batches in flight): the word is copied to pinned memory in stream order and
         # looked at by the NEXT call / by check_status(); the host does not wait here.  The flag is sticky on the device.
-        with torch.cuda.device(dev):
+        with torch.cuda.device(m.device):
             if defer_status:
-                if getattr(self, "_status_host", None) is None:
+                if self._status_host is None:
                     self._status_host = torch.zeros(1, dtype=torch.int32).pin_memory()
                 A.ehm_gcn_stack_status_async(gcn, self._status_host.data_ptr(), _lib.stream_ptr())
                 self._status_event = torch.cuda.Event()
@@ -759,16 +753,15 @@ class FusedSampler:
                 m.backbone.check_status()                 # (the stream has been waited for: the trunk's stream-K time-out word is there)
         # ddim_sample_with_grad hands out the GUIDED x0 of its last step as pred_xstart (gaussian_diffusion.py:587-592) while other_outputs keep the model's own;
         # that step has alpha_bar_prev = 1, so its sample IS the guided x0 (x0g * 1 + 0 * eps)
-        return {"sample": x_final, "pred_xstart": x_final if (ddim and any_guided) else x0, "other_outputs": out}
+        return {"sample": o.x_final, "pred_xstart": o.x_final if guided_ddim else o.x0, "other_outputs": out}
 
     def check_status(self):
         """Raise if a sampling call issued with defer_status=True flagged its chained launches (see run()), or if a stream-K conv of the ResNet-50
         trunk timed out in a hand-off (ResNet50Features.check_status).  Waits for that call."""
         self.model.backbone.check_status()
-        ev = getattr(self, "_status_event", None)
-        if ev is None:
+        if self._status_event is None:
             return
-        ev.synchronize()
+        self._status_event.synchronize()
         self._status_event = None
         if int(self._status_host[0]) != 0:
             self._status_host.zero_()

@@ -16,6 +16,7 @@ denoiser, rot6d->rotmat, SMPL LBS and the sampler update are hand-written HIP ke
 from __future__ import annotations
 
 import ctypes as C
+import math
 from types import SimpleNamespace
 
 import numpy as np
@@ -48,6 +49,17 @@ def smpl_tree_adjacency() -> torch.Tensor:
     a = a / a.sum(1, keepdims=True)
     np.fill_diagonal(a, 1.0)
     return torch.from_numpy(a)
+
+
+def _split_pack(w):
+    """float32 [N, K] weights (N a multiple of 128, K of 32) on a HIP device -> (X2 split buffer for ehm_conv_nhwc_split, its power-of-two scale)."""
+    N, K = w.shape
+    amax = float(w.abs().max())
+    scale = 2.0 ** math.floor(math.log2(2048.0 / amax)) if amax > 0 else 1.0
+    buf = torch.empty(N, K, device=w.device)
+    with torch.cuda.device(w.device):
+        _lib.api().ehm_split_pack(w, buf, N, K, K, scale, _lib.stream_ptr())
+    return buf, scale
 
 
 # ---------------------------------------------------------------------------------------------- parameter holders
@@ -111,6 +123,8 @@ class ModulatedGCN(nn.Module):
         self.nonlocal_layer = bool(nonlocal_layer)
         if self.nonlocal_layer:                                     # modulated_gcn.py:93-94, reference parameter names
             self.non_local = _NonLocalBlock(hid_dim)
+        self._nl_packed = self._nl_key = None                       # nonlocal_packed()
+        self._sa = self._sa_key = self._sa_keyfn = None             # _standalone()
 
     # ------------------------------------------------------------------ native handle (ehm_gcn_create) - shared with FusedSampler.gcn()
     def create_native_handle(self, device):
@@ -146,23 +160,16 @@ class ModulatedGCN(nn.Module):
     # ------------------------------------------------------------------ the optional non-local block (modulated_gcn.py:93-94, :104-110)
     def nonlocal_packed(self):
         """The non-local block's two 1x1-conv GEMMs in ehm_conv_nhwc_split's operand format: ([theta | phi | g] weights, scale, bias),
-        (W.0 with BatchNorm(eval) folded, scale, bias); re-packed when a parameter of the block changes."""
-        import math
+        (W.0 with BatchNorm(eval) folded, scale, bias), and the weight key they were packed for; re-packed when a parameter of the block changes."""
         nl = self.non_local
         device = nl.theta.weight.device
         key = tuple((p.data_ptr(), p._version) for p in list(nl.parameters()) + list(nl.buffers()))
-        if getattr(self, "_nl_key", None) != key:
+        if self._nl_key != key:
             def pack(w2, bias):                                   # [Co, K] float32 -> X2 split weights for the conv kernel
                 Co, K = w2.shape
-                Co_pad = (Co + 127) // 128 * 128
-                wp = torch.zeros(Co_pad, K, device=device)
+                wp = torch.zeros((Co + 127) // 128 * 128, K, device=device)
                 wp[:Co] = w2
-                amax = float(wp.abs().max())
-                scale = 2.0 ** math.floor(math.log2(2048.0 / amax)) if amax > 0 else 1.0
-                buf = torch.empty(Co_pad, K, device=device)
-                with torch.cuda.device(device):
-                    _lib.api().ehm_split_pack(wp, buf, Co_pad, K, K, scale, _lib.stream_ptr())
-                return buf, scale, bias.float().contiguous()
+                return _split_pack(wp) + (bias.float().contiguous(),)
             wqkv = torch.cat([nl.theta.weight, nl.phi.weight, nl.g.weight], 0).flatten(1).float()
             bqkv = torch.cat([nl.theta.bias, nl.phi.bias, nl.g.bias], 0)
             bn = nl.W[1]
@@ -170,7 +177,7 @@ class ModulatedGCN(nn.Module):
             ww = (nl.W[0].weight.flatten(1).double() * sc[:, None]).float()
             bw = ((nl.W[0].bias.double() - bn.running_mean.double()) * sc + bn.bias.double()).float()
             self._nl_packed, self._nl_key = (pack(wqkv.detach(), bqkv.detach()), pack(ww.detach(), bw.detach())), key
-        return self._nl_packed
+        return self._nl_packed, self._nl_key
 
     @torch.no_grad()
     def non_local_native(self, X, rows, rows_pad):
@@ -180,7 +187,7 @@ class ModulatedGCN(nn.Module):
         A, P = _lib.api(), _lib.ptr
         nl = self.non_local
         hid, ci = self.hid_dim, nl.inter_channels
-        (wq, sq, bq), (wo, so, bo) = self.nonlocal_packed()
+        (wq, sq, bq), (wo, so, bo) = self.nonlocal_packed()[0]
         s = _lib.stream_ptr()
         qkv = torch.empty(rows, 3 * ci, device=X.device)
         d = _lib.ConvDesc(P(X), P(wq), P(bq), None, P(qkv), rows, 1, 1, hid, 3 * ci, 1, 1, 1, 0, 0, sq)
@@ -192,18 +199,42 @@ class ModulatedGCN(nn.Module):
         A.ehm_conv_nhwc_split(C.byref(d), s)
         return Z
 
+    # ------------------------------------------------------------------ everything after the input conv (forward below, FusedSampler.denoise_once)
+    NONLOCAL_F16 = "the optional non-local GCN block runs on float32 features; use precision 'f16x3' or 'f32' (EgoHMR.gcn_precision, ModulatedGCN.precision) with it"
+
+    @torch.no_grad()
+    def denoiser_tail(self, h, fill, *, rows, B, passes, vis, precision, device):
+        """x0 [B, 144] from the native handle `h`: fill(X0) writes the input conv's `rows` rows into a zeroed [rows_pad, hid] buffer, then the residual blocks as
+        ONE chained launch, the optional non-local block and gconv_output (vis / passes: the image-masked second pass).  precision: its name, as set on `h`."""
+        A = _lib.api()
+        tile = A.ehm_gcn_row_tile()
+        rows_pad = (rows + tile - 1) // tile * tile
+        X = [torch.zeros(rows_pad, self.hid_dim, device=device) for _ in range(3)]
+        s = _lib.stream_ptr()
+        fill(X[0])
+        bufs = (C.c_void_p * 3)(*map(_lib.ptr, X))
+        res = C.c_int(0)
+        A.ehm_gcn_hidden_stack(h, bufs, rows_pad, C.byref(res), s)
+        feat = X[res.value]
+        if self.nonlocal_layer:
+            if precision == "f16":
+                raise _lib.EgoHMRHipError(self.NONLOCAL_F16)
+            feat = self.non_local_native(feat, rows, rows_pad)
+        x0 = torch.empty(B, 144, device=device)
+        A.ehm_gcn_output_layer(h, feat, vis, x0, B, passes, s)
+        return x0
+
     # ------------------------------------------------------------------ ModulatedGCN.forward on its own (modulated_gcn.py:99-116)
     precision = "f16x3"      # arithmetic of the standalone call: 'f16x3' (f32-grade, default) | 'f32' | 'f16' (fused.PRECISIONS)
 
     def _standalone(self, device):
         """(handle, packed input-conv weights) for forward(): rebuilt when a parameter changes; its own handle (EgoHMR.fused_sampler's carries the
         sampler's pass map / precision schedule)."""
-        import math
-        if getattr(self, "_sa_keyfn", None) is None:
+        if self._sa_keyfn is None:
             self._sa_keyfn = _lib.TensorKey(self)
         key = (self._sa_keyfn(), str(device))
-        if getattr(self, "_sa_key", None) != key:
-            if getattr(self, "_sa", None) is not None:
+        if self._sa_key != key:
+            if self._sa is not None:
                 self._sa[0].close()
             h, keep = self.create_native_handle(device)
             h = _lib.Handle(h, _lib.api().ehm_gcn_destroy, keep)
@@ -214,12 +245,7 @@ class ModulatedGCN(nn.Module):
             Cop = (Co + 127) // 128 * 128
             w2 = torch.zeros(Cop, Kp, device=device)
             w2[:Co, :K] = W.permute(0, 2, 1).reshape(Co, K)                                   # row k * hid + n = W[k][:, n]
-            amax = float(w2.abs().max())
-            scale = 2.0 ** math.floor(math.log2(2048.0 / amax)) if amax > 0 else 1.0
-            buf = torch.empty(Cop, Kp, device=device)
-            with torch.cuda.device(device):
-                _lib.api().ehm_split_pack(w2, buf, Cop, Kp, Kp, scale, _lib.stream_ptr())
-            self._sa, self._sa_key = (h, buf, scale, K, Kp), key
+            self._sa, self._sa_key = (h, *_split_pack(w2), K, Kp), key
         return self._sa
 
     @torch.no_grad()
@@ -238,7 +264,6 @@ class ModulatedGCN(nn.Module):
             raise ValueError(f"ModulatedGCN.forward: expected [B, 24, {self.in_dim}], got {tuple(x.shape)}")
         if self.out_dim != 6:
             raise NotImplementedError("the output-conv kernels are built for out_dim = 6 (the 6-D rotation head, egohmr.py:132)")
-        from .fused import PRECISIONS
         A = _lib.api()
         dev = x.device
         B, hid = x.shape[0], self.hid_dim
@@ -253,20 +278,8 @@ class ModulatedGCN(nn.Module):
             pre = torch.empty(rows, 2 * hid, device=dev)
             d = _lib.ConvDesc(_lib.ptr(xp), _lib.ptr(wbuf), None, None, _lib.ptr(pre), rows, 1, 1, Kp, 2 * hid, 1, 1, 1, 0, 0, scale)
             A.ehm_conv_nhwc_split(C.byref(d), s)
-            tile = A.ehm_gcn_row_tile()
-            rows_pad = (rows + tile - 1) // tile * tile
-            X = [torch.zeros(rows_pad, hid, device=dev) for _ in range(3)]
-            A.ehm_gcn_input_layer_rows(h, pre, X[0], B, s)
-            bufs = (C.c_void_p * 3)(*map(_lib.ptr, X))
-            res = C.c_int(0)
-            A.ehm_gcn_hidden_stack(h, bufs, rows_pad, C.byref(res), s)
-            feat = X[res.value]
-            if self.nonlocal_layer:
-                if self.precision == "f16":
-                    raise _lib.EgoHMRHipError("the optional non-local GCN block runs on float32 features; use precision 'f16x3' or 'f32' with it")
-                feat = self.non_local_native(feat, rows, rows_pad)
-            out = torch.empty(B, 144, device=dev)
-            A.ehm_gcn_output_layer(h, feat, None, out, B, 1, s)
+            out = self.denoiser_tail(h, lambda X0: A.ehm_gcn_input_layer_rows(h, pre, X0, B, s), rows=rows, B=B, passes=1, vis=None,
+                                     precision=self.precision, device=dev)
             A.ehm_gcn_stack_status(h, s)
         return out.view(B, 24, 6)
 
@@ -373,10 +386,7 @@ class EgoHMR(nn.Module):
         # config 3: 2.40 -> 2.50 k; profiles/r06r_loop_bodies_ab.txt).  Results do not depend on the grouping (bodies are independent).
         self.loop_bodies = 256
         self.per_step_launches = False     # True: the separate per-step launches of rounds 2-3 instead of step_fused_kernel (same bits; A/B runs and tests)
-        self.pass_group = 1                # second passes pruned per item (1) or per group of this many consecutive items (FusedSampler.prepare)
         self.prune_passes = True           # exact: items whose 24 joints are all visible skip the image-masked pass (egohmr.py:239-254)
-        self.overlap_encoders = False      # True: ResNet-50 and the scene PointNet on two HIP streams - measured 0.5 ms SLOWER than one after the other
-                                           # (17.27 vs 16.75 ms, tools/enc_split.py, three alternations: both fill the chip on their own)
         # arithmetic of the hidden GCN convs: 'f32' (f32-input MFMA), 'f16x3' (split-f16 MFMA, f32-grade), 'f16' (plain f16, not parity-grade)
         self.gcn_precision = "f16x3"
         # arithmetic of the two conditioning encoders: 'f16x3' (split-f16, f32 grade - the parity path) | 'f16' (plain f16 operands and activations: the
@@ -438,7 +448,7 @@ class EgoHMR(nn.Module):
             tv = fs.timestep_vectors(uniq)
             for i, t in enumerate(uniq.tolist()):
                 sel = torch.nonzero(ts == t).reshape(-1)
-                x0[sel] = fs.denoise_once(fs._subset(st, sel), x_t[sel].contiguous(), tv[i], passes)
+                x0[sel] = fs.denoise_once(st.take(sel), x_t[sel].contiguous(), tv[i], passes)
         mean, std = self._std_mean()
         verts = torch.empty(B, self.smpl.num_verts, 3, device=self.device)
         joints = torch.empty(B, self.smpl.num_joints_out, 3, device=self.device)
@@ -522,8 +532,4 @@ class EgoHMRVolsmpl(EgoHMR):
         self.guide_reduction = "sum"
         self.guide_all_points = True
 
-    def eval_coll_volsmpl(self, output):
-        p = output["pred_smpl_params"]
-        so = self.smpl(betas=p["betas"], body_pose=p["body_pose"], global_orient=p["global_orient"], pose2rot=False)
-        _, _, hits = self.fused_sampler.collision(so.vertices, self.scene_pcd_verts, want_grad=False, want_hits=True, all_points=False)
-        return (hits.float() / self.scene_pcd_verts.shape[1]).tolist()
+    eval_coll_volsmpl = EgoHMR.eval_coll       # (the build's proxy stands in for both metrics, bbox-selected points in both)

@@ -1,7 +1,11 @@
 """CPU: the pure parts of the per-checkpoint precision-schedule calibration (egohmr_amd/fused.py): the ladder of candidate k, the
-search over it, and the cache key's sensitivity.  The measured part (the sampling loops) is covered by tests/test_gpu_schedule.py."""
+search over it, the cache key's sensitivity and the guided-step count inside that key.  The measured part (the sampling loops) is covered by
+tests/test_gpu_schedule.py."""
 import math
 
+import pytest
+
+from egohmr_amd.diffusion import create_gaussian_diffusion
 from egohmr_amd.fused import FusedSampler
 
 
@@ -49,3 +53,22 @@ def test_pick_k_non_monotone_blip_is_conservative():
         return 0.0 if k >= 100 else (1e-5 if k in (27, 36) else 1e-6 if k >= 15 else 1e-3)
     k, _ = _search(ea, ea)
     assert ea(k) <= 5e-6 and k in (15, 20, 47)
+
+
+@pytest.mark.parametrize("steps,respacing", [(50, ""), (100, ""), (1000, ""), (50, "ddim5"), (100, "ddim10"), (100, "ddim50"), (1000, "ddim50")])
+def test_guided_step_count_is_the_number_of_rows_with_a_gradient_scale(steps, respacing):
+    """schedule_key's n_guided - for the run, the calibration and install_schedule alike - against an independent count: the rows of
+    diffusion.step_coefs whose grad_scale is not zero.  (The calibration used to count them in the first 16 rows only, the run from the
+    step table's first guided row: one integer for every sampler here.)"""
+    diffusion = create_gaussian_diffusion(num_diffusion_timesteps=steps, timestep_respacing=respacing)
+    T = diffusion.num_timesteps
+    assert T == (int(respacing[4:]) if respacing else steps)
+    for ddim in (False, True):
+        for guided in (False, True):
+            for w in (0.0, 1.0, 30.0):
+                rows = [diffusion.step_coefs(i, ddim, 0.0, w, guided).grad_scale != 0.0 for i in range(T)]
+                n = FusedSampler.guided_steps(diffusion, ddim, w, guided)
+                assert n == sum(rows), (ddim, guided, w)
+                assert rows == [True] * n + [False] * (T - n)                     # a contiguous tail of the loop (lowest t)
+                assert n == T - FusedSampler.step_table(diffusion, ddim, w, guided)[1]
+                assert n == ((min(T, 4) if ddim else min(T, 11) if w else 0) if guided else 0)

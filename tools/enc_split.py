@@ -1,6 +1,6 @@
 #!/usr/bin/env python3
-"""Where FusedSampler.prepare's time goes at the benchmark shape: ResNet-50 alone, PointNet alone, both sequentially, both on two
-streams, and the full prepare (encoders + projections).  GPU time by events, host time by perf_counter."""
+"""Where FusedSampler.prepare's time goes at the benchmark shape: ResNet-50 alone, PointNet alone, both one after the other, and the full
+prepare (encoders + projections).  Wall time with a final synchronize, host-side issue time by perf_counter."""
 import os
 import sys
 import time
@@ -40,11 +40,18 @@ for name, fn in (("ResNet-50 trunk", lambda: backbone(img)), ("ResNet-50, shortc
                  ("scene PointNet", lambda: scene(pts))):
     wall, host = timed(fn)
     print(f"{name:42s}: {wall:7.2f} ms wall, {host:6.2f} ms of it host-side issue")
-for mode in (False, True, False, True, False, True):
-    model.overlap_encoders = mode
 
-    def prep():
-        fs.invalidate()
-        fs.prepare(b)
-    wall, host = timed(prep)
-    print(f"prepare overlap={mode!s:5s}: {wall:7.2f} ms wall, {host:6.2f} ms host-side issue")
+
+def both():
+    backbone(img)
+    scene(pts)
+
+
+def prep():
+    fs.invalidate()
+    fs.prepare(b)
+
+
+for name, fn in (("both encoders, one after the other", both), ("prepare", prep), ("both encoders, one after the other", both), ("prepare", prep)):
+    wall, host = timed(fn)
+    print(f"{name:42s}: {wall:7.2f} ms wall, {host:6.2f} ms of it host-side issue")
