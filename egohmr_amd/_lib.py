@@ -16,6 +16,7 @@ from torch tensors are valid inside the kernels' launches.
 from __future__ import annotations
 
 import ctypes as C
+import glob
 import itertools
 import os
 import subprocess
@@ -43,9 +44,6 @@ class EgoHMRRangeError(EgoHMRHipError):
     and re-runs the call)."""
 
 
-HEADERS = ["common.h", "smpl_dev.h", "gcn_dev.h", "step_dev.h", "internal.h"]
-
-
 def build(verbose: bool = False, force: bool = False) -> str:
     """Compile the gfx950 library in-tree with hipcc (cross-compiles without a GPU): one object per source, the sources in parallel, objects
     kept under egohmr_amd/build/ and reused while neither their source, a header nor the flags changed."""
@@ -54,7 +52,7 @@ def build(verbose: bool = False, force: bool = False) -> str:
     hipcc = os.environ.get("HIPCC", "/opt/rocm/bin/hipcc")
     extra = os.environ.get("EHM_HIPCC_FLAGS", "").split()   # e.g. -DEHM_STAMPS (tools/stamp_*.py)
     flags = ["--offload-arch=gfx950", "-O3", "-std=c++17", "-fPIC", f"-I{INCLUDE}", f"-I{CSRC}", *extra]
-    hdrs = [os.path.join(CSRC, h) for h in HEADERS] + [os.path.join(INCLUDE, "egohmr_hip.h")]
+    hdrs = glob.glob(os.path.join(CSRC, "*.h")) + [os.path.join(INCLUDE, "egohmr_hip.h")]   # every header: an edit of any of them rebuilds every object
     hdr_time = max(os.path.getmtime(h) for h in hdrs)
     tag = hashlib.sha1(" ".join([hipcc] + flags).encode()).hexdigest()[:10]
     objdir = os.path.join(_HERE, "build", os.path.basename(LIB_PATH) + "." + tag)

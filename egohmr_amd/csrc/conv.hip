@@ -15,17 +15,13 @@
 //     the loads of tile k+1 are issued before the MFMAs of tile k and converted after them.
 //   B (weights, pre-split X2<32> [Co_pad][K], scaled by a power of two): global_load_lds DMA, double buffered.
 //   Epilogue: through a float [128][128] LDS tile so that rows leave as 16-byte stores with the residual read the same way.
-#include <type_traits>
-
 #include "common.h"
 #include "egohmr_hip.h"
 #include "gcn_dev.h"
 #include "internal.h"
+#include "x2_tile_dev.h"
 
 namespace {
-
-#define AS1 __attribute__((address_space(1)))
-#define AS3 __attribute__((address_space(3)))
 
 constexpr int CBM = 128, CBN = 128, CBK = 32;
 constexpr int C_STAGE = (CBM + CBN) * CBK;   // floats: 32 KiB
@@ -229,7 +225,7 @@ __global__ __launch_bounds__(256, 2) void conv_nhwc_split_kernel(ConvArgs p) {
 // image or the row is past M - and the DMA gathers the tile.  The float32 path above re-reads and re-SPLITS every input value once
 // per tap in the vector ALU.  Engine = linear.hip's linear_tile_kernel: persistent blocks, 192 x 128 tiles, next tile's DMA before
 // the epilogue, barrier-free epilogue through each wave's own pieces of stage 1, residual read and output written as X2 rows.
-constexpr int XBM = 192, XRK = 32;
+constexpr int XBM = 192, XRK = X2_RK;
 constexpr int XA_T = XBM * XRK;                                          // floats of a stage's activation region (24 KiB)
 constexpr int x_stage_floats(int nu) { return XA_T + 64 * nu * XRK; }    // + 8 KiB of weights per 64 output channels
 
@@ -260,11 +256,6 @@ constexpr int kSkFlagBytes = 4096;         // arrival counters of up to 1023 cut
 constexpr int kSkPoisonWord = kSkFlagBytes / 4 - 1;   // ... and, in its last word, the sticky count of hand-off time-outs (ehm_conv_x2_workspace_status)
 constexpr int kSkHandoffKTiles = 14;   // what a cut tile's hand-off costs, in K-tile times (measured, see sk_plan)
 
-template <int NU>
-struct XFrags {
-  half8 ah[3], al[3], bh[NU], bl[NU];
-};
-
 // NU = 2: 192 x 128 tiles (96 x 64 per wave); NU = 1: 192 x 64 tiles (96 x 32 per wave) for Co = 64 layers (no padding columns through
 // the matrix cores).
 // HO ("hi only", ehm_conv_x2_desc.hi_only): the plain-f16 tier of the encoders (BASELINE config 5's fp16 tier; NOT parity grade: 0.4 - 1.4 mm of final
@@ -274,14 +265,10 @@ template <int NU, bool SK, bool DS = false, bool HO = false>
 __global__ __launch_bounds__(256, 2) void conv_x2_tile_kernel(ConvX2Args p) {
   constexpr int XBN = 64 * NU, XSTG = x_stage_floats(NU);
   __shared__ __attribute__((aligned(16))) float lds[2 * XSTG];   // 80 / 64 KiB; the ONLY LDS object
-  // MODE.FP16_OVFL = 1 for the life of the wave: every f32 -> f16 conversion of the epilogue clamps to +-65504 instead of producing inf - the
-  // same results on finite values as the explicit clamps it replaces (4 of the ~8 vector-ALU instructions per output value: v_med3 + its
-  // canonicalising v_max, twice), as in the GCN tile engine (gcn_tile.hip)
-  __builtin_amdgcn_s_setreg(1 | (23 << 6), 1);
+  x2_fp16_ovfl_on();
 
   constexpr int KS = 2, NM = 9 * NU, NR = 6 + 2 * NU, NBD = 2 * NU;
-  // split-f16 products on v_mfma_f32_16x16x32_f16 (a K tile = ONE k-step; the K loop of gcn_tile.hip's split mode: four (row half, column half) phases in
-  // snake order, no operand half double-buffered); the hi-only tier keeps the 32 x 32 x 16 form
+  // split-f16 products on the 16 x 16 x 32 MFMA (x2_tile_dev.h; see tile16 in gcn_tile.hip); the hi-only tier keeps the 32 x 32 x 16 form
   constexpr bool M16 = !HO;
   const int tid = threadIdx.x;
   const int K = p.KH * p.KW * p.Ci + (DS ? p.Ci2 : 0);
@@ -292,54 +279,23 @@ __global__ __launch_bounds__(256, 2) void conv_x2_tile_kernel(ConvX2Args p) {
   const int m_tiles = (int)((p.M + XBM - 1) / XBM);
 
   int lane, wave, wm, wn, mi, g, r0, swz;
-  bool hi_lane;                                   // my 16-byte chunk of an operand piece holds hi halves (logical chunks 0-3 of the 128-byte K tile)
-  int oA[KS][2], oB[KS][2];
+  bool hi_lane;
+  int oA[KS][2][1], oB[KS][2];
   [[maybe_unused]] int oA16[2], oB16[2];
-  auto thread_consts = [&]() {
-    int t = tid;
-    asm volatile("" : "+v"(t));
-    lane = t & 63;
-    wave = __builtin_amdgcn_readfirstlane(t >> 6);
+  auto thread_consts = [&]() {                    // re-derived per tile (x2_tile_dev.h)
+    x2_lane_wave(tid, lane, wave);
     wm = wave >> 1; wn = wave & 1;
     mi = lane & 31; g = lane >> 5;
-    r0 = 8 * wave + (lane >> 3);
-    swz = ((lane & 7) ^ ((r0 >> 1) & 7)) << 2;
-    hi_lane = swz < 16;
-    const int rA = 96 * wm + mi, rB = 32 * NU * wn + mi;
-    const int keyA = (rA >> 1) & 7, keyB = (rB >> 1) & 7;
-#pragma unroll
-    for (int s = 0; s < KS; ++s)
-#pragma unroll
-      for (int hl = 0; hl < 2; ++hl) {
-        const int c = 4 * hl + 2 * s + g;
-        oA[s][hl] = rA * XRK + ((c ^ keyA) << 2);
-        oB[s][hl] = XA_T + rB * XRK + ((c ^ keyB) << 2);
-      }
-    if constexpr (M16) {      // lane (i = l & 15, kg = l >> 4): row i of a 16-row tile, logical chunk kg (hi) / 4 + kg (lo) of the 128-byte K tile
-      const int i16 = lane & 15, kg = lane >> 4, key = (i16 >> 1) & 7;
-#pragma unroll
-      for (int hl = 0; hl < 2; ++hl) {
-        oA16[hl] = (96 * wm + i16) * XRK + (((4 * hl + kg) ^ key) << 2);
-        oB16[hl] = XA_T + (32 * NU * wn + i16) * XRK + (((4 * hl + kg) ^ key) << 2);
-      }
-    }
+    x2_dma_lane(lane, wave, r0, swz);
+    hi_lane = x2_hi_lane(swz);
+    X2_FRAG_OFFSETS32(oA, oB, KS, 2, 1, XA_T, 96 * wm + mi, 32 * NU * wn + mi, g);
+    if constexpr (M16) X2_FRAG_OFFSETS16(oA16, oB16, XA_T, 96 * wm, 32 * NU * wn, lane);
   };
   thread_consts();
 
   const int G = gridDim.x, b = blockIdx.x;
-  const bool xcd_order = (G % 8 == 0) && ((G / 8) % n_tiles == 0);
-  auto tile_of = [&](int it, int& m, int& n) -> bool {
-    if (xcd_order) {
-      const int x = b & 7, j = b >> 3, per = (G >> 3) / n_tiles;
-      m = (it * per + j / n_tiles) * 8 + x;
-      n = j % n_tiles;
-    } else {
-      const long long t = (long long)it * G + b;
-      m = (int)(t / n_tiles);
-      n = (int)(t % n_tiles);
-    }
-    return m < m_tiles;
-  };
+  const bool xcd_order = x2_xcd_order(G, n_tiles);
+  auto tile_of = [&](int it, int& m, int& n) -> bool { return x2_xcd_tile_of(xcd_order, it, b, G, n_tiles, m_tiles, m, n); };
 
   // my six activation rows of the tile: float offset of the (kh = 0, kw = 0) tap pixel's channel 0 (+ my swizzled chunk) and the taps
   // that lie inside the image
@@ -398,67 +354,51 @@ __global__ __launch_bounds__(256, 2) void conv_x2_tile_kernel(ConvX2Args p) {
 #pragma unroll
     for (int i = 0; i < NBD; ++i) dma_b(buf, kt, i);
   };
-  auto read_frags = [&](XFrags<NU>& f, int buf, int s) {
+  typedef X2Frags<NU, !HO> XFrags;
+  auto read_frags = [&](XFrags& f, int buf, int s) {
     const float* S = lds + buf * XSTG;
 #pragma unroll
     for (int t = 0; t < 3; ++t) {
-      f.ah[t] = *(const half8*)(S + oA[s][0] + 32 * t * XRK);
-      if constexpr (!HO) f.al[t] = *(const half8*)(S + oA[s][1] + 32 * t * XRK);
+      f.ah[t] = *(const half8*)(S + oA[s][0][0] + 32 * t * XRK);
+      if constexpr (!HO) f.al[t] = *(const half8*)(S + oA[s][1][0] + 32 * t * XRK);
     }
- #pragma unroll
+#pragma unroll
     for (int u = 0; u < NU; ++u) {
       f.bh[u] = *(const half8*)(S + oB[s][0] + 32 * u * XRK);
       if constexpr (!HO) f.bl[u] = *(const half8*)(S + oB[s][1] + 32 * u * XRK);
     }
   };
   f32x16 acc[3][NU];
-  auto mfmas = [&](const XFrags<NU>& f) {
-#pragma unroll
-    for (int t = 0; t < 3; ++t)
-#pragma unroll
-      for (int u = 0; u < NU; ++u) {                             // small cross terms first, leading term last
-        if constexpr (!HO) {
-          acc[t][u] = __builtin_amdgcn_mfma_f32_32x32x16_f16(f.al[t], f.bh[u], acc[t][u], 0, 0, 0);
-          acc[t][u] = __builtin_amdgcn_mfma_f32_32x32x16_f16(f.ah[t], f.bl[u], acc[t][u], 0, 0, 0);
-        }
-        acc[t][u] = __builtin_amdgcn_mfma_f32_32x32x16_f16(f.ah[t], f.bh[u], acc[t][u], 0, 0, 0);
-      }
-  };
+  auto mfmas = [&](const XFrags& f) { x2_mfmas(acc, f); };
   auto pin_reads = [&]() {
-    if constexpr (HO) return;                     // (the hi-only instruction mix is left to the scheduler)
-#pragma unroll
-    for (int i = 0; i < NR; ++i) {
-      __builtin_amdgcn_sched_group_barrier(0x008, 1, 0);
-      __builtin_amdgcn_sched_group_barrier(0x100, 1, 0);
-    }
-    __builtin_amdgcn_sched_group_barrier(0x008, NM - NR, 0);
+    if constexpr (!HO) x2_pin_reads<NR, NM>();    // (the hi-only instruction mix is left to the scheduler)
   };
   auto pin_reads_dma = [&]() {
     if constexpr (HO) return;
     if constexpr (NU == 2) {                                      // 18 MFMAs, 10 reads, 10 DMAs
 #pragma unroll
       for (int i = 0; i < NR; ++i) {
-        __builtin_amdgcn_sched_group_barrier(0x008, 1, 0);
-        __builtin_amdgcn_sched_group_barrier(0x100, 1, 0);
+        __builtin_amdgcn_sched_group_barrier(SG_MFMA, 1, 0);
+        __builtin_amdgcn_sched_group_barrier(SG_DS_READ, 1, 0);
       }
 #pragma unroll
       for (int i = 0; i < 2; ++i) {
-        __builtin_amdgcn_sched_group_barrier(0x008, 1, 0);
-        __builtin_amdgcn_sched_group_barrier(0x010, 2, 0);
+        __builtin_amdgcn_sched_group_barrier(SG_MFMA, 1, 0);
+        __builtin_amdgcn_sched_group_barrier(SG_VMEM, 2, 0);
       }
 #pragma unroll
       for (int i = 0; i < 6; ++i) {
-        __builtin_amdgcn_sched_group_barrier(0x008, 1, 0);
-        __builtin_amdgcn_sched_group_barrier(0x010, 1, 0);
+        __builtin_amdgcn_sched_group_barrier(SG_MFMA, 1, 0);
+        __builtin_amdgcn_sched_group_barrier(SG_VMEM, 1, 0);
       }
     } else {                                                      // 9 MFMAs, 8 reads, 8 DMAs
 #pragma unroll
       for (int i = 0; i < NR; ++i) {
-        __builtin_amdgcn_sched_group_barrier(0x008, 1, 0);
-        __builtin_amdgcn_sched_group_barrier(0x100, 1, 0);
-        __builtin_amdgcn_sched_group_barrier(0x010, 1, 0);
+        __builtin_amdgcn_sched_group_barrier(SG_MFMA, 1, 0);
+        __builtin_amdgcn_sched_group_barrier(SG_DS_READ, 1, 0);
+        __builtin_amdgcn_sched_group_barrier(SG_VMEM, 1, 0);
       }
-      __builtin_amdgcn_sched_group_barrier(0x008, 1, 0);
+      __builtin_amdgcn_sched_group_barrier(SG_MFMA, 1, 0);
     }
   };
 
@@ -519,56 +459,24 @@ __global__ __launch_bounds__(256, 2) void conv_x2_tile_kernel(ConvX2Args p) {
       for (int u = 0; u < NU; ++u)
 #pragma unroll
         for (int r = 0; r < 16; ++r) acc[t][u][r] = 0.f;
-    XFrags<NU> f0, f1;
+    XFrags f0, f1;
     if constexpr (!M16) read_frags(f0, 0, 0);
     const int KL = pc.k1 - pc.k0;                                // K tiles of this piece (>= 2)
     // ---- 16 x 16 x 32: operand halves A[rh] (row tiles 3 rh .. + 2 of 16 rows), B[ch] (column tiles NU ch .. + NU - 1 of 16), 6 x 2 NU accumulators
     [[maybe_unused]] half8 Ah[2][3], Al[2][3], Bh[2][NU], Bl[2][NU];
-    typedef float f32x4a __attribute__((ext_vector_type(4)));
     [[maybe_unused]] f32x4a c16[6][2 * NU];
-    typedef std::integral_constant<int, 0> I0;
-    typedef std::integral_constant<int, 1> I1;
     [[maybe_unused]] auto ldA = [&](auto rhc, int buf) __attribute__((always_inline)) {
       constexpr int rh = decltype(rhc)::value;
       const float* S = lds + buf * XSTG;
-#pragma unroll
-      for (int t = 0; t < 3; ++t) {
-        Ah[rh][t] = *(const half8*)(S + oA16[0] + 16 * (3 * rh + t) * XRK);
-        Al[rh][t] = *(const half8*)(S + oA16[1] + 16 * (3 * rh + t) * XRK);
-      }
+      X2_LD16(t, 3, Ah[rh], Al[rh], S, oA16[0], oA16[1], 16 * (3 * rh + t));
     };
     [[maybe_unused]] auto ldB = [&](auto chc, int buf) __attribute__((always_inline)) {
       constexpr int ch = decltype(chc)::value;
       const float* S = lds + buf * XSTG;
-#pragma unroll
-      for (int u = 0; u < NU; ++u) {
-        Bh[ch][u] = *(const half8*)(S + oB16[0] + 16 * (NU * ch + u) * XRK);
-        Bl[ch][u] = *(const half8*)(S + oB16[1] + 16 * (NU * ch + u) * XRK);
-      }
+      X2_LD16(u, NU, Bh[ch], Bl[ch], S, oB16[0], oB16[1], 16 * (NU * ch + u));
     };
-    [[maybe_unused]] auto mm = [&](auto rhc, auto chc) __attribute__((always_inline)) {      // 9 NU MFMAs: small cross terms first, 3 NU independent accumulators per term
-      constexpr int rh = decltype(rhc)::value, ch = decltype(chc)::value;
-#pragma unroll
-      for (int t = 0; t < 3; ++t)
-#pragma unroll
-        for (int u = 0; u < NU; ++u) c16[3 * rh + t][NU * ch + u] = __builtin_amdgcn_mfma_f32_16x16x32_f16(Al[rh][t], Bh[ch][u], c16[3 * rh + t][NU * ch + u], 0, 0, 0);
-#pragma unroll
-      for (int t = 0; t < 3; ++t)
-#pragma unroll
-        for (int u = 0; u < NU; ++u) c16[3 * rh + t][NU * ch + u] = __builtin_amdgcn_mfma_f32_16x16x32_f16(Ah[rh][t], Bl[ch][u], c16[3 * rh + t][NU * ch + u], 0, 0, 0);
-#pragma unroll
-      for (int t = 0; t < 3; ++t)
-#pragma unroll
-        for (int u = 0; u < NU; ++u) c16[3 * rh + t][NU * ch + u] = __builtin_amdgcn_mfma_f32_16x16x32_f16(Ah[rh][t], Bh[ch][u], c16[3 * rh + t][NU * ch + u], 0, 0, 0);
-    };
-    [[maybe_unused]] auto pin16 = [&](int reads, int dmas) __attribute__((always_inline)) {   // reads one per MFMA from the start, DMAs behind them
-#pragma unroll
-      for (int i = 0; i < 9 * NU; ++i) {                          // reads behind every second MFMA, DMAs in the gaps (as in gcn_tile.hip)
-        __builtin_amdgcn_sched_group_barrier(0x008, 1, 0);
-        if ((i & 1) == 0 && (i >> 1) < reads) __builtin_amdgcn_sched_group_barrier(0x100, 1, 0);
-        else if ((i & 1) == 1 && (i >> 1) < dmas) __builtin_amdgcn_sched_group_barrier(0x010, 1, 0);
-      }
-    };
+    [[maybe_unused]] auto mm = [&](auto rhc, auto chc) __attribute__((always_inline)) { x2_mm16<decltype(rhc)::value, decltype(chc)::value, NU>(c16, Ah, Al, Bh, Bl); };
+    [[maybe_unused]] auto pin16 = [&](int reads, int dmas) __attribute__((always_inline)) { x2_pin16<9 * NU>(reads, dmas); };
     // K tile j of the piece (parity PAR = j & 1 = its stage).  Phases (0, cf) (0, cs) | barrier | (1, cs) (1, cf) with cf = PAR: the next tile's first phase
     // is (0, cs) - the halves that are free to be refilled during this tile's last two phases.  Returns false behind the barrier of the piece's LAST K tile
     // (its last two phases run below); K tile j + 2 is staged while there is one.
@@ -763,7 +671,6 @@ __global__ __launch_bounds__(256, 2) void conv_x2_tile_kernel(ConvX2Args p) {
       // row tile (16 rows x 32 NU columns through 2 NU of the wave's six 1 KiB pieces): piece NU (row >> 3) + (col >> 5) holds [8 rows][32 columns]; inside a piece
       // row (row & 7) sits at (row & 7) ^ (row >> 3) and its two 16-column halves swap places for odd rg (four lane groups of a write -> four 16-bank groups).
       // Read items = (row, 8 columns): NU per lane.
-      typedef unsigned int u32x4_t __attribute__((ext_vector_type(4)));
       const unsigned int yrow = (unsigned int)p.Co * 4u;
       const __amdgpu_buffer_rsrc_t yB = ehm_buffer_rsrc(p.y + (row0 + 96 * wm) * (size_t)yrow);
       const __amdgpu_buffer_rsrc_t rB = ehm_buffer_rsrc((p.res ? p.res : p.y) + (row0 + 96 * wm) * (size_t)yrow);
@@ -787,7 +694,7 @@ __global__ __launch_bounds__(256, 2) void conv_x2_tile_kernel(ConvX2Args p) {
       }
 #pragma unroll
       for (int rt = 0; rt < 6; ++rt) {
-        u32x4_t rq[NU][2];
+        u32x4 rq[NU][2];
         if (has_res) {
 #pragma unroll
           for (int k = 0; k < NU; ++k) {
@@ -821,13 +728,12 @@ __global__ __launch_bounds__(256, 2) void conv_x2_tile_kernel(ConvX2Args p) {
           for (int c = 0; c < 8; ++c) {
             // (stream-K: a poisoned tile must stay NaN through the ReLU - v_max_f32 returns its non-NaN operand)
             if (relu) v[c] = SK ? (v[c] < 0.f ? 0.f : v[c]) : fmaxf(v[c], 0.f);
-            hh[c] = (half_t)v[c];                              // (MODE.FP16_OVFL: the conversions saturate at +-65504, see the kernel's head)
-            ll[c] = (half_t)(v[c] - (float)hh[c]);
+            X2_SPLIT(v[c], hh[c], ll[c]);
           }
           const unsigned int vo = (unsigned int)(16 * rt + (NU == 2 ? irow0 + 8 * k : irow0)) * yrow + col_off;
           if (colw < p.Co) {
-            __builtin_amdgcn_raw_buffer_store_b128(__builtin_bit_cast(u32x4_t, hh), yB, vo, 0, 0);
-            __builtin_amdgcn_raw_buffer_store_b128(__builtin_bit_cast(u32x4_t, ll), yB, vo + 64u, 0, 0);
+            __builtin_amdgcn_raw_buffer_store_b128(__builtin_bit_cast(u32x4, hh), yB, vo, 0, 0);
+            __builtin_amdgcn_raw_buffer_store_b128(__builtin_bit_cast(u32x4, ll), yB, vo + 64u, 0, 0);
           }
         }
       }
@@ -854,10 +760,9 @@ __global__ __launch_bounds__(256, 2) void conv_x2_tile_kernel(ConvX2Args p) {
       }
       constexpr int ISTEP = NU == 2 ? 8 : 16;                    // rows between my consecutive items
       const unsigned int col_off = (unsigned int)(((colw >> 5) * 64 + (colw & 31)) * 2);
-      typedef unsigned int u32x4_t __attribute__((ext_vector_type(4)));
 #pragma unroll
       for (int ps = 0; ps < NPASS; ++ps) {
-        u32x4_t rq[3][2];
+        u32x4 rq[3][2];
         if (has_res) {
 #pragma unroll
           for (int it3 = 0; it3 < 3; ++it3) {
@@ -901,13 +806,12 @@ __global__ __launch_bounds__(256, 2) void conv_x2_tile_kernel(ConvX2Args p) {
           for (int c = 0; c < 8; ++c) {
             // (stream-K: a poisoned tile must stay NaN through the ReLU - v_max_f32 returns its non-NaN operand)
             if (relu) v[c] = SK ? (v[c] < 0.f ? 0.f : v[c]) : fmaxf(v[c], 0.f);
-            hh[c] = (half_t)v[c];                              // (MODE.FP16_OVFL: the conversions saturate at +-65504, see the kernel's head)
-            ll[c] = (half_t)(v[c] - (float)hh[c]);
+            X2_SPLIT(v[c], hh[c], ll[c]);
           }
           const unsigned int vo = (unsigned int)(8 * GP * ps + ISTEP * it3 + irow) * yrow + col_off;
           if (colw < p.Co) {
-            __builtin_amdgcn_raw_buffer_store_b128(__builtin_bit_cast(u32x4_t, hh), yB, vo, 0, 0);
-            if constexpr (!HO) __builtin_amdgcn_raw_buffer_store_b128(__builtin_bit_cast(u32x4_t, ll), yB, vo + 64u, 0, 0);
+            __builtin_amdgcn_raw_buffer_store_b128(__builtin_bit_cast(u32x4, hh), yB, vo, 0, 0);
+            if constexpr (!HO) __builtin_amdgcn_raw_buffer_store_b128(__builtin_bit_cast(u32x4, ll), yB, vo + 64u, 0, 0);
           }
         }
       }

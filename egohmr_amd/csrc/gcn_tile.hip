@@ -2,7 +2,7 @@
 // _ResGraphConv, modulated_gcn.py:38-42) on the f16 matrix cores of gfx950, two arithmetic modes from one tile engine:
 //   P = 3  "f16x3": both GEMM operands stored as hi + lo f16 pairs (X2<32>, gcn_dev.h), three MFMAs per product
 //          (lo*hi + hi*lo + hi*hi), f32 accumulate: 22-bit operands, f32-grade results (the parity path).  Since round 5 on
-//          v_mfma_f32_16x16x32_f16: at the socket's power cap - where this kernel runs - the matrix pipe sustains 2.26 PFLOP/s
+//          v_mfma_f32_16x16x32 (f16): at the socket's power cap - where this kernel runs - the matrix pipe sustains 2.26 PFLOP/s
 //          in that form against 1.86 as 32x32x16 on the same operands (tools/mfma_ceiling.py: a quarter of the accumulator
 //          traffic per MAC); chain kernel 1014 -> 905 us per launch, same box.  See "16 x 16 x 32" in run_tiles;
 //   P = 1  "f16":   plain f16 storage [rows][hid] and one MFMA per product (BASELINE config 5's fp16 denoiser, and the early
@@ -29,23 +29,19 @@
 
 #include <vector>
 
-#include <type_traits>
-
 #include "common.h"
 #include "egohmr_hip.h"
 #include "gcn_dev.h"
 #include "internal.h"
 #include "smpl_dev.h"
 #include "step_dev.h"
+#include "x2_tile_dev.h"
 
 namespace {
 
-#define AS1 __attribute__((address_space(1)))
-#define AS3 __attribute__((address_space(3)))
-
 typedef unsigned int u32x2 __attribute__((ext_vector_type(2)));
 
-constexpr int RK = 32;                                            // floats per row and K tile = 128 bytes
+constexpr int RK = X2_RK;
 constexpr int A_T = 192 * RK;                                      // floats of a stage's activation region (24 KiB)
 constexpr int stage_floats(int nw) { return A_T + 32 * nw * RK; }  // + weights: 64 channels x 2 branches per 4 waves -> 40 KiB (4 waves) / 56 KiB (8 waves)
 constexpr int kStoreAux = 16;                                     // sc1: activation stores write through to L2 (chained launch hand-off)
@@ -60,9 +56,7 @@ __device__ unsigned long long* g_tdbg = nullptr;
 #endif
 
 template <int P>
-struct Frags {
-  half8 ah[3], al[P == 3 ? 3 : 1], bh[2], bl[P == 3 ? 2 : 1];
-};
+using Frags = X2Frags<2, P == 3>;
 
 // Block-uniform identity of one output tile; everything else is derived from the launch arguments when it is needed, so that
 // only three SGPRs per tile stay live across the K loop / the epilogue.
@@ -120,12 +114,9 @@ __device__ __forceinline__ const float* layer_weights(const LayerDev& L) {
 template <int P, int MODE, int NW, class Args>
 __device__ __forceinline__ void run_tiles(float* lds, const Args& a) {
   constexpr bool CHAIN = MODE == 1;
-  constexpr bool M16 = P == 3;       // split-f16 mode: v_mfma_f32_16x16x32_f16 (see "16 x 16 x 32" below); plain f16: v_mfma_f32_32x32x16_f16
+  constexpr bool M16 = P == 3;       // split-f16 mode: v_mfma_f32_16x16x32 (f16) (see "16 x 16 x 32" below); plain f16: v_mfma_f32_32x32x16_f16
   static_assert(NW == 4 || (NW == 8 && P == 1 && CHAIN), "the 8-wave tile exists for the chained f16 kernel (f16x3 is power-bound: 8 waves measured 150 vs 152 us)");
-  // MODE.FP16_OVFL = 1 for the life of the wave: every f32 -> f16 conversion of the epilogue clamps to +-65504 instead of producing inf
-  // (hwreg MODE = 1, bit 23).  The explicit clamps this replaces were 144 v_med3_f32 + their canonicalising v_max_f32 per wave and tile,
-  // in an epilogue during which the block's matrix pipes idle.
-  __builtin_amdgcn_s_setreg(1 | (23 << 6), 1);
+  x2_fp16_ovfl_on();
   constexpr int NWN = NW / 2;                 // waves across the channels
   constexpr int NT = 32 * NWN;                // channels per tile
   constexpr int BROWS = 2 * NT;               // weight rows per stage (W0 | W1 per 64 channels)
@@ -135,8 +126,7 @@ __device__ __forceinline__ void run_tiles(float* lds, const Args& a) {
   constexpr int NM = P == 3 ? 18 : 6;         // MFMAs per k-step
   constexpr int NR = P == 3 ? 10 : 5;         // ds_read_b128 per k-step
   const int tid = threadIdx.x;
-  // Per-thread constants are RE-DERIVED at the head of every tile from an opaque copy of the thread id (thread_consts below), so
-  // that none of them has to stay in a register across the epilogue - with them live the chained kernel spilled ~120 VGPRs.
+  // Per-thread constants are RE-DERIVED at the head of every tile (thread_consts below; x2_lane_wave in x2_tile_dev.h)
   int lane, wave, wm, wn, mi, g;
   bool odd;
 
@@ -145,8 +135,7 @@ __device__ __forceinline__ void run_tiles(float* lds, const Args& a) {
   const int rowf = P == 3 ? K : K / 2;        // floats per operand row
   const int KT = rowf / RK;
 
-  // ---- DMA: one wave instruction = 8 rows x 128 B; physical 16-byte chunk c of row r holds logical chunk c ^ ((r>>1)&7)
-  int r0, swz;                                               // r0 = 8 wave + lane / 8; swz = ((lane & 7) ^ ((r0 >> 1) & 7)) << 2; r0 + 32 i keeps the key
+  int r0, swz;                                               // my DMA row and swizzled chunk (x2_dma_lane)
   const size_t row32 = (size_t)(8 * NW) * rowf;              // a wave's consecutive DMA instructions are 32 (64) rows apart
   // operand stream addressing: buffer form - a tile's base in an SGPR descriptor, the lane's row / chunk in ONE 32-bit VGPR offset that is
   // the same for every piece of the tile, the piece (rows + K tile) in the scalar offset: no vector-ALU address arithmetic in the K loop
@@ -207,15 +196,11 @@ __device__ __forceinline__ void run_tiles(float* lds, const Args& a) {
   // activation stage 1 (whose pieces are the epilogue's scratch) after it = "late" = what a wave issues last = what the head of the K
   // loop leaves in flight.  (NW = 8: a wave owns only three 1 KiB activation pieces; the other half of its scratch is a dedicated 24 KiB
   // region behind the stages - 136 KiB of LDS per block - so that the weights of stage 1 need not wait for the epilogue.)
-  constexpr bool B1_LATE = false;
-  constexpr int LATE = NDA + (B1_LATE ? NDB : 0);
   auto issue_b_early = [&]() {
 #pragma unroll
     for (int i = 0; i < NDB; ++i) dma_b(0, 0, i);
-    if constexpr (!B1_LATE) {
 #pragma unroll
-      for (int i = 0; i < NDB; ++i) dma_b(1, 1, i);
-    }
+    for (int i = 0; i < NDB; ++i) dma_b(1, 1, i);
   };
   auto issue_a0 = [&]() {
 #pragma unroll
@@ -224,10 +209,6 @@ __device__ __forceinline__ void run_tiles(float* lds, const Args& a) {
   auto issue_late = [&]() {
 #pragma unroll
     for (int i = 0; i < NDA; ++i) dma_a(1, 1, i);
-    if constexpr (B1_LATE) {
-#pragma unroll
-      for (int i = 0; i < NDB; ++i) dma_b(1, 1, i);
-    }
   };
 
   // ---- fragments (v_mfma_f32_32x32x16_f16: lane l holds row l&31, k = 8*(l>>5) .. +7 of a 16-wide step = one 16-byte chunk)
@@ -235,40 +216,19 @@ __device__ __forceinline__ void run_tiles(float* lds, const Args& a) {
   // With the C layout (row = (reg&3) + 8*(reg>>2) + 4*(lane>>5)) lane (mi, g) then owns, for ONE channel, all 24 joints of the
   // wave's bodies 2g and 2g+1, joint j of the two bodies in the ADJACENT registers 2*(j&7), 2*(j&7)+1 of accumulator j>>3.
   //   rA = 96 wm + 48 ((mi>>2)&1) + 24 (mi&1) + ((mi>>1)&1) + 2 (mi>>3);  rB = 32 wn + mi (+ 64 for the W1 branch)
-  //   keyA = (rA>>1)&7 (+8t flips its bit 2 for odd t), keyB = (rB>>1)&7 (+64 leaves it)
-  // logical chunk of (k-step s, hi/lo hl, lane half g): X2 tile = [hi k0-31 | lo k0-31] -> 4 hl + 2 s + g;  f16 tile = k0-63 -> 2 s + g
+  //   A block t sits 8 t rows further: its key has bit 2 flipped for odd t (oA[..][t & 1]); the W1 branch's + 64 leaves keyB alone
   int oA[KS][P == 3 ? 2 : 1][2], oB[KS][P == 3 ? 2 : 1];
   [[maybe_unused]] int oA16[2], oB16[2];
   auto thread_consts = [&]() {
-    int t = tid;
-    asm volatile("" : "+v"(t));                              // opaque: keeps hipcc from hoisting what follows out of the tile loop
-    lane = t & 63;
-    wave = __builtin_amdgcn_readfirstlane(t >> 6);
+    x2_lane_wave(tid, lane, wave);
     wm = wave / NWN; wn = wave % NWN;
     mi = lane & 31; g = lane >> 5;
     odd = lane & 1;
-    r0 = 8 * wave + (lane >> 3);
-    swz = ((lane & 7) ^ ((r0 >> 1) & 7)) << 2;
+    x2_dma_lane(lane, wave, r0, swz);
     const int rA = 96 * wm + 48 * ((mi >> 2) & 1) + 24 * (mi & 1) + ((mi >> 1) & 1) + 2 * (mi >> 3);
     const int rB = NW == 8 ? 128 * (wn >> 1) + 32 * (wn & 1) + mi : 32 * wn + mi;   // 8 waves: 64-channel weight group wn >> 1 of the pair
-    const int keyA = (rA >> 1) & 7, keyB = (rB >> 1) & 7;
-#pragma unroll
-    for (int s = 0; s < KS; ++s)
-#pragma unroll
-      for (int hl = 0; hl < (P == 3 ? 2 : 1); ++hl) {
-        const int c = (P == 3 ? 4 * hl : 0) + 2 * s + g;
-#pragma unroll
-        for (int o = 0; o < 2; ++o) oA[s][hl][o] = rA * RK + (((c ^ keyA) ^ (4 * o)) << 2);
-        oB[s][hl] = A_T + rB * RK + ((c ^ keyB) << 2);
-      }
-    if constexpr (M16) {
-      const int i16 = lane & 15, kg = lane >> 4, key = (i16 >> 1) & 7;
-#pragma unroll
-      for (int hl = 0; hl < 2; ++hl) {
-        oA16[hl] = (96 * wm + i16) * RK + (((4 * hl + kg) ^ key) << 2);
-        oB16[hl] = A_T + (32 * wn + i16) * RK + (((4 * hl + kg) ^ key) << 2);
-      }
-    }
+    X2_FRAG_OFFSETS32(oA, oB, KS, P == 3 ? 2 : 1, 2, A_T, rA, rB, g);
+    if constexpr (M16) X2_FRAG_OFFSETS16(oA16, oB16, A_T, 96 * wm, 32 * wn, lane);
   };
   thread_consts();
   auto read_frags = [&](Frags<P>& f, int buf, int s) {
@@ -305,53 +265,45 @@ __device__ __forceinline__ void run_tiles(float* lds, const Args& a) {
       acc1[t] = __builtin_amdgcn_mfma_f32_32x32x16_f16(f.ah[t], f.bh[1], acc1[t], 0, 0, 0);
     }
   };
-  // sched_group_barrier masks: 0x008 MFMA, 0x100 DS read, 0x010 VMEM
-  auto pin_reads = [&]() {                      // MFMA, read, MFMA, read, ... then the remaining MFMAs
-#pragma unroll
-    for (int i = 0; i < NR; ++i) {
-      __builtin_amdgcn_sched_group_barrier(0x008, 1, 0);
-      __builtin_amdgcn_sched_group_barrier(0x100, 1, 0);
-    }
-    __builtin_amdgcn_sched_group_barrier(0x008, NM - NR, 0);
-  };
+  auto pin_reads = [&]() { x2_pin_reads<NR, NM>(); };
   auto pin_reads_dma = [&]() {                  // the reads one per MFMA, the ten DMAs spread over the phase
     if constexpr (P == 3) {                     // 18 MFMAs: 10 x (MFMA, read), then 2,2,1,1,1,1,1,1 DMAs behind the last 8
 #pragma unroll
       for (int i = 0; i < NR; ++i) {
-        __builtin_amdgcn_sched_group_barrier(0x008, 1, 0);
-        __builtin_amdgcn_sched_group_barrier(0x100, 1, 0);
+        __builtin_amdgcn_sched_group_barrier(SG_MFMA, 1, 0);
+        __builtin_amdgcn_sched_group_barrier(SG_DS_READ, 1, 0);
       }
-      __builtin_amdgcn_sched_group_barrier(0x008, 1, 0);
-      __builtin_amdgcn_sched_group_barrier(0x010, 2, 0);
-      __builtin_amdgcn_sched_group_barrier(0x008, 1, 0);
-      __builtin_amdgcn_sched_group_barrier(0x010, 2, 0);
+      __builtin_amdgcn_sched_group_barrier(SG_MFMA, 1, 0);
+      __builtin_amdgcn_sched_group_barrier(SG_VMEM, 2, 0);
+      __builtin_amdgcn_sched_group_barrier(SG_MFMA, 1, 0);
+      __builtin_amdgcn_sched_group_barrier(SG_VMEM, 2, 0);
 #pragma unroll
       for (int i = 0; i < 6; ++i) {
-        __builtin_amdgcn_sched_group_barrier(0x008, 1, 0);
-        __builtin_amdgcn_sched_group_barrier(0x010, 1, 0);
+        __builtin_amdgcn_sched_group_barrier(SG_MFMA, 1, 0);
+        __builtin_amdgcn_sched_group_barrier(SG_VMEM, 1, 0);
       }
     } else if constexpr (NW == 4) {             // 6 MFMAs: 5 x (MFMA, read, 2 DMA), MFMA
 #pragma unroll
       for (int i = 0; i < NR; ++i) {
-        __builtin_amdgcn_sched_group_barrier(0x008, 1, 0);
-        __builtin_amdgcn_sched_group_barrier(0x100, 1, 0);
-        __builtin_amdgcn_sched_group_barrier(0x010, 2, 0);
+        __builtin_amdgcn_sched_group_barrier(SG_MFMA, 1, 0);
+        __builtin_amdgcn_sched_group_barrier(SG_DS_READ, 1, 0);
+        __builtin_amdgcn_sched_group_barrier(SG_VMEM, 2, 0);
       }
-      __builtin_amdgcn_sched_group_barrier(0x008, 1, 0);
+      __builtin_amdgcn_sched_group_barrier(SG_MFMA, 1, 0);
     } else {                                    // 7 DMAs: 2 x (MFMA, read, 2 DMA), 3 x (MFMA, read, DMA), MFMA
 #pragma unroll
       for (int i = 0; i < 2; ++i) {
-        __builtin_amdgcn_sched_group_barrier(0x008, 1, 0);
-        __builtin_amdgcn_sched_group_barrier(0x100, 1, 0);
-        __builtin_amdgcn_sched_group_barrier(0x010, 2, 0);
+        __builtin_amdgcn_sched_group_barrier(SG_MFMA, 1, 0);
+        __builtin_amdgcn_sched_group_barrier(SG_DS_READ, 1, 0);
+        __builtin_amdgcn_sched_group_barrier(SG_VMEM, 2, 0);
       }
 #pragma unroll
       for (int i = 2; i < NR; ++i) {
-        __builtin_amdgcn_sched_group_barrier(0x008, 1, 0);
-        __builtin_amdgcn_sched_group_barrier(0x100, 1, 0);
-        __builtin_amdgcn_sched_group_barrier(0x010, 1, 0);
+        __builtin_amdgcn_sched_group_barrier(SG_MFMA, 1, 0);
+        __builtin_amdgcn_sched_group_barrier(SG_DS_READ, 1, 0);
+        __builtin_amdgcn_sched_group_barrier(SG_VMEM, 1, 0);
       }
-      __builtin_amdgcn_sched_group_barrier(0x008, 1, 0);
+      __builtin_amdgcn_sched_group_barrier(SG_MFMA, 1, 0);
     }
   };
 
@@ -479,53 +431,19 @@ __device__ __forceinline__ void run_tiles(float* lds, const Args& a) {
     // operand half and the other is refilled from LDS while it is not in use: 80 fragment registers, nothing double-buffered.
     // Operand halves A[rh] (row tiles 3 rh .. + 2 of 16 rows), B[ch] (branch ch: two 16-channel column tiles), 6 x 4 accumulators
     [[maybe_unused]] half8 Ah[2][3], Al[2][3], Bh[2][2], Bl[2][2];
-    typedef float f32x4a __attribute__((ext_vector_type(4)));
     [[maybe_unused]] f32x4a c16[6][4];
     [[maybe_unused]] auto ldA = [&](auto rhc, int buf) {
       constexpr int rh = decltype(rhc)::value;
       const float* S = lds + buf * STG;
-#pragma unroll
-      for (int t = 0; t < 3; ++t) {
-        Ah[rh][t] = *(const half8*)(S + oA16[0] + 16 * (3 * rh + t) * RK);
-        Al[rh][t] = *(const half8*)(S + oA16[1] + 16 * (3 * rh + t) * RK);
-      }
+      X2_LD16(t, 3, Ah[rh], Al[rh], S, oA16[0], oA16[1], 16 * (3 * rh + t));
     };
     [[maybe_unused]] auto ldB = [&](auto chc, int buf) {
       constexpr int ch = decltype(chc)::value;
       const float* S = lds + buf * STG;
-#pragma unroll
-      for (int u = 0; u < 2; ++u) {
-        Bh[ch][u] = *(const half8*)(S + oB16[0] + (16 * u + 64 * ch) * RK);
-        Bl[ch][u] = *(const half8*)(S + oB16[1] + (16 * u + 64 * ch) * RK);
-      }
+      X2_LD16(u, 2, Bh[ch], Bl[ch], S, oB16[0], oB16[1], 16 * u + 64 * ch);   // (the W1 branch's rows start 64 further)
     };
-    [[maybe_unused]] auto mm = [&](auto rhc, auto chc) {            // 18 MFMAs: small cross terms first, six independent accumulators per term
-      constexpr int rh = decltype(rhc)::value, ch = decltype(chc)::value;
-#pragma unroll
-      for (int t = 0; t < 3; ++t)
-#pragma unroll
-        for (int u = 0; u < 2; ++u) c16[3 * rh + t][2 * ch + u] = __builtin_amdgcn_mfma_f32_16x16x32_f16(Al[rh][t], Bh[ch][u], c16[3 * rh + t][2 * ch + u], 0, 0, 0);
-#pragma unroll
-      for (int t = 0; t < 3; ++t)
-#pragma unroll
-        for (int u = 0; u < 2; ++u) c16[3 * rh + t][2 * ch + u] = __builtin_amdgcn_mfma_f32_16x16x32_f16(Ah[rh][t], Bl[ch][u], c16[3 * rh + t][2 * ch + u], 0, 0, 0);
-#pragma unroll
-      for (int t = 0; t < 3; ++t)
-#pragma unroll
-        for (int u = 0; u < 2; ++u) c16[3 * rh + t][2 * ch + u] = __builtin_amdgcn_mfma_f32_16x16x32_f16(Ah[rh][t], Bh[ch][u], c16[3 * rh + t][2 * ch + u], 0, 0, 0);
-    };
-    // LDS reads behind every second MFMA of a phase, DMA instructions in the gaps between them (same box: 918 -> 903 us per launch against
-    // "reads one per MFMA from the start, DMAs behind them"; no pinning at all measured like the latter)
-    [[maybe_unused]] auto pin16 = [&](int reads, int dmas) {
-#pragma unroll
-      for (int i = 0; i < 18; ++i) {
-        __builtin_amdgcn_sched_group_barrier(0x008, 1, 0);
-        if ((i & 1) == 0 && (i >> 1) < reads) __builtin_amdgcn_sched_group_barrier(0x100, 1, 0);
-        else if ((i & 1) == 1 && (i >> 1) < dmas) __builtin_amdgcn_sched_group_barrier(0x010, 1, 0);
-      }
-    };
-    typedef std::integral_constant<int, 0> I0;
-    typedef std::integral_constant<int, 1> I1;
+    [[maybe_unused]] auto mm = [&](auto rhc, auto chc) { x2_mm16<decltype(rhc)::value, decltype(chc)::value, 2>(c16, Ah, Al, Bh, Bl); };
+    [[maybe_unused]] auto pin16 = [&](int reads, int dmas) { x2_pin16<18>(reads, dmas); };
     // one K tile of parity PAR (snake order of the four (row half, branch) phases: only one operand half changes between consecutive phases, so
     // no half is ever double-buffered).  mode 0: steady (stages K tile kt + 2 into `buf`), 1: second-last, 2: last (no next-tile loads)
     [[maybe_unused]] auto tile16 = [&](auto parc, int buf, int kt, int mode) {
@@ -676,12 +594,11 @@ __device__ __forceinline__ void run_tiles(float* lds, const Args& a) {
 #pragma unroll
         for (int s3 = 0; s3 < 3; ++s3) af[s3] = ((const half8*)io.AoffH)[s3 * 64 + lane];
       }
-      typedef unsigned int u32x4_tbl __attribute__((ext_vector_type(4)));
       const unsigned int nrow = (unsigned int)n * (unsigned int)(kJ * 4);      // tables are [N][24]: my channel's 96 bytes
 #pragma unroll
       for (int q4 = 0; q4 < kJ / 4; ++q4) {
-        const u32x4_tbl d4 = __builtin_amdgcn_raw_buffer_load_b128(dsB, nrow, 16 * q4, 0);
-        const u32x4_tbl m4 = __builtin_amdgcn_raw_buffer_load_b128(m1B, nrow, 16 * q4, 0);
+        const u32x4 d4 = __builtin_amdgcn_raw_buffer_load_b128(dsB, nrow, 16 * q4, 0);
+        const u32x4 m4 = __builtin_amdgcn_raw_buffer_load_b128(m1B, nrow, 16 * q4, 0);
 #pragma unroll
         for (int i = 0; i < 4; ++i) {
           const unsigned int du = d4[i], mu = m4[i];       // (hipcc: __builtin_bit_cast of a vector ELEMENT expression reads element 0)
@@ -698,8 +615,8 @@ __device__ __forceinline__ void run_tiles(float* lds, const Args& a) {
         shb = io.shift[n + 16];
 #pragma unroll
         for (int q4 = 0; q4 < kJ / 4; ++q4) {
-          const u32x4_tbl d4 = __builtin_amdgcn_raw_buffer_load_b128(dsB, nrow + 16u * (kJ * 4), 16 * q4, 0);
-          const u32x4_tbl m4 = __builtin_amdgcn_raw_buffer_load_b128(m1B, nrow + 16u * (kJ * 4), 16 * q4, 0);
+          const u32x4 d4 = __builtin_amdgcn_raw_buffer_load_b128(dsB, nrow + 16u * (kJ * 4), 16 * q4, 0);
+          const u32x4 m4 = __builtin_amdgcn_raw_buffer_load_b128(m1B, nrow + 16u * (kJ * 4), 16 * q4, 0);
 #pragma unroll
           for (int i = 0; i < 4; ++i) {
             const unsigned int du = d4[i], mu = m4[i];
@@ -760,9 +677,8 @@ __device__ __forceinline__ void run_tiles(float* lds, const Args& a) {
       if constexpr (M16) return (unsigned int)(24 * (lr & 3) + 12 * p + 4 * it + (lr >> 2));
       return (unsigned int)(P == 1 ? 48 * p + rl : 24 * p + rl + (rl >= 24 ? 24 : 0));
     };
-    typedef unsigned int u32x4_t __attribute__((ext_vector_type(4)));
     typedef _Float16 half2_t __attribute__((ext_vector_type(2)));
-    u32x4_t rq[6];                                                         // residual: P == 1 both passes (3 + 3 items), P == 3 the current pass (hi, lo per item)
+    u32x4 rq[6];                                                         // residual: P == 1 both passes (3 + 3 items), P == 3 the current pass (hi, lo per item)
     auto load_res_pass = [&](int p) {
       if (has_res) {
 #pragma unroll
@@ -824,7 +740,7 @@ __device__ __forceinline__ void run_tiles(float* lds, const Args& a) {
       for (int s3 = 0; s3 < 3; ++s3) {
 #pragma unroll
         for (int beta = 0; beta < 2; ++beta) {
-          u32x4_t Pw, Qw;
+          u32x4 Pw, Qw;
 #pragma unroll
           for (int e = 0; e < 4; ++e) {
             const int kp = 16 * s3 + 2 * e, kq = kp + 8;           // < 24: gp[k], else dp[k - 24]
@@ -934,17 +850,13 @@ __device__ __forceinline__ void run_tiles(float* lds, const Args& a) {
         }
         const unsigned int vo = item_vrow(p, it) * orow + col_out;
         if (out_f32) {
-          __builtin_amdgcn_raw_buffer_store_b128(__builtin_bit_cast(u32x4_t, f32x4{v[0], v[1], v[2], v[3]}), yB, vo, 0, kStoreAux);
-          __builtin_amdgcn_raw_buffer_store_b128(__builtin_bit_cast(u32x4_t, f32x4{v[4], v[5], v[6], v[7]}), yB, vo + 16u, 0, kStoreAux);
+          __builtin_amdgcn_raw_buffer_store_b128(__builtin_bit_cast(u32x4, f32x4{v[0], v[1], v[2], v[3]}), yB, vo, 0, kStoreAux);
+          __builtin_amdgcn_raw_buffer_store_b128(__builtin_bit_cast(u32x4, f32x4{v[4], v[5], v[6], v[7]}), yB, vo + 16u, 0, kStoreAux);
         } else {
           half8 hh, ll;
-#pragma unroll
-          for (int c = 0; c < 8; ++c) {
-            hh[c] = (half_t)v[c];                                  // saturating (MODE.FP16_OVFL): |v| > 131008 saturates both halves, never inf
-            if constexpr (P == 3) ll[c] = (half_t)(v[c] - (float)hh[c]);
-          }
-          __builtin_amdgcn_raw_buffer_store_b128(__builtin_bit_cast(u32x4_t, hh), yB, vo, 0, kStoreAux);
-          if constexpr (P == 3) __builtin_amdgcn_raw_buffer_store_b128(__builtin_bit_cast(u32x4_t, ll), yB, vo + 64u, 0, kStoreAux);
+          X2_SPLIT8(P == 3, v, hh, ll);                               // saturating (MODE.FP16_OVFL): |v| > 131008 saturates both halves, never inf
+          __builtin_amdgcn_raw_buffer_store_b128(__builtin_bit_cast(u32x4, hh), yB, vo, 0, kStoreAux);
+          if constexpr (P == 3) __builtin_amdgcn_raw_buffer_store_b128(__builtin_bit_cast(u32x4, ll), yB, vo + 64u, 0, kStoreAux);
         }
       }
     }

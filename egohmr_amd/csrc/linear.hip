@@ -10,20 +10,16 @@
 //   * the global max-pool over the N points is fused into the epilogue (wave shuffle -> LDS -> one atomic per column and block).
 // Operands are in the X2 split format of gcn_dev.h (32 hi halves + 32 lo halves per 32-k group).  Tile 192 x 128 x 32,
 // 4 waves (2 x 2, 96 x 64 each), persistent blocks, see linear_tile_kernel.
-#include <type_traits>
-
 #include "common.h"
 #include "egohmr_hip.h"
 #include "gcn_dev.h"
 #include "internal.h"
+#include "x2_tile_dev.h"
 
 namespace {
 
-#define AS1 __attribute__((address_space(1)))
-#define AS3 __attribute__((address_space(3)))
-
 constexpr int LBM = 192, LBN = 128;       // output tile; 4 waves as 2 x 2, 96 x 64 per wave (6 x 4 MFMA blocks of 16 x 16; hi-only tier: 3 x 2 of 32 x 32)
-constexpr int RK = BK;                    // floats per operand row and K tile (X2: 32 hi halves | 32 lo halves = 128 bytes)
+constexpr int RK = X2_RK;
 constexpr int LA_T = LBM * RK, LB_T = LBN * RK, LSTG = LA_T + LB_T;   // floats; one stage = 40 KiB
 
 struct LinArgs {
@@ -38,14 +34,9 @@ struct LinArgs {
   int gstride;                                          // floats between the rows of gbias
 };
 
-struct LFrags {
-  half8 ah[3], al[3], bh[2], bl[2];
-};
-
 // ReLU of a split value: hi' = max(hi, 0), lo' = hi > 0 ? lo : 0 - on packed halves, 4 VALU per two elements (written as
 // instructions: from C the u16 minimum came back as 800 v_cmp + v_cndmask and their lane masks spilled 480 SGPRs)
 __device__ __forceinline__ void relu_split(half8& hi, half8& lo) {
-  typedef unsigned int u32x4 __attribute__((ext_vector_type(4)));
   u32x4 h = __builtin_bit_cast(u32x4, hi), l = __builtin_bit_cast(u32x4, lo);
 #pragma unroll
   for (int e = 0; e < 4; ++e) {
@@ -86,14 +77,10 @@ template <bool RELU_A, bool LIFT, bool HO = false>
 __global__ __launch_bounds__(256, 2) void linear_tile_kernel(LinArgs p) {
   static_assert(!(RELU_A && LIFT), "the generated operand is already rectified");
   __shared__ __attribute__((aligned(16))) float lds[2 * LSTG];   // 80 KiB; the ONLY LDS object
-  // MODE.FP16_OVFL = 1 for the life of the wave: every f32 -> f16 conversion of the epilogue clamps to +-65504 instead of producing inf - the
-  // same results on finite values as the explicit clamps it replaces (4 of the ~8 vector-ALU instructions per output value: v_med3 + its
-  // canonicalising v_max, twice), as in the GCN tile engine (gcn_tile.hip)
-  __builtin_amdgcn_s_setreg(1 | (23 << 6), 1);
+  x2_fp16_ovfl_on();
 
   constexpr int KS = 2, NM = 18, NR = 10;
-  // split-f16 products on v_mfma_f32_16x16x32_f16 (a K tile = ONE k-step; the K loop of gcn_tile.hip's split mode: four (row half, column half) phases in
-  // snake order, no operand half double-buffered); the hi-only tier keeps the 32 x 32 x 16 form
+  // split-f16 products on the 16 x 16 x 32 MFMA (x2_tile_dev.h; see tile16 in gcn_tile.hip); the hi-only tier keeps the 32 x 32 x 16 form
   constexpr bool M16 = !HO;
   const int tid = threadIdx.x;
   const int K = p.K0 + p.K1;
@@ -101,55 +88,24 @@ __global__ __launch_bounds__(256, 2) void linear_tile_kernel(LinArgs p) {
   const int n_tiles = p.N / LBN, m_tiles = p.M / LBM;
 
   int lane, wave, wm, wn, mi, g, r0, swz;
-  bool hi_lane;                                                // my 16-byte chunk of an operand piece holds hi halves
-  int oA[KS][2], oB[KS][2];
+  bool hi_lane;
+  int oA[KS][2][1], oB[KS][2];
   [[maybe_unused]] int oA16[2], oB16[2];
-  auto thread_consts = [&]() {                                 // re-derived per tile: nothing of this stays live across the epilogue
-    int t = tid;
-    asm volatile("" : "+v"(t));
-    lane = t & 63;
-    wave = __builtin_amdgcn_readfirstlane(t >> 6);
+  auto thread_consts = [&]() {                                 // re-derived per tile (x2_tile_dev.h)
+    x2_lane_wave(tid, lane, wave);
     wm = wave >> 1; wn = wave & 1;
     mi = lane & 31; g = lane >> 5;
-    r0 = 8 * wave + (lane >> 3);                               // DMA: one wave instruction = 8 rows x 128 B, rows r0 + 32 i share a key
-    swz = ((lane & 7) ^ ((r0 >> 1) & 7)) << 2;
-    hi_lane = swz < 16;
-    const int rA = 96 * wm + mi, rB = 64 * wn + mi;            // (+ 32 t / + 32 u leave the swizzle key alone)
-    const int keyA = (rA >> 1) & 7, keyB = (rB >> 1) & 7;
-#pragma unroll
-    for (int s = 0; s < KS; ++s)
-#pragma unroll
-      for (int hl = 0; hl < 2; ++hl) {
-        const int c = 4 * hl + 2 * s + g;                      // logical 16-byte chunk: [hi k0-31 | lo k0-31]
-        oA[s][hl] = rA * RK + ((c ^ keyA) << 2);
-        oB[s][hl] = LA_T + rB * RK + ((c ^ keyB) << 2);
-      }
-    if constexpr (M16) {      // lane (i = l & 15, kg = l >> 4): row i of a 16-row tile, logical chunk kg (hi) / 4 + kg (lo) of the 128-byte K tile
-      const int i16 = lane & 15, kg = lane >> 4, key = (i16 >> 1) & 7;
-#pragma unroll
-      for (int hl = 0; hl < 2; ++hl) {
-        oA16[hl] = (96 * wm + i16) * RK + (((4 * hl + kg) ^ key) << 2);
-        oB16[hl] = LA_T + (64 * wn + i16) * RK + (((4 * hl + kg) ^ key) << 2);
-      }
-    }
+    x2_dma_lane(lane, wave, r0, swz);
+    hi_lane = x2_hi_lane(swz);
+    X2_FRAG_OFFSETS32(oA, oB, KS, 2, 1, LA_T, 96 * wm + mi, 64 * wn + mi, g);
+    if constexpr (M16) X2_FRAG_OFFSETS16(oA16, oB16, LA_T, 96 * wm, 64 * wn, lane);
   };
   thread_consts();
 
   // ---- tiles of this block: iteration it -> (row tile, column tile)
   const int G = gridDim.x, b = blockIdx.x;
-  const bool xcd_order = (G % 8 == 0) && ((G / 8) % n_tiles == 0);
-  auto tile_of = [&](int it, int& m, int& n) -> bool {
-    if (xcd_order) {
-      const int x = b & 7, j = b >> 3, per = (G >> 3) / n_tiles;
-      m = (it * per + j / n_tiles) * 8 + x;
-      n = j % n_tiles;
-    } else {
-      const long long t = (long long)it * G + b;
-      m = (int)(t / n_tiles);
-      n = (int)(t % n_tiles);
-    }
-    return m < m_tiles;
-  };
+  const bool xcd_order = x2_xcd_order(G, n_tiles);
+  auto tile_of = [&](int it, int& m, int& n) -> bool { return x2_xcd_tile_of(xcd_order, it, b, G, n_tiles, m_tiles, m, n); };
 
   // operand pieces in buffer form (as in gcn_tile.hip): the tile's base in an SGPR descriptor, the lane's row / swizzled chunk in one 32-bit
   // offset per operand, the piece in the scalar offset - no vector-ALU address arithmetic per piece
@@ -200,8 +156,7 @@ __global__ __launch_bounds__(256, 2) void linear_tile_kernel(LinArgs p) {
 #pragma unroll
       for (int e = 0; e < 8; ++e) {
         const float v = fmaxf(fmaf(wk[e][2], pz[j], fmaf(wk[e][1], py[j], fmaf(wk[e][0], px[j], wk[e][3]))), 0.f);
-        hi[e] = (half_t)v;                                   // (MODE.FP16_OVFL: saturating conversions)
-        lo[e] = (half_t)(v - (float)hi[e]);
+        X2_SPLIT(v, hi[e], lo[e]);
       }
       float* dst = lds + buf * LSTG + row * RK;
       *(half8*)(dst + ((wave ^ key) << 2)) = hi;                  // logical chunk 2 s + g = wave: k = 8 wave .. + 7
@@ -219,12 +174,13 @@ __global__ __launch_bounds__(256, 2) void linear_tile_kernel(LinArgs p) {
     for (int i = 0; i < 4; ++i) dma_b(buf, kt, i);
   };
 
+  typedef X2Frags<2, !HO> LFrags;
   auto read_frags = [&](LFrags& f, int buf, int s) {
     const float* S = lds + buf * LSTG;
 #pragma unroll
     for (int t = 0; t < 3; ++t) {
-      f.ah[t] = *(const half8*)(S + oA[s][0] + 32 * t * RK);
-      if constexpr (!HO) f.al[t] = *(const half8*)(S + oA[s][1] + 32 * t * RK);
+      f.ah[t] = *(const half8*)(S + oA[s][0][0] + 32 * t * RK);
+      if constexpr (!HO) f.al[t] = *(const half8*)(S + oA[s][1][0] + 32 * t * RK);
     }
 #pragma unroll
     for (int u = 0; u < 2; ++u) {
@@ -236,8 +192,7 @@ __global__ __launch_bounds__(256, 2) void linear_tile_kernel(LinArgs p) {
       for (int t = 0; t < 3; ++t) {
         if constexpr (HO) {
           typedef _Float16 half2_r __attribute__((ext_vector_type(2)));
-          typedef unsigned int u32x4_r __attribute__((ext_vector_type(4)));
-          u32x4_r h = __builtin_bit_cast(u32x4_r, f.ah[t]);
+          u32x4 h = __builtin_bit_cast(u32x4, f.ah[t]);
 #pragma unroll
           for (int e = 0; e < 4; ++e) {
             const unsigned int he = h[e];
@@ -252,44 +207,26 @@ __global__ __launch_bounds__(256, 2) void linear_tile_kernel(LinArgs p) {
     }
   };
   f32x16 acc[3][2];
-  auto mfmas = [&](const LFrags& f) {
-#pragma unroll
-    for (int t = 0; t < 3; ++t)
-#pragma unroll
-      for (int u = 0; u < 2; ++u) {                             // small cross terms first, leading term last
-        if constexpr (!HO) {
-          acc[t][u] = __builtin_amdgcn_mfma_f32_32x32x16_f16(f.al[t], f.bh[u], acc[t][u], 0, 0, 0);
-          acc[t][u] = __builtin_amdgcn_mfma_f32_32x32x16_f16(f.ah[t], f.bl[u], acc[t][u], 0, 0, 0);
-        }
-        acc[t][u] = __builtin_amdgcn_mfma_f32_32x32x16_f16(f.ah[t], f.bh[u], acc[t][u], 0, 0, 0);
-      }
-  };
-  // sched_group_barrier masks: 0x008 MFMA, 0x100 DS read, 0x010 VMEM
+  auto mfmas = [&](const LFrags& f) { x2_mfmas(acc, f); };
   auto pin_reads = [&]() {
-    if constexpr (HO) return;                                   // (the hi-only instruction mix is left to the scheduler)
-#pragma unroll
-    for (int i = 0; i < NR; ++i) {
-      __builtin_amdgcn_sched_group_barrier(0x008, 1, 0);
-      __builtin_amdgcn_sched_group_barrier(0x100, 1, 0);
-    }
-    __builtin_amdgcn_sched_group_barrier(0x008, NM - NR, 0);
+    if constexpr (!HO) x2_pin_reads<NR, NM>();                  // (the hi-only instruction mix is left to the scheduler)
   };
   auto pin_reads_dma = [&]() {                                  // 10 x (MFMA, read), then the ten DMAs behind the last 8 MFMAs
     if constexpr (HO) return;
 #pragma unroll
     for (int i = 0; i < NR; ++i) {
-      __builtin_amdgcn_sched_group_barrier(0x008, 1, 0);
-      __builtin_amdgcn_sched_group_barrier(0x100, 1, 0);
+      __builtin_amdgcn_sched_group_barrier(SG_MFMA, 1, 0);
+      __builtin_amdgcn_sched_group_barrier(SG_DS_READ, 1, 0);
     }
 #pragma unroll
     for (int i = 0; i < 2; ++i) {
-      __builtin_amdgcn_sched_group_barrier(0x008, 1, 0);
-      __builtin_amdgcn_sched_group_barrier(0x010, 2, 0);
+      __builtin_amdgcn_sched_group_barrier(SG_MFMA, 1, 0);
+      __builtin_amdgcn_sched_group_barrier(SG_VMEM, 2, 0);
     }
 #pragma unroll
     for (int i = 0; i < (LIFT ? 0 : 6); ++i) {
-      __builtin_amdgcn_sched_group_barrier(0x008, 1, 0);
-      __builtin_amdgcn_sched_group_barrier(0x010, 1, 0);
+      __builtin_amdgcn_sched_group_barrier(SG_MFMA, 1, 0);
+      __builtin_amdgcn_sched_group_barrier(SG_VMEM, 1, 0);
     }
   };
 
@@ -329,52 +266,20 @@ __global__ __launch_bounds__(256, 2) void linear_tile_kernel(LinArgs p) {
 
     // ---- 16 x 16 x 32: operand halves A[rh] (row tiles 3 rh .. + 2 of 16 rows), B[ch] (column tiles 2 ch, 2 ch + 1 of 16), 6 x 4 accumulators
     [[maybe_unused]] half8 Ah[2][3], Al[2][3], Bh[2][2], Bl[2][2];
-    typedef float f32x4a __attribute__((ext_vector_type(4)));
     [[maybe_unused]] f32x4a c16[6][4];
-    typedef std::integral_constant<int, 0> I0;
-    typedef std::integral_constant<int, 1> I1;
     [[maybe_unused]] auto ldA = [&](auto rhc, int buf) __attribute__((always_inline)) {
       constexpr int rh = decltype(rhc)::value;
       const float* S = lds + buf * LSTG;
-#pragma unroll
-      for (int t = 0; t < 3; ++t) {
-        Ah[rh][t] = *(const half8*)(S + oA16[0] + 16 * (3 * rh + t) * RK);
-        Al[rh][t] = *(const half8*)(S + oA16[1] + 16 * (3 * rh + t) * RK);
-        if constexpr (RELU_A) relu_split(Ah[rh][t], Al[rh][t]);
-      }
+      X2_LD16(t, 3, Ah[rh], Al[rh], S, oA16[0], oA16[1], 16 * (3 * rh + t), if constexpr (RELU_A) relu_split(Ah[rh][t], Al[rh][t]));
     };
     [[maybe_unused]] auto ldB = [&](auto chc, int buf) __attribute__((always_inline)) {
       constexpr int ch = decltype(chc)::value;
       const float* S = lds + buf * LSTG;
-#pragma unroll
-      for (int u = 0; u < 2; ++u) {
-        Bh[ch][u] = *(const half8*)(S + oB16[0] + 16 * (2 * ch + u) * RK);
-        Bl[ch][u] = *(const half8*)(S + oB16[1] + 16 * (2 * ch + u) * RK);
-      }
+      X2_LD16(u, 2, Bh[ch], Bl[ch], S, oB16[0], oB16[1], 16 * (2 * ch + u));
     };
-    [[maybe_unused]] auto mm = [&](auto rhc, auto chc) __attribute__((always_inline)) {            // 18 MFMAs: small cross terms first, six independent accumulators per term
-      constexpr int rh = decltype(rhc)::value, ch = decltype(chc)::value;
-#pragma unroll
-      for (int t = 0; t < 3; ++t)
-#pragma unroll
-        for (int u = 0; u < 2; ++u) c16[3 * rh + t][2 * ch + u] = __builtin_amdgcn_mfma_f32_16x16x32_f16(Al[rh][t], Bh[ch][u], c16[3 * rh + t][2 * ch + u], 0, 0, 0);
-#pragma unroll
-      for (int t = 0; t < 3; ++t)
-#pragma unroll
-        for (int u = 0; u < 2; ++u) c16[3 * rh + t][2 * ch + u] = __builtin_amdgcn_mfma_f32_16x16x32_f16(Ah[rh][t], Bl[ch][u], c16[3 * rh + t][2 * ch + u], 0, 0, 0);
-#pragma unroll
-      for (int t = 0; t < 3; ++t)
-#pragma unroll
-        for (int u = 0; u < 2; ++u) c16[3 * rh + t][2 * ch + u] = __builtin_amdgcn_mfma_f32_16x16x32_f16(Ah[rh][t], Bh[ch][u], c16[3 * rh + t][2 * ch + u], 0, 0, 0);
-    };
-    [[maybe_unused]] auto pin16 = [&](int reads, int dmas) __attribute__((always_inline)) {          // reads one per MFMA from the start, DMAs one per MFMA behind them
-      if constexpr (RELU_A) return;                               // (the rectifying loads are left to the scheduler)
-#pragma unroll
-      for (int i = 0; i < 18; ++i) {                          // reads behind every second MFMA, DMAs in the gaps (as in gcn_tile.hip)
-        __builtin_amdgcn_sched_group_barrier(0x008, 1, 0);
-        if ((i & 1) == 0 && (i >> 1) < reads) __builtin_amdgcn_sched_group_barrier(0x100, 1, 0);
-        else if ((i & 1) == 1 && (i >> 1) < dmas) __builtin_amdgcn_sched_group_barrier(0x010, 1, 0);
-      }
+    [[maybe_unused]] auto mm = [&](auto rhc, auto chc) __attribute__((always_inline)) { x2_mm16<decltype(rhc)::value, decltype(chc)::value, 2>(c16, Ah, Al, Bh, Bl); };
+    [[maybe_unused]] auto pin16 = [&](int reads, int dmas) __attribute__((always_inline)) {
+      if constexpr (!RELU_A) x2_pin16<18>(reads, dmas);           // (the rectifying loads are left to the scheduler)
     };
     // one K tile of parity PAR = kt & 1 (stage kt & 1).  Phases (0, cf) (0, cs) | barrier | (1, cs) (1, cf) with cf = PAR: the next tile's first phase is
     // (0, cs) - exactly the halves that are free to be refilled during this tile's last two phases.  Returns false behind the barrier of the LAST K tile
@@ -498,7 +403,6 @@ __global__ __launch_bounds__(256, 2) void linear_tile_kernel(LinArgs p) {
     const __amdgpu_buffer_rsrc_t yB = ehm_buffer_rsrc(p.Y ? p.Y + (row0 + 96 * wm) * (size_t)p.N * 4 : (char*)p.A0);
     const unsigned int yrow = (unsigned int)p.N * 4u;
     const bool relu_out = p.relu_out != 0, has_y = p.Y != nullptr;
-    typedef unsigned int u32x4_t __attribute__((ext_vector_type(4)));
     if constexpr (M16) {
       // accumulator layout: lane (i = l & 15, rg = l >> 4) owns columns 64 wn + 16 ct + i; register r of c16[rt][ct] is row 16 rt + 4 rg + r.
       // One pass per row tile (16 rows x 64 columns through four of the wave's six 1 KiB pieces): piece 2 (row >> 3) + (col >> 5) holds [8 rows][32 columns];
@@ -544,14 +448,10 @@ __global__ __launch_bounds__(256, 2) void linear_tile_kernel(LinArgs p) {
           for (int k = 0; k < 2; ++k) {
             const float v[8] = {tq[k][0][0], tq[k][0][1], tq[k][0][2], tq[k][0][3], tq[k][1][0], tq[k][1][1], tq[k][1][2], tq[k][1][3]};
             half8 hh, ll;
-#pragma unroll
-            for (int c = 0; c < 8; ++c) {
-              hh[c] = (half_t)v[c];                              // (MODE.FP16_OVFL: the conversions saturate at +-65504, see the kernel's head)
-              ll[c] = (half_t)(v[c] - (float)hh[c]);
-            }
+            X2_SPLIT8(true, v, hh, ll);
             const unsigned int vo = (unsigned int)(16 * rt + 8 * k + rr) * yrow + col_off;
-            __builtin_amdgcn_raw_buffer_store_b128(__builtin_bit_cast(u32x4_t, hh), yB, vo, 0, 0);
-            __builtin_amdgcn_raw_buffer_store_b128(__builtin_bit_cast(u32x4_t, ll), yB, vo + 64u, 0, 0);
+            __builtin_amdgcn_raw_buffer_store_b128(__builtin_bit_cast(u32x4, hh), yB, vo, 0, 0);
+            __builtin_amdgcn_raw_buffer_store_b128(__builtin_bit_cast(u32x4, ll), yB, vo + 64u, 0, 0);
           }
         }
       }
@@ -616,14 +516,10 @@ __global__ __launch_bounds__(256, 2) void linear_tile_kernel(LinArgs p) {
           const int Gq = 3 * ps + gi;
           const float v[8] = {tq[gi][0][0], tq[gi][0][1], tq[gi][0][2], tq[gi][0][3], tq[gi][1][0], tq[gi][1][1], tq[gi][1][2], tq[gi][1][3]};
           half8 hh, ll;
-#pragma unroll
-          for (int c = 0; c < 8; ++c) {
-            hh[c] = (half_t)v[c];                              // (MODE.FP16_OVFL: the conversions saturate at +-65504, see the kernel's head)
-            ll[c] = (half_t)(v[c] - (float)hh[c]);
-          }
+          X2_SPLIT8(!HO, v, hh, ll);
           const unsigned int vo = (unsigned int)(8 * Gq + rr) * yrow + col_off;
-          __builtin_amdgcn_raw_buffer_store_b128(__builtin_bit_cast(u32x4_t, hh), yB, vo, 0, 0);
-          if constexpr (!HO) __builtin_amdgcn_raw_buffer_store_b128(__builtin_bit_cast(u32x4_t, ll), yB, vo + 64u, 0, 0);
+          __builtin_amdgcn_raw_buffer_store_b128(__builtin_bit_cast(u32x4, hh), yB, vo, 0, 0);
+          if constexpr (!HO) __builtin_amdgcn_raw_buffer_store_b128(__builtin_bit_cast(u32x4, ll), yB, vo + 64u, 0, 0);
         }
       }
     }
