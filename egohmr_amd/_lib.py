@@ -29,7 +29,7 @@ _HERE = os.path.dirname(os.path.abspath(__file__))
 LIB_PATH = os.environ.get("EHM_LIB_PATH") or os.path.join(_HERE, "libegohmr_hip.so")   # EHM_LIB_PATH: A/B a second build (experiments)
 CSRC = os.path.join(_HERE, "csrc")
 INCLUDE = os.path.join(os.path.dirname(_HERE), "include")
-SOURCES = ["gcn.hip", "gcn_tile.hip", "linear.hip", "conv.hip", "stem.hip", "metrics.hip", "smpl.hip", "sampler.hip", "guidance.hip", "prep.hip", "step.hip", "eval.hip", "stage1.hip", "scene.hip"]
+SOURCES = ["gcn.hip", "gcn_tile.hip", "linear.hip", "conv.hip", "stem.hip", "metrics.hip", "smpl.hip", "sampler.hip", "guidance.hip", "prep.hip", "step.hip", "eval.hip", "stage1.hip", "scene.hip", "loss.hip"]
 
 
 class EgoHMRHipError(RuntimeError):
@@ -163,6 +163,23 @@ class PackDesc(C.Structure):
                 ("focal", C.c_void_p), ("center", C.c_void_p), ("finite_out", C.c_void_p)]
 
 
+class ValLossesDesc(C.Structure):
+    """ehm_val_losses_desc"""
+    _fields_ = ([(n, C.c_int) for n in ("B", "V", "pred_joints", "gt_joints", "kp3d_points", "kp3d_full_points", "kp2d_points")] +
+                [(n, C.c_void_p) for n in ("pred_vertices", "pred_keypoints_3d", "pred_keypoints_3d_full", "pred_keypoints_2d_full",
+                                           "pred_global_orient", "pred_body_pose", "pred_betas", "pred_pose_6d",
+                                           "keypoints_2d", "keypoints_3d", "keypoints_3d_full",
+                                           "gt_vertices_male", "gt_vertices_female", "gt_joints_male", "gt_joints_female", "gender",
+                                           "gt_global_orient", "gt_body_pose", "gt_betas", "focal", "center", "penetration")] +
+                [("weights", C.c_double * 9), ("workspace", C.c_void_p), ("workspace_bytes", C.c_int64)] +
+                [(n, C.c_void_p) for n in ("losses", "joint_vis_num", "per_item", "per_item_vis", "vis_mask")])
+
+
+# columns of ehm_val_losses' per_item / losses = the keys of the reference's `losses` dict in its order (egohmr.py:432-443; EHM_LOSS_* of the header)
+LOSS_KEYS = ("loss", "loss_v2v", "loss_keypoints_3d", "loss_keypoints_3d_full", "loss_keypoints_2d_full", "loss_betas", "loss_body_pose",
+             "loss_global_orient", "loss_pose_6d_ortho", "loss_coap_penetration", "loss_keypoints_3d_vis_batch_sum")
+
+
 class StepCoefs(C.Structure):
     """ehm_step_coefs"""
     _fields_ = [(n, C.c_float) for n in ("coef1", "coef2", "log_variance", "variance", "sqrt_recip_ac", "sqrt_recipm1_ac",
@@ -264,6 +281,9 @@ PROTOTYPES = {
     "ehm_sample_loop": (_I, [_P, _P, C.POINTER(SampleDesc), C.POINTER(StepCoefs)] + [_P] * 18 + [_L, _P]),
     "ehm_item_prep": (_I, [C.POINTER(ItemPrepDesc), _P]),
     "ehm_pack_outputs": (_I, [C.POINTER(PackDesc), _P]),
+    "ehm_val_losses_workspace_bytes": (_I, [_I, _I, C.POINTER(C.c_int64)]),
+    "ehm_val_losses": (_I, [C.POINTER(ValLossesDesc), _P]),
+    "ehm_scene_cap_points": (_I, [_P, _P, _P, _P, _I, _I, _I, _I, _P]),
     "ehm_profile_begin": (_I, []),
     "ehm_profile_end": (_I, [C.POINTER(C.c_double), C.POINTER(C.c_int64), _I]),
 }

@@ -208,3 +208,43 @@ class Stage1Driver:
 
     def save(self, save_root: str, model_id: str) -> str:
         return eio.save_stage1_results(save_root, model_id, self.results()["pred_cam_full_list"])
+
+
+def aggregate_val_losses(per_batch) -> dict:
+    """The aggregation of train_egohmr.py:176-207 over an iterable of (losses dict, joint_vis_num_batch): every key summed over the batches (on the
+    tensors' device) and divided by the number of batches, except 'loss_keypoints_3d_vis_batch_sum' (the plain sum), plus
+    'loss_keypoints_3d_vis' = batch_sum / joint_vis_num * 1000 (mm per visible joint; the figure that picks best_model_vis.pt) and 'joint_vis_num'.
+    (The reference's loop goes on to divide 'loss_keypoints_3d_vis' by the number of batches as well, :203-205 - an accident of iterating the dict it is
+    adding to; not reproduced.)  Values are tensors / numbers as given: no host read-back here."""
+    sums, vis_num, n = {}, 0, 0
+    for losses, num in per_batch:
+        for k, v in losses.items():
+            sums[k] = sums[k] + v if k in sums else v + 0
+        vis_num = vis_num + num
+        n += 1
+    if n == 0:
+        raise ValueError("validate: no batches")
+    out = {k: (v if k == "loss_keypoints_3d_vis_batch_sum" else v / n) for k, v in sums.items()}
+    out["loss_keypoints_3d_vis"] = out["loss_keypoints_3d_vis_batch_sum"] / vis_num * 1000
+    out["joint_vis_num"] = vis_num
+    return out
+
+
+@torch.no_grad()
+def validate(model, diffusion, batches, timestep_respacing="", cur_epoch=0, noise_stacks=None) -> dict:
+    """The validation loop of train_egohmr.py:176-213 without logging: one sampling loop + EgoHMR.compute_loss per batch
+    (`diffusion.val_losses(..., compute_loss=True)`), the loss tensors summed on the device, ONE host read-back at the end.
+    batches: an iterable of annotated batches on the model's device (EgoHMR.compute_loss lists the keys); noise_stacks: optional, one
+    [T+1, B, 144] stack per batch.  -> {key: float} for the reference's eleven keys, 'loss_keypoints_3d_vis' and 'joint_vis_num' (int)."""
+    def run():
+        for i, batch in enumerate(batches):
+            B = batch["img"].shape[0]
+            o = diffusion.val_losses(model=model, batch=batch, shape=[B, 144], progress=False, clip_denoised=False, cur_epoch=cur_epoch,
+                                     timestep_respacing=timestep_respacing, noise_stack=None if noise_stacks is None else noise_stacks[i])
+            if not o["losses"]:
+                raise KeyError("validate: batch %d carries no 'keypoints_3d' (a sampling-only batch has no validation loss)" % i)
+            yield o["losses"], o["joint_vis_num_batch"]
+    agg = aggregate_val_losses(run())
+    keys = list(agg)
+    host = torch.stack([agg[k].double() for k in keys]).cpu().tolist()
+    return {k: (int(round(v)) if k == "joint_vis_num" else v) for k, v in zip(keys, host)}

@@ -325,6 +325,27 @@ class TranslEnc(nn.Module):
         return self.layers(x)
 
 
+def val_losses_native(t, weights, penetration=None) -> dict:
+    """ehm_val_losses (csrc/loss.hip) on a dict of contiguous device tensors named like the fields of ehm_val_losses_desc (EgoHMR.loss_inputs builds it), the
+    nine weights of egohmr.py:422-430 and the per-item penetration term [B] or None -> losses [11], joint_vis_num [1] int64, per_item [B,11],
+    per_item_vis [B] int64, vis_mask [B,24] uint8 (columns: _lib.LOSS_KEYS).  No host synchronisation."""
+    dev, P, A, n = t["pred_vertices"].device, _lib.ptr, _lib.api(), len(_lib.LOSS_KEYS)
+    B, V = t["pred_vertices"].shape[0], t["pred_vertices"].shape[1]
+    out = dict(losses=torch.empty(n, device=dev), joint_vis_num=torch.empty(1, device=dev, dtype=torch.int64), per_item=torch.empty(B, n, device=dev),
+               per_item_vis=torch.empty(B, device=dev, dtype=torch.int64), vis_mask=torch.empty(B, 24, device=dev, dtype=torch.uint8))
+    with _lib.on_device(dev):
+        nb = C.c_int64(0)
+        A.ehm_val_losses_workspace_bytes(B, V, C.byref(nb))
+        nbytes = nb.value
+        ws = torch.empty(nbytes // 8, device=dev, dtype=torch.float64)
+        d = _lib.ValLossesDesc(B=B, V=V, pred_joints=t["pred_keypoints_3d"].shape[1], gt_joints=t["gt_joints_male"].shape[1],
+                               kp3d_points=t["keypoints_3d"].shape[1], kp3d_full_points=t["keypoints_3d_full"].shape[1], kp2d_points=t["keypoints_2d"].shape[1],
+                               penetration=P(penetration), weights=(C.c_double * 9)(*[float(w) for w in weights]), workspace=P(ws), workspace_bytes=nbytes,
+                               **{k: P(v) for k, v in t.items()}, **{k: P(v) for k, v in out.items()})
+        A.ehm_val_losses(C.byref(d), _lib.stream_ptr())
+    return out
+
+
 # ---------------------------------------------------------------------------------------------- model
 class EgoHMR(nn.Module):
     def __init__(self, cfg=None, device=None, body_rep_mean=None, body_rep_std=None,
@@ -334,7 +355,8 @@ class EgoHMR(nn.Module):
                  weight_loss_betas=0, weight_loss_body_pose=0, weight_loss_global_orient=0, weight_loss_pose_6d_ortho=0,
                  weight_coap_penetration=0, start_coap_epoch=0, cond_mask_prob=0, only_mask_img_cond=False,
                  diffusion_blk=4, gcn_dropout=0.0, gcn_nonlocal_layer=False, gcn_hid_dim=1024,
-                 pelvis_vis_loosen=False, diffuse_fuse=False, smpl_asset=None, smpl_model_path="data/smpl", allow_synthetic_smpl=False):
+                 pelvis_vis_loosen=False, diffuse_fuse=False, smpl_asset=None, smpl_model_path="data/smpl", allow_synthetic_smpl=False,
+                 smpl_asset_male=None, smpl_asset_female=None):
         super().__init__()
         self.cfg = cfg if cfg is not None else default_cfg()
         self.device = torch.device(device) if device is not None else torch.device("cuda")
@@ -348,6 +370,16 @@ class EgoHMR(nn.Module):
         self.only_mask_img_cond, self.diffuse_fuse = only_mask_img_cond, diffuse_fuse
         # cond_mask_prob only acts under self.training (mask_cond, egohmr.py:159-168): the sampling path is eval-only, so it is kept and ignored
         self.cond_mask_prob = float(cond_mask_prob)
+        # egohmr.py:121-122, :130-137: read by compute_loss only
+        self.weight_loss_v2v, self.weight_loss_keypoints_3d = weight_loss_v2v, weight_loss_keypoints_3d
+        self.weight_loss_keypoints_3d_full, self.weight_loss_keypoints_2d_full = weight_loss_keypoints_3d_full, weight_loss_keypoints_2d_full
+        self.weight_loss_betas, self.weight_loss_body_pose = weight_loss_betas, weight_loss_body_pose
+        self.weight_loss_global_orient, self.weight_loss_pose_6d_ortho = weight_loss_global_orient, weight_loss_pose_6d_ortho
+        self.weight_coap_penetration, self.start_coap_epoch = weight_coap_penetration, start_coap_epoch
+        # the ground-truth bodies of compute_loss (egohmr.py:106-107), created on first use and kept OUT of the module tree (a plain dict): no key in
+        # state_dict(), nothing in parameters(), no cost for a sampling-only user
+        self._gt_smpl = {}
+        self._gt_smpl_src = dict(model_path=smpl_model_path, allow_synthetic=allow_synthetic_smpl, male=smpl_asset_male, female=smpl_asset_female)
         self.diffuse_feat_dim = 6
         dev = self.device
         self.register_buffer("body_rep_mean_buf", torch.as_tensor(body_rep_mean, dtype=torch.float32).reshape(144).clone(), persistent=False)
@@ -506,10 +538,115 @@ class EgoHMR(nn.Module):
         _, _, hits = self.fused_sampler.collision(so.vertices, self.scene_pcd_verts, want_grad=False, want_hits=True, all_points=False)
         return (hits.float() / self.scene_pcd_verts.shape[1]).tolist()
 
+    # ------------------------------------------------------------------ validation losses (egohmr.py:307-449, evaluation branch)
+    def _gt_body_model(self, gender):
+        m = self._gt_smpl.get(gender)
+        if m is None:
+            src = self._gt_smpl_src
+            m = self._gt_smpl[gender] = smpl_mod.create(src["model_path"], model_type="smpl", gender=gender, asset=src[gender],
+                                                        allow_synthetic=src["allow_synthetic"])
+        if m.v_template.device != self.device:
+            m.to(self.device)
+        return m
+
+    @property
+    def smpl_male(self):
+        return self._gt_body_model("male")
+
+    @property
+    def smpl_female(self):
+        return self._gt_body_model("female")
+
+    PENETRATION_POINT_CAP = 4000               # egohmr.py:411-412
+
+    def _penetration_term(self):
+        """egohmr.py:399-419 per item, with the build's collision proxy in place of `coap.collision_loss` (NOT a COAP number): the proxy over the scene
+        points inside the bounding box of the item's predicted vertices; where more than 4000 points are selected the points of INDEX >= 4000 are dropped
+        (`inds[:, 4000:] = False`); no selected point -> 0.  [B], no host read-back."""
+        verts, scene = _lib.f32(self.smpl_output.vertices, self.device), _lib.f32(self.scene_pcd_verts, self.device)
+        B, V, N = verts.shape[0], verts.shape[1], scene.shape[1]
+        if N > self.PENETRATION_POINT_CAP:
+            capped = torch.empty_like(scene)
+            count = torch.empty(B, device=self.device, dtype=torch.int32)
+            _lib.api().ehm_scene_cap_points(verts, scene, capped, count, B, V, N, self.PENETRATION_POINT_CAP, _lib.stream_ptr())
+            scene = capped
+        return self.fused_sampler.collision(verts, scene, want_grad=False, all_points=False)[0]
+
+    @torch.no_grad()
     def compute_loss(self, batch, output, cur_epoch=0):
-        """Evaluation losses need ground-truth annotations (egohmr.py:307-449); the sampling path has none."""
-        output["losses"] = {}
-        return torch.zeros((), device=self.device)
+        """egohmr.py:307-449 in the evaluation branch, on the device (csrc/loss.hip: ehm_val_losses), for the output of `model(batch, t)` or of a sampling
+        loop (`diffusion.val_losses`).  Fills output['losses'] with the reference's eleven keys in its order (0-d float32 device tensors),
+        output['joint_vis_num_batch'] (0-d int64) and, beyond the reference, output['losses_per_item'] ({key: [B]} plus 'joint_vis_num' [B] int64 and
+        'joint_vis_mask' [B,24] bool: what a sharded run needs for global means); returns `loss`.  No host synchronisation.
+
+        A batch WITHOUT 'keypoints_3d' is a sampling-only batch: output['losses'] = {} and a zero scalar, nothing is computed.  A batch that has
+        'keypoints_3d' but lacks 'keypoints_3d_full', 'gender', 'smpl_params_is_axis_angle' or a key of 'smpl_params' raises KeyError naming it.
+        Ground-truth poses are axis-angle (the EgoBody loader's; `smpl_params_is_axis_angle`, read on the host, must be all-true for 'global_orient' and
+        'body_pose', else NotImplementedError).  The penetration term uses the build's collision proxy, not COAP (_penetration_term)."""
+        if "keypoints_3d" not in batch:
+            output["losses"] = {}
+            return torch.zeros((), device=self.device)
+        for k in ("keypoints_3d_full", "gender", "smpl_params_is_axis_angle", "smpl_params", "orig_keypoints_2d"):
+            if k not in batch:
+                raise KeyError(k)
+        sp, flags = batch["smpl_params"], batch["smpl_params_is_axis_angle"]
+        for k in ("global_orient", "body_pose", "betas", "transl"):
+            if k not in sp:
+                raise KeyError(f"smpl_params[{k!r}]")
+        for k in ("global_orient", "body_pose"):
+            if k not in flags:
+                raise KeyError(f"smpl_params_is_axis_angle[{k!r}]")
+            f = flags[k]
+            if isinstance(f, torch.Tensor) and f.is_cuda:
+                raise ValueError(f"smpl_params_is_axis_angle[{k!r}] is on the device; the loader's flags stay on the host (train_egohmr.py:182)")
+            if not bool(np.asarray(f).all()):
+                raise NotImplementedError(f"smpl_params_is_axis_angle[{k!r}] is not all-true: compute_loss takes axis-angle ground-truth poses "
+                                          "(the EgoBody loader's; egohmr.py:380-381 decodes a mixed batch inconsistently)")
+        with _lib.on_device(self.device):
+            pen = None
+            if self.weight_coap_penetration > 0 and cur_epoch >= self.start_coap_epoch:                                         # :392
+                pen = self._penetration_term()
+            res = val_losses_native(self.loss_inputs(batch, output), self.loss_weights(), pen)
+        K = _lib.LOSS_KEYS
+        output["losses"] = {k: res["losses"][i] for i, k in enumerate(K)}                                                         # :432-443
+        output["joint_vis_num_batch"] = res["joint_vis_num"][0]                                                                 # :447
+        output["losses_per_item"] = {**{k: res["per_item"][:, i] for i, k in enumerate(K)}, "joint_vis_num": res["per_item_vis"],
+                                     "joint_vis_mask": res["vis_mask"].bool()}
+        return output["losses"]["loss"]
+
+    def loss_inputs(self, batch, output) -> dict:
+        """The device arrays ehm_val_losses reads for an annotated batch and a model output, named like the descriptor's fields: the prediction as the
+        output dict holds it, the male AND female ground-truth bodies (egohmr.py:344-349: axis-angle input, `transl` applied), the ground-truth rotations
+        through aa_to_rotmat (:380-381), focal length and camera centre of the last forward (:283-285)."""
+        dev, f32 = self.device, _lib.f32
+        pp, sp = output["pred_smpl_params"], batch["smpl_params"]
+        pv = f32(output["pred_vertices"], dev)
+        B = pv.shape[0]
+        gt = {k: f32(v, dev) for k, v in sp.items()}                                   # :344, :347 (`v.float()`)
+        male, female = self.smpl_male(**gt), self.smpl_female(**gt)
+        rot = {k: geometry.aa_to_rotmat(gt[k].reshape(-1, 3)).reshape(B, -1).contiguous() for k in ("global_orient", "body_pose")}
+
+        def aligned(t):                        # the vertex kernel loads 16 bytes at a time (a slice of a stacked [S,B,V,3] result may start anywhere)
+            return t if t.data_ptr() % 16 == 0 else t.clone()
+        t = dict(pred_vertices=aligned(pv), pred_keypoints_3d=f32(output["pred_keypoints_3d"], dev), pred_keypoints_3d_full=f32(output["pred_keypoints_3d_full"], dev),
+                 pred_keypoints_2d_full=f32(output["pred_keypoints_2d_full"], dev), pred_global_orient=f32(pp["global_orient"], dev),
+                 pred_body_pose=f32(pp["body_pose"], dev), pred_betas=f32(pp["betas"], dev), pred_pose_6d=f32(output["pred_pose_6d"], dev),
+                 keypoints_2d=f32(batch["orig_keypoints_2d"], dev), keypoints_3d=f32(batch["keypoints_3d"], dev),
+                 keypoints_3d_full=f32(batch["keypoints_3d_full"], dev), gt_vertices_male=aligned(male.vertices.contiguous()),
+                 gt_vertices_female=aligned(female.vertices.contiguous()), gt_joints_male=male.joints.contiguous(), gt_joints_female=female.joints.contiguous(),
+                 gender=torch.as_tensor(batch["gender"]).to(dev).long().reshape(-1).contiguous(), gt_global_orient=rot["global_orient"], gt_body_pose=rot["body_pose"],
+                 gt_betas=gt["betas"], focal=f32(self.focal_length, dev), center=f32(self.camera_center_full, dev))
+        if (t["gender"].numel() != B or t["pred_pose_6d"].numel() != B * 144 or t["gt_vertices_male"].shape != t["pred_vertices"].shape
+                or any(t[k].shape[0] != B for k in t) or t["pred_keypoints_2d_full"].shape[1] != t["pred_keypoints_3d"].shape[1]
+                or t["pred_keypoints_3d_full"].shape[1] != t["pred_keypoints_3d"].shape[1]):
+            raise ValueError("compute_loss: batch and output do not describe the same B bodies")
+        return t
+
+    def loss_weights(self):
+        """The nine weights of egohmr.py:422-430 in ehm_val_losses' order."""
+        return [float(w) for w in (self.weight_loss_v2v, self.weight_loss_keypoints_3d, self.weight_loss_keypoints_3d_full, self.weight_loss_keypoints_2d_full,
+                                   self.weight_loss_betas, self.weight_loss_body_pose, self.weight_loss_global_orient, self.weight_loss_pose_6d_ortho,
+                                   self.weight_coap_penetration)]
 
     def training_step(self, *a, **k):
         raise NotImplementedError("training is outside the sampling hot path this package implements")

@@ -535,6 +535,59 @@ typedef struct ehm_pack_desc {
 } ehm_pack_desc;
 int ehm_pack_outputs(const ehm_pack_desc* d, void* stream);
 
+/* ------------------------------------------------------------------ validation losses -------- */
+/* EgoHMR.compute_loss in its evaluation branch (models/egohmr/egohmr.py:307-449, self.training == False) on arrays that are already on the
+ * device.  Terms, in the order of the reference's `losses` dict (:432-443) = the columns of `per_item` and the entries of `losses`:
+ *   EHM_LOSS_TOTAL           :422-430  weights[0..8] . (V2V, KP3D, KP3D_FULL, KP2D_FULL, BETAS, BODY_POSE, GLOBAL_ORIENT, POSE_6D_ORTHO, PENETRATION)
+ *   EHM_LOSS_V2V             :344-355  mean over B V 3 of |(pred_vertices - pred_keypoints_3d[:, 0]) - (gt_vertices - gt_joints[:, 0])|; the ground truth of
+ *                                      item b is the FEMALE body where gender[b] == 1, else the male one (:350-351) - only the selected one is read
+ *   EHM_LOSS_KP3D            :334-336, losses.py:44-50  joints 0..23 of pred_keypoints_3d / keypoints_3d, each minus its own joint 0, L1 summed per item
+ *   EHM_LOSS_KP3D_FULL       :339-341  the same on pred_keypoints_3d_full / keypoints_3d_full without alignment
+ *   EHM_LOSS_KP2D_FULL       :314-331, losses.py:20-25  pred_keypoints_2d_full[:, smpl_to_openpose] (:108-109) against keypoints_2d[:, :, :2], L1 times the
+ *                                      confidence keypoints_2d[:, :, 2] with joints 1, 9, 12 set to 0, summed per item
+ *   EHM_LOSS_BETAS / _BODY_POSE / _GLOBAL_ORIENT   :376-383  squared differences summed over the item ([10] / [23,3,3] / [1,3,3] rotation matrices)
+ *   EHM_LOSS_POSE_6D_ORTHO   :386-388  per joint x = pose_6d.reshape(3, 2): sum of (x^T x - I_2)^2 over the 24 joints / 96
+ *   EHM_LOSS_PENETRATION     :390-419  handed in: penetration [B] (NULL = 0)
+ *   EHM_LOSS_KP3D_VIS_SUM    :358-372  selected ground-truth joints 0..23 projected with zero translation, focal [B,2], center [B,2]; visible = 0 <= u < 1920
+ *                                      and 0 <= v < 1080; sum over the joints of (pelvis-aligned joint distance pred_keypoints_3d / keypoints_3d) * visible
+ *                                      (a product: the NaN error of an invisible joint gives NaN, as in the reference)
+ * per_item [B, EHM_LOSS_TERMS]: the contribution of each item; losses[k] = mean over B of per_item[:, k] (EHM_LOSS_KP3D_VIS_SUM: the sum), formed from the
+ * float64 per-item sums and rounded once.  per_item_vis [B] int64 / joint_vis_num [1] int64: visible joints (:372); vis_mask [B,24] u8 (may be NULL).
+ * Every input element is widened to float64 before the first subtraction, every sum runs in float64 in a fixed order (per-block partial sums in the
+ * workspace, no atomics): results are bit-equal from run to run.  Vertex arrays must be 16-byte aligned.  gender [B] int64.
+ * pred_joints >= 45: joints per item of the three pred_keypoints arrays; gt_joints / kp3d_points / kp3d_full_points >= 24, kp2d_points >= 25: points per
+ * item of gt_joints_*, keypoints_3d, keypoints_3d_full, keypoints_2d.  workspace: *bytes of ehm_val_losses_workspace_bytes(B, V, &bytes), 8-byte aligned. */
+enum {
+  EHM_LOSS_TOTAL = 0, EHM_LOSS_V2V = 1, EHM_LOSS_KP3D = 2, EHM_LOSS_KP3D_FULL = 3, EHM_LOSS_KP2D_FULL = 4, EHM_LOSS_BETAS = 5, EHM_LOSS_BODY_POSE = 6,
+  EHM_LOSS_GLOBAL_ORIENT = 7, EHM_LOSS_POSE_6D_ORTHO = 8, EHM_LOSS_PENETRATION = 9, EHM_LOSS_KP3D_VIS_SUM = 10, EHM_LOSS_TERMS = 11
+};
+typedef struct ehm_val_losses_desc {
+  int B, V, pred_joints, gt_joints, kp3d_points, kp3d_full_points, kp2d_points;
+  const float *pred_vertices, *pred_keypoints_3d, *pred_keypoints_3d_full, *pred_keypoints_2d_full; /* [B,V,3], [B,pred_joints,3] x 2, [B,pred_joints,2] */
+  const float *pred_global_orient, *pred_body_pose, *pred_betas, *pred_pose_6d;                      /* [B,9], [B,207], [B,10], [B,144] */
+  const float *keypoints_2d, *keypoints_3d, *keypoints_3d_full;                                     /* [B,kp2d_points,3], [B,kp3d_points,3], [B,kp3d_full_points,3] */
+  const float *gt_vertices_male, *gt_vertices_female, *gt_joints_male, *gt_joints_female;           /* [B,V,3] x 2, [B,gt_joints,3] x 2 */
+  const int64_t* gender;                                                                            /* [B] */
+  const float *gt_global_orient, *gt_body_pose, *gt_betas;                                          /* [B,9], [B,207] rotation matrices, [B,10] */
+  const float *focal, *center;                                                                      /* [B,2] each */
+  const float* penetration;                                                                         /* [B] or NULL */
+  double weights[9];
+  void* workspace;
+  int64_t workspace_bytes;
+  float* losses;          /* [EHM_LOSS_TERMS] */
+  int64_t* joint_vis_num; /* [1] */
+  float* per_item;        /* [B, EHM_LOSS_TERMS] */
+  int64_t* per_item_vis;  /* [B] */
+  uint8_t* vis_mask;      /* [B,24] or NULL */
+} ehm_val_losses_desc;
+int ehm_val_losses_workspace_bytes(int B, int V, int64_t* bytes);
+int ehm_val_losses(const ehm_val_losses_desc* d, void* stream);
+
+/* The point cap of the penetration term (egohmr.py:406-412): count [B] int32 = scene points of item b inside the bounding box of verts[b] (both ends
+ * inclusive); scene_out [B,N,3] = scene, except that in an item with count > cap the points of index >= cap are moved out of every box (3e38) - the
+ * reference's `inds[:, 4000:] = False`, not "the first 4000 selected".  ehm_collision_query on scene_out then gives the capped term. */
+int ehm_scene_cap_points(const float* verts, const float* scene, float* scene_out, int32_t* count, int B, int V, int N, int cap, void* stream);
+
 /* ------------------------------------------------------------------ whole sampling loop ------- */
 /* One executed step of the loop (host-side table lookup already done, float32 like
  * _extract_into_tensor, gaussian_diffusion.py:794). */
