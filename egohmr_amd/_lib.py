@@ -269,6 +269,8 @@ PROTOTYPES = {
     "ehm_collision_query": (_I, [_P, _P, _P, _P, _P, _I, _I, _I, _F, _I, _P]),
     "ehm_smpl_backward_rot6d": (_I, [_P, _P, _P, _P, _P, _P, _P, _I, _P]),
     "ehm_guidance_grad_finish": (_I, [_P, _P, _P, _I, _F, _P]),
+    "ehm_smpl_backward": (_I, [_P, _P, _P, _P, _P, _P, _P, _I, _P, _L, _P]),
+    "ehm_smpl_backward_workspace_bytes": (_I, [_P, _I, C.POINTER(C.c_int64)]),
     "ehm_nn_dist2": (_I, [_P, _P, _P, _P, _I, _I, _I, _P]),
     "ehm_eval_point_errors": (_I, [C.POINTER(EvalPointsDesc), _P]),
     "ehm_eval_procrustes": (_I, [_P, _P, _P, _P, _P, _P, _P, _P, _I, _I, _I, _P]),

@@ -743,6 +743,177 @@ __global__ __launch_bounds__(64) void chain_bwd_kernel(const float* __restrict__
   o[1] = ga2[0]; o[3] = ga2[1]; o[5] = ga2[2];
 }
 
+// ------------------------------------------------------------------------------------------------ general VJP (ehm_smpl_backward)
+// The n_extra joints are vertex picks: their cotangent rows go into the private vertex cotangent.  thread = (body, coordinate), the picks in
+// index order (an index may repeat: fixed sum order, no atomics)
+__global__ void extra_joints_bwd_kernel(const float* __restrict__ gjoints, const int32_t* __restrict__ idx, float* __restrict__ gv, int B, int V,
+                                        int n_extra) {
+  const int i = blockIdx.x * blockDim.x + threadIdx.x;
+  if (i >= B * 3) return;
+  const int b = i / 3, c = i % 3;
+  for (int e = 0; e < n_extra; ++e) gv[((size_t)b * V + idx[e]) * 3 + c] += gjoints[((size_t)b * (kJ + n_extra) + kJ + e) * 3 + c];
+}
+
+// Shape path of the blend: gbetas_v[b][l] = sum_k shape_t[l][k] * gvp[b][k] over the 3 V blended-rest-vertex cotangents that skin_bwd_kernel left.
+// Block = kSbB bodies x all of K: a thread walks k = tid, tid + 256, ... (coalesced rows of both operands; the ten basis rows, 0.8 MB, stay in L2 and
+// are reused by the block's bodies in registers), then a fixed-order reduction: xor shuffles inside a wave, the four waves in index order through LDS.
+constexpr int kSbB = 4;
+__global__ __launch_bounds__(256) void shape_bwd_kernel(const float* __restrict__ gvp, const float* __restrict__ shape_t, float* __restrict__ gbetas_v,
+                                                        int B, int V3) {
+  __shared__ float red[4][kSbB * 10];
+  const int tid = threadIdx.x, b0 = blockIdx.x * kSbB, nb = min(kSbB, B - b0);
+  float acc[kSbB][10];
+#pragma unroll
+  for (int bb = 0; bb < kSbB; ++bb)
+#pragma unroll
+    for (int l = 0; l < 10; ++l) acc[bb][l] = 0.f;
+  for (int k = tid; k < V3; k += 256) {
+    float g[kSbB];
+#pragma unroll
+    for (int bb = 0; bb < kSbB; ++bb) g[bb] = bb < nb ? gvp[(size_t)(b0 + bb) * V3 + k] : 0.f;
+#pragma unroll
+    for (int l = 0; l < 10; ++l) {
+      const float sv = shape_t[(size_t)l * V3 + k];
+#pragma unroll
+      for (int bb = 0; bb < kSbB; ++bb) acc[bb][l] = fmaf(sv, g[bb], acc[bb][l]);
+    }
+  }
+#pragma unroll
+  for (int bb = 0; bb < kSbB; ++bb)
+#pragma unroll
+    for (int l = 0; l < 10; ++l) {
+      float v = acc[bb][l];
+#pragma unroll
+      for (int o = 32; o >= 1; o >>= 1) v += __shfl_xor(v, o);
+      if ((tid & 63) == 0) red[tid >> 6][bb * 10 + l] = v;
+    }
+  __syncthreads();
+  if (tid < nb * 10) gbetas_v[(size_t)b0 * 10 + tid] = ((red[0][tid] + red[1][tid]) + red[2][tid]) + red[3][tid];
+}
+
+// chain_bwd_kernel's twin for rotation-matrix inputs: one wave per body, lane = joint, the same level-by-level reverse pass through LDS in
+// child-index order.  Beyond it: the posed joints' cotangent (joints = translation column of G) enters dG.t, the local rotation gradient is
+// emitted as it is (no Gram-Schmidt VJP), and the rest joints' gradient dJ - t_j = J_j - J_parent (the root: J_0), A_j.t = G_j.t - G_j.R J_j -
+// is contracted with J_shape into gbetas in the same wave (+ the blend's share gbetas_v).  Every sum HERE has a fixed order; the input gA does not
+// (skin_bwd_kernel's float atomics), so grotmats and gbetas inherit its last-bit spread from call to call.
+__global__ __launch_bounds__(64) void chain_bwd_rotmat_kernel(const float* __restrict__ betas, const float* __restrict__ rotmats, SmplDev S,
+                                                              const float* __restrict__ gA, const float* __restrict__ gpf,
+                                                              const float* __restrict__ gjoints, int jstride,
+                                                              const float* __restrict__ gbetas_v, float* __restrict__ grotmats,
+                                                              float* __restrict__ gbetas) {
+  __shared__ float sC[kJ][12];      // contribution of child c to its parent's dG
+  __shared__ float sT[kJ][3];       // dt of joint c (its parent's rest joint receives -dt)
+  __shared__ float sJ[kJ][3];       // d loss / d rest joint
+  const int b = blockIdx.x, lane = threadIdx.x;
+  const int j = lane < kJ ? lane : 0;
+  float R[9];
+#pragma unroll
+  for (int k = 0; k < 9; ++k) R[k] = rotmats[((size_t)b * kJ + j) * 9 + k];
+  float Jx[3];
+#pragma unroll
+  for (int c = 0; c < 3; ++c) {
+    float s = 0.f;
+#pragma unroll
+    for (int l = 0; l < 10; ++l) s = fmaf(S.J_shape[j * 30 + c * 10 + l], betas[(size_t)b * 10 + l], s);
+    Jx[c] = S.J_template[j * 3 + c] + s;
+  }
+  const int par = S.tree.parent[j], plane = par < 0 ? 0 : par, my_depth = S.tree.depth[j];
+  float t[3];
+#pragma unroll
+  for (int c = 0; c < 3; ++c) {
+    const float pj = __shfl(Jx[c], plane);
+    t[c] = par < 0 ? Jx[c] : Jx[c] - pj;
+  }
+  float G[12], GP[9];               // G: own global transform; GP: parent's global rotation
+#pragma unroll
+  for (int r = 0; r < 3; ++r) { G[r * 4] = R[r * 3]; G[r * 4 + 1] = R[r * 3 + 1]; G[r * 4 + 2] = R[r * 3 + 2]; G[r * 4 + 3] = t[r]; }
+#pragma unroll
+  for (int e = 0; e < 9; ++e) GP[e] = (e == 0 || e == 4 || e == 8) ? 1.f : 0.f;
+  for (int d = 1; d <= S.tree.max_depth; ++d) {
+    float P[12];
+#pragma unroll
+    for (int k = 0; k < 12; ++k) P[k] = __shfl(G[k], plane);
+    if (my_depth == d) {
+#pragma unroll
+      for (int r = 0; r < 3; ++r) {
+        const float p0 = P[r * 4], p1 = P[r * 4 + 1], p2 = P[r * 4 + 2], p3 = P[r * 4 + 3];
+        GP[r * 3] = p0; GP[r * 3 + 1] = p1; GP[r * 3 + 2] = p2;
+        G[r * 4 + 0] = p0 * R[0] + p1 * R[3] + p2 * R[6];
+        G[r * 4 + 1] = p0 * R[1] + p1 * R[4] + p2 * R[7];
+        G[r * 4 + 2] = p0 * R[2] + p1 * R[5] + p2 * R[8];
+        G[r * 4 + 3] = p0 * t[0] + p1 * t[1] + p2 * t[2] + p3;
+      }
+    }
+  }
+  // dG from dA and the posed joints:  A.R = G.R,  A.t = G.t - G.R J,  joint = G.t   =>  dG.R = dA.R - dA.t (x) J,  dG.t = dA.t + d joint
+  float dG[12], gAt[3];
+#pragma unroll
+  for (int r = 0; r < 3; ++r) {
+    const float gt = lane < kJ ? gA[((size_t)b * kJ + j) * 12 + r * 4 + 3] : 0.f;
+    gAt[r] = gt;
+#pragma unroll
+    for (int c = 0; c < 3; ++c) dG[r * 4 + c] = (lane < kJ ? gA[((size_t)b * kJ + j) * 12 + r * 4 + c] : 0.f) - gt * Jx[c];
+    dG[r * 4 + 3] = gt + ((gjoints && lane < kJ) ? gjoints[(size_t)b * jstride + j * 3 + r] : 0.f);
+  }
+  // reverse levels: a child's dG reaches its parent as  dGp.R += dG.R R^T + dG.t (x) t ,  dGp.t += dG.t
+  for (int d = S.tree.max_depth; d >= 1; --d) {
+    if (lane < kJ && my_depth == d) {
+#pragma unroll
+      for (int r = 0; r < 3; ++r) {
+#pragma unroll
+        for (int c = 0; c < 3; ++c)
+          sC[j][r * 4 + c] = dG[r * 4] * R[c * 3] + dG[r * 4 + 1] * R[c * 3 + 1] + dG[r * 4 + 2] * R[c * 3 + 2] + dG[r * 4 + 3] * t[c];
+        sC[j][r * 4 + 3] = dG[r * 4 + 3];
+      }
+    }
+    __syncthreads();
+    if (lane < kJ && my_depth == d - 1) {
+      for (int c = j + 1; c < kJ; ++c) {                     // children in index order: deterministic sum
+        if (S.tree.parent[c] == j) {
+#pragma unroll
+          for (int e = 0; e < 12; ++e) dG[e] += sC[c][e];
+        }
+      }
+    }
+    __syncthreads();
+  }
+  // local rotation gradient: dR = Gp.R^T dG.R (+ pose-feature path for joints 1..23)
+  if (grotmats && lane < kJ) {
+#pragma unroll
+    for (int r = 0; r < 3; ++r)
+#pragma unroll
+      for (int c = 0; c < 3; ++c) {
+        float s = GP[0 * 3 + r] * dG[0 * 4 + c] + GP[1 * 3 + r] * dG[1 * 4 + c] + GP[2 * 3 + r] * dG[2 * 4 + c];
+        if (j > 0) s += gpf[(size_t)b * 208 + (j - 1) * 9 + r * 3 + c];
+        grotmats[((size_t)b * kJ + j) * 9 + r * 3 + c] = s;
+      }
+  }
+  if (!gbetas) return;                                         // (uniform: a kernel argument)
+  // rest joints: dt_j = Gp.R^T dG_j.t goes to J_j and, negated, to J_parent(j);  A_j.t gives  - G_j.R^T dA_j.t
+  float dJ[3];
+#pragma unroll
+  for (int c = 0; c < 3; ++c) {
+    const float dt = GP[0 * 3 + c] * dG[0 * 4 + 3] + GP[1 * 3 + c] * dG[1 * 4 + 3] + GP[2 * 3 + c] * dG[2 * 4 + 3];
+    dJ[c] = dt - (G[0 * 4 + c] * gAt[0] + G[1 * 4 + c] * gAt[1] + G[2 * 4 + c] * gAt[2]);
+    if (lane < kJ) sT[j][c] = dt;
+  }
+  __syncthreads();
+  if (lane < kJ) {
+    for (int c = j + 1; c < kJ; ++c) {                         // children in index order
+      if (S.tree.parent[c] == j) { dJ[0] -= sT[c][0]; dJ[1] -= sT[c][1]; dJ[2] -= sT[c][2]; }
+    }
+    sJ[j][0] = dJ[0]; sJ[j][1] = dJ[1]; sJ[j][2] = dJ[2];
+  }
+  __syncthreads();
+  if (lane < 10) {                                             // J = J_template + J_shape . beta: lane = shape coefficient, joints in index order
+    float s = 0.f;
+    for (int jj = 0; jj < kJ; ++jj)
+#pragma unroll
+      for (int c = 0; c < 3; ++c) s = fmaf(S.J_shape[jj * 30 + c * 10 + lane], sJ[jj][c], s);
+    gbetas[(size_t)b * 10 + lane] = gbetas_v[(size_t)b * 10 + lane] + s;
+  }
+}
+
 __global__ void finish_kernel(const float* __restrict__ gpose, float* __restrict__ grad, int B, float denom) {
   const int i = blockIdx.x * blockDim.x + threadIdx.x;
   if (i >= B * kPoseDim) return;
@@ -833,8 +1004,9 @@ int collision_impl(const float* verts, const float* scene, float* loss, float* g
   return 0;
 }
 
-int backward_impl(ehm_smpl* h, const float* betas, const float* x, const float* mean, const float* std_, const float* Rws,
-                  const float* Aws, float* gverts, float* gpose, int B, const Scratch& s, hipStream_t st, const float* vposed = nullptr) {
+// the part of the VJP that both chain kernels share: gverts -> d loss / d blended rest vertex (in place), gA, and (want_gpf) the pose-feature gradient
+int skin_posefeat_bwd(ehm_smpl* h, const float* betas, const float* Rws, const float* Aws, float* gverts, int B, const Scratch& s, hipStream_t st,
+                      const float* vposed, bool want_gpf) {
   const SmplDev& d = h->d;
   EHM_HIP(hipMemsetAsync(s.gA, 0, (size_t)B * kJ * 12 * sizeof(float), st));
   const int v_tiles = (int)ceil_div(d.V, kVT), b_groups = (int)ceil_div(B, kBG);
@@ -843,11 +1015,19 @@ int backward_impl(ehm_smpl* h, const float* betas, const float* x, const float* 
     hipLaunchKernelGGL(skin_bwd_kernel, dim3((unsigned)(round_up(v_tiles, 8) * b_groups)), dim3(kVT), 0, st, betas, Rws, Aws, d, gverts,
                        s.gA, B, v_tiles, b_groups, vposed);
   }
-  {
+  if (want_gpf) {
     EhmProfScope ps(EHM_PROF_G_POSEFEAT_BWD, st);
     hipLaunchKernelGGL(posefeat_bwd_mfma_kernel, dim3((unsigned)ceil_div(B, 32), kPfSplit), dim3(256), 0, st, gverts, d.posedirs, s.gpf_part, B, d.V * 3);
     hipLaunchKernelGGL(posefeat_sum_kernel, dim3((unsigned)ceil_div((int64_t)B * 208, 256)), dim3(256), 0, st, s.gpf_part, s.gpf, B * 208);
   }
+  EHM_LAUNCH_CHECK();
+  return 0;
+}
+
+int backward_impl(ehm_smpl* h, const float* betas, const float* x, const float* mean, const float* std_, const float* Rws,
+                  const float* Aws, float* gverts, float* gpose, int B, const Scratch& s, hipStream_t st, const float* vposed = nullptr) {
+  const SmplDev& d = h->d;
+  if (int rc = skin_posefeat_bwd(h, betas, Rws, Aws, gverts, B, s, st, vposed, true)) return rc;
   hipLaunchKernelGGL(chain_bwd_kernel, dim3(B), dim3(64), 0, st, betas, x, mean, std_, d, s.gA, s.gpf, gpose);
   EHM_LAUNCH_CHECK();
   return 0;
@@ -920,6 +1100,52 @@ extern "C" int ehm_smpl_backward_rot6d(ehm_smpl* h, const float* betas, const fl
   rc = ehm_smpl_pose_impl(h, betas, x, mean, std_, Rws, Aws, jws, B, st);
   if (rc) return rc;
   return backward_impl(h, betas, x, mean, std_, Rws, Aws, gcopy, gpose6d, B, carve_scratch(sc, B, 1), st);
+}
+
+// ehm_smpl_backward's workspace: the guidance block (gA, gpf and its partial tiles) + R [B,24,9] + A [B,24,12] + joints + the private vertex
+// cotangent [B,V,3] (the VJP works in place) + gbetas_v [B,10]
+static int64_t smpl_backward_bytes(const ehm_smpl* h, int B) {
+  return ehm_guidance_scratch_bytes(B, 1) + round_up((int64_t)B * kJ * 9 * 4, 256) + round_up((int64_t)B * kJ * 12 * 4, 256) +
+         round_up((int64_t)B * (kJ + 64) * 3 * 4, 256) + round_up((int64_t)B * h->d.V * 3 * 4, 256) + round_up((int64_t)B * 10 * 4, 256);
+}
+
+extern "C" int ehm_smpl_backward_workspace_bytes(const ehm_smpl* h, int B, int64_t* bytes) {
+  EHM_CHECK_ARG(h && bytes && B > 0);
+  *bytes = smpl_backward_bytes(h, B);
+  return 0;
+}
+
+extern "C" int ehm_smpl_backward(ehm_smpl* h, const float* betas, const float* rotmats, const float* gverts, const float* gjoints, float* gbetas,
+                                 float* grotmats, int B, void* workspace, int64_t workspace_bytes, void* stream) {
+  EHM_CHECK_ARG(h && betas && rotmats && B > 0);
+  EHM_CHECK_ARG(gverts || gjoints);
+  EHM_CHECK_ARG(gbetas || grotmats);
+  EHM_CHECK_ARG(workspace && ((uintptr_t)workspace & 15) == 0 && workspace_bytes >= smpl_backward_bytes(h, B));
+  hipStream_t st = (hipStream_t)stream;
+  const SmplDev& d = h->d;
+  const int V = d.V;
+  const int64_t gs = ehm_guidance_scratch_bytes(B, 1);
+  const Scratch s = carve_scratch(workspace, B, 1);
+  char* p = (char*)workspace + gs;
+  float* Rws = (float*)p;     p += round_up((int64_t)B * kJ * 9 * 4, 256);
+  float* Aws = (float*)p;     p += round_up((int64_t)B * kJ * 12 * 4, 256);
+  float* jws = (float*)p;     p += round_up((int64_t)B * (kJ + 64) * 3 * 4, 256);
+  float* gcopy = (float*)p;   p += round_up((int64_t)B * V * 3 * 4, 256);
+  float* gbv = (float*)p;
+  if (gverts) EHM_HIP(hipMemcpyAsync(gcopy, gverts, (size_t)B * V * 3 * sizeof(float), hipMemcpyDeviceToDevice, st));
+  else EHM_HIP(hipMemsetAsync(gcopy, 0, (size_t)B * V * 3 * sizeof(float), st));
+  if (gjoints && d.n_extra)
+    hipLaunchKernelGGL(extra_joints_bwd_kernel, dim3((unsigned)ceil_div((int64_t)B * 3, 256)), dim3(256), 0, st, gjoints, d.extra_idx, gcopy, B, V,
+                       d.n_extra);
+  int rc = ehm_smpl_pose_rotmat_impl(h, betas, rotmats, Rws, Aws, jws, B, st);
+  if (rc) return rc;
+  rc = skin_posefeat_bwd(h, betas, Rws, Aws, gcopy, B, s, st, nullptr, grotmats != nullptr);
+  if (rc) return rc;
+  if (gbetas) hipLaunchKernelGGL(shape_bwd_kernel, dim3((unsigned)ceil_div(B, kSbB)), dim3(256), 0, st, gcopy, d.shape_t, gbv, B, V * 3);
+  hipLaunchKernelGGL(chain_bwd_rotmat_kernel, dim3(B), dim3(64), 0, st, betas, rotmats, d, s.gA, s.gpf, gjoints, (kJ + d.n_extra) * 3, gbv, grotmats,
+                     gbetas);
+  EHM_LAUNCH_CHECK();
+  return 0;
 }
 
 extern "C" int ehm_guidance_grad_finish(const float* gpose6d, const float* loss, float* grad, int B, float denom, void* stream) {

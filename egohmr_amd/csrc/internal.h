@@ -11,6 +11,8 @@ int ehm_smpl_writes_vposed(const ehm_smpl* h, int B);             //   1 when a 
 // rot6d -> R, joint regression, kinematic chain only (no skinning): R [B,24,9], A [B,24,12], joints24 into jws [B,(24+n_extra),3]
 int ehm_smpl_pose_impl(ehm_smpl* h, const float* betas, const float* x, const float* mean, const float* std_, float* Rws, float* Aws,
                        float* jws, int B, hipStream_t st);
+// the same from rotation matrices [B,24,3,3] (Rws, may be nullptr, receives a copy): the chain of ehm_smpl_backward
+int ehm_smpl_pose_rotmat_impl(ehm_smpl* h, const float* betas, const float* rotmats, float* Rws, float* Aws, float* jws, int B, hipStream_t st);
 // output-conv mix + sampler update + pose chain + blend-coefficient fragments in one launch, then skinning (sampling loop only)
 int ehm_step_body_impl(ehm_smpl* h, const float* hs, const void* out_dev, const uint8_t* vis, const float* x, const float* noise,
                        const float* grad, float* x_next, float* x0, const ehm_step_coefs* c, int ddim, int passes, const int32_t* mask_slot, int do_pose,

@@ -713,6 +713,14 @@ int ehm_smpl_pose_impl(ehm_smpl* h, const float* betas, const float* x, const fl
   return 0;
 }
 
+int ehm_smpl_pose_rotmat_impl(ehm_smpl* h, const float* betas, const float* rotmats, float* Rws, float* Aws, float* jws, int B, hipStream_t st) {
+  const SmplDev& d = h->d;
+  hipLaunchKernelGGL(pose_chain_kernel<false>, dim3(B), dim3(64), 0, st, betas, rotmats, (const float*)nullptr, (const float*)nullptr, d, Rws, Aws,
+                     jws, (float*)nullptr, (kJ + d.n_extra) * 3);
+  EHM_LAUNCH_CHECK();
+  return 0;
+}
+
 extern "C" int ehm_smpl_forward(ehm_smpl* h, const float* betas, const float* rotmats, float* verts, float* joints, float* A_out,
                                 int B, void* stream) {
   EHM_CHECK_ARG(h && betas && rotmats && verts && joints && B > 0);

@@ -1,5 +1,7 @@
 // Device-side view of the SMPL constants, shared by smpl.hip (forward) and guidance.hip (backward).
 #pragma once
+#include <stddef.h>
+
 #include "common.h"
 
 constexpr int kBG = 8;       // bodies per block of the skinning VJP (guidance.hip)
@@ -65,3 +67,7 @@ struct ehm_smpl {
   void* pf = nullptr;          // blend coefficients of the current batch as MFMA A fragments [ceil(B/32)][14][hi/lo][64][8 halves]
   int pf_cap = 0;              // bodies
 };
+// tests/test_smpl_autograd_cpu.py hands the argument checks of ehm_smpl_backward a host stand-in for a handle that holds V and n_extra only:
+// the two ints lead the handle.  Moving them fails the build here, not the test in host code that reads garbage.
+static_assert(offsetof(ehm_smpl, d) == 0 && offsetof(SmplDev, V) == 0 && offsetof(SmplDev, n_extra) == sizeof(int),
+              "ehm_smpl must start with SmplDev{int V; int n_extra; ...}");

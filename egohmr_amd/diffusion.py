@@ -273,7 +273,11 @@ class GaussianDiffusion:
         yield from self._loop(model, batch, shape, True, noise, device, progress, eta, skip_timesteps, init_data,
                               cond_fn_with_grad, 1.0, noise_stack)
 
-    def _fused_ok(self, model, skip_timesteps, init_data, dump_steps, progress, eta):
+    def _fused_ok(self, model, skip_timesteps, init_data, dump_steps, progress, eta, guided=False):
+        """Whether a loop may run as the one native call.  A GUIDED loop of a model with `collision_model` attached may not: the native loop cannot
+        call Python between steps, so it takes the generic per-step route (model.guide_coll in every guided step); unguided loops stay fused."""
+        if guided and getattr(model, "collision_model", None) is not None:
+            return False
         return (getattr(self, "allow_fused", True) and getattr(model, "fused_sampler", None) is not None
                 and not skip_timesteps and init_data is None
                 and dump_steps is None and not progress and eta == 0.0)
@@ -288,8 +292,9 @@ class GaussianDiffusion:
     def p_sample_loop(self, model, batch, shape, noise=None, clip_denoised=True, denoised_fn=None, device=None, progress=False,
                       skip_timesteps=0, init_data=None, cond_fn_with_grad=False, cond_grad_weight=1.0, dump_steps=None,
                       noise_stack=None):
-        """gaussian_diffusion.py:391-446 -> dict(sample, pred_xstart, other_outputs) of the last step."""
-        if self._fused_ok(model, skip_timesteps, init_data, dump_steps, progress, 0.0):
+        """gaussian_diffusion.py:391-446 -> dict(sample, pred_xstart, other_outputs) of the last step.  One native call where _fused_ok allows it; a
+        guided loop of a model with `collision_model` attached runs step by step (the attached model is Python)."""
+        if self._fused_ok(model, skip_timesteps, init_data, dump_steps, progress, 0.0, guided=cond_fn_with_grad):
             device = self._device_of(model, device)
             stack = noise_stack if noise_stack is not None else self._draw_stack(shape, device, noise)
             return model.fused_sampler.run(self, batch, stack, ddim=False, guided=cond_fn_with_grad, cond_grad_weight=cond_grad_weight)
@@ -306,7 +311,7 @@ class GaussianDiffusion:
     def ddim_sample_loop(self, model, batch, shape, noise=None, clip_denoised=True, denoised_fn=None, device=None, progress=False,
                          eta=0.0, skip_timesteps=0, init_data=None, cond_fn_with_grad=False, noise_stack=None):
         """gaussian_diffusion.py:618-658."""
-        if self._fused_ok(model, skip_timesteps, init_data, None, progress, eta):
+        if self._fused_ok(model, skip_timesteps, init_data, None, progress, eta, guided=cond_fn_with_grad):
             # (cond_fn_with_grad: ddim_sample_with_grad inside the one-call loop - the collision gradient enters eps on the last four respaced steps)
             device = self._device_of(model, device)
             stack = noise_stack if noise_stack is not None else self._draw_stack(shape, device, noise)

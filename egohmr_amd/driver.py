@@ -56,7 +56,7 @@ class Stage2Driver:
         coll = np.zeros((B, self.S))
         batched = None
         ddim = self.respacing[0:4] == "ddim"
-        if self.S > 1 and self.batch_samples and self.diffusion._fused_ok(self.model, 0, None, None, False, 0.0) and not (ddim and self.guided):
+        if self.S > 1 and self.batch_samples and self.diffusion._fused_ok(self.model, 0, None, None, False, 0.0, guided=self.guided) and not (ddim and self.guided):
             # the S loops of the reference (test_egohmr.py:251-266) as ONE loop over S*B bodies (FusedSampler.run_samples): same noise
             # draws in the same order, same per-body arithmetic
             self.model.validation_setup()

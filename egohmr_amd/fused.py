@@ -609,8 +609,12 @@ class FusedSampler:
     def run(self, diffusion, batch, noise_stack, ddim=False, guided=False, cond_grad_weight=1.0, trace=False, prepared=None, denom_items=None,
             defer_status=False, lowprec=None):
         """p_sample_loop / ddim_sample_loop (gaussian_diffusion.py:391-508 / :618-718) in one native call.
-        Returns the reference's dict(sample, pred_xstart, other_outputs)."""
+        Returns the reference's dict(sample, pred_xstart, other_outputs).  The in-loop guidance is the build's collision proxy: a guided call on a
+        model with `collision_model` attached raises (the samplers of diffusion.py route such a loop step by step through model.guide_coll)."""
         m = self.model
+        if guided and getattr(m, "collision_model", None) is not None:
+            raise _lib.EgoHMRHipError("FusedSampler.run(guided=True): the one-call loop cannot call the attached collision_model between steps and will "
+                                      "not fall back to the build's proxy; sample through diffusion.p_sample_loop / ddim_sample_loop / val_losses")
         call = dict(diffusion=diffusion, batch=batch, noise_stack=noise_stack, ddim=ddim, guided=guided, cond_grad_weight=cond_grad_weight, trace=trace,
                     prepared=prepared, denom_items=denom_items)
         with _lib.on_device(m.device):

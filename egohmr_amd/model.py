@@ -404,6 +404,11 @@ class EgoHMR(nn.Module):
         self.openpose_to_smpl = OPENPOSE_TO_SMPL_LOOSE if pelvis_vis_loosen else OPENPOSE_TO_SMPL
         self.smpl_to_openpose = [24, 12, 17, 19, 21, 16, 18, 20, 0, 2, 5, 8, 1, 4, 7, 25, 26, 27, 28, 29, 30, 31, 32, 33, 34]
         self.collision_tau = 0.05
+        # None: the build's nearest-vertex proxy (csrc/guidance.hip), inside the one-call loop.  Else an object with the two calls the reference makes on
+        # `self.smpl.coap` (COAP) / `self.smpl_volsmpl.volume` (VolumetricSMPL): collision_loss(points, smpl_output, ret_collision_mask=None) and
+        # query(points, smpl_output); guide_coll / eval_coll / _penetration_term then run the reference's autograd route through the differentiable
+        # SMPL.forward, and guided loops take the per-step route (the native loop cannot call Python between steps); unguided loops stay fused
+        self.collision_model = None
         self.guide_reduction = "mean"          # COAP variant: -loss.mean() (egohmr.py:562); 'sum' = VolSMPL variant (egohmr_volsmpl.py:618)
         self.guide_denom_override = None       # sharded / sub-batch runs: the GLOBAL batch size of `-loss.mean()`, else None
         self.guide_all_points = False          # COAP variant: bbox-selected scene points (egohmr.py:550-552); True = all points (egohmr_volsmpl.py:609-612)
@@ -522,16 +527,102 @@ class EgoHMR(nn.Module):
         }
 
     def guide_coll(self, batch, output, t, compute_grad="x_t"):
-        """egohmr.py:517-570 with the build's collision proxy in place of COAP; returns [B,144]."""
+        """egohmr.py:517-570 with the build's collision proxy in place of COAP; returns [B,144].  With `collision_model` attached: the reference's
+        own autograd route through that model (_guide_coll_model), for compute_grad 'x_t' and 'x_0' alike."""
         fs = self.fused_sampler
         st = fs.prepare(batch)
         x = _lib.f32(batch["x_t"] if compute_grad == "x_t" else output["pred_x_start"], self.device).reshape(-1, 144)
-        return fs.guidance_gradient(st, x, _lib.f32(output["pred_smpl_params"]["betas"], self.device))
+        betas = _lib.f32(output["pred_smpl_params"]["betas"], self.device)
+        if self.collision_model is not None:
+            if compute_grad not in ("x_t", "x_0"):                       # (the reference leaves x_t unbound for anything else, egohmr.py:519-523)
+                raise ValueError(f"compute_grad must be 'x_t' or 'x_0' (got {compute_grad!r})")
+            with _lib.on_device(self.device):
+                return self._guide_coll_model(st.scene, x, betas)
+        return fs.guidance_gradient(st, x, betas)
+
+    # ------------------------------------------------------------------ an attached collision model (COAP / VolumetricSMPL)
+    GUIDE_ZEROED_JOINTS = (0, 3, 6, 9, 12, 13, 14, 15, 16, 17, 18, 19, 20, 21, 22, 23)      # egohmr.py:567 "ignore upper body part"
+
+    def _collision_bodies(self, betas, global_orient, body_pose):
+        """The `smpl_output_mode` of egohmr.py:537-540 / :492-495: vertices, joints and the axis-angle full_pose [B,72], all in the autograd graph of the
+        inputs when gradients are enabled."""
+        so = self.smpl(betas=betas, body_pose=body_pose, global_orient=global_orient, return_full_pose=True, pose2rot=False)
+        B = so.vertices.shape[0]
+        aa = geometry.rotation_matrix_to_angle_axis(so.full_pose.reshape(-1, 3, 3)).reshape(B, -1)
+        return smpl_mod.SMPLOutput(vertices=so.vertices, joints=so.joints, full_pose=aa)
+
+    @staticmethod
+    def _collision_item(bodies, i, clone=False):
+        f = (lambda t: t[[i]].clone()) if clone else (lambda t: t[[i]])
+        return smpl_mod.SMPLOutput(vertices=f(bodies.vertices), joints=f(bodies.joints), full_pose=f(bodies.full_pose))
+
+    @staticmethod
+    def _bbox_points(item, scene_i, cap=None):
+        """egohmr.py:550-552: the scene points [1,n,3] inside the bounding box of the item's vertices, or None when there is none (one host read-back
+        per item, like the reference); cap: `inds[:, cap:] = False` where more than `cap` are selected (:411-412)."""
+        v = item.vertices.detach()
+        bb_min, bb_max = v.min(1).values.reshape(1, 3), v.max(1).values.reshape(1, 3)
+        inds = (scene_i >= bb_min).all(-1) & (scene_i <= bb_max).all(-1)
+        if cap is not None and inds.sum() > cap:
+            inds[:, cap:] = False
+        if not inds.any():
+            return None
+        return scene_i[inds].unsqueeze(0)
+
+    def _collision_losses(self, bodies, scene):
+        """[B] losses of the attached model: per item over the bbox-selected points (egohmr.py:545-559); with guide_all_points ONE batched call over every
+        scene point (egohmr_volsmpl.py:609-614)."""
+        cm = self.collision_model
+        B = bodies.vertices.shape[0]
+        if self.guide_all_points:
+            return cm.collision_loss(scene, bodies, ret_collision_mask=None).reshape(B)
+        losses = []
+        for i in range(B):
+            item = self._collision_item(bodies, i)
+            pts = self._bbox_points(item, scene[[i]])
+            losses.append(torch.zeros((), device=self.device) if pts is None else cm.collision_loss(pts, item, ret_collision_mask=None).reshape(()))
+        return torch.stack(losses)
+
+    def _guide_coll_model(self, scene, x, betas):
+        """egohmr.py:517-570 (egohmr_volsmpl.py:582-629 with guide_all_points / guide_reduction = 'sum') through `collision_model`: de-normalise,
+        rot6d_to_rotmat, the differentiable SMPL.forward (ehm_smpl_backward behind it), rotation_matrix_to_angle_axis, the model's loss, then
+        torch.autograd.grad of -loss.mean() (denominator: FusedSampler.guide_denom, so guide_denom_override acts as on the proxy route) or -loss.sum()
+        w.r.t. the DE-NORMALISED pose, joints 3.. doubled, the upper body zeroed; an all-zero loss gives zeros."""
+        B = x.shape[0]
+        mean, std = self._std_mean()
+        with torch.enable_grad():
+            x_t = x.detach().requires_grad_() * std + mean                                               # :523, :528
+            R = geometry.rot6d_to_rotmat(x_t.reshape(-1, 6), rot6d_mode="diffusion").view(B, 24, 3, 3)   # :529
+            bodies = self._collision_bodies(betas.detach(), R[:, [0]], R[:, 1:])                         # :532-540
+            loss = self._collision_losses(bodies, _lib.f32(scene, self.device))
+            if not bool((loss != 0).any()):                                                              # :561, :569-570
+                return torch.zeros(B, 144, device=self.device)
+            g = torch.autograd.grad([-(loss.sum() / self.fused_sampler.guide_denom(B))], [x_t])[0]       # :562
+        g = g.reshape(-1, 24, 6).clone()
+        g[:, 3:] = g[:, 3:] * 2                                                                          # :564-565
+        g[:, list(self.GUIDE_ZEROED_JOINTS)] = 0                                                         # :567
+        return g.reshape(-1, 144)
+
+    def _hit_share_model(self, output, query, inside):
+        """egohmr.py:487-514: per item, the share of ALL its scene points that are bbox-selected and `inside(query(points, item))`."""
+        p = output["pred_smpl_params"]
+        with _lib.on_device(self.device), torch.no_grad():
+            bodies = self._collision_bodies(_lib.f32(p["betas"], self.device), _lib.f32(p["global_orient"], self.device), _lib.f32(p["body_pose"], self.device))
+            scene = _lib.f32(self.scene_pcd_verts, self.device)
+            out = []
+            for i in range(bodies.vertices.shape[0]):
+                item = self._collision_item(bodies, i, clone=True)
+                pts = self._bbox_points(item, scene[[i]])
+                out.append(0.0 if pts is None else (inside(query(pts, item)).sum() / scene.shape[1]).item())
+        return out
 
     def eval_coll(self, output):
         """egohmr.py:487-514 with the build's proxy in place of `coap.query(...) > 0.5`: per item, the share of the scene points that
         lie inside the body's bounding box AND closer than tau to its surface.  One kernel sequence for the batch, one host sync
-        (`.tolist()`, the reference syncs per item); returns the reference's python list [B] of floats.  NOT a COAP number."""
+        (`.tolist()`, the reference syncs per item); returns the reference's python list [B] of floats.  NOT a COAP number - unless
+        `collision_model` is attached: then `collision_model.query(points, smpl_output) > 0.5` per item, as the reference runs it."""
+        if self.collision_model is not None:
+            return self._hit_share_model(output, self.collision_model.query, lambda occ: occ > 0.5)
         p = output["pred_smpl_params"]
         so = self.smpl(betas=p["betas"], body_pose=p["body_pose"], global_orient=p["global_orient"], pose2rot=False)
         # bbox-selected points in BOTH reference files (egohmr.py:499-505, egohmr_volsmpl.py:531-537), whatever the guidance uses
@@ -562,7 +653,10 @@ class EgoHMR(nn.Module):
     def _penetration_term(self):
         """egohmr.py:399-419 per item, with the build's collision proxy in place of `coap.collision_loss` (NOT a COAP number): the proxy over the scene
         points inside the bounding box of the item's predicted vertices; where more than 4000 points are selected the points of INDEX >= 4000 are dropped
-        (`inds[:, 4000:] = False`); no selected point -> 0.  [B], no host read-back."""
+        (`inds[:, 4000:] = False`); no selected point -> 0.  [B], no host read-back.  With `collision_model` attached the reference's loop runs as it
+        stands (_penetration_term_model: its `collision_loss`, one host read-back per item)."""
+        if self.collision_model is not None:
+            return self._penetration_term_model()
         verts, scene = _lib.f32(self.smpl_output.vertices, self.device), _lib.f32(self.scene_pcd_verts, self.device)
         B, V, N = verts.shape[0], verts.shape[1], scene.shape[1]
         if N > self.PENETRATION_POINT_CAP:
@@ -571,6 +665,20 @@ class EgoHMR(nn.Module):
             _lib.api().ehm_scene_cap_points(verts, scene, capped, count, B, V, N, self.PENETRATION_POINT_CAP, _lib.stream_ptr())
             scene = capped
         return self.fused_sampler.collision(verts, scene, want_grad=False, all_points=False)[0]
+
+    def _penetration_term_model(self):
+        """egohmr.py:393-418 through `collision_model.collision_loss`: the bodies of the last forward, bbox-selected points capped at index 4000 -> [B]."""
+        so, scene = self.smpl_output, _lib.f32(self.scene_pcd_verts, self.device)
+        B = so.vertices.shape[0]
+        aa = geometry.rotation_matrix_to_angle_axis(_lib.f32(so.full_pose, self.device).reshape(-1, 3, 3)).reshape(B, -1)               # :397
+        bodies = smpl_mod.SMPLOutput(vertices=_lib.f32(so.vertices, self.device), joints=_lib.f32(so.joints, self.device), full_pose=aa)
+        out = torch.zeros(B, device=self.device)
+        for i in range(B):
+            item = self._collision_item(bodies, i, clone=True)
+            pts = self._bbox_points(item, scene[[i]], cap=self.PENETRATION_POINT_CAP)
+            if pts is not None:
+                out[i] = _lib.f32(self.collision_model.collision_loss(pts, item, ret_collision_mask=None), self.device).reshape(())
+        return out
 
     @torch.no_grad()
     def compute_loss(self, batch, output, cur_epoch=0):
@@ -582,7 +690,8 @@ class EgoHMR(nn.Module):
         A batch WITHOUT 'keypoints_3d' is a sampling-only batch: output['losses'] = {} and a zero scalar, nothing is computed.  A batch that has
         'keypoints_3d' but lacks 'keypoints_3d_full', 'gender', 'smpl_params_is_axis_angle' or a key of 'smpl_params' raises KeyError naming it.
         Ground-truth poses are axis-angle (the EgoBody loader's; `smpl_params_is_axis_angle`, read on the host, must be all-true for 'global_orient' and
-        'body_pose', else NotImplementedError).  The penetration term uses the build's collision proxy, not COAP (_penetration_term)."""
+        'body_pose', else NotImplementedError).  The penetration term uses the build's collision proxy, not COAP - unless `collision_model` is attached: then its
+        `collision_loss` per item, as the reference runs it (_penetration_term)."""
         if "keypoints_3d" not in batch:
             output["losses"] = {}
             return torch.zeros((), device=self.device)
@@ -660,7 +769,9 @@ class EgoHMRVolsmpl(EgoHMR):
       eval_coll_volsmpl   :548-579  per item, bbox-selected points with `volume.query_fast(...) < 0` over N
       eval_coll           :519-546  the COAP metric, kept (the reference keeps COAP attached for training)
     VolumetricSMPL is a learned SDF that cannot be obtained offline: the collision term is the build's proxy (docs/EXPERIMENTS.md 3.5),
-    with `sdf < 0` read as `distance to the surface < tau`.  Numbers from it are NOT VolumetricSMPL numbers."""
+    with `sdf < 0` read as `distance to the surface < tau`.  Numbers from it are NOT VolumetricSMPL numbers - unless the user's model is attached as
+    `collision_model`: guide_coll then makes the reference's one batched `collision_loss(scene, smpl_output)` call and differentiates `-loss.sum()` through
+    the differentiable SMPL.forward, eval_coll_volsmpl reads its `query_fast` (or `query`) as a signed distance, and guided loops run step by step."""
 
     DEFAULT_COND_GRAD_WEIGHT = 30.0            # test_egohmr_volsmpl.py:62
 
@@ -669,4 +780,10 @@ class EgoHMRVolsmpl(EgoHMR):
         self.guide_reduction = "sum"
         self.guide_all_points = True
 
-    eval_coll_volsmpl = EgoHMR.eval_coll       # (the build's proxy stands in for both metrics, bbox-selected points in both)
+    def eval_coll_volsmpl(self, output):
+        """egohmr_volsmpl.py:548-579.  Without a collision model the build's proxy stands in for both metrics (bbox-selected points in both); with one,
+        its `query_fast` (or, lacking that, `query`) is read as a signed distance: `< 0` = inside."""
+        cm = self.collision_model
+        if cm is None:
+            return EgoHMR.eval_coll(self, output)
+        return self._hit_share_model(output, getattr(cm, "query_fast", cm.query), lambda sdf: sdf < 0)

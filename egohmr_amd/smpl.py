@@ -34,6 +34,49 @@ class SMPLOutput:
             setattr(self, k, v)
 
 
+def _f32_graph(t, dev):
+    """_lib.f32 without the detach: float32 on the device, still in the autograd graph."""
+    return t.to(device=dev, dtype=torch.float32)
+
+
+class _SMPLForward(torch.autograd.Function):
+    """ehm_smpl_forward with ehm_smpl_backward (csrc/guidance.hip) as its VJP: (betas [B,10], rotmats [B,24,3,3]) -> (vertices, joints).
+    First derivatives only."""
+
+    @staticmethod
+    def forward(ctx, model, betas, full):
+        betas, full = betas.detach().contiguous(), full.detach().contiguous()
+        B, dev = full.shape[0], full.device
+        verts = torch.empty(B, model.num_verts, 3, device=dev, dtype=torch.float32)
+        joints = torch.empty(B, model.num_joints_out, 3, device=dev, dtype=torch.float32)
+        with torch.cuda.device(dev):
+            _lib.api().ehm_smpl_forward(model.handle(), betas, full, verts, joints, None, B, _lib.stream_ptr())
+        ctx.model = model
+        ctx.save_for_backward(betas, full)
+        ctx.set_materialize_grads(False)            # an unused output reaches the kernel as NULL, not as a zero tensor
+        return verts, joints
+
+    @staticmethod
+    @torch.autograd.function.once_differentiable
+    def backward(ctx, gverts, gjoints):
+        betas, full = ctx.saved_tensors
+        need_betas, need_rot = ctx.needs_input_grad[1], ctx.needs_input_grad[2]
+        if (gverts is None and gjoints is None) or not (need_betas or need_rot):
+            return None, None, None
+        B, dev = full.shape[0], full.device
+        gverts = None if gverts is None else _lib.f32(gverts, dev)
+        gjoints = None if gjoints is None else _lib.f32(gjoints, dev)
+        gbetas = torch.empty_like(betas) if need_betas else None
+        grot = torch.empty_like(full) if need_rot else None
+        A, h = _lib.api(), ctx.model.handle()
+        nb = C.c_int64()
+        A.ehm_smpl_backward_workspace_bytes(h, B, C.byref(nb))
+        ws = torch.empty(nb.value, device=dev, dtype=torch.uint8)
+        with torch.cuda.device(dev):
+            A.ehm_smpl_backward(h, betas, full, gverts, gjoints, gbetas, grot, B, ws, nb.value, _lib.stream_ptr())
+        return None, gbetas, grot
+
+
 class SMPL(nn.Module):
     NUM_JOINTS = 23
     NUM_BODY_JOINTS = 23
@@ -95,11 +138,15 @@ class SMPL(nn.Module):
         if pose2rot:        # axis-angle inputs (ground-truth bodies of the driver, test_egohmr.py:307-310): Rodrigues like smplx's batch_rodrigues
             from .geometry import aa_to_rotmat
             B0 = max(body_pose.shape[0], global_orient.shape[0])
-            global_orient = aa_to_rotmat(_lib.f32(global_orient, dev).reshape(-1, 3)).reshape(B0, 1, 3, 3)
-            body_pose = aa_to_rotmat(_lib.f32(body_pose, dev).reshape(-1, 3)).reshape(B0, 23, 3, 3)
+            # (plain torch ops: with gradients enabled the axis-angle inputs stay in the graph)
+            f32 = _f32_graph if torch.is_grad_enabled() and (body_pose.requires_grad or global_orient.requires_grad) else _lib.f32
+            global_orient = aa_to_rotmat(f32(global_orient, dev).reshape(-1, 3)).reshape(B0, 1, 3, 3)
+            body_pose = aa_to_rotmat(f32(body_pose, dev).reshape(-1, 3)).reshape(B0, 23, 3, 3)
         if dev.type != "cuda":
             raise _lib.EgoHMRHipError("SMPL.forward needs the module on a HIP device (.to('cuda')); egohmr_amd has no CPU path")
         B = max(betas.shape[0], body_pose.shape[0], global_orient.shape[0])
+        if torch.is_grad_enabled() and any(isinstance(t, torch.Tensor) and t.requires_grad for t in (betas, body_pose, global_orient)):
+            return self._forward_with_grad(B, betas, body_pose, global_orient, transl, return_verts, return_full_pose)
         betas = _lib.f32(betas, dev)
         if betas.shape[0] != B:
             betas = betas.expand(B, -1).contiguous()
@@ -108,6 +155,24 @@ class SMPL(nn.Module):
         joints = torch.empty(B, self.num_joints_out, 3, device=dev, dtype=torch.float32)
         with torch.cuda.device(dev):
             _lib.api().ehm_smpl_forward(self.handle(), betas, full, verts, joints, None, B, _lib.stream_ptr())
+        if transl is not None:
+            joints = joints + transl.unsqueeze(1)
+            verts = verts + transl.unsqueeze(1)
+        return SMPLOutput(vertices=verts if return_verts else None, joints=joints, betas=betas, body_pose=body_pose,
+                          global_orient=global_orient, full_pose=full if return_full_pose else None)
+
+
+    def _forward_with_grad(self, B, betas, body_pose, global_orient, transl, return_verts, return_full_pose):
+        """The differentiable route (gradients enabled and betas, body_pose or global_orient requires grad): the same kernels behind a
+        torch.autograd.Function whose backward is ehm_smpl_backward.  `full_pose` is the tensor the graph holds, so a consumer's
+        rotation_matrix_to_angle_axis(full_pose) (egohmr.py:540) backpropagates into the same inputs; a betas row shared by B poses is
+        expanded in torch, so autograd sums its gradient; `transl` is a torch add.  No second derivatives."""
+        dev = self.v_template.device
+        betas = _f32_graph(betas, dev)
+        if betas.shape[0] != B:
+            betas = betas.expand(B, -1)
+        full = torch.cat([_f32_graph(global_orient, dev).reshape(B, 1, 3, 3), _f32_graph(body_pose, dev).reshape(B, 23, 3, 3)], dim=1)
+        verts, joints = _SMPLForward.apply(self, betas, full)
         if transl is not None:
             joints = joints + transl.unsqueeze(1)
             verts = verts + transl.unsqueeze(1)

@@ -359,6 +359,22 @@ int ehm_collision_query(const float* verts, const float* scene, float* loss, flo
 int ehm_smpl_backward_rot6d(ehm_smpl* h, const float* betas, const float* x, const float* mean, const float* std,
                             const float* gverts, float* gpose6d, int B, void* stream);
 
+/* General VJP of ehm_smpl_forward (smplx lbs.py `lbs` / SMPL.forward: blend shapes, joint regression, rigid chain, skinning, vertex-picked
+ * extra joints) - what autograd does behind `self.smpl(...)` at egohmr.py:537 when `torch.autograd.grad` is taken at :562:
+ *   gverts  [B,V,3]          cotangent of the vertices, or NULL
+ *   gjoints [B,24+n_extra,3] cotangent of the joints (posed joints, then the vertex picks), or NULL    (at least one of the two)
+ *   gbetas  [B,10]           d / d betas, or NULL
+ *   grotmats [B,24,3,3]      d / d the local rotation matrices, entry by entry (no orthogonality constraint), or NULL   (at least one of the two)
+ * betas / rotmats: the forward's inputs (the chain is recomputed).  Reproducibility: the pose-blend and shape contractions, the extra-joint
+ * scatter and the chain pass sum in a fixed order, but the skinning VJP they share with ehm_smpl_backward_rot6d accumulates the per-joint
+ * transform gradients with float atomics, and both outputs are derived from those: with more than two contributing vertices per joint,
+ * grotmats and gbetas are reproducible from call to call only up to the last bits (order of float32 additions).  Launches on `stream`
+ * out of `workspace` (16-byte aligned, at least *bytes of ehm_smpl_backward_workspace_bytes(h, B, &bytes)): no allocation, no host
+ * synchronisation.  Bad arguments are refused with EINVAL before anything is launched. */
+int ehm_smpl_backward(ehm_smpl* h, const float* betas, const float* rotmats, const float* gverts, const float* gjoints, float* gbetas,
+                      float* grotmats, int B, void* workspace, int64_t workspace_bytes, void* stream);
+int ehm_smpl_backward_workspace_bytes(const ehm_smpl* h, int B, int64_t* bytes);
+
 /* egohmr.py:561-570: g = -(1/denom) * gpose6d (denom = B for loss.mean(), 1 for loss.sum()),
  * joints 3..23 scaled by 2, joints {0,3,6,9,12..23} zeroed; all-zero loss -> zeros. */
 int ehm_guidance_grad_finish(const float* gpose6d, const float* loss, float* grad, int B, float denom, void* stream);
