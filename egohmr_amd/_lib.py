@@ -29,7 +29,7 @@ _HERE = os.path.dirname(os.path.abspath(__file__))
 LIB_PATH = os.environ.get("EHM_LIB_PATH") or os.path.join(_HERE, "libegohmr_hip.so")   # EHM_LIB_PATH: A/B a second build (experiments)
 CSRC = os.path.join(_HERE, "csrc")
 INCLUDE = os.path.join(os.path.dirname(_HERE), "include")
-SOURCES = ["gcn.hip", "gcn_tile.hip", "linear.hip", "conv.hip", "stem.hip", "metrics.hip", "smpl.hip", "sampler.hip", "guidance.hip", "prep.hip", "step.hip", "eval.hip", "stage1.hip", "scene.hip", "loss.hip"]
+SOURCES = ["gcn.hip", "gcn_tile.hip", "linear.hip", "conv.hip", "stem.hip", "metrics.hip", "smpl.hip", "sampler.hip", "guidance.hip", "prep.hip", "step.hip", "eval.hip", "stage1.hip", "scene.hip", "loss.hip", "gcn_bwd.hip"]
 
 
 class EgoHMRHipError(RuntimeError):
@@ -180,6 +180,9 @@ LOSS_KEYS = ("loss", "loss_v2v", "loss_keypoints_3d", "loss_keypoints_3d_full", 
              "loss_global_orient", "loss_pose_6d_ortho", "loss_coap_penetration", "loss_keypoints_3d_vis_batch_sum")
 
 
+GCN_CONV_INPUT, GCN_CONV_OUTPUT = -1, -2        # EHM_GCN_CONV_* of the header: how the backward entries address a conv (hidden convs: their index)
+
+
 class StepCoefs(C.Structure):
     """ehm_step_coefs"""
     _fields_ = [(n, C.c_float) for n in ("coef1", "coef2", "log_variance", "variance", "sqrt_recip_ac", "sqrt_recipm1_ac",
@@ -250,6 +253,9 @@ PROTOTYPES = {
     "ehm_gcn_stack_status": (_I, [_P, _P]),
     "ehm_gcn_stack_status_async": (_I, [_P, _P, _P]),
     "ehm_gcn_output_layer": (_I, [_P, _P, _P, _P, _I, _I, _P]),
+    "ehm_gcn_bwd_epilogue": (_I, [_P, _I, _P, _P, _P, _I, _I, _P]),
+    "ehm_gcn_bwd_params_workspace_bytes": (_I, [_P, _I, _I, C.POINTER(C.c_int64)]),
+    "ehm_gcn_bwd_params": (_I, [_P, _I, _P, _P, _P, _I, _I, _P, _P, _P, _P, _P, _P, _L, _P]),
     "ehm_linear_split": (_I, [C.POINTER(LinearDesc), _P]),
     "ehm_split_pack": (_I, [_P, _P, _L, _I, _I, _F, _P]),
     "ehm_skinny_gemm_f32": (_I, [_P, _P, _P, _P, _I, _I, _I, _I, _P]),

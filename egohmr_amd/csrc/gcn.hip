@@ -419,6 +419,10 @@ extern "C" int ehm_gcn_create(ehm_gcn** out, const float* adj, const ehm_gconv_p
   if (const char* e = getenv("EHM_F16_CHAIN")) g->chain = atoi(e);   // 0: one launch per hidden conv (debugging aid; bit-identical results)
   g->hid = hid_dim;
   g->num_hidden = num_hidden;
+  g->adj = adj;
+  g->raw_input = *input_conv;
+  for (int i = 0; i < num_hidden; ++i) g->raw_hidden[i] = hidden[i];
+  g->raw_out = *output_conv;
   const size_t epi = (size_t)2 * kJ * hid_dim + hid_dim + kJ * kJ + 768;
   size_t floats = epi * (1 + num_hidden) + (size_t)num_hidden * (5 * (size_t)hid_dim * hid_dim + 2 * kJ * hid_dim) + 2 * (size_t)kJ * hid_dim +
                   12 * (size_t)hid_dim + kJ * 6 + kJ * kJ + 8 + 64;

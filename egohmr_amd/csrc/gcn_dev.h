@@ -77,7 +77,10 @@ struct ehm_gcn {
   float* hs = nullptr;      // [hs_rows,12] responses of the output conv (gcn_out_dot_kernel -> gcn_out_mix_kernel)
   int64_t hs_rows = 0;
   int64_t reserved_rows = 0;   // rows_pad the sync words / hs scratch were sized for (ehm_gcn_reserve)
-  ehm_nonlocal_params nonlocal{};   // optional non-local block of the one-call loop (ehm_gcn_set_nonlocal); Ci == 0: none
+  ehm_nonlocal_params nonlocal{};   // optional non-local block of the one-call loop (ehm_gcn_set_nonlocal); Ci == 0: none  // the parameter arrays ehm_gcn_create was given (device pointers, owned by the caller): the backward entries (gcn_bwd.hip) read M, adj2, bias and the
+  // BatchNorm vectors unfolded
+  const float* adj = nullptr;
+  ehm_gconv_params raw_input{}, raw_hidden[16]{}, raw_out{};
 };
 
 // Activation format of the rows the input conv writes under precision `prec` (EHM_PREC_* values as formats: float32 / X2 / f16 rows).  The output

@@ -23,7 +23,7 @@ import numpy as np
 import torch
 import torch.nn as nn
 
-from . import _lib, geometry, synthetic
+from . import _lib, gcn_grad, geometry, synthetic
 from . import smpl as smpl_mod
 from .encoders import ResnetPointnet, ResNet50Features
 from .fused import PRECISIONS, FusedSampler  # noqa: F401  (PRECISIONS re-exported)
@@ -125,6 +125,7 @@ class ModulatedGCN(nn.Module):
             self.non_local = _NonLocalBlock(hid_dim)
         self._nl_packed = self._nl_key = None                       # nonlocal_packed()
         self._sa = self._sa_key = self._sa_keyfn = None             # _standalone()
+        self._cw = self._cw_key = None                              # _conv_weights()
 
     # ------------------------------------------------------------------ native handle (ehm_gcn_create) - shared with FusedSampler.gcn()
     def create_native_handle(self, device):
@@ -248,14 +249,38 @@ class ModulatedGCN(nn.Module):
             self._sa, self._sa_key = (h, *_split_pack(w2), K, Kp), key
         return self._sa
 
-    @torch.no_grad()
-    def forward(self, x):
-        """modulated_gcn.py:99-116 in eval mode on the HIP kernels: x [B, 24, in_dim] -> [B, 24, out_dim=6].
+    # ------------------------------------------------------------------ the autograd route (gcn_grad.GCNFunction; csrc/gcn_bwd.hip)
+    # False: a call under grad mode differentiates w.r.t. x only (x.requires_grad) and leaves the parameters' .grad alone; True: it also reaches W, M, adj2, bias of
+    # every conv and bn.weight / bn.bias of the input and hidden convs (eval-mode BatchNorm: frozen statistics) - those of them that require grad
+    grad_params = False
 
-        gconv_input as a split-f16 GEMM x @ [W[0] | W[1]] (ehm_conv_nhwc_split, H = W = 1) + ehm_gcn_input_layer_rows (modulation, adjacency mix, bias,
-        BatchNorm, ReLU), the residual blocks as ONE chained launch (ehm_gcn_hidden_stack), the optional non-local block, gconv_output
-        (ehm_gcn_output_layer).  EgoHMR.forward / the sampler do NOT come through here: they hoist the step-invariant slices of the input feature
-        (FusedSampler.prepare) - this is the module's own call surface for a user who feeds it a full feature tensor, as the reference allows."""
+    def _convs(self):
+        """(gconv, bn or None) of every conv in the order of the native handle: input conv, hidden convs, output conv."""
+        gi = self.gconv_input[0]
+        out = [(gi.gconv, gi.bn)]
+        for blk in self.gconv_layers:
+            out += [(blk.gconv1.gconv, blk.gconv1.bn), (blk.gconv2.gconv, blk.gconv2.bn)]
+        return out + [(self.gconv_output, None)]
+
+    def grad_parameters(self):
+        """The parameters the autograd route differentiates, in GCNFunction's order."""
+        out = []
+        for gc, bn in self._convs():
+            out += [gc.W, gc.M, gc.adj2, gc.bias] + ([bn.weight, bn.bias] if bn is not None else [])
+        return out
+
+    def _wants_grad(self, x):
+        return torch.is_grad_enabled() and (x.requires_grad or (self.grad_params and any(p.requires_grad for p in self.grad_parameters())))
+
+    def _conv_weights(self, device):
+        """gcn_grad.ConvWeights of every conv (the backward's packed GEMM operands, made on first use), rebuilt with the native handle."""
+        key = self._sa_key
+        if self._cw_key != key or self._cw is None:
+            self._cw = [gcn_grad.ConvWeights(_lib.f32(gc.W, device)) for gc, _ in self._convs()]
+            self._cw_key = key
+        return self._cw
+
+    def _check_input(self, x):
         if self.training:
             raise NotImplementedError("ModulatedGCN.forward: inference only (BatchNorm in eval mode, no dropout); training is out of scope (SURVEY.md section 2)")
         if not x.is_cuda:
@@ -264,6 +289,89 @@ class ModulatedGCN(nn.Module):
             raise ValueError(f"ModulatedGCN.forward: expected [B, 24, {self.in_dim}], got {tuple(x.shape)}")
         if self.out_dim != 6:
             raise NotImplementedError("the output-conv kernels are built for out_dim = 6 (the 6-D rotation head, egohmr.py:132)")
+
+    GRAD_F16 = "the autograd route of ModulatedGCN.forward keeps float32 activations for its backward; use precision 'f16x3' or 'f32' (ModulatedGCN.precision) with it"
+
+    @torch.no_grad()
+    def _forward_saving(self, x):
+        """forward() for GCNFunction: the same input conv, then the hidden convs ONE launch each (ehm_gcn_hidden_layer, no residual inside: the add
+        happens on the float32 copies, so that every conv's ReLU output - its gate - exists on its own), then gconv_output.  Returns
+        (out [B, 24, 6], what the backward needs: every conv's float32 input and float32 activation before the residual add)."""
+        if self.precision == "f16":
+            raise _lib.EgoHMRHipError(self.GRAD_F16)
+        if self.nonlocal_layer:
+            raise NotImplementedError("ModulatedGCN.forward: the non-local block has no backward; the autograd route needs nonlocal_layer=False")
+        A = _lib.api()
+        dev = x.device
+        B, hid, nh = x.shape[0], self.hid_dim, 2 * self.num_layers
+        with _lib.on_device(dev):
+            h, wbuf, scale, K, Kp = self._standalone(dev)
+            if A.ehm_gcn_get_precision(h) != PRECISIONS[self.precision]:
+                A.ehm_gcn_set_precision(h, PRECISIONS[self.precision])
+            s = _lib.stream_ptr()
+            rows = B * 24
+            tile = A.ehm_gcn_row_tile()
+            rows_pad = (rows + tile - 1) // tile * tile
+            split = self.precision == "f16x3"                    # activations between the convs in the X2 split format (the last hidden conv writes float32)
+
+            def to_f32(buf, is_f32):
+                if is_f32:
+                    return buf
+                out = torch.empty(rows_pad, hid, device=dev)
+                A.ehm_gcn_unpack_activations(buf, out, rows_pad, hid, 32, s)
+                return out
+
+            def to_mode(f):
+                if not split:
+                    return f
+                out = torch.zeros(rows_pad, hid, device=dev)
+                A.ehm_gcn_pack_activations_checked(h, f, out, rows, s)
+                return out
+
+            xp = torch.zeros(rows, Kp, device=dev)
+            xp[:, :K] = _lib.f32(x).reshape(rows, K)
+            pre = torch.empty(rows, 2 * hid, device=dev)
+            d = _lib.ConvDesc(_lib.ptr(xp), _lib.ptr(wbuf), None, None, _lib.ptr(pre), rows, 1, 1, Kp, 2 * hid, 1, 1, 1, 0, 0, scale)
+            A.ehm_conv_nhwc_split(C.byref(d), s)
+            cur = torch.zeros(rows_pad, hid, device=dev)
+            A.ehm_gcn_input_layer_rows(h, pre, cur, B, s)
+            cur_f = to_f32(cur, not split or nh == 0)
+            ys, acts = [cur_f], [None] * (nh + 1)
+            for l in range(0, nh, 2):
+                acts[l] = cur_f
+                y1 = torch.zeros(rows_pad, hid, device=dev)
+                A.ehm_gcn_hidden_layer(h, l, cur, None, y1, rows_pad, s)
+                y1_f = to_f32(y1, not split)
+                y2 = torch.zeros(rows_pad, hid, device=dev)
+                A.ehm_gcn_hidden_layer(h, l + 1, y1, None, y2, rows_pad, s)
+                y2_f = to_f32(y2, not split or l + 2 == nh)
+                ys += [y1_f, y2_f]
+                cur_f = y2_f + cur_f                              # modulated_gcn.py:42
+                cur = to_mode(cur_f) if l + 2 < nh else cur_f
+            acts[nh] = cur_f
+            x0 = torch.empty(B, 144, device=dev)
+            A.ehm_gcn_output_layer(h, cur_f, None, x0, B, 1, s)
+            A.ehm_gcn_stack_status(h, s)
+        return x0.view(B, 24, 6), dict(h=h, B=B, xp=xp, ys=ys, acts=acts, x_dtype=x.dtype)
+
+    def forward(self, x):
+        """modulated_gcn.py:99-116 in eval mode on the HIP kernels: x [B, 24, in_dim] -> [B, 24, out_dim=6].
+
+        With grad mode on and x.requires_grad - or `grad_params` set and a parameter that requires grad - the result carries a grad_fn: the same convs one
+        launch each with their backward in HIP (gcn_grad.GCNFunction: eval-mode BatchNorm, first derivatives, precision 'f16x3' or 'f32', no non-local
+        block).  Every other call runs the route below and returns a tensor without grad_fn."""
+        self._check_input(x)
+        if self._wants_grad(x):
+            return gcn_grad.GCNFunction.apply(self, x, *(self.grad_parameters() if self.grad_params else ()))
+        return self._forward_nograd(x)
+
+    @torch.no_grad()
+    def _forward_nograd(self, x):
+        """forward() without a backward:
+        gconv_input as a split-f16 GEMM x @ [W[0] | W[1]] (ehm_conv_nhwc_split, H = W = 1) + ehm_gcn_input_layer_rows (modulation, adjacency mix, bias,
+        BatchNorm, ReLU), the residual blocks as ONE chained launch (ehm_gcn_hidden_stack), the optional non-local block, gconv_output
+        (ehm_gcn_output_layer).  EgoHMR.forward / the sampler do NOT come through here: they hoist the step-invariant slices of the input feature
+        (FusedSampler.prepare) - this is the module's own call surface for a user who feeds it a full feature tensor, as the reference allows."""
         A = _lib.api()
         dev = x.device
         B, hid = x.shape[0], self.hid_dim

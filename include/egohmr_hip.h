@@ -201,6 +201,35 @@ int ehm_gcn_stack_status_async(ehm_gcn* h, uint32_t* host_flag, void* stream);
 int ehm_gcn_output_layer(ehm_gcn* h, const float* X, const uint8_t* vis, float* x0, int B, int passes,
                          void* stream);
 
+/* ------------------------------------------------------------------ Modulated-GCN denoiser: backward ---- */
+/* First derivatives of one graph conv in eval mode (frozen BatchNorm statistics) - modulated_gcn_conv.py:39-50, modulated_gcn.py:21-28, :38-42 -
+ * for ModulatedGCN.forward's autograd route (modulated_gcn.py:99-116).  A conv is addressed as the handle holds it: EHM_GCN_CONV_INPUT, the index of
+ * a hidden conv (0 .. num_hidden-1) or EHM_GCN_CONV_OUTPUT; N = its out_dim (hid_dim, 6 for the output conv), rows = bodies*24.
+ * With h_k = X W_k, u_k = M (.) h_k, A = sym(adj + adj2), c = bn_weight / sqrt(bn_var + eps), z[j] = A_jj u0[j] + sum_{i != j} A_ji u1[i] + bias,
+ * v = c (z - bn_mean) + bn_bias, y = relu(v) (output conv: y = z), out = y (+ residual) and g = dL/dout [rows, N]:
+ *   vbar = g (.) [y > 0]  (output conv: zbar = g),  zbar = c vbar,  h0bar[j] = M_j A_jj zbar[j],  h1bar[i] = M_i sum_{j != i} A_ji zbar[j].
+ * The gradient of the residual is g itself.  The GEMMs of the conv's backward are ehm_conv_nhwc_split calls (H = W = 1) of the caller:
+ *   Xbar = G [W0; W1]^T,   [W0bar | W1bar] = X^T G  (G^T packed with ehm_split_pack as the weight operand),   pre = X [W0 | W1] for ehm_gcn_bwd_params.
+ * The backward entries read the parameter arrays ehm_gcn_create was given (M, adj2, bias, bn_*) and adj: they must be alive and unchanged since then.
+ * No allocation, no host synchronisation, no atomics. */
+#define EHM_GCN_CONV_INPUT (-1)
+#define EHM_GCN_CONV_OUTPUT (-2)
+/* Backward of the ReLU, BatchNorm1d(eval), bias, adjacency mix and modulation (modulated_gcn.py:21-28, :42; modulated_gcn_conv.py:43-50) down to the two
+ * branch responses.  G [rows, ldg] (ldg >= 2N): columns [0, N) = h0bar, [N, 2N) = h1bar; columns past 2N are left alone.
+ * gate [rows, N] = the conv's activation y BEFORE the residual add as the forward produced it (only its sign is read); NULL for the output conv, and
+ * only for it (-22 otherwise). */
+int ehm_gcn_bwd_epilogue(const ehm_gcn* h, int conv, const float* gout, const float* gate, float* G, int ldg, int bodies, void* stream);
+/* The gradients of M, adj2, bias (modulated_gcn_conv.py:16-37, used at :43-50) and of the BatchNorm affine (modulated_gcn.py:23): the parameter
+ * gradients that are not GEMMs, summed over bodies and joints in a fixed order (two calls on the same inputs give the same bits):
+ *   gM [24,N] = sum_b (u0bar h0 + u1bar h1),  gadj2 [24,24] = (Abar + Abar^T)/2 with Abar_jj = sum zbar[j] u0[j], Abar_ji = sum zbar[j] u1[i],
+ *   gbias [N] = sum zbar,  gbn_bias [N] = sum vbar,  gbn_weight [N] = sum vbar (z - bn_mean) / sqrt(bn_var + eps)   (both NULL for the output conv).
+ * pre [rows][ld_pre] float32 (ld_pre >= 2N): columns [0, N) = X W0, [N, 2N) = X W1, the layout ehm_gcn_input_layer_rows reads.
+ * workspace: at least *bytes of ehm_gcn_bwd_params_workspace_bytes(h, conv, bodies, &bytes), 4-byte aligned. */
+int ehm_gcn_bwd_params_workspace_bytes(const ehm_gcn* h, int conv, int bodies, int64_t* bytes);
+int ehm_gcn_bwd_params(const ehm_gcn* h, int conv, const float* gout, const float* gate, const float* pre, int ld_pre, int bodies,
+                       float* gM, float* gadj2, float* gbias, float* gbn_weight, float* gbn_bias, void* workspace, int64_t workspace_bytes,
+                       void* stream);
+
 /* ------------------------------------------------------------------ scene PointNet (conditioning) ----------- */
 /* Building blocks of ResnetPointnet.forward (models/respointnet.py:33-59, ResnetBlockFC :89-97) on the split-f16
  * matrix-core path (f32-grade, see ehm_gcn_set_precision mode 1).  All activation / weight operands are in the "X2"
