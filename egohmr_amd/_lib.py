@@ -175,6 +175,18 @@ class ValLossesDesc(C.Structure):
                 [(n, C.c_void_p) for n in ("losses", "joint_vis_num", "per_item", "per_item_vis", "vis_mask")])
 
 
+class ValLossesBwdDesc(C.Structure):
+    """ehm_val_losses_bwd_desc"""
+    INPUTS = ("pred_vertices", "pred_keypoints_3d", "pred_keypoints_3d_full", "pred_keypoints_2d_full", "pred_global_orient", "pred_body_pose",
+              "pred_betas", "pred_pose_6d", "keypoints_2d", "keypoints_3d", "keypoints_3d_full", "gt_vertices_male", "gt_vertices_female",
+              "gt_joints_male", "gt_joints_female", "gender", "gt_global_orient", "gt_body_pose", "gt_betas", "focal", "center")
+    PREDICTIONS = INPUTS[:8]          # the arrays with a gradient, in the order of the g_* outputs
+    _fields_ = ([(n, C.c_int) for n in ("B", "V", "pred_joints", "gt_joints", "kp3d_points", "kp3d_full_points", "kp2d_points")] +
+                [(n, C.c_void_p) for n in INPUTS + ("gloss",)] +
+                [("weights", C.c_double * 9), ("workspace", C.c_void_p), ("workspace_bytes", C.c_int64)] +
+                [("g_" + n, C.c_void_p) for n in PREDICTIONS + ("penetration",)])
+
+
 # columns of ehm_val_losses' per_item / losses = the keys of the reference's `losses` dict in its order (egohmr.py:432-443; EHM_LOSS_* of the header)
 LOSS_KEYS = ("loss", "loss_v2v", "loss_keypoints_3d", "loss_keypoints_3d_full", "loss_keypoints_2d_full", "loss_betas", "loss_body_pose",
              "loss_global_orient", "loss_pose_6d_ortho", "loss_coap_penetration", "loss_keypoints_3d_vis_batch_sum")
@@ -291,6 +303,8 @@ PROTOTYPES = {
     "ehm_pack_outputs": (_I, [C.POINTER(PackDesc), _P]),
     "ehm_val_losses_workspace_bytes": (_I, [_I, _I, C.POINTER(C.c_int64)]),
     "ehm_val_losses": (_I, [C.POINTER(ValLossesDesc), _P]),
+    "ehm_val_losses_backward_workspace_bytes": (_I, [_I, _I, C.POINTER(C.c_int64)]),
+    "ehm_val_losses_backward": (_I, [C.POINTER(ValLossesBwdDesc), _P]),
     "ehm_scene_cap_points": (_I, [_P, _P, _P, _P, _I, _I, _I, _I, _P]),
     "ehm_profile_begin": (_I, []),
     "ehm_profile_end": (_I, [C.POINTER(C.c_double), C.POINTER(C.c_int64), _I]),

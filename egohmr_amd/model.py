@@ -23,7 +23,7 @@ import numpy as np
 import torch
 import torch.nn as nn
 
-from . import _lib, gcn_grad, geometry, synthetic
+from . import _lib, gcn_grad, geometry, loss_grad, synthetic
 from . import smpl as smpl_mod
 from .encoders import ResnetPointnet, ResNet50Features
 from .fused import PRECISIONS, FusedSampler  # noqa: F401  (PRECISIONS re-exported)
@@ -765,30 +765,35 @@ class EgoHMR(nn.Module):
         stands (_penetration_term_model: its `collision_loss`, one host read-back per item)."""
         if self.collision_model is not None:
             return self._penetration_term_model()
-        verts, scene = _lib.f32(self.smpl_output.vertices, self.device), _lib.f32(self.scene_pcd_verts, self.device)
+        return self._penetration_term_proxy(self.smpl_output.vertices)[0]
+
+    def _penetration_term_proxy(self, verts, want_grad=False):
+        """The proxy's term [B] on `verts` and, with want_grad, its derivative [B,V,3] (else None): what loss_grad.ProxyPenetration runs behind."""
+        verts, scene = _lib.f32(verts, self.device), _lib.f32(self.scene_pcd_verts, self.device)
         B, V, N = verts.shape[0], verts.shape[1], scene.shape[1]
         if N > self.PENETRATION_POINT_CAP:
             capped = torch.empty_like(scene)
             count = torch.empty(B, device=self.device, dtype=torch.int32)
             _lib.api().ehm_scene_cap_points(verts, scene, capped, count, B, V, N, self.PENETRATION_POINT_CAP, _lib.stream_ptr())
             scene = capped
-        return self.fused_sampler.collision(verts, scene, want_grad=False, all_points=False)[0]
+        return self.fused_sampler.collision(verts, scene, want_grad=want_grad, all_points=False)[:2]
 
     def _penetration_term_model(self):
-        """egohmr.py:393-418 through `collision_model.collision_loss`: the bodies of the last forward, bbox-selected points capped at index 4000 -> [B]."""
+        """egohmr.py:393-418 through `collision_model.collision_loss`: the bodies of the last forward, bbox-selected points capped at index 4000 -> [B].
+        With gradients enabled (compute_loss's autograd route) the bodies and the model's losses stay in the graph."""
+        f32 = loss_grad.f32_graph if torch.is_grad_enabled() else _lib.f32
         so, scene = self.smpl_output, _lib.f32(self.scene_pcd_verts, self.device)
         B = so.vertices.shape[0]
-        aa = geometry.rotation_matrix_to_angle_axis(_lib.f32(so.full_pose, self.device).reshape(-1, 3, 3)).reshape(B, -1)               # :397
-        bodies = smpl_mod.SMPLOutput(vertices=_lib.f32(so.vertices, self.device), joints=_lib.f32(so.joints, self.device), full_pose=aa)
+        aa = geometry.rotation_matrix_to_angle_axis(f32(so.full_pose, self.device).reshape(-1, 3, 3)).reshape(B, -1)               # :397
+        bodies = smpl_mod.SMPLOutput(vertices=f32(so.vertices, self.device), joints=f32(so.joints, self.device), full_pose=aa)
         out = torch.zeros(B, device=self.device)
         for i in range(B):
             item = self._collision_item(bodies, i, clone=True)
             pts = self._bbox_points(item, scene[[i]], cap=self.PENETRATION_POINT_CAP)
             if pts is not None:
-                out[i] = _lib.f32(self.collision_model.collision_loss(pts, item, ret_collision_mask=None), self.device).reshape(())
+                out[i] = f32(self.collision_model.collision_loss(pts, item, ret_collision_mask=None), self.device).reshape(())
         return out
 
-    @torch.no_grad()
     def compute_loss(self, batch, output, cur_epoch=0):
         """egohmr.py:307-449 in the evaluation branch, on the device (csrc/loss.hip: ehm_val_losses), for the output of `model(batch, t)` or of a sampling
         loop (`diffusion.val_losses`).  Fills output['losses'] with the reference's eleven keys in its order (0-d float32 device tensors),
@@ -799,7 +804,14 @@ class EgoHMR(nn.Module):
         'keypoints_3d' but lacks 'keypoints_3d_full', 'gender', 'smpl_params_is_axis_angle' or a key of 'smpl_params' raises KeyError naming it.
         Ground-truth poses are axis-angle (the EgoBody loader's; `smpl_params_is_axis_angle`, read on the host, must be all-true for 'global_orient' and
         'body_pose', else NotImplementedError).  The penetration term uses the build's collision proxy, not COAP - unless `collision_model` is attached: then its
-        `collision_loss` per item, as the reference runs it (_penetration_term)."""
+        `collision_loss` per item, as the reference runs it (_penetration_term).
+
+        The autograd route: with gradients enabled and a prediction of `output` that requires grad (pred_vertices, pred_keypoints_3d, pred_keypoints_3d_full,
+        pred_keypoints_2d_full, pred_pose_6d, an entry of pred_smpl_params or, with the penetration term active, self.smpl_output.vertices) the returned
+        `loss` carries a grad_fn (loss_grad.ValLossesFunction: ehm_val_losses_backward is its VJP; first derivatives only) and has the same bits (the
+        proxy's penetration term is a float-atomic sum on either route: it repeats to the last bits only);
+        everything stored in `output` is detached, as the reference detaches it (:432-443).  `decode_output` builds such an output from a pred_x_start.
+        self.training is not consulted.  Every other call runs without a graph, as before."""
         if "keypoints_3d" not in batch:
             output["losses"] = {}
             return torch.zeros((), device=self.device)
@@ -819,40 +831,69 @@ class EgoHMR(nn.Module):
             if not bool(np.asarray(f).all()):
                 raise NotImplementedError(f"smpl_params_is_axis_angle[{k!r}] is not all-true: compute_loss takes axis-angle ground-truth poses "
                                           "(the EgoBody loader's; egohmr.py:380-381 decodes a mixed batch inconsistently)")
+        with_pen = self.weight_coap_penetration > 0 and cur_epoch >= self.start_coap_epoch                                        # :392
         with _lib.on_device(self.device):
-            pen = None
-            if self.weight_coap_penetration > 0 and cur_epoch >= self.start_coap_epoch:                                         # :392
-                pen = self._penetration_term()
-            res = val_losses_native(self.loss_inputs(batch, output), self.loss_weights(), pen)
+            if self._loss_wants_grad(output, with_pen):
+                loss, res = self._val_losses_graph(batch, output, with_pen)
+            else:
+                with torch.no_grad():
+                    res = val_losses_native(self.loss_inputs(batch, output), self.loss_weights(), self._penetration_term() if with_pen else None)
+                loss = None
         K = _lib.LOSS_KEYS
         output["losses"] = {k: res["losses"][i] for i, k in enumerate(K)}                                                         # :432-443
         output["joint_vis_num_batch"] = res["joint_vis_num"][0]                                                                 # :447
         output["losses_per_item"] = {**{k: res["per_item"][:, i] for i, k in enumerate(K)}, "joint_vis_num": res["per_item_vis"],
                                      "joint_vis_mask": res["vis_mask"].bool()}
-        return output["losses"]["loss"]
+        return output["losses"]["loss"] if loss is None else loss
 
-    def loss_inputs(self, batch, output) -> dict:
+    def _loss_wants_grad(self, output, with_pen) -> bool:
+        """compute_loss's route: True = gradients are enabled and one of the predictions the total depends on requires grad."""
+        if not torch.is_grad_enabled():
+            return False
+        ts = [output.get(k) for k in ("pred_vertices", "pred_keypoints_3d", "pred_keypoints_3d_full", "pred_keypoints_2d_full", "pred_pose_6d")]
+        ts += list(output.get("pred_smpl_params", {}).values())
+        if with_pen:
+            ts.append(getattr(getattr(self, "smpl_output", None), "vertices", None))
+        return any(isinstance(t, torch.Tensor) and t.requires_grad for t in ts)
+
+    def _val_losses_graph(self, batch, output, with_pen):
+        """The autograd route of compute_loss -> (total with a grad_fn, the detached results as val_losses_native names them)."""
+        pen = None
+        if with_pen:                                                                                                                    # :390-419
+            if self.collision_model is not None:
+                pen = loss_grad.f32_graph(self._penetration_term_model(), self.device)
+            else:
+                pen = loss_grad.ProxyPenetration.apply(self, loss_grad.f32_graph(self.smpl_output.vertices, self.device))
+        t = self.loss_inputs(batch, output, graph=True)
+        preds = [t.pop(k) for k in loss_grad.PREDICTIONS]
+        loss, *rest = loss_grad.ValLossesFunction.apply(t, self.loss_weights(), pen, *preds)
+        return loss, dict(zip(("losses", "joint_vis_num", "per_item", "per_item_vis", "vis_mask"), rest))
+
+    def loss_inputs(self, batch, output, graph=False) -> dict:
         """The device arrays ehm_val_losses reads for an annotated batch and a model output, named like the descriptor's fields: the prediction as the
         output dict holds it, the male AND female ground-truth bodies (egohmr.py:344-349: axis-angle input, `transl` applied), the ground-truth rotations
-        through aa_to_rotmat (:380-381), focal length and camera centre of the last forward (:283-285)."""
-        dev, f32 = self.device, _lib.f32
+        through aa_to_rotmat (:380-381), focal length and camera centre of the last forward (:283-285).  graph: the eight prediction arrays are converted
+        without detaching (compute_loss's autograd route); the ground truth never carries a graph."""
+        dev, g32 = self.device, _lib.f32
+        f32 = loss_grad.f32_graph if graph else g32
         pp, sp = output["pred_smpl_params"], batch["smpl_params"]
         pv = f32(output["pred_vertices"], dev)
         B = pv.shape[0]
-        gt = {k: f32(v, dev) for k, v in sp.items()}                                   # :344, :347 (`v.float()`)
-        male, female = self.smpl_male(**gt), self.smpl_female(**gt)
-        rot = {k: geometry.aa_to_rotmat(gt[k].reshape(-1, 3)).reshape(B, -1).contiguous() for k in ("global_orient", "body_pose")}
+        with torch.no_grad():
+            gt = {k: g32(v, dev) for k, v in sp.items()}                                   # :344, :347 (`v.float()`)
+            male, female = self.smpl_male(**gt), self.smpl_female(**gt)
+            rot = {k: geometry.aa_to_rotmat(gt[k].reshape(-1, 3)).reshape(B, -1).contiguous() for k in ("global_orient", "body_pose")}
 
         def aligned(t):                        # the vertex kernel loads 16 bytes at a time (a slice of a stacked [S,B,V,3] result may start anywhere)
             return t if t.data_ptr() % 16 == 0 else t.clone()
         t = dict(pred_vertices=aligned(pv), pred_keypoints_3d=f32(output["pred_keypoints_3d"], dev), pred_keypoints_3d_full=f32(output["pred_keypoints_3d_full"], dev),
                  pred_keypoints_2d_full=f32(output["pred_keypoints_2d_full"], dev), pred_global_orient=f32(pp["global_orient"], dev),
                  pred_body_pose=f32(pp["body_pose"], dev), pred_betas=f32(pp["betas"], dev), pred_pose_6d=f32(output["pred_pose_6d"], dev),
-                 keypoints_2d=f32(batch["orig_keypoints_2d"], dev), keypoints_3d=f32(batch["keypoints_3d"], dev),
-                 keypoints_3d_full=f32(batch["keypoints_3d_full"], dev), gt_vertices_male=aligned(male.vertices.contiguous()),
+                 keypoints_2d=g32(batch["orig_keypoints_2d"], dev), keypoints_3d=g32(batch["keypoints_3d"], dev),
+                 keypoints_3d_full=g32(batch["keypoints_3d_full"], dev), gt_vertices_male=aligned(male.vertices.contiguous()),
                  gt_vertices_female=aligned(female.vertices.contiguous()), gt_joints_male=male.joints.contiguous(), gt_joints_female=female.joints.contiguous(),
                  gender=torch.as_tensor(batch["gender"]).to(dev).long().reshape(-1).contiguous(), gt_global_orient=rot["global_orient"], gt_body_pose=rot["body_pose"],
-                 gt_betas=gt["betas"], focal=f32(self.focal_length, dev), center=f32(self.camera_center_full, dev))
+                 gt_betas=gt["betas"], focal=g32(self.focal_length, dev), center=g32(self.camera_center_full, dev))
         if (t["gender"].numel() != B or t["pred_pose_6d"].numel() != B * 144 or t["gt_vertices_male"].shape != t["pred_vertices"].shape
                 or any(t[k].shape[0] != B for k in t) or t["pred_keypoints_2d_full"].shape[1] != t["pred_keypoints_3d"].shape[1]
                 or t["pred_keypoints_3d_full"].shape[1] != t["pred_keypoints_3d"].shape[1]):
@@ -865,8 +906,44 @@ class EgoHMR(nn.Module):
                                    self.weight_loss_betas, self.weight_loss_body_pose, self.weight_loss_global_orient, self.weight_loss_pose_6d_ortho,
                                    self.weight_coap_penetration)]
 
+    def decode_output(self, batch, pred_x_start, betas=None):
+        """egohmr.py:256-303 as an autograd graph: a pred_x_start [B,144] (and optionally betas [B,10]; default: the prepared batch's, a constant) -> the
+        output dict of `forward` - the same keys as _pack_output - through torch ops and the differentiable geometry.rot6d_to_rotmat, SMPL.forward and
+        geometry.perspective_projection, so that `compute_loss(batch, decode_output(batch, x0))` backpropagates into x0 (and betas).  Sets smpl_output,
+        scene_pcd_verts, input_transl, focal_length and camera_center_full like `forward`.  It does NOT apply the NaN rule of ehm_pack_outputs (an item
+        with a non-finite input is not blanked: values propagate as torch computes them)."""
+        dev = self.device
+        with _lib.on_device(dev):
+            st = self.fused_sampler.prepare(batch)
+            x0 = loss_grad.f32_graph(pred_x_start, dev).reshape(-1, 144)
+            B = x0.shape[0]
+            mean, std = self._std_mean()
+            pose6d = x0 * std + mean                                                                        # :258
+            R = geometry.rot6d_to_rotmat(pose6d.reshape(-1, 6), rot6d_mode="diffusion").view(B, 24, 3, 3)   # :260
+            betas = st.betas if betas is None else loss_grad.f32_graph(betas, dev)
+            params = {"global_orient": R[:, [0]], "body_pose": R[:, 1:], "betas": betas}                   # :268-270
+            so = self.smpl(**params, return_full_pose=True, pose2rot=False)                                 # :276
+            focal = (st.fx.reshape(B, 1) * self.cfg.CAM.FX_NORM_COEFF).repeat(1, 2)                          # :283-285
+            center = torch.stack([st.cam_cx.reshape(B), st.cam_cy.reshape(B)], dim=-1)                     # :286
+            kp2d = geometry.perspective_projection(so.joints, translation=st.transl, camera_center=center, focal_length=focal)   # :295-298
+            kp2d = torch.stack([kp2d[:, :, 0] / 1920 - 0.5, kp2d[:, :, 1] / 1080 - 0.5], dim=-1)           # :299-300
+        self.scene_pcd_verts, self.input_transl = st.scene, st.transl
+        self.smpl_output = smpl_mod.SMPLOutput(vertices=so.vertices, joints=so.joints, full_pose=so.full_pose)
+        self.focal_length, self.camera_center_full = focal, center
+        return {
+            "pred_x_start": x0,
+            "pred_smpl_params": {k: v.clone() for k, v in params.items()},                                 # :273
+            "pred_pose_6d": pose6d,
+            "pred_keypoints_3d": so.joints,
+            "pred_vertices": so.vertices,
+            "pred_keypoints_3d_full": so.joints + st.transl.unsqueeze(1),                                  # :294
+            "pred_keypoints_2d_full": kp2d,
+        }
+
     def training_step(self, *a, **k):
-        raise NotImplementedError("training is outside the sampling hot path this package implements")
+        raise NotImplementedError("training_step is not built: compute_loss has a backward (the loss, SMPL.forward, rot6d_to_rotmat and ModulatedGCN.forward "
+                                  "are differentiable; decode_output chains them), but train-mode BatchNorm, the conditioning encoders' backward and the "
+                                  "non-local block's backward are missing")
 
 
 class EgoHMRVolsmpl(EgoHMR):

@@ -628,6 +628,41 @@ typedef struct ehm_val_losses_desc {
 int ehm_val_losses_workspace_bytes(int B, int V, int64_t* bytes);
 int ehm_val_losses(const ehm_val_losses_desc* d, void* stream);
 
+/* The VJP of losses[EHM_LOSS_TOTAL] of ehm_val_losses with respect to the eight prediction arrays and the penetration term.  The input fields are those of
+ * ehm_val_losses_desc (focal / center are kept for symmetry and never read; they may be NULL); gloss: device scalar, the cotangent of the total, NULL = 1 -
+ * read on the device only.  Every g_* output may be NULL: it is then not computed (the vertex pass runs only for g_pred_vertices or g_pred_keypoints_3d).
+ * A requested array is written in full - joints 24.. and the 2-D joints outside smpl_to_openpose get 0 - so the caller clears nothing.
+ * With s_k = gloss weights[k] / B:
+ *   V2V             d = (pv - pj0_c) - (gv - gj0_c) in float64 as the forward forms it; g_pv = s_0 / (3 V) sign(d); pelvis joint c: -s_0 / (3 V) sum_v sign(d)
+ *   KP3D            joints 0..23, d as in the forward: +s_1 sign(d) to joint j, -s_1 sum_j sign(d) to joint 0
+ *   KP3D_FULL       s_2 sign(pf - gf) on joints 0..23
+ *   KP2D_FULL       at prediction joint smpl_to_openpose[j]: s_3 conf_j sign(p - g) per coordinate (conf of joints 1, 9, 12 is 0)
+ *   BETAS / BODY_POSE / GLOBAL_ORIENT   2 s_k (pred - gt)
+ *   POSE_6D_ORTHO   s_7 times the derivative of (m00^2 + m11^2 + 2 m01^2) / 96 per joint
+ *   PENETRATION     g_penetration[b] = s_8;   KP3D_VIS_SUM is not part of the total: no gradient
+ * sign(0) = 0 and sign(NaN) = NaN (torch.sign).  Everything that lands on one element - the pelvis joint's three sources included - is added in float64 in a
+ * fixed order and rounded to float32 once; the vertex signs are summed as integers per block (workspace), no float atomics: two calls give the same bits.
+ * pred_vertices, gt_vertices_* and g_pred_vertices must be 16-byte aligned.  workspace: *bytes of ehm_val_losses_backward_workspace_bytes, 4-byte aligned. */
+typedef struct ehm_val_losses_bwd_desc {
+  int B, V, pred_joints, gt_joints, kp3d_points, kp3d_full_points, kp2d_points;
+  const float *pred_vertices, *pred_keypoints_3d, *pred_keypoints_3d_full, *pred_keypoints_2d_full;
+  const float *pred_global_orient, *pred_body_pose, *pred_betas, *pred_pose_6d;
+  const float *keypoints_2d, *keypoints_3d, *keypoints_3d_full;
+  const float *gt_vertices_male, *gt_vertices_female, *gt_joints_male, *gt_joints_female;
+  const int64_t* gender;
+  const float *gt_global_orient, *gt_body_pose, *gt_betas;
+  const float *focal, *center;
+  const float* gloss;     /* [1] on the device, or NULL = 1 */
+  double weights[9];
+  void* workspace;
+  int64_t workspace_bytes;
+  float *g_pred_vertices, *g_pred_keypoints_3d, *g_pred_keypoints_3d_full, *g_pred_keypoints_2d_full; /* [B,V,3], [B,pred_joints,3] x 2, [B,pred_joints,2] */
+  float *g_pred_global_orient, *g_pred_body_pose, *g_pred_betas, *g_pred_pose_6d;                      /* [B,9], [B,207], [B,10], [B,144] */
+  float* g_penetration;                                                                               /* [B] */
+} ehm_val_losses_bwd_desc;
+int ehm_val_losses_backward_workspace_bytes(int B, int V, int64_t* bytes);
+int ehm_val_losses_backward(const ehm_val_losses_bwd_desc* d, void* stream);
+
 /* The point cap of the penetration term (egohmr.py:406-412): count [B] int32 = scene points of item b inside the bounding box of verts[b] (both ends
  * inclusive); scene_out [B,N,3] = scene, except that in an item with count > cap the points of index >= cap are moved out of every box (3e38) - the
  * reference's `inds[:, 4000:] = False`, not "the first 4000 selected".  ehm_collision_query on scene_out then gives the capped term. */
