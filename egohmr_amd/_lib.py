@@ -29,7 +29,7 @@ _HERE = os.path.dirname(os.path.abspath(__file__))
 LIB_PATH = os.environ.get("EHM_LIB_PATH") or os.path.join(_HERE, "libegohmr_hip.so")   # EHM_LIB_PATH: A/B a second build (experiments)
 CSRC = os.path.join(_HERE, "csrc")
 INCLUDE = os.path.join(os.path.dirname(_HERE), "include")
-SOURCES = ["gcn.hip", "gcn_tile.hip", "linear.hip", "conv.hip", "stem.hip", "metrics.hip", "smpl.hip", "sampler.hip", "guidance.hip", "prep.hip", "step.hip", "eval.hip", "stage1.hip", "scene.hip", "loss.hip", "gcn_bwd.hip"]
+SOURCES = ["gcn.hip", "gcn_tile.hip", "linear.hip", "conv.hip", "stem.hip", "metrics.hip", "smpl.hip", "sampler.hip", "guidance.hip", "prep.hip", "step.hip", "eval.hip", "stage1.hip", "scene.hip", "loss.hip", "gcn_bwd.hip", "gcn_train.hip"]
 
 
 class EgoHMRHipError(RuntimeError):
@@ -268,6 +268,15 @@ PROTOTYPES = {
     "ehm_gcn_bwd_epilogue": (_I, [_P, _I, _P, _P, _P, _I, _I, _P]),
     "ehm_gcn_bwd_params_workspace_bytes": (_I, [_P, _I, _I, C.POINTER(C.c_int64)]),
     "ehm_gcn_bwd_params": (_I, [_P, _I, _P, _P, _P, _I, _I, _P, _P, _P, _P, _P, _P, _L, _P]),
+    "ehm_gcn_train_workspace_bytes": (_I, [_P, _I, _I, C.POINTER(C.c_int64)]),
+    "ehm_gcn_train_adjacency": (_I, [_P, _I, _P, _P]),
+    "ehm_gcn_train_preact": (_I, [_P, _I, _P, _I, _I, _P, _P, _P, _L, _P]),
+    "ehm_gcn_train_stats": (_I, [_P, _I, _P, _I, _I, C.c_double, C.c_double, _P, _P, _P, _P, _P, _L, _P]),
+    "ehm_gcn_train_normalize": (_I, [_P, _I, _P, _P, _P, _P, _P, _P, _I, _P]),
+    "ehm_gcn_train_bn_backward": (_I, [_P, _I, _P, _P, _P, _P, _P, _I, _P, _P, _P, _P, _L, _P]),
+    "ehm_gcn_train_bwd_epilogue": (_I, [_P, _I, _P, _P, _P, _I, _I, _P]),
+    "ehm_gcn_train_bwd_params_workspace_bytes": (_I, [_P, _I, _I, C.POINTER(C.c_int64)]),
+    "ehm_gcn_train_bwd_params": (_I, [_P, _I, _P, _P, _P, _I, _I, _P, _P, _P, _L, _P]),
     "ehm_linear_split": (_I, [C.POINTER(LinearDesc), _P]),
     "ehm_split_pack": (_I, [_P, _P, _L, _I, _I, _F, _P]),
     "ehm_skinny_gemm_f32": (_I, [_P, _P, _P, _P, _I, _I, _I, _I, _P]),

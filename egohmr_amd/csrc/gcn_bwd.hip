@@ -326,3 +326,78 @@ extern "C" int ehm_gcn_bwd_params(const ehm_gcn* h, int conv, const float* gout,
   EHM_LAUNCH_CHECK();
   return 0;
 }
+
+// ---------------------------------------------------------------------------------------------- train-mode BatchNorm (gcn_train.hip)
+// Behind ehm_gcn_train_bn_backward a BatchNorm'd conv's backward is the output conv's algebra on its own M and N: zbar = the cotangent, no gate, T0 = T1 = M,
+// the full symmetrised adjacency A of ehm_gcn_train_adjacency.  The OUT instantiations above run unchanged (the parameter kernel's bias / BatchNorm sums
+// come out unused: the bias gradient is zero on this route and the BatchNorm ones are ehm_gcn_train_bn_backward's).
+namespace {
+
+int train_conv_of(const ehm_gcn* h, int conv, const float* A, BwdConv* c) {
+  EHM_CHECK_ARG(h && (conv == EHM_GCN_CONV_INPUT || (conv >= 0 && conv < h->num_hidden)));
+  c->raw = conv == EHM_GCN_CONV_INPUT ? h->raw_input : h->raw_hidden[conv];
+  c->adj = h->adj;
+  c->T0 = c->T1 = c->raw.M;
+  c->A = A;
+  c->N = c->raw.out_dim; c->bn = 0; c->out = 1;
+  EHM_CHECK_ARG(c->adj && c->raw.M && c->raw.adj2 && c->N > 0);
+  return 0;
+}
+
+// workspace of ehm_gcn_train_bwd_params: the unused bias sums [N] | ehm_gcn_bwd_params' partial sums
+int64_t train_param_floats(int N, int bodies) { return N + param_floats(N, bodies); }
+
+}  // namespace
+
+extern "C" int ehm_gcn_train_bwd_epilogue(const ehm_gcn* h, int conv, const float* zbar, const float* A, float* G, int ldg, int bodies, void* stream) {
+  BwdConv c;
+  const int rc = train_conv_of(h, conv, A, &c);
+  if (rc != 0) return rc;
+  EHM_CHECK_ARG(zbar && G && A && bodies > 0 && ldg >= 2 * c.N && (const void*)zbar != (const void*)G);
+  const long long total = (long long)bodies * c.N;
+  EHM_CHECK_ARG(ceil_div(total, 256) < (1ll << 31));
+  hipLaunchKernelGGL(gcn_bwd_epilogue_kernel<true>, dim3((unsigned)ceil_div(total, 256)), dim3(256), 0, (hipStream_t)stream, zbar, (const float*)nullptr,
+                     c.T0, c.T1, c.A, G, c.N, ldg, total);
+  EHM_LAUNCH_CHECK();
+  return 0;
+}
+
+extern "C" int ehm_gcn_train_bwd_params_workspace_bytes(const ehm_gcn* h, int conv, int bodies, int64_t* bytes) {
+  BwdConv c;
+  const int rc = train_conv_of(h, conv, nullptr, &c);
+  if (rc != 0) return rc;
+  EHM_CHECK_ARG(bytes && bodies > 0);
+  *bytes = train_param_floats(c.N, bodies) * (int64_t)sizeof(float);
+  return 0;
+}
+
+extern "C" int ehm_gcn_train_bwd_params(const ehm_gcn* h, int conv, const float* zbar, const float* A, const float* pre, int ld_pre, int bodies, float* gM,
+                                        float* gadj2, void* workspace, int64_t workspace_bytes, void* stream) {
+  BwdConv c;
+  const int rc = train_conv_of(h, conv, A, &c);
+  if (rc != 0) return rc;
+  EHM_CHECK_ARG(zbar && A && pre && bodies > 0 && ld_pre >= 2 * c.N && gM && gadj2 && workspace);
+  EHM_CHECK_ARG(workspace_bytes >= train_param_floats(c.N, bodies) * (int64_t)sizeof(float) && (uintptr_t)workspace % 4 == 0);
+  float* w = (float*)workspace;
+  float* gbias = w;  w += c.N;       // sum zbar: zero up to rounding (the batch mean removes the bias), not handed out
+  ParamArgs a;
+  a.gout = zbar; a.gate = nullptr; a.pre = pre;
+  a.c = c;
+  a.ld_pre = ld_pre; a.bodies = bodies;
+  a.groups = param_groups(bodies);
+  a.chunks = (int)ceil_div(c.N, NT);
+  a.Mpart = w;  w += (size_t)a.groups * kJ * c.N;
+  a.bpart = w;  w += (size_t)a.groups * c.N;
+  a.gpart = w;  w += (size_t)a.groups * c.N;
+  a.Apart = w;
+  hipLaunchKernelGGL(gcn_bwd_params_kernel, dim3((unsigned)(a.groups * a.chunks)), dim3(NT), 0, (hipStream_t)stream, a);
+  FinishArgs f;
+  f.Mpart = a.Mpart; f.bpart = a.bpart; f.gpart = a.gpart; f.Apart = a.Apart;
+  f.raw = c.raw;
+  f.N = c.N; f.bn = 0; f.groups = a.groups; f.chunks = a.chunks;
+  f.gM = gM; f.gadj2 = gadj2; f.gbias = gbias; f.gbn_weight = nullptr; f.gbn_bias = nullptr;
+  const int items = kJ * c.N > kJ * kJ ? kJ * c.N : kJ * kJ;
+  hipLaunchKernelGGL(gcn_bwd_params_finish, dim3((unsigned)ceil_div(items, 256)), dim3(256), 0, (hipStream_t)stream, f);
+  EHM_LAUNCH_CHECK();
+  return 0;
+}

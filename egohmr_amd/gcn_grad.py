@@ -83,6 +83,36 @@ class ConvWeights:
         return self._bwd
 
 
+def _new_G(rows, cw, dev):
+    return torch.empty(rows, cw.ldg, device=dev) if cw.ldg == 2 * cw.N else torch.zeros(rows, cw.ldg, device=dev)
+
+
+def _gemm_grads(G, cw, X, rows, need_x, need_w, out, res):
+    """The two GEMMs behind a backward epilogue's G = [h0bar | h1bar]: res['x'] = G [W0; W1]^T (need_x), res['W'] = X^T G (need_w)."""
+    A, s, N, K, dev = _lib.api(), _lib.stream_ptr(), cw.N, cw.K, G.device
+    sc = pow2_scale(G)
+    G.mul_(sc)
+    inv = 1.0 / sc
+    if need_x:
+        xb = gemm_rows(G, cw.bwd).mul_(inv)        # [rows, K rounded up to the engine's 8-column granule]
+        res["x"] = xb if xb.shape[1] == K else xb[:, :K].contiguous()
+    if need_w:
+        rp = _up(rows, 32)                         # the contraction runs over the rows: padded to the engine's K granule with zeros
+        alloc = lambda r: torch.empty(r, rp, device=dev) if rp == rows else torch.zeros(r, rp, device=dev)
+        Xt = alloc(X.shape[1])
+        Xt[:, :rows] = X[:rows].t()
+        Gt = alloc(2 * N) if 2 * N % 128 == 0 else torch.zeros(_up(2 * N, 128), rp, device=dev)
+        Gt[:2 * N, :rows] = G[:, :2 * N].t()
+        Gp = torch.empty_like(Gt)
+        A.ehm_split_pack(Gt, Gp, Gt.shape[0], rp, rp, 1.0, s)
+        Wg = gemm_rows(Xt, (Gp, 1.0, _up(2 * N, 8)))[:K, :2 * N].mul_(inv)          # [K, 2N]
+        gW = out.get("W")
+        if gW is None:
+            gW = torch.empty(2, K, N, device=dev)
+        gW.copy_(Wg.reshape(K, 2, N).permute(1, 0, 2))
+        res["W"] = gW
+
+
 def conv_backward(h, conv, cw, X, gate, gout, bodies, need_x=True, need_w=False, need_params=False, has_bn=True, out=None):
     """VJP of the handle's conv `conv` (INPUT, a hidden conv's index, OUTPUT).
 
@@ -95,29 +125,9 @@ def conv_backward(h, conv, cw, X, gate, gout, bodies, need_x=True, need_w=False,
     out = {} if out is None else out
     res = {}
     if need_x or need_w:
-        G = torch.empty(rows, cw.ldg, device=dev) if cw.ldg == 2 * N else torch.zeros(rows, cw.ldg, device=dev)
+        G = _new_G(rows, cw, dev)
         A.ehm_gcn_bwd_epilogue(h, conv, gout, gate, G, cw.ldg, bodies, s)
-        sc = pow2_scale(G)
-        G.mul_(sc)
-        inv = 1.0 / sc
-        if need_x:
-            xb = gemm_rows(G, cw.bwd).mul_(inv)        # [rows, K rounded up to the engine's 8-column granule]
-            res["x"] = xb if xb.shape[1] == K else xb[:, :K].contiguous()
-        if need_w:
-            rp = _up(rows, 32)                         # the contraction runs over the rows: padded to the engine's K granule with zeros
-            alloc = lambda r: torch.empty(r, rp, device=dev) if rp == rows else torch.zeros(r, rp, device=dev)
-            Xt = alloc(X.shape[1])
-            Xt[:, :rows] = X[:rows].t()
-            Gt = alloc(2 * N) if 2 * N % 128 == 0 else torch.zeros(_up(2 * N, 128), rp, device=dev)
-            Gt[:2 * N, :rows] = G[:, :2 * N].t()
-            Gp = torch.empty_like(Gt)
-            A.ehm_split_pack(Gt, Gp, Gt.shape[0], rp, rp, 1.0, s)
-            Wg = gemm_rows(Xt, (Gp, 1.0, _up(2 * N, 8)))[:K, :2 * N].mul_(inv)          # [K, 2N]
-            gW = out.get("W")
-            if gW is None:
-                gW = torch.empty(2, K, N, device=dev)
-            gW.copy_(Wg.reshape(K, 2, N).permute(1, 0, 2))
-            res["W"] = gW
+        _gemm_grads(G, cw, X, rows, need_x, need_w, out, res)
     if need_params:
         pre = gemm_rows(X, cw.fwd, rows)
         nb = C.c_int64(0)
@@ -192,4 +202,115 @@ class GCNFunction(torch.autograd.Function):
                 put(0, r, True)
                 if need_x:
                     gx = r["x"].reshape(B, 24, m.in_dim).to(sv["x_dtype"])
+        return (None, gx, *grads)
+
+
+# ---------------------------------------------------------------------------------------------- train-mode BatchNorm (csrc/gcn_train.hip)
+def _train_ws(h, conv, bodies, dev):
+    nb = C.c_int64(0)
+    _lib.api().ehm_gcn_train_workspace_bytes(h, conv, bodies, C.byref(nb))
+    return torch.empty(nb.value // 8, device=dev, dtype=torch.float64), nb.value
+
+
+def train_conv_forward(h, conv, cw, X, bodies, eps, momentum, running=None, res=None, y=None, out=None):
+    """One BatchNorm'd conv (INPUT or a hidden conv's index) with batch statistics: X [>= rows, Kp] float32 (K padded to a multiple of 32 with zeros).
+
+    running: (running_mean, running_var) float32 [N] on the device, updated in place, or None; res [rows, N] or None; y / out: float32 buffers of at
+    least rows x N for relu(bn(z)) and for y + res (None: not written; with res, out is required).  Returns dict(z, mean, invstd): what the
+    backward needs besides X and y (A: the conv's symmetrised adjacency, built once here)."""
+    A, s, dev = _lib.api(), _lib.stream_ptr(), X.device
+    rows, N = bodies * 24, cw.N
+    pre = gemm_rows(X, cw.fwd, rows)
+    ws, nb = _train_ws(h, conv, bodies, dev)
+    z, mean, invstd = torch.empty(rows, N, device=dev), torch.empty(N, device=dev), torch.empty(N, device=dev)
+    adjm = torch.empty(24, 24, device=dev)
+    A.ehm_gcn_train_adjacency(h, conv, adjm, s)
+    A.ehm_gcn_train_preact(h, conv, pre, pre.shape[1], bodies, adjm, z, ws, nb, s)
+    rm, rv = running if running is not None else (None, None)
+    A.ehm_gcn_train_stats(h, conv, z, bodies, 1, float(eps), float(momentum), mean, invstd, rm, rv, ws, nb, s)
+    A.ehm_gcn_train_normalize(h, conv, z, mean, invstd, res, y, out, bodies, s)
+    return dict(z=z, mean=mean, invstd=invstd, A=adjm)
+
+
+def train_conv_backward(h, conv, cw, X, st, gate, gout, bodies, need_x=True, need_w=False, need_params=False, out=None):
+    """VJP of train_conv_forward through the batch statistics.  st: its result; gate [>= rows, N]: its y; gout [rows, N] float32.  Returns what
+    conv_backward returns for a BatchNorm'd conv; 'bias' is exact zeros (the batch mean removes the bias)."""
+    A, s = _lib.api(), _lib.stream_ptr()
+    rows, N, dev = bodies * 24, cw.N, gout.device
+    out = {} if out is None else out
+    res = {}
+    ws, nb = _train_ws(h, conv, bodies, dev)
+    zbar = torch.empty(rows, N, device=dev)
+    g = {}
+    if need_params:
+        g = {k: out[k] if out.get(k) is not None else torch.empty(shp, device=dev)
+             for k, shp in (("M", (24, N)), ("adj2", (24, 24)), ("bn_weight", (N,)), ("bn_bias", (N,)))}
+    A.ehm_gcn_train_bn_backward(h, conv, gout, gate, st["z"], st["mean"], st["invstd"], bodies, zbar, g.get("bn_weight"), g.get("bn_bias"), ws, nb, s)
+    if need_x or need_w:
+        G = _new_G(rows, cw, dev)
+        A.ehm_gcn_train_bwd_epilogue(h, conv, zbar, st["A"], G, cw.ldg, bodies, s)
+        _gemm_grads(G, cw, X, rows, need_x, need_w, out, res)
+    if need_params:
+        pre = gemm_rows(X, cw.fwd, rows)
+        pb = C.c_int64(0)
+        A.ehm_gcn_train_bwd_params_workspace_bytes(h, conv, bodies, C.byref(pb))
+        A.ehm_gcn_train_bwd_params(h, conv, zbar, st["A"], pre, pre.shape[1], bodies, g["M"], g["adj2"], torch.empty(pb.value // 4, device=dev), pb.value, s)
+        bias = out["bias"].zero_() if out.get("bias") is not None else torch.zeros(N, device=dev)
+        res.update(g, bias=bias)
+    return res
+
+
+class GCNTrainFunction(torch.autograd.Function):
+    """ModulatedGCN.forward in training mode (ModulatedGCN.train_batchnorm): batch statistics in every BatchNorm, the running statistics updated in the
+    forward, and a backward through the mean and the variance.  Arguments and gradient order as GCNFunction."""
+
+    @staticmethod
+    def forward(ctx, module, x, *params):
+        out, saved = module._forward_train(x, save=True)
+        ctx.module, ctx.saved, ctx.n_params = module, saved, len(params)
+        return out
+
+    @staticmethod
+    @torch.autograd.function.once_differentiable
+    def backward(ctx, gout):
+        m, sv = ctx.module, ctx.saved
+        need = ctx.needs_input_grad
+        need_x, pneed = need[1], need[2:]
+        dev = gout.device
+        B, nh = sv["B"], 2 * m.num_layers
+        grads = [None] * ctx.n_params
+
+        def wants(ci, nparams=6):
+            if not pneed:
+                return False, False
+            f = pneed[6 * ci: 6 * ci + nparams]
+            return bool(f[0]), any(f[1:])
+
+        def put(ci, r, has_bn):
+            for k, name in enumerate(PARAMS_PER_CONV if has_bn else PARAMS_PER_CONV[:4]):
+                if name in r and pneed[6 * ci + k]:
+                    grads[6 * ci + k] = r[name]
+
+        def bn_conv(ci, conv, g, need_x=True):            # conv number ci of the parameter list = the handle's conv `conv`
+            nw, npar = wants(ci)
+            if not (need_x or nw or npar):
+                return None
+            r = train_conv_backward(h, conv, cws[ci], sv["X"][ci], sv["st"][ci], sv["y"][ci], g, B, need_x, nw, npar)
+            put(ci, r, True)
+            return r.get("x")
+
+        with _lib.on_device(dev):
+            h, cws = sv["h"], sv["cws"]
+            g = _lib.f32(gout, dev).reshape(B * 24, 6)
+            nw, npar = wants(nh + 1, 4)
+            r = conv_backward(h, OUTPUT, cws[nh + 1], sv["X"][nh + 1], None, g, B, True, nw, npar, has_bn=False)
+            put(nh + 1, r, False)
+            g = r["x"]
+            for blk in reversed(range(m.num_layers)):
+                l1, l2 = 2 * blk, 2 * blk + 1
+                g1 = bn_conv(l1 + 1, l1, bn_conv(l2 + 1, l2, g))
+                g = g1.add_(g)                              # + the residual's gradient
+            gx = bn_conv(0, INPUT, g, need_x)
+            if gx is not None:
+                gx = gx.reshape(B, 24, m.in_dim).to(sv["x_dtype"])
         return (None, gx, *grads)

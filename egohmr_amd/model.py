@@ -121,6 +121,7 @@ class ModulatedGCN(nn.Module):
         self.gconv_layers = nn.Sequential(*[_ResGraphConv(adj, hid_dim) for _ in range(num_layers)])
         self.gconv_output = ModulatedGraphConv(hid_dim, out_dim, adj)
         self.nonlocal_layer = bool(nonlocal_layer)
+        self.p_dropout = p_dropout                                  # modulated_gcn.py:68: read by the train-mode route only (it has no dropout)
         if self.nonlocal_layer:                                     # modulated_gcn.py:93-94, reference parameter names
             self.non_local = _NonLocalBlock(hid_dim)
         self._nl_packed = self._nl_key = None                       # nonlocal_packed()
@@ -280,9 +281,32 @@ class ModulatedGCN(nn.Module):
             self._cw_key = key
         return self._cw
 
+    # False: a call under .train() is refused.  True: it runs BatchNorm1d as torch does in training mode - batch statistics over all 24 B rows, the running
+    # statistics and num_batches_tracked updated in place, a backward through the mean and the variance (gcn_grad.GCNTrainFunction; csrc/gcn_train.hip).
+    # eval() calls do not depend on it
+    train_batchnorm = False
+
+    def _check_train(self):
+        """What the train-mode route cannot run, refused before any device call."""
+        if self.p_dropout is not None and self.p_dropout != 0:
+            raise NotImplementedError(f"ModulatedGCN.forward: the train-mode route has no dropout (p_dropout = {self.p_dropout}); use p_dropout = None or 0")
+        if self.nonlocal_layer:
+            raise NotImplementedError("ModulatedGCN.forward: the non-local block has no backward; the train-mode route needs nonlocal_layer=False")
+        if self.precision == "f16":
+            raise _lib.EgoHMRHipError(self.GRAD_F16)
+        for _, bn in self._convs()[:-1]:
+            if bn.momentum is None or not bn.track_running_stats:
+                raise NotImplementedError("ModulatedGCN.forward: the train-mode route updates the running statistics with a fixed momentum; "
+                                          "BatchNorm1d(momentum=None) and track_running_stats=False are not built")
+            if bn.training != self.training:
+                raise ValueError("ModulatedGCN.forward: a BatchNorm1d of the denoiser is in eval mode while the module is in training mode; "
+                                 "call .train() / .eval() on the whole ModulatedGCN")
+
     def _check_input(self, x):
         if self.training:
-            raise NotImplementedError("ModulatedGCN.forward: inference only (BatchNorm in eval mode, no dropout); training is out of scope (SURVEY.md section 2)")
+            if not self.train_batchnorm:
+                raise NotImplementedError("ModulatedGCN.forward: inference only (BatchNorm in eval mode, no dropout); training is out of scope (SURVEY.md section 2)")
+            self._check_train()
         if not x.is_cuda:
             raise _lib.EgoHMRHipError("ModulatedGCN.forward needs its input on a HIP device; egohmr_amd has no CPU path")
         if x.dim() != 3 or x.shape[1] != 24 or x.shape[2] != self.in_dim:
@@ -361,9 +385,69 @@ class ModulatedGCN(nn.Module):
         launch each with their backward in HIP (gcn_grad.GCNFunction: eval-mode BatchNorm, first derivatives, precision 'f16x3' or 'f32', no non-local
         block).  Every other call runs the route below and returns a tensor without grad_fn."""
         self._check_input(x)
+        if self.training:                                    # train_batchnorm (_check_input)
+            if self._wants_grad(x):
+                return gcn_grad.GCNTrainFunction.apply(self, x, *(self.grad_parameters() if self.grad_params else ()))
+            return self._forward_train(x, save=False)[0]
         if self._wants_grad(x):
             return gcn_grad.GCNFunction.apply(self, x, *(self.grad_parameters() if self.grad_params else ()))
         return self._forward_nograd(x)
+
+    @torch.no_grad()
+    def _forward_train(self, x, save):
+        """forward() under .train() with `train_batchnorm`: per BatchNorm'd conv the split-f16 GEMM X [W0 | W1], then ehm_gcn_train_preact (modulation,
+        adjacency mix, bias), ehm_gcn_train_stats (batch mean / biased variance, running statistics) and ehm_gcn_train_normalize (BatchNorm, ReLU,
+        residual) on float32 activations; gconv_output as in eval mode.  The handle is this call's own: the running statistics change here, so the
+        eval-mode one (_standalone) is rebuilt by the next eval() call through its TensorKey.  Returns (out [B, 24, 6], what the backward needs or None)."""
+        A = _lib.api()
+        dev = x.device
+        B, hid, nh = x.shape[0], self.hid_dim, 2 * self.num_layers
+        convs = self._convs()
+        with _lib.on_device(dev):
+            h, keep = self.create_native_handle(dev)
+            h = _lib.Handle(h, A.ehm_gcn_destroy, keep)
+            A.ehm_gcn_set_precision(h, PRECISIONS[self.precision])
+            cws = [gcn_grad.ConvWeights(_lib.f32(gc.W, dev)) for gc, _ in convs]
+            s = _lib.stream_ptr()
+            rows = B * 24
+            tile = A.ehm_gcn_row_tile()
+            rows_pad = (rows + tile - 1) // tile * tile
+            K = self.in_dim
+            Kp = (K + 31) // 32 * 32
+            xp = torch.zeros(rows, Kp, device=dev)
+            xp[:, :K] = _lib.f32(x).reshape(rows, K)
+            Xs, sts, ys = [xp], [], []
+
+            def conv(ci, idx, res, last):
+                """conv number ci of convs = the handle's conv idx on Xs[ci]; the result (the output conv reads whole row tiles: zeros behind the last one's rows)"""
+                bn = convs[ci][1]
+                running = (_lib.f32(bn.running_mean, dev).clone(), _lib.f32(bn.running_var, dev).clone())
+                if res is None:                               # the result is y itself
+                    y, out = (None, torch.zeros(rows_pad, hid, device=dev)) if last else (torch.empty(rows, hid, device=dev), None)
+                else:                                         # y is kept for the backward only: its gate
+                    y = torch.empty(rows, hid, device=dev) if save else None
+                    out = torch.zeros(rows_pad, hid, device=dev) if last else torch.empty(rows, hid, device=dev)
+                st = gcn_grad.train_conv_forward(h, idx, cws[ci], Xs[ci], B, bn.eps, bn.momentum, running, res, y, out)
+                bn.running_mean.copy_(running[0])             # (copy_: the buffers' _version moves, which the eval-mode handle's key sees)
+                bn.running_var.copy_(running[1])
+                bn.num_batches_tracked.add_(1)
+                result = out if out is not None else y
+                sts.append(st)
+                ys.append(y if y is not None else result)
+                return result
+
+            cur = conv(0, gcn_grad.INPUT, None, nh == 0)
+            for l in range(0, nh, 2):
+                Xs.append(cur)
+                y1 = conv(l + 1, l, None, False)
+                Xs.append(y1)
+                cur = conv(l + 2, l + 1, cur, l + 2 == nh)
+            Xs.append(cur)
+            x0 = torch.empty(B, 144, device=dev)
+            A.ehm_gcn_output_layer(h, cur, None, x0, B, 1, s)
+            A.ehm_gcn_stack_status(h, s)
+        saved = dict(h=h, cws=cws, B=B, X=Xs, st=sts, y=ys, x_dtype=x.dtype) if save else None
+        return x0.view(B, 24, 6), saved
 
     @torch.no_grad()
     def _forward_nograd(self, x):
@@ -942,8 +1026,8 @@ class EgoHMR(nn.Module):
 
     def training_step(self, *a, **k):
         raise NotImplementedError("training_step is not built: compute_loss has a backward (the loss, SMPL.forward, rot6d_to_rotmat and ModulatedGCN.forward "
-                                  "are differentiable; decode_output chains them), but train-mode BatchNorm, the conditioning encoders' backward and the "
-                                  "non-local block's backward are missing")
+                                  "are differentiable, ModulatedGCN.train_batchnorm runs BatchNorm in training mode; decode_output chains them), but the "
+                                  "conditioning encoders' backward and the non-local block's backward are missing")
 
 
 class EgoHMRVolsmpl(EgoHMR):

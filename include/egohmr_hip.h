@@ -230,6 +230,46 @@ int ehm_gcn_bwd_params(const ehm_gcn* h, int conv, const float* gout, const floa
                        float* gM, float* gadj2, float* gbias, float* gbn_weight, float* gbn_bias, void* workspace, int64_t workspace_bytes,
                        void* stream);
 
+/* ------------------------------------------------------------------ Modulated-GCN denoiser: train-mode BatchNorm ---- */
+/* One BatchNorm'd graph conv (EHM_GCN_CONV_INPUT or a hidden conv's index; EHM_GCN_CONV_OUTPUT has no BatchNorm: -22) with nn.BatchNorm1d in training
+ * mode (modulated_gcn.py:21-28 under self.training), for ModulatedGCN.train_batchnorm.  R = rows = bodies*24, N = hid_dim, everything float32 [rows, N]:
+ *   z[j] = A_jj M_j h0[j] + sum_{i != j} A_ji M_i h1[i] + bias,  mean = sum z / R,  var = sum (z - mean)^2 / R,  invstd = 1 / sqrt(var + eps),
+ *   xhat = (z - mean) invstd,  y = relu(bn_weight xhat + bn_bias),  out = y (+ residual),
+ * and with g = dL/dout:  vbar = g (.) [y > 0],  betabar = sum vbar,  gammabar = sum vbar xhat,
+ *   zbar = bn_weight invstd (vbar - betabar / R - xhat gammabar / R),
+ * after which the conv's backward is that of a conv without BatchNorm and ReLU on the cotangent zbar (ehm_gcn_train_bwd_*), with the same three caller-side
+ * GEMMs as above.  bias has a zero gradient (the batch mean removes it).  The entries read the raw parameter arrays ehm_gcn_create was given (M, adj2, bias,
+ * bn_weight, bn_bias) and adj, never the handle's BatchNorm-folded tables, and neither bn_mean nor bn_var.  All sums run in float64 in a fixed order: two calls
+ * on the same inputs give the same bits.  No allocation, no host synchronisation, no atomics.  NULL handle or a bad conv: -22 before any device call.
+ * workspace of ehm_gcn_train_preact / _stats / _bn_backward: at least *bytes of ehm_gcn_train_workspace_bytes, 16-byte aligned.
+ * A [24 x 24]: the conv's symmetrised adjacency (adj + adj2 on the diagonal), written by ehm_gcn_train_adjacency once per conv and call and read by
+ * ehm_gcn_train_preact and the two ehm_gcn_train_bwd_* entries. */
+int ehm_gcn_train_workspace_bytes(const ehm_gcn* h, int conv, int bodies, int64_t* bytes);
+int ehm_gcn_train_adjacency(const ehm_gcn* h, int conv, float* A, void* stream);
+/* pre [rows][ld_pre] = X [W0 | W1] (the layout ehm_gcn_input_layer_rows reads) -> z, and the partial column sums of z in the workspace (for a following
+ * ehm_gcn_train_stats with have_sums = 1 on the same workspace). */
+int ehm_gcn_train_preact(const ehm_gcn* h, int conv, const float* pre, int ld_pre, int bodies, const float* A, float* z, void* workspace,
+                         int64_t workspace_bytes, void* stream);
+/* Batch statistics of z, two-pass in float64: mean [N], invstd [N] = 1 / sqrt(biased var + eps), and - unless both are NULL - the in-place updates
+ * running_mean <- (1 - momentum) running_mean + momentum mean,  running_var <- (1 - momentum) running_var + momentum var R / (R - 1).
+ * have_sums: 1 = the workspace holds ehm_gcn_train_preact's column sums of this z; 0 = they are computed here (one more pass over z). */
+int ehm_gcn_train_stats(const ehm_gcn* h, int conv, const float* z, int bodies, int have_sums, double eps, double momentum, float* mean, float* invstd,
+                        float* running_mean, float* running_var, void* workspace, int64_t workspace_bytes, void* stream);
+/* y = relu(bn_weight xhat + bn_bias) (the gate of the backward; may be NULL) and out = y + residual (out may be NULL without a residual).  16-byte
+ * aligned arrays. */
+int ehm_gcn_train_normalize(const ehm_gcn* h, int conv, const float* z, const float* mean, const float* invstd, const float* residual, float* y,
+                            float* out, int bodies, void* stream);
+/* gbn_bias [N] = betabar, gbn_weight [N] = gammabar (either may be NULL) and zbar [rows, N].  gate: y of the forward (only its sign is read).  16-byte
+ * aligned arrays. */
+int ehm_gcn_train_bn_backward(const ehm_gcn* h, int conv, const float* gout, const float* gate, const float* z, const float* mean, const float* invstd,
+                              int bodies, float* zbar, float* gbn_weight, float* gbn_bias, void* workspace, int64_t workspace_bytes, void* stream);
+/* ehm_gcn_bwd_epilogue / ehm_gcn_bwd_params for a train-mode conv: zbar -> G [rows, ldg] = [h0bar | h1bar], and gM [24,N], gadj2 [24,24].
+ * workspace: *bytes of ehm_gcn_train_bwd_params_workspace_bytes, 4-byte aligned. */
+int ehm_gcn_train_bwd_epilogue(const ehm_gcn* h, int conv, const float* zbar, const float* A, float* G, int ldg, int bodies, void* stream);
+int ehm_gcn_train_bwd_params_workspace_bytes(const ehm_gcn* h, int conv, int bodies, int64_t* bytes);
+int ehm_gcn_train_bwd_params(const ehm_gcn* h, int conv, const float* zbar, const float* A, const float* pre, int ld_pre, int bodies, float* gM,
+                             float* gadj2, void* workspace, int64_t workspace_bytes, void* stream);
+
 /* ------------------------------------------------------------------ scene PointNet (conditioning) ----------- */
 /* Building blocks of ResnetPointnet.forward (models/respointnet.py:33-59, ResnetBlockFC :89-97) on the split-f16
  * matrix-core path (f32-grade, see ehm_gcn_set_precision mode 1).  All activation / weight operands are in the "X2"
