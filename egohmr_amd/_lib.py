@@ -210,7 +210,7 @@ class NonlocalParams(C.Structure):
 class SampleDesc(C.Structure):
     """ehm_sample_desc"""
     _fields_ = [("B", C.c_int), ("passes", C.c_int), ("num_steps", C.c_int), ("ddim", C.c_int), ("lbs_every_step", C.c_int),
-                ("num_scene_points", C.c_int), ("guide_denom", C.c_float), ("tau", C.c_float), ("num_masked", C.c_int), ("guide_all_points", C.c_int), ("lowprec_steps", C.c_int), ("nonlocal_ci", C.c_int), ("per_step_launches", C.c_int)]
+                ("num_scene_points", C.c_int), ("guide_denom", C.c_float), ("tau", C.c_float), ("num_masked", C.c_int), ("guide_all_points", C.c_int), ("lowprec_steps", C.c_int), ("nonlocal_ci", C.c_int), ("per_step_launches", C.c_int), ("twoterm_steps", C.c_int)]
 
 
 class Stage1Desc(C.Structure):
@@ -319,7 +319,8 @@ PROTOTYPES = {
     "ehm_profile_end": (_I, [C.POINTER(C.c_double), C.POINTER(C.c_int64), _I]),
 }
 PROF_CLASSES = ("input", "chain_f16x3", "chain_f16", "hidden_f32", "out_dot", "step_body", "skin_input", "guidance", "reserved_8", "reserved_9",
-                "guid_nearest", "guid_skin_bwd", "guid_posefeat_bwd", "step_fused", "guid_nearest_evals")   # EHM_PROF_* of the header (the last one is a COUNT in `launches`)
+                "guid_nearest", "guid_skin_bwd", "guid_posefeat_bwd", "step_fused", "guid_nearest_evals",   # EHM_PROF_* of the header ("guid_nearest_evals" is a COUNT in `launches`)
+                "chain_f16x2")
 # the entry points that return a value (a size, a tile, a mode) rather than a status: negative = error.  Every other int-returning one is a status
 VALUE_FUNCTIONS = frozenset({"ehm_gcn_row_tile", "ehm_gcn_get_precision", "ehm_gcn_activation_group", "ehm_conv_x2_rows", "ehm_conv_x2_workspace_bytes",
                              "ehm_sample_workspace_bytes", "ehm_resnet_stem_scratch_bytes"})

@@ -684,7 +684,7 @@ extern "C" int ehm_gcn_set_nonlocal(ehm_gcn* h, const ehm_nonlocal_params* p) {
 }
 
 extern "C" int ehm_gcn_set_precision(ehm_gcn* h, int mode) {
-  EHM_CHECK_ARG(h && (mode == EHM_PREC_F32 || mode == EHM_PREC_F16X3 || mode == EHM_PREC_F16));
+  EHM_CHECK_ARG(h && (mode == EHM_PREC_F32 || mode == EHM_PREC_F16X3 || mode == EHM_PREC_F16 || mode == EHM_PREC_F16X2));
   h->run.precision = mode;
   return 0;
 }

@@ -39,7 +39,7 @@ struct OutDev {
 };
 
 
-enum { EHM_PREC_F32 = 0, EHM_PREC_F16X3 = 1, EHM_PREC_F16 = 2 };
+// (EHM_PREC_F32 / _F16X3 / _F16 / _F16X2: the public header's ehm_gcn_set_precision modes)
 
 // What a GCN call runs with besides the weights, an argument of every internal function: the extern "C" entry points pass the handle's
 // ehm_gcn::run (ehm_gcn_set_precision / _set_pass_map / _set_uncond_mode), the sampling loop a copy per step.
@@ -86,7 +86,9 @@ struct ehm_gcn {
 // Activation format of the rows the input conv writes under precision `prec` (EHM_PREC_* values as formats: float32 / X2 / f16 rows).  The output
 // conv reads f16 rows in mode 2 and float32 rows otherwise, so in mode 1 the conv in front of it writes float32: the last hidden conv, or - with
 // no hidden conv at all - the input conv itself.
+// The two-term tier (EHM_PREC_F16X2) reads and writes exactly what mode 1 does: its format IS the X2 format, so a switch between the two is no format transition.
 static inline int gcn_input_format(const ehm_gcn* h, int prec) {
+  if (prec == EHM_PREC_F16X2) prec = EHM_PREC_F16X3;
   return (prec == EHM_PREC_F16X3 && h->num_hidden == 0) ? (int)EHM_PREC_F32 : prec;
 }
 

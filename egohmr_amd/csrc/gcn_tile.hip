@@ -1,10 +1,15 @@
 // Modulated-GCN hidden conv (_GraphConv hid -> hid, modulated_gcn.py:21-28 / modulated_gcn_conv.py:39-50, + the residual of
-// _ResGraphConv, modulated_gcn.py:38-42) on the f16 matrix cores of gfx950, two arithmetic modes from one tile engine:
+// _ResGraphConv, modulated_gcn.py:38-42) on the f16 matrix cores of gfx950, three arithmetic modes from one tile engine:
 //   P = 3  "f16x3": both GEMM operands stored as hi + lo f16 pairs (X2<32>, gcn_dev.h), three MFMAs per product
 //          (lo*hi + hi*lo + hi*hi), f32 accumulate: 22-bit operands, f32-grade results (the parity path).  Since round 5 on
 //          v_mfma_f32_16x16x32 (f16): at the socket's power cap - where this kernel runs - the matrix pipe sustains 2.26 PFLOP/s
 //          in that form against 1.86 as 32x32x16 on the same operands (tools/mfma_ceiling.py: a quarter of the accumulator
 //          traffic per MAC); chain kernel 1014 -> 905 us per launch, same box.  See "16 x 16 x 32" in run_tiles;
+//   P = 2  "f16x2": P = 3's operands, buffers, K loop, epilogue and stores (hi + lo, so that a P = 3 conv behind it reads full operands) with TWO MFMAs
+//          per product, wl*ah + wh*ah = a_hi * (w_hi + w_lo): the activation lo fragments are neither read from LDS nor multiplied (12 MFMAs and 3 / 4
+//          fragment reads per phase instead of 18 and 6 / 4).  The weight rounding W - f16(W) is the same perturbation in every conv of every step - a
+//          coherent bias over a sampling loop - while the activation rounding is fresh in every conv: dropping al*wh costs an order of magnitude less accuracy
+//          than dropping ah*wl (docs/EXPERIMENTS.md R13.1).  The middle tier of the precision schedule (ehm_sample_desc.twoterm_steps);
 //   P = 1  "f16":   plain f16 storage [rows][hid] and one MFMA per product (BASELINE config 5's fp16 denoiser, and the early
 //          steps of the precision schedule).
 // Tile = 192 rows (8 bodies x 24 joints) x 64 channels x both branches (W0 | W1); 4 waves as 2 x 2, 96 x 32(x2) per wave;
@@ -56,7 +61,7 @@ __device__ unsigned long long* g_tdbg = nullptr;
 #endif
 
 template <int P>
-using Frags = X2Frags<2, P == 3>;
+using Frags = X2Frags<2, P != 1>;
 
 // Block-uniform identity of one output tile; everything else is derived from the launch arguments when it is needed, so that
 // only three SGPRs per tile stay live across the K loop / the epilogue.
@@ -100,7 +105,7 @@ struct OneArgs {
 
 template <int P>
 __device__ __forceinline__ const float* layer_weights(const LayerDev& L) {
-  return P == 3 ? (const float*)L.Ws : (const float*)L.Wh;
+  return P != 1 ? (const float*)L.Ws : (const float*)L.Wh;
 }
 
 // The engine.  CHAIN = true: persistent blocks, per-XCD ticket queues over (layer, row tile, channel tile) with per-row-tile
@@ -114,7 +119,9 @@ __device__ __forceinline__ const float* layer_weights(const LayerDev& L) {
 template <int P, int MODE, int NW, class Args>
 __device__ __forceinline__ void run_tiles(float* lds, const Args& a) {
   constexpr bool CHAIN = MODE == 1;
-  constexpr bool M16 = P == 3;       // split-f16 mode: v_mfma_f32_16x16x32 (f16) (see "16 x 16 x 32" below); plain f16: v_mfma_f32_32x32x16_f16
+  constexpr bool SPLIT = P != 1;     // operands and activation stores in the X2 format: P = 3 (three MFMAs per product) and P = 2 (two: the activation lo halves are neither read nor multiplied)
+  constexpr bool M16 = SPLIT;        // split-f16 modes: v_mfma_f32_16x16x32 (f16) (see "16 x 16 x 32" below); plain f16: v_mfma_f32_32x32x16_f16
+  static_assert(P == 1 || P == 2 || P == 3, "MFMAs per product: 1 = plain f16, 3 = split-f16, 2 = split-f16 without the al * bh term");
   static_assert(NW == 4 || (NW == 8 && P == 1 && CHAIN), "the 8-wave tile exists for the chained f16 kernel (f16x3 is power-bound: 8 waves measured 150 vs 152 us)");
   x2_fp16_ovfl_on();
   constexpr int NWN = NW / 2;                 // waves across the channels
@@ -122,9 +129,9 @@ __device__ __forceinline__ void run_tiles(float* lds, const Args& a) {
   constexpr int BROWS = 2 * NT;               // weight rows per stage (W0 | W1 per 64 channels)
   constexpr int STG = stage_floats(NW);
   constexpr int NDA = 24 / NW, NDB = BROWS / (8 * NW);   // DMA instructions per wave and stage: activations 6 / 3, weights 4 / 4
-  constexpr int KS = P == 3 ? 2 : 4;          // 16-wide k-steps per K tile
-  constexpr int NM = P == 3 ? 18 : 6;         // MFMAs per k-step
-  constexpr int NR = P == 3 ? 10 : 5;         // ds_read_b128 per k-step
+  constexpr int KS = SPLIT ? 2 : 4;          // 16-wide k-steps per K tile
+  constexpr int NM = SPLIT ? 18 : 6;         // MFMAs per k-step
+  constexpr int NR = SPLIT ? 10 : 5;         // ds_read_b128 per k-step
   const int tid = threadIdx.x;
   // Per-thread constants are RE-DERIVED at the head of every tile (thread_consts below; x2_lane_wave in x2_tile_dev.h)
   int lane, wave, wm, wn, mi, g;
@@ -132,7 +139,7 @@ __device__ __forceinline__ void run_tiles(float* lds, const Args& a) {
 
   int K, N;
   if constexpr (CHAIN) { K = a.layers[0].K; N = a.layers[0].N; } else { K = a.L.K; N = a.L.N; }
-  const int rowf = P == 3 ? K : K / 2;        // floats per operand row
+  const int rowf = SPLIT ? K : K / 2;        // floats per operand row
   const int KT = rowf / RK;
 
   int r0, swz;                                               // my DMA row and swizzled chunk (x2_dma_lane)
@@ -156,11 +163,11 @@ __device__ __forceinline__ void run_tiles(float* lds, const Args& a) {
       o.Y = (char*)(oddl ? a.buf[nb] : a.buf[1]);
       o.Ds = L.Ds; o.M1s = L.M1s; o.shift = L.shift; o.Aoff = L.Aoff; o.AoffH = L.AoffH;
       o.relu = L.relu;
-      o.out_f32 = P == 3 && t.layer == a.nl - 1;   // (f16 rows are half as long: a float32 row of the last conv would land on two f16 rows of OTHER row tiles still being read)
+      o.out_f32 = SPLIT && t.layer == a.nl - 1;   // (f16 rows are half as long: a float32 row of the last conv would land on two f16 rows of OTHER row tiles still being read)
     } else {
       o.X = (const float*)a.X; o.W = layer_weights<P>(a.L); o.Res = (const char*)a.Res; o.Y = (char*)a.Y;
       o.Ds = a.L.Ds; o.M1s = a.L.M1s; o.shift = a.L.shift; o.Aoff = a.L.Aoff; o.AoffH = a.L.AoffH;
-      o.relu = a.L.relu; o.out_f32 = P == 3 && a.out_f32;
+      o.relu = a.L.relu; o.out_f32 = SPLIT && a.out_f32;
     }
     return o;
   };
@@ -217,7 +224,7 @@ __device__ __forceinline__ void run_tiles(float* lds, const Args& a) {
   // wave's bodies 2g and 2g+1, joint j of the two bodies in the ADJACENT registers 2*(j&7), 2*(j&7)+1 of accumulator j>>3.
   //   rA = 96 wm + 48 ((mi>>2)&1) + 24 (mi&1) + ((mi>>1)&1) + 2 (mi>>3);  rB = 32 wn + mi (+ 64 for the W1 branch)
   //   A block t sits 8 t rows further: its key has bit 2 flipped for odd t (oA[..][t & 1]); the W1 branch's + 64 leaves keyB alone
-  int oA[KS][P == 3 ? 2 : 1][2], oB[KS][P == 3 ? 2 : 1];
+  int oA[KS][SPLIT ? 2 : 1][2], oB[KS][SPLIT ? 2 : 1];
   [[maybe_unused]] int oA16[2], oB16[2];
   auto thread_consts = [&]() {
     x2_lane_wave(tid, lane, wave);
@@ -227,7 +234,7 @@ __device__ __forceinline__ void run_tiles(float* lds, const Args& a) {
     x2_dma_lane(lane, wave, r0, swz);
     const int rA = 96 * wm + 48 * ((mi >> 2) & 1) + 24 * (mi & 1) + ((mi >> 1) & 1) + 2 * (mi >> 3);
     const int rB = NW == 8 ? 128 * (wn >> 1) + 32 * (wn & 1) + mi : 32 * wn + mi;   // 8 waves: 64-channel weight group wn >> 1 of the pair
-    X2_FRAG_OFFSETS32(oA, oB, KS, P == 3 ? 2 : 1, 2, A_T, rA, rB, g);
+    X2_FRAG_OFFSETS32(oA, oB, KS, SPLIT ? 2 : 1, 2, A_T, rA, rB, g);
     if constexpr (M16) X2_FRAG_OFFSETS16(oA16, oB16, A_T, 96 * wm, 32 * wn, lane);
   };
   thread_consts();
@@ -236,12 +243,12 @@ __device__ __forceinline__ void run_tiles(float* lds, const Args& a) {
 #pragma unroll
     for (int t = 0; t < 3; ++t) {
       f.ah[t] = *(const half8*)(S + oA[s][0][t & 1] + 8 * t * RK);
-      if constexpr (P == 3) f.al[t] = *(const half8*)(S + oA[s][1][t & 1] + 8 * t * RK);
+      if constexpr (SPLIT) f.al[t] = *(const half8*)(S + oA[s][1][t & 1] + 8 * t * RK);
     }
 #pragma unroll
     for (int u = 0; u < 2; ++u) {
       f.bh[u] = *(const half8*)(S + oB[s][0] + 64 * u * RK);
-      if constexpr (P == 3) f.bl[u] = *(const half8*)(S + oB[s][1] + 64 * u * RK);
+      if constexpr (SPLIT) f.bl[u] = *(const half8*)(S + oB[s][1] + 64 * u * RK);
     }
   };
 
@@ -255,7 +262,7 @@ __device__ __forceinline__ void run_tiles(float* lds, const Args& a) {
   auto mfmas = [&](const Frags<P>& f) {
 #pragma unroll
     for (int t = 0; t < 3; ++t) {
-      if constexpr (P == 3) {                           // small cross terms first, leading term last
+      if constexpr (SPLIT) {                           // small cross terms first, leading term last
         acc0[t] = __builtin_amdgcn_mfma_f32_32x32x16_f16(f.al[t], f.bh[0], acc0[t], 0, 0, 0);
         acc1[t] = __builtin_amdgcn_mfma_f32_32x32x16_f16(f.al[t], f.bh[1], acc1[t], 0, 0, 0);
         acc0[t] = __builtin_amdgcn_mfma_f32_32x32x16_f16(f.ah[t], f.bl[0], acc0[t], 0, 0, 0);
@@ -267,7 +274,7 @@ __device__ __forceinline__ void run_tiles(float* lds, const Args& a) {
   };
   auto pin_reads = [&]() { x2_pin_reads<NR, NM>(); };
   auto pin_reads_dma = [&]() {                  // the reads one per MFMA, the ten DMAs spread over the phase
-    if constexpr (P == 3) {                     // 18 MFMAs: 10 x (MFMA, read), then 2,2,1,1,1,1,1,1 DMAs behind the last 8
+    if constexpr (SPLIT) {                     // 18 MFMAs: 10 x (MFMA, read), then 2,2,1,1,1,1,1,1 DMAs behind the last 8
 #pragma unroll
       for (int i = 0; i < NR; ++i) {
         __builtin_amdgcn_sched_group_barrier(SG_MFMA, 1, 0);
@@ -406,7 +413,7 @@ __device__ __forceinline__ void run_tiles(float* lds, const Args& a) {
     if constexpr (NW == 8) {
       asm volatile("s_waitcnt vmcnt(3)" ::: "memory");                         // everything but the three late pieces (the stores are older)
     } else if (pending_publish) {
-      if constexpr (P == 3) asm volatile("s_waitcnt vmcnt(18)" ::: "memory");   // 12 sixteen-byte stores per wave and tile (X2 hi + lo, or float32)
+      if constexpr (SPLIT) asm volatile("s_waitcnt vmcnt(18)" ::: "memory");   // 12 sixteen-byte stores per wave and tile (X2 hi + lo, or float32)
       else asm volatile("s_waitcnt vmcnt(12)" ::: "memory");                   // 6
     } else {
       asm volatile("s_waitcnt vmcnt(6)" ::: "memory");
@@ -435,15 +442,19 @@ __device__ __forceinline__ void run_tiles(float* lds, const Args& a) {
     [[maybe_unused]] auto ldA = [&](auto rhc, int buf) {
       constexpr int rh = decltype(rhc)::value;
       const float* S = lds + buf * STG;
-      X2_LD16(t, 3, Ah[rh], Al[rh], S, oA16[0], oA16[1], 16 * (3 * rh + t));
+      if constexpr (P == 2) { X2_LD16_HI(t, 3, Ah[rh], S, oA16[0], 16 * (3 * rh + t)); }   // two-term product: the activation lo halves stay in LDS
+      else { X2_LD16(t, 3, Ah[rh], Al[rh], S, oA16[0], oA16[1], 16 * (3 * rh + t)); }
     };
     [[maybe_unused]] auto ldB = [&](auto chc, int buf) {
       constexpr int ch = decltype(chc)::value;
       const float* S = lds + buf * STG;
       X2_LD16(u, 2, Bh[ch], Bl[ch], S, oB16[0], oB16[1], 16 * u + 64 * ch);   // (the W1 branch's rows start 64 further)
     };
-    [[maybe_unused]] auto mm = [&](auto rhc, auto chc) { x2_mm16<decltype(rhc)::value, decltype(chc)::value, 2>(c16, Ah, Al, Bh, Bl); };
-    [[maybe_unused]] auto pin16 = [&](int reads, int dmas) { x2_pin16<18>(reads, dmas); };
+    [[maybe_unused]] auto mm = [&](auto rhc, auto chc) { x2_mm16<decltype(rhc)::value, decltype(chc)::value, 2, P == 2 ? 2 : 3>(c16, Ah, Al, Bh, Bl); };
+    // a phase = 18 MFMAs (P = 3) / 12 (P = 2); its fragment reads: 4 (a B half, hi + lo) or 6 / 3 (an A half: hi + lo / hi alone).  12 MFMAs still
+    // leave a slot behind every second one for the 6 activation / 4 weight DMA instructions of a staging phase
+    constexpr int PH_MFMA = P == 2 ? 12 : 18, RD_A = P == 2 ? 3 : 6, RD_B = 4;
+    [[maybe_unused]] auto pin16 = [&](int reads, int dmas) { x2_pin16<PH_MFMA>(reads, dmas); };
     // one K tile of parity PAR (snake order of the four (row half, branch) phases: only one operand half changes between consecutive phases, so
     // no half is ever double-buffered).  mode 0: steady (stages K tile kt + 2 into `buf`), 1: second-last, 2: last (no next-tile loads)
     [[maybe_unused]] auto tile16 = [&](auto parc, int buf, int kt, int mode) {
@@ -452,11 +463,11 @@ __device__ __forceinline__ void run_tiles(float* lds, const Args& a) {
       typedef std::integral_constant<int, 1 - PAR> CS;
       ldB(CS{}, buf);
       mm(I0{}, CF{});
-      pin16(4, 0);
+      pin16(RD_B, 0);
       __builtin_amdgcn_sched_barrier(0);
       ldA(I1{}, buf);
       mm(I0{}, CS{});
-      pin16(6, 0);
+      pin16(RD_A, 0);
       asm volatile("s_waitcnt vmcnt(0)" ::: "memory");
       __syncthreads();
       if (pending_publish) { publish(prev); pending_publish = false; }
@@ -468,7 +479,7 @@ __device__ __forceinline__ void run_tiles(float* lds, const Args& a) {
         for (int i = 0; i < NDA; ++i) dma_a(buf, kt + 2, i);
       }
       mm(I1{}, CS{});
-      pin16(6, mode == 0 ? NDA : 0);
+      pin16(RD_A, mode == 0 ? NDA : 0);
       __builtin_amdgcn_sched_barrier(0);
       ldB(CS{}, buf ^ 1);
       if (mode == 0) {
@@ -476,7 +487,7 @@ __device__ __forceinline__ void run_tiles(float* lds, const Args& a) {
         for (int i = 0; i < NDB; ++i) dma_b(buf, kt + 2, i);
       }
       mm(I1{}, CF{});
-      pin16(4, mode == 0 ? NDB : 0);
+      pin16(RD_B, mode == 0 ? NDB : 0);
       if (mode == 0) __builtin_amdgcn_s_setprio(0);
     };
     if constexpr (M16) {
@@ -540,11 +551,11 @@ __device__ __forceinline__ void run_tiles(float* lds, const Args& a) {
       // second-last K tile (stage 0): its first half up to the barrier by hand so that the slot words can be written behind the barrier
       ldB(I1{}, 0);
       mm(I0{}, I0{});
-      pin16(4, 0);
+      pin16(RD_B, 0);
       __builtin_amdgcn_sched_barrier(0);
       ldA(I1{}, 0);
       mm(I0{}, I1{});
-      pin16(6, 0);
+      pin16(RD_A, 0);
       asm volatile("s_waitcnt vmcnt(0)" ::: "memory");
       __syncthreads();
       if (pending_publish) { publish(prev); pending_publish = false; }
@@ -554,11 +565,11 @@ __device__ __forceinline__ void run_tiles(float* lds, const Args& a) {
         }
       ldA(I0{}, 1);
       mm(I1{}, I1{});
-      pin16(6, 0);
+      pin16(RD_A, 0);
       __builtin_amdgcn_sched_barrier(0);
       ldB(I1{}, 1);
       mm(I1{}, I0{});
-      pin16(4, 0);
+      pin16(RD_B, 0);
     } else
     {
       const int buf = (KT - 2) & 1;
@@ -655,7 +666,7 @@ __device__ __forceinline__ void run_tiles(float* lds, const Args& a) {
     //      wave-private 6 KiB scratch in LDS - the six 1 KiB pieces of stage 1's activation region that its own DMA instructions
     //      fill, so no other wave ever touches them and no barrier is needed - into rows of 4 consecutive channels per lane:
     //      residual and output move as 8 / 16-byte accesses, 8 lanes per 64-byte row segment.  Two passes of 48 rows.
-    const unsigned int arow = (unsigned int)N * (P == 3 ? 4u : 2u);       // bytes per activation row
+    const unsigned int arow = (unsigned int)N * (SPLIT ? 4u : 2u);       // bytes per activation row
     const bool out_f32 = io.out_f32 != 0, has_res = io.Res != nullptr, relu = io.relu != 0;
     const float floor_v = relu ? 0.f : -3.4e38f;              // one v_max per value instead of a v_max and a select (the values are finite)
     const __amdgpu_buffer_rsrc_t yB = ehm_buffer_rsrc(io.Y + ((size_t)cur.m_tile * 192 + 96 * wm) * (out_f32 ? (size_t)N * 4 : (size_t)arow));
@@ -665,11 +676,11 @@ __device__ __forceinline__ void run_tiles(float* lds, const Args& a) {
     const int lr = lane >> 2, c8 = 8 * (lane & 3);
     const int ch0 = NT * cur.n_tile + 32 * wn + c8;                        // first channel of my items
     unsigned int col_in, col_out;                                           // byte offsets of the item's columns: residual / output
-    if constexpr (P == 3) col_in = (unsigned int)(((ch0 >> 5) * 64 + (ch0 & 31)) * 2);   // X2: 8 hi halves here, 8 lo halves 64 B on
+    if constexpr (SPLIT) col_in = (unsigned int)(((ch0 >> 5) * 64 + (ch0 & 31)) * 2);   // X2: 8 hi halves here, 8 lo halves 64 B on
     else col_in = (unsigned int)ch0 * 2u;
     col_out = out_f32 ? (unsigned int)ch0 * 4u : col_in;
     const unsigned int orow = out_f32 ? tblrow : arow;
-    // wave row of scratch row rl in pass p:  P == 1: pass = half-wave x -> 48 p + rl;  P == 3: pass = body beta, scratch rows = 24 g + joint
+    // wave row of scratch row rl in pass p:  P == 1: pass = half-wave x -> 48 p + rl;  SPLIT: pass = body beta, scratch rows = 24 g + joint
     // -> 48 (rl / 24) + 24 p + rl % 24
     // M16: pass = joints 12 p .. + 11 of the wave's four bodies, scratch row = 4 (joint - 12 p) + body -> wave row 24 (rl & 3) + 12 p + (rl >> 2)
     auto item_vrow = [&](int p, int it) -> unsigned int {
@@ -678,13 +689,13 @@ __device__ __forceinline__ void run_tiles(float* lds, const Args& a) {
       return (unsigned int)(P == 1 ? 48 * p + rl : 24 * p + rl + (rl >= 24 ? 24 : 0));
     };
     typedef _Float16 half2_t __attribute__((ext_vector_type(2)));
-    u32x4 rq[6];                                                         // residual: P == 1 both passes (3 + 3 items), P == 3 the current pass (hi, lo per item)
+    u32x4 rq[6];                                                         // residual: P == 1 both passes (3 + 3 items), SPLIT the current pass (hi, lo per item)
     auto load_res_pass = [&](int p) {
       if (has_res) {
 #pragma unroll
         for (int it = 0; it < 3; ++it) {
           const unsigned int vo = item_vrow(p, it) * arow + col_in;
-          if constexpr (P == 3) {
+          if constexpr (SPLIT) {
             rq[2 * it] = __builtin_amdgcn_raw_buffer_load_b128(resB, vo, 0, kLoadAux);
             rq[2 * it + 1] = __builtin_amdgcn_raw_buffer_load_b128(resB, vo + 64u, 0, kLoadAux);
           } else {
@@ -810,7 +821,7 @@ __device__ __forceinline__ void run_tiles(float* lds, const Args& a) {
     const unsigned int valid_wave_rows = a.rows_valid > wave_row0 ? a.rows_valid - wave_row0 : 0u;   // rows of this wave's 96 that are real
 #pragma unroll
     for (int p = 0; p < 2; ++p) {
-      if constexpr (P == 3) { if (p == 1) load_res_pass(1); }
+      if constexpr (SPLIT) { if (p == 1) load_res_pass(1); }
       if constexpr (M16) {
 #pragma unroll
         for (int jj = 0; jj < 12; ++jj) {
@@ -833,7 +844,7 @@ __device__ __forceinline__ void run_tiles(float* lds, const Args& a) {
       for (int it = 0; it < 3; ++it) {
         float v[8] = {t[it][0][0], t[it][0][1], t[it][0][2], t[it][0][3], t[it][1][0], t[it][1][1], t[it][1][2], t[it][1][3]};
         if (has_res) {
-          if constexpr (P == 3) {
+          if constexpr (SPLIT) {
             const half8 rh = __builtin_bit_cast(half8, rq[2 * it]), rl = __builtin_bit_cast(half8, rq[2 * it + 1]);
 #pragma unroll
             for (int c = 0; c < 8; ++c) v[c] += (float)rh[c] + (float)rl[c];
@@ -854,9 +865,9 @@ __device__ __forceinline__ void run_tiles(float* lds, const Args& a) {
           __builtin_amdgcn_raw_buffer_store_b128(__builtin_bit_cast(u32x4, f32x4{v[4], v[5], v[6], v[7]}), yB, vo + 16u, 0, kStoreAux);
         } else {
           half8 hh, ll;
-          X2_SPLIT8(P == 3, v, hh, ll);                               // saturating (MODE.FP16_OVFL): |v| > 131008 saturates both halves, never inf
+          X2_SPLIT8(SPLIT, v, hh, ll);                               // saturating (MODE.FP16_OVFL): |v| > 131008 saturates both halves, never inf
           __builtin_amdgcn_raw_buffer_store_b128(__builtin_bit_cast(u32x4, hh), yB, vo, 0, kStoreAux);
-          if constexpr (P == 3) __builtin_amdgcn_raw_buffer_store_b128(__builtin_bit_cast(u32x4, ll), yB, vo + 64u, 0, kStoreAux);
+          if constexpr (SPLIT) __builtin_amdgcn_raw_buffer_store_b128(__builtin_bit_cast(u32x4, ll), yB, vo + 64u, 0, kStoreAux);
         }
       }
     }
@@ -959,10 +970,10 @@ __global__ void unpack_x2_kernel(const half_t* __restrict__ X, float* __restrict
 }
 
 bool shape_ok(const ehm_gcn* h, int prec, int64_t rows_pad) {
-  const int P = prec == EHM_PREC_F16X3 ? 3 : 1;
-  const int kt = P == 3 ? h->hid / 32 : h->hid / 64;
+  const bool split = prec == EHM_PREC_F16X3 || prec == EHM_PREC_F16X2;
+  const int kt = split ? h->hid / 32 : h->hid / 64;
   if (h->hid % 64 != 0 || kt < 2 || rows_pad % 192 != 0) {
-    ehm_set_error("f16 matrix-core convs need hid %% 64 == 0, hid >= %d and rows_pad %% 192 == 0 (hid = %d, rows_pad = %lld)", P == 3 ? 64 : 128,
+    ehm_set_error("f16 matrix-core convs need hid %% 64 == 0, hid >= %d and rows_pad %% 192 == 0 (hid = %d, rows_pad = %lld)", split ? 64 : 128,
                   h->hid, (long long)rows_pad);
     return false;
   }
@@ -994,6 +1005,7 @@ int ehm_gcn_tile_layer_impl(const ehm_gcn* h, const GcnRun& r, int layer, const 
   a.rows_valid = r.guarded_rows(rows_pad);
   const int blocks = a.m_tiles * (h->hid / 64);
   if (r.precision == EHM_PREC_F16X3) hipLaunchKernelGGL(gcn_hidden_tile_kernel<3>, dim3(blocks), dim3(256), 0, st, a);
+  else if (r.precision == EHM_PREC_F16X2) hipLaunchKernelGGL(gcn_hidden_tile_kernel<2>, dim3(blocks), dim3(256), 0, st, a);
   else hipLaunchKernelGGL(gcn_hidden_tile_kernel<1>, dim3(blocks), dim3(256), 0, st, a);
   EHM_LAUNCH_CHECK();
   return 0;
@@ -1017,7 +1029,7 @@ int ehm_gcn_tile_chain_impl(ehm_gcn* h, const GcnRun& r, void* const bufs[3], in
     ehm_set_error("chained hidden convs need an even number (>= 2) of them");
     return EHM_EINVAL;
   }
-  const bool wide = r.precision != EHM_PREC_F16X3 && h->hid % 128 == 0;   // f16 mode: one 8-wave block per CU, 128-channel tiles
+  const bool wide = r.precision == EHM_PREC_F16 && h->hid % 128 == 0;   // f16 mode: one 8-wave block per CU, 128-channel tiles
   const int m_tiles = (int)(rows_pad / 192), n_tiles = h->hid / (wide ? 128 : 64);
   const size_t need = 8 + (size_t)nl * m_tiles + 8;   // tickets | done | err, finished
   if (h->chain_sync_words < need) {
@@ -1052,6 +1064,7 @@ int ehm_gcn_tile_chain_impl(ehm_gcn* h, const GcnRun& r, void* const bufs[3], in
   if (a.nq < 1) a.nq = 1;
   if (a.nq > 8) a.nq = 8;
   if (r.precision == EHM_PREC_F16X3) hipLaunchKernelGGL((gcn_hidden_chain_kernel<3, 4>), dim3(blocks), dim3(256), 0, st, a);
+  else if (r.precision == EHM_PREC_F16X2) hipLaunchKernelGGL((gcn_hidden_chain_kernel<2, 4>), dim3(blocks), dim3(256), 0, st, a);
   else if (wide) hipLaunchKernelGGL((gcn_hidden_chain_kernel<1, 8>), dim3(blocks), dim3(512), 0, st, a);
   else hipLaunchKernelGGL((gcn_hidden_chain_kernel<1, 4>), dim3(blocks), dim3(256), 0, st, a);
   EHM_LAUNCH_CHECK();

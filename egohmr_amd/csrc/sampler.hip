@@ -244,6 +244,9 @@ extern "C" int ehm_sample_loop(ehm_gcn* gcn, ehm_smpl* smpl, const ehm_sample_de
   const ehm_nonlocal_params* nlp = &gcn->nonlocal;
   EHM_CHECK_ARG(d->nonlocal_ci == nlp->Ci);                                            // the descriptor sized the workspace for the block that is set
   EHM_CHECK_ARG(nlp->Ci == 0 || (base.precision != EHM_PREC_F16 && d->lowprec_steps == 0));   // the block reads float32 features
+  // the two-term tier is a tier of a split-f16 loop (like lowprec_steps, of no meaning elsewhere: rejected, not ignored)
+  EHM_CHECK_ARG(d->twoterm_steps == 0 || (d->twoterm_steps > 0 && base.precision == EHM_PREC_F16X3 && nlp->Ci == 0 && d->lowprec_steps >= 0 &&
+                                          (int64_t)d->lowprec_steps + d->twoterm_steps <= d->num_steps));
   Workspace w = carve(d, hid, V, 64 + kJ, (char*)workspace);
   EHM_CHECK_ARG(workspace_bytes >= w.total_bytes);
   hipStream_t st = (hipStream_t)stream;
@@ -258,7 +261,10 @@ extern "C" int ehm_sample_loop(ehm_gcn* gcn, ehm_smpl* smpl, const ehm_sample_de
   int rc = 0;
   base.valid_rows = w.rows;     // what every step's input conv produces
   const int lowprec = base.precision == EHM_PREC_F16X3 ? d->lowprec_steps : 0;
-  auto prec_of = [&](int k) { return (lowprec > 0 && k < lowprec) ? (int)EHM_PREC_F16 : base.precision; };   // (the same X2 buffers)
+  const int twoterm_end = lowprec + d->twoterm_steps;
+  // steps [0, lowprec): plain f16; [lowprec, twoterm_end): two-term split-f16; the rest: the handle's mode   (all in the same buffers)
+  auto prec_of = [&](int k) { return (lowprec > 0 && k < lowprec) ? (int)EHM_PREC_F16 : k < twoterm_end ? (int)EHM_PREC_F16X2 : base.precision; };
+  auto fmt_of = [&](int k) { return gcn_input_format(gcn, prec_of(k)); };   // what step k's input conv writes: two-term and three-term steps share the X2 format
   // ---- deferred skinning of the per-step launches (see carve): slots filled since the last skinning launch
   // (a body model with dense skinning weights has no MFMA fragments: its steps keep the VALU skinning launch of ehm_step_body_impl - the workspace
   //  was sized without looking at the handle, the slots simply stay unused)
@@ -308,7 +314,7 @@ extern "C" int ehm_sample_loop(ehm_gcn* gcn, ehm_smpl* smpl, const ehm_sample_de
     int in = 0;
     if (rc == 0) {
       const int p = run.precision;
-      EhmProfScope ps(p == EHM_PREC_F16X3 ? EHM_PROF_CHAIN_F16X3 : p == EHM_PREC_F16 ? EHM_PROF_CHAIN_F16 : EHM_PROF_HIDDEN_F32, st);
+      EhmProfScope ps(p == EHM_PREC_F16X3 ? EHM_PROF_CHAIN_F16X3 : p == EHM_PREC_F16X2 ? EHM_PROF_CHAIN_F16X2 : p == EHM_PREC_F16 ? EHM_PROF_CHAIN_F16 : EHM_PROF_HIDDEN_F32, st);
       rc = ehm_gcn_hidden_stack_impl(gcn, run, w.X, w.rows_pad, &in, st);
     }
     const float* hs = nullptr;
@@ -328,7 +334,7 @@ extern "C" int ehm_sample_loop(ehm_gcn* gcn, ehm_smpl* smpl, const ehm_sample_de
     // ---- fused: responses + x0 + x_{t-1} + the next step's input conv in one launch (the same arithmetic as the launches below).  Not for a
     //      step whose successor reads another activation format (the next rows would land on other bodies' rows of `feat`), nor - without
     //      deferred skinning - for the last step (its pose and skinning follow at once).
-    if (rc == 0 && fused_steps && (last ? defer_skin : run.precision == prec_of(k + 1))) {
+    if (rc == 0 && fused_steps && (last ? defer_skin : fmt_of(k) == fmt_of(k + 1))) {
       if (defer_skin && pending > 0 && !pending_poses) rc = flush_skin(false);      // (slots filled by per-step launches carry their poses already)
       const float* eps = noise + (int64_t)(1 + k) * n;
       float* dst = last ? x_final : w.x_cur;

@@ -95,14 +95,21 @@ static __device__ __forceinline__ bool x2_hi_lane(int swz) { return swz < 16; }
     (l)[t] = *(const half8*)((S) + (o_lo) + (row) * X2_RK);       \
     __VA_ARGS__;                                                  \
   }
-// one phase (row half RH, column half CH) = 9 NU MFMAs: small cross terms first, leading term last, 3 NU independent accumulators per term
-template <int RH, int CH, int NU>
+// ... the hi fragments alone (the two-term product reads no activation lo half)
+#define X2_LD16_HI(t, N, h, S, o_hi, row)                         \
+  _Pragma("unroll") for (int t = 0; t < (N); ++t) (h)[t] = *(const half8*)((S) + (o_hi) + (row) * X2_RK);
+// one phase (row half RH, column half CH) = 3 TERMS NU MFMAs: small cross terms first, leading term last, 3 NU independent accumulators per term.
+// TERMS = 3: al*bh + ah*bl + ah*bh.  TERMS = 2: ah*bl + ah*bh = a_hi * (b_hi + b_lo) - the A operand taken as its hi half, B in full (Al is not read).
+template <int RH, int CH, int NU, int TERMS = 3>
 static __device__ __forceinline__ void x2_mm16(f32x4a (&c16)[6][2 * NU], const half8 (&Ah)[2][3], const half8 (&Al)[2][3], const half8 (&Bh)[2][NU],
                                                 const half8 (&Bl)[2][NU]) {
+  static_assert(TERMS == 2 || TERMS == 3, "two or three terms per product");
+  if constexpr (TERMS == 3) {
 #pragma unroll
-  for (int t = 0; t < 3; ++t)
+    for (int t = 0; t < 3; ++t)
 #pragma unroll
-    for (int u = 0; u < NU; ++u) c16[3 * RH + t][NU * CH + u] = __builtin_amdgcn_mfma_f32_16x16x32_f16(Al[RH][t], Bh[CH][u], c16[3 * RH + t][NU * CH + u], 0, 0, 0);
+      for (int u = 0; u < NU; ++u) c16[3 * RH + t][NU * CH + u] = __builtin_amdgcn_mfma_f32_16x16x32_f16(Al[RH][t], Bh[CH][u], c16[3 * RH + t][NU * CH + u], 0, 0, 0);
+  }
 #pragma unroll
   for (int t = 0; t < 3; ++t)
 #pragma unroll

@@ -94,8 +94,8 @@ def gather_floats(value: float, device) -> list:
 
 
 def agree_schedule(fused_sampler, diffusion, batch, ddim=False, guided=False, cond_grad_weight=1.0, denom_items=None, **kw):
-    """One precision-schedule calibration for the whole job: rank 0 measures k on ITS batch (FusedSampler.calibrate_schedule - with the
-    contiguous sharding of `shard_range` these are the first items of the data set whatever the world size), every rank installs that k.
+    """One precision-schedule calibration for the whole job: rank 0 measures k (and, in the same info dict, the two-term steps j) on ITS batch (FusedSampler.calibrate_schedule - with the
+    contiguous sharding of `shard_range` these are the first items of the data set whatever the world size), every rank installs that k and j.
     Without this each rank would calibrate on its own shard at first use and the result rows would depend on how the items were
     sharded.  Single-process: just calibrates.  Returns the info dict."""
     B = int(denom_items or next(v for v in batch.values() if torch.is_tensor(v)).shape[0])

@@ -17,7 +17,7 @@ import torch
 from . import _lib
 from . import smpl as smpl_mod
 
-PRECISIONS = {"f32": 0, "f16x3": 1, "f16": 2}
+PRECISIONS = {"f32": 0, "f16x3": 1, "f16": 2, "f16x2": 3}   # EHM_PREC_* ("f16x2": a tier of the f16x3 schedule and of the kernel tests, not a value of EgoHMR.gcn_precision)
 
 # ---------------------------------------------------------------------------------------------- native engine
 def pass_map(need):
@@ -95,6 +95,7 @@ class FusedSampler:
         self._sched_cache = {}          # schedule_key -> calibration info (calibrate_schedule)
         self.schedule_info = None       # the calibration the most recent 'auto' run used (None: ran all-f16x3 / explicit k)
         self.last_lowprec = 0
+        self.last_twoterm = 0           # two-term steps (behind the plain-f16 ones) of the last call
         self.last_trace = None
 
     @property
@@ -408,7 +409,7 @@ class FusedSampler:
         return (self._param_key(), self._cond_param_key(), tuple(diffusion.timestep_map), int(getattr(diffusion, "original_num_steps", diffusion.num_timesteps)),
                 bool(ddim), int(n_guided), (float(cond_grad_weight), str(m.guide_reduction)) if n_guided else None, bool(m.guide_all_points) if n_guided else False,
                 bool(m.diffuse_fuse),
-                float(m.schedule_tol))
+                float(m.schedule_tol), str(getattr(m, "f16x2_steps", 0)))
 
     def lowprec_steps(self, T: int, guided=False, ddim: bool = True, key=None) -> int:
         """How many LEADING steps of a T-step fused loop run on plain f16 operands (EgoHMR.f16x3_last_steps): None -> 0 (every step
@@ -424,6 +425,27 @@ class FusedSampler:
                 return 0
             k = info["k"]
         return max(0, T - int(k))
+
+    def twoterm_steps(self, T: int, lowprec: int, key=None) -> int:
+        """How many steps BEHIND the `lowprec` plain-f16 ones run two-term split-f16 products (EgoHMR.f16x2_steps): 0 -> 0, an int j -> j (at most
+        the T - lowprec split steps), 'auto' -> the j that `calibrate_schedule` measured for `key`, and 0 when there is no calibration for it or when
+        f16x3_last_steps is not 'auto' itself (an explicit k, or None, runs exactly the arithmetic it names)."""
+        m = self.model
+        j = getattr(m, "f16x2_steps", 0)
+        if not j or m.gcn_precision != "f16x3":
+            return 0
+        if j == "auto":
+            info = self._sched_cache.get(key) if (key is not None and m.f16x3_last_steps == "auto") else None
+            j = 0 if info is None else info.get("two_term_steps", 0)
+        return max(0, min(int(j), T - int(lowprec)))
+
+    @staticmethod
+    def pick_two_term(ladder, k, err_a, err_b, bar):
+        """The second search of `calibrate_schedule`: with the last k steps split-f16, how many of them must stay three-term?  Candidates = the
+        entries of the same `ladder` below k, then k itself (= no two-term step: error 0 by definition); `err_a(m)` / `err_b(m)` = error of the
+        schedule [f16 x (T - k)] [two-term x (k - m)] [three-term x m].  Returns j = k - m for the smallest passing m, found like k is (`pick_k`)."""
+        sub = [m for m in ladder if m < k] + [k]
+        return int(k - sub[FusedSampler.pick_k(sub, err_a, err_b, bar)])
 
     @staticmethod
     def _k_ladder(T: int, floor: int = 2):
@@ -465,7 +487,9 @@ class FusedSampler:
         for any weights, so must this be).  Procedure: the first `bodies` items of the batch (conditioning already encoded), two private noise
         draws; bisection over a geometric ladder of k with draw A against tol / 2, then draw B must pass too (k moves up the ladder until
         it does).  k = T (no f16 step at all) always passes, so the result is always safe; cost = ~6-10 small sampling loops, once per
-        (weights, sampler).  Returns the info dict that `schedule_info` / bench.py report."""
+        (weights, sampler).  With EgoHMR.f16x2_steps = 'auto' a second search on the same ladder, draws and criterion then finds the largest j such that the
+        first j of those k steps may run two-term products, a_hi (w_hi + w_lo) (`pick_two_term`; info["two_term_steps"], info["two_term_trials"]; k itself is
+        found first and does not depend on it).  Returns the info dict that `schedule_info` / bench.py report."""
         m = self.model
         if m.gcn_precision != "f16x3":
             raise _lib.EgoHMRHipError("calibrate_schedule: the precision schedule only exists for gcn_precision='f16x3'")
@@ -493,9 +517,9 @@ class FusedSampler:
         nb, dev = st.B, m.device
         sub_batch = dict(batch) if batch is not None else {}
 
-        def loop(noise, lowprec):
+        def loop(noise, lowprec, twoterm=0):
             r = self.run(diffusion, sub_batch, noise, ddim=ddim, guided=guided, cond_grad_weight=cond_grad_weight, prepared=st,
-                         denom_items=denom_items, lowprec=lowprec)
+                         denom_items=denom_items, lowprec=lowprec, twoterm=twoterm)
             o = r["other_outputs"]
             return o["pred_vertices"].clone(), o["pred_keypoints_3d"].clone()
 
@@ -522,7 +546,20 @@ class FusedSampler:
 
         idx = self.pick_k(ladder, lambda k: err(k, 0), err1, 0.5 * tol)
         k = ladder[idx]
-        info = {"k": int(k), "T": int(T), "f16_steps": int(T - k), "tol_m": tol, "criterion": "max vertex/joint distance to the all-f16x3 loop <= tol/2 on two noise draws",
+        # ---- the middle tier: of the k split steps, the first j as two-term products.  Same ladder, same criterion, same draws and references; m = the
+        # three-term steps that remain.  (m = k is j = 0, today's schedule: always passes, so the result is always safe.)
+        tried2, j = {}, 0
+        if getattr(m, "f16x2_steps", 0) == "auto" and k > ladder[0]:
+            def err2(mm, d):
+                if (mm, d) not in tried2:
+                    if d == 1 and len(refs) < 2:
+                        refs.append(loop(draws[1], 0))
+                    tried2[(mm, d)] = 0.0 if mm >= k else dist(loop(draws[d], T - k, k - mm), refs[d])
+                return tried2[(mm, d)]
+            j = self.pick_two_term(ladder, k, lambda mm: err2(mm, 0), lambda mm: err2(mm, 1), 0.5 * tol)
+        info = {"k": int(k), "T": int(T), "f16_steps": int(T - k), "two_term_steps": int(j), "tol_m": tol,
+                "two_term_trials": sorted([{"three_term_steps": mm, "two_term_steps": k - mm, "draw": d, "max_dist_m": e} for (mm, d), e in tried2.items()],
+                                          key=lambda r: (r["three_term_steps"], r["draw"])), "criterion": "max vertex/joint distance to the all-f16x3 loop <= tol/2 on two noise draws",
                 "bodies": int(nb), "ddim": bool(ddim), "guided_steps": int(n_guided),
                 "trials": sorted([{"k": kk, "draw": d, "max_dist_m": e} for (kk, d), e in tried.items()], key=lambda r: (r["k"], r["draw"]))}
         self._sched_cache[key] = info
@@ -607,7 +644,7 @@ class FusedSampler:
     # ------------------------------------------------------------------ whole loop
     @torch.no_grad()
     def run(self, diffusion, batch, noise_stack, ddim=False, guided=False, cond_grad_weight=1.0, trace=False, prepared=None, denom_items=None,
-            defer_status=False, lowprec=None):
+            defer_status=False, lowprec=None, twoterm=None):
         """p_sample_loop / ddim_sample_loop (gaussian_diffusion.py:391-508 / :618-718) in one native call.
         Returns the reference's dict(sample, pred_xstart, other_outputs).  The in-loop guidance is the build's collision proxy: a guided call on a
         model with `collision_model` attached raises (the samplers of diffusion.py route such a loop step by step through model.guide_coll)."""
@@ -619,7 +656,7 @@ class FusedSampler:
                     prepared=prepared, denom_items=denom_items)
         with _lib.on_device(m.device):
             try:
-                return self._run_on_device(**call, defer_status=defer_status, lowprec=lowprec)
+                return self._run_on_device(**call, defer_status=defer_status, lowprec=lowprec, twoterm=twoterm)
             except _lib.EgoHMRRangeError:
                 # an activation left the f16 range and was clamped (status bit 2 of the handle, raised by the conv kernels' stores): never silent.
                 # on_saturation = 'f32': this checkpoint gets float32 activations from now on (exact-f32 MFMA path, ~3x slower) and the call runs again
@@ -629,9 +666,9 @@ class FusedSampler:
                 warnings.warn("egohmr_amd: a denoiser activation reached the f16 range (|x| >= 65504) and was clamped in the split-f16 / f16 path; "
                               "EgoHMR.on_saturation = 'f32': switching this model to gcn_precision = 'f32' and re-running the call", RuntimeWarning)
                 m.gcn_precision = "f32"
-                return self._run_on_device(**call, defer_status=False, lowprec=None)
+                return self._run_on_device(**call, defer_status=False, lowprec=None, twoterm=None)
 
-    def _run_on_device(self, *, diffusion, batch, noise_stack, ddim, guided, cond_grad_weight, trace, prepared, denom_items, defer_status, lowprec):
+    def _run_on_device(self, *, diffusion, batch, noise_stack, ddim, guided, cond_grad_weight, trace, prepared, denom_items, defer_status, lowprec, twoterm):
         m = self.model
         nonlocal_ci = m.diffusion_model.non_local.inter_channels if m.diffusion_model.nonlocal_layer else 0
         if nonlocal_ci and m.gcn_precision == "f16":
@@ -646,12 +683,15 @@ class FusedSampler:
         any_guided = first_guided < T
         tvecs = self.timestep_vectors([diffusion.timestep_map[i] for i in range(T - 1, -1, -1)])   # [T,2,hid]
         if nonlocal_ci:
-            lowprec = 0                                   # the block reads float32 features: no plain-f16 steps
+            lowprec, twoterm = 0, 0                       # the block reads float32 features: no plain-f16 steps (and the loop keeps one arithmetic)
         elif lowprec is None:
-            lowprec = self._scheduled_lowprec(diffusion=diffusion, batch=batch, st=st, ddim=ddim, guided=guided, cond_grad_weight=cond_grad_weight,
-                                              n_guided=T - first_guided, denom_items=denom_items or B)
+            lowprec, twoterm = self._scheduled_lowprec(diffusion=diffusion, batch=batch, st=st, ddim=ddim, guided=guided, cond_grad_weight=cond_grad_weight,
+                                                       n_guided=T - first_guided, denom_items=denom_items or B)
+        twoterm = int(twoterm or 0) if m.gcn_precision == "f16x3" else 0   # (an explicit lowprec without twoterm: no two-term step)
         self.last_lowprec = int(lowprec)                  # leading steps of THIS call on plain f16 operands
-        desc, nbytes = self._describe(st=st, T=T, ddim=ddim, any_guided=any_guided, denom_items=denom_items or B, lowprec=lowprec, nonlocal_ci=nonlocal_ci)
+        self.last_twoterm = twoterm                       # ... and behind them on two-term split-f16 products
+        desc, nbytes = self._describe(st=st, T=T, ddim=ddim, any_guided=any_guided, denom_items=denom_items or B, lowprec=lowprec, nonlocal_ci=nonlocal_ci,
+                                      twoterm=twoterm)
         gcn, smpl_h = self.gcn(), m.smpl.handle()
         launch = partial(self._launch, gcn=gcn, smpl_h=smpl_h, desc=desc, steps=steps, nbytes=nbytes, any_guided=any_guided)
         ins = dict(h_img=st.h_img, h_oth=st.h_oth, vis=st.vis, tvecs=tvecs, noise=noise[: T + 1].contiguous(), betas=st.betas, scene=st.scene)
@@ -666,7 +706,8 @@ class FusedSampler:
         return self._finish(batch=batch, st=st, o=o, tr=tr, noise=noise, T=T, guided_ddim=ddim and any_guided, gcn=gcn, defer_status=defer_status)
 
     def _scheduled_lowprec(self, *, diffusion, batch, st, ddim, guided, cond_grad_weight, n_guided, denom_items):
-        """Leading plain-f16 steps by EgoHMR.f16x3_last_steps; 'auto' = the k calibrated for THESE weights and THIS sampler, measured now if need be."""
+        """(leading plain-f16 steps, two-term steps behind them) by EgoHMR.f16x3_last_steps / f16x2_steps; 'auto' = the k and j calibrated for THESE
+        weights and THIS sampler, measured now if need be."""
         m, skey = self.model, None
         if m.f16x3_last_steps == "auto" and m.gcn_precision == "f16x3":
             skey = self.schedule_key(diffusion, ddim, n_guided, cond_grad_weight, self.guide_denom(denom_items))
@@ -674,9 +715,10 @@ class FusedSampler:
                 self.calibrate_schedule(diffusion, batch, ddim=ddim, guided=guided, cond_grad_weight=cond_grad_weight, prepared=st,
                                         denom_items=denom_items, n_guided=n_guided)
             self.schedule_info = self._sched_cache.get(skey)
-        return self.lowprec_steps(diffusion.num_timesteps, n_guided, ddim, key=skey)
+        lowprec = self.lowprec_steps(diffusion.num_timesteps, n_guided, ddim, key=skey)
+        return lowprec, self.twoterm_steps(diffusion.num_timesteps, lowprec, key=skey)
 
-    def _describe(self, *, st, T, ddim, any_guided, denom_items, lowprec, nonlocal_ci):
+    def _describe(self, *, st, T, ddim, any_guided, denom_items, lowprec, nonlocal_ci, twoterm=0):
         """(the loop's descriptor, its workspace size) after giving the handle this batch's pass map."""
         m = self.model
         passes = 2 if m.diffuse_fuse else 1
@@ -684,7 +726,7 @@ class FusedSampler:
         desc = _lib.SampleDesc(B=st.B, passes=passes, num_steps=T, ddim=int(ddim), per_step_launches=int(bool(m.per_step_launches)),
                                lbs_every_step=int(m.lbs_every_step), num_scene_points=st.scene.shape[1] if any_guided else 0,
                                guide_denom=self.guide_denom(denom_items), tau=m.collision_tau, num_masked=num_masked,
-                               guide_all_points=int(bool(m.guide_all_points)), lowprec_steps=int(lowprec), nonlocal_ci=int(nonlocal_ci))
+                               guide_all_points=int(bool(m.guide_all_points)), lowprec_steps=int(lowprec), nonlocal_ci=int(nonlocal_ci), twoterm_steps=int(twoterm))
         return desc, _lib.api().ehm_sample_workspace_bytes(C.byref(desc), m.diffusion_model.hid_dim, m.smpl.num_verts)
 
     def _out_bufs(self, B):
@@ -706,7 +748,7 @@ class FusedSampler:
         mean, std = m._std_mean()
         # (every pointer the captured launches bake in that is not inside `bufs`: the two native handles - by serial, a recreated handle
         # can reuse a destroyed one's address - and the mean / std buffers)
-        key = (st.B, desc.num_steps, desc.ddim, desc.passes, desc.lbs_every_step, desc.lowprec_steps, m.gcn_precision, gcn.serial,
+        key = (st.B, desc.num_steps, desc.ddim, desc.passes, desc.lbs_every_step, desc.lowprec_steps, desc.twoterm_steps, m.gcn_precision, gcn.serial,
                bytes(steps), st.scene.shape[1], desc.num_masked, smpl_h.serial,
                mean.data_ptr(), std.data_ptr(), self._folded.Wx.data_ptr(), self._nl_set)
         ent = self._graphs.get(key)

@@ -628,6 +628,10 @@ class EgoHMR(nn.Module):
         # responsibility; None = off.  There is no constant default: whether early rounding errors are contracted away depends on
         # d x0 / d x_t of the checkpoint.
         self.f16x3_last_steps = "auto"
+        # middle tier of the schedule: of those k steps the FIRST j run two-term products, a_hi * (w_hi + w_lo) - 2 MFMAs per product
+        # instead of 3, same X2 buffers.  'auto' = the j that calibrate_schedule measured behind k (same criterion, same ladder; only when
+        # f16x3_last_steps is 'auto' too: an explicit k or None leaves j = 0); an int = that j (capped at k), on the caller's responsibility; 0 = off.
+        self.f16x2_steps = "auto"
         self.schedule_tol = 1e-5           # metres, max vertex / joint distance to the all-f16x3 loop (the north-star bar is 1e-4)
         self.auto_calibrate = True
         # hipGraph replay of the whole T-step loop (one graph launch instead of ~5 T kernel launches), unguided loops only.  Off by

@@ -114,13 +114,18 @@ void ehm_gcn_destroy(ehm_gcn* h);
 /* Arithmetic of the hidden convs (docs/EXPERIMENTS.md 3.2).  0 = f32-input MFMA (exact f32 products; what a fresh handle is in);
  * 1 = "f16x3": f16 MFMA on hi/lo-split operands, three products per term, f32 accumulate (22-bit operands,
  * f32-grade results); 2 = plain f16 operands and f16 activation storage (NOT parity-grade on its own - BASELINE config 5's
- * fp16 denoiser, and the early steps of ehm_sample_desc.lowprec_steps).
+ * fp16 denoiser, and the early steps of ehm_sample_desc.lowprec_steps);
+ * 3 = "f16x2": mode 1's operands, buffers and activation formats bit for bit, but TWO products per term: a_hi * (w_hi + w_lo) - the
+ * activations enter as their f16 hi halves, the weights in full (the al * wh MFMAs are not issued: 2/3 of mode 1's matrix work).  The stores
+ * still write hi + lo, so a mode-1 conv behind it reads full operands.  Not parity-grade on its own either: the middle tier of the
+ * calibrated precision schedule (ehm_sample_desc.twoterm_steps).
  * Activation matrices exchanged between ehm_gcn_input_layer -> ehm_gcn_hidden_layer / _stack: mode 0 float32 [rows_pad,hid];
  * mode 1 the opaque "X2" split format (same byte size), except that the LAST hidden conv writes float32 (with no hidden conv: the input conv); mode 2 f16
  * [rows_pad,hid] throughout.  ehm_gcn_output_layer reads what the handle's mode produces.  ehm_gcn_pack/unpack_activations convert float32 <-> the mode's format (tests, interop). */
+enum { EHM_PREC_F32 = 0, EHM_PREC_F16X3 = 1, EHM_PREC_F16 = 2, EHM_PREC_F16X2 = 3 };
 int ehm_gcn_set_precision(ehm_gcn* h, int mode);
 int ehm_gcn_get_precision(const ehm_gcn* h);
-/* group = ehm_gcn_activation_group(h): 32 = X2 split format (mode 1), 0 = plain f16 (mode 2); pass it to pack / unpack */
+/* group = ehm_gcn_activation_group(h): 32 = X2 split format (modes 1 and 3), 0 = plain f16 (mode 2); pass it to pack / unpack */
 int ehm_gcn_activation_group(const ehm_gcn* h);
 /* Size the handle's internal scratch (chained-launch counters, output-conv responses) for batches of up to max_bodies bodies x
  * passes.  ehm_gcn_create reserves 256 x 2; a larger batch grows the scratch on first use (a hipMalloc - so call this first when
@@ -737,6 +742,9 @@ typedef struct {
   int per_step_launches; /* 0 (default) = two launches per step: chained hidden convs, then step_fused_kernel (output responses + per-body
                          update + the next step's input conv); 1 = the separate launches of rounds 2-3 (input conv, chain, responses, per-body
                          step) - same bits, kept for A/B runs and the bit-equality tests                                                      */
+  int twoterm_steps;  /* precision schedule, middle tier: executed steps [lowprec_steps, lowprec_steps + twoterm_steps) of a mode-1 loop run
+                         the hidden convs as two-term products (ehm_gcn_set_precision mode 3: same X2 buffers, no format transition); 0 = off.
+                         Needs handle mode 1 and no non-local block; lowprec_steps + twoterm_steps <= num_steps                               */
 } ehm_sample_desc;
 
 /* GaussianDiffusion.p_sample_loop / ddim_sample_loop (gaussian_diffusion.py:391-508, :618-718)
@@ -775,7 +783,8 @@ enum {
   EHM_PROF_G_POSEFEAT_BWD = 12, /* inside EHM_PROF_GUIDANCE: posefeat_bwd_kernel ([B, 20670] x [20670, 207] contraction) */
   EHM_PROF_STEP_FUSED = 13,  /* step_fused_kernel: a step's output responses + per-body update + the NEXT step's input conv, one block per body */
   EHM_PROF_G_NEAREST_EVALS = 14, /* not a launch class: launches[14] = point-to-vertex distance evaluations of nearest_grid_kernel while the profile was open (ms[14] = 0) */
-  EHM_PROF_N = 15
+  EHM_PROF_CHAIN_F16X2 = 15, /* gcn_hidden_chain_kernel<2, 4>: the 8 hidden convs of a two-term step (ehm_sample_desc.twoterm_steps)                */
+  EHM_PROF_N = 16
 };
 int ehm_profile_begin(void);
 int ehm_profile_end(double* ms, int64_t* launches, int n);
