@@ -326,8 +326,9 @@ class GaussianDiffusion:
 
     def training_losses(self, model, batch, t, cur_epoch=0, noise=None):
         raise NotImplementedError("training_losses (gaussian_diffusion.py:721-746) is not built: EgoHMR.compute_loss has a backward and EgoHMR.decode_output "
-                                  "chains x_0 -> SMPL -> loss, but model(batch, t) itself carries no graph (the encoders' backward and the non-local block's "
-                                  "backward are missing; train-mode BatchNorm exists behind ModulatedGCN.train_batchnorm)")
+                                  "chains x_0 -> SMPL -> loss, but model(batch, t) itself carries no graph (the ResNet-50 trunk's backward, the non-local block's "
+                                  "backward and the wiring of EgoHMR.forward are missing; the scene PointNet and ModulatedGCN have theirs, train-mode "
+                                  "BatchNorm exists behind ModulatedGCN.train_batchnorm)")
 
     def val_losses(self, model, batch, shape, clip_denoised=True, progress=False, cond_fn_with_grad=False, cond_grad_weight=1.0,
                    cur_epoch=0, timestep_respacing="", compute_loss=True, noise_stack=None):

@@ -278,6 +278,11 @@ class ResnetPointnet(nn.Module):
     into bias vectors, fc_1 + shortcut fused into one dual-source GEMM and the max-pool fused into its epilogue."""
 
     hi_only = False      # True: the plain-f16 tier (ehm_linear_desc.hi_only) - NOT parity grade
+    # False: an autograd call (grad mode on, p.requires_grad) differentiates w.r.t. p only and leaves the parameters' .grad alone; True: the backward
+    # also fills the 24 parameters' gradients (grad_parameters()).  Calls with no gradient to compute run the chained route either way.
+    grad_params = False
+    GRAD_HI_ONLY = ("the autograd route of ResnetPointnet.forward keeps f32-grade activations for its backward; the plain-f16 tier "
+                    "(ResnetPointnet.hi_only = True) stores none: set hi_only = False with it")
 
     def __init__(self, out_dim=512, hidden_dim=256):
         super().__init__()
@@ -287,6 +292,15 @@ class ResnetPointnet(nn.Module):
             setattr(self, f"block_{b}", _ResBlockFC(2 * hidden_dim, hidden_dim, hidden_dim))
         self.fc_c = nn.Linear(hidden_dim, out_dim)
         self._packed = self._packed_key = self._tkey = None
+        self._grad_packed = self._grad_packed_key = None                                 # pointnet_grad._weights
+
+    def grad_parameters(self):
+        """The parameters the autograd route delivers gradients to with `grad_params`, in the order of its backward (pointnet_grad.PARAM_NAMES)."""
+        from .pointnet_grad import PARAM_NAMES
+        return [self.get_parameter(n) for n in PARAM_NAMES]
+
+    def _wants_grad(self, p):
+        return torch.is_grad_enabled() and (p.requires_grad or (self.grad_params and any(q.requires_grad for q in self.grad_parameters())))
 
     # ------------------------------------------------------------------ weight preparation (once per weight version)
     @staticmethod
@@ -330,14 +344,22 @@ class ResnetPointnet(nn.Module):
         self._packed, self._packed_key = P, key
         return P
 
-    @torch.no_grad()
     def forward(self, p):
+        """With grad mode on and p.requires_grad - or `grad_params` set and a parameter that requires grad - the result carries a grad_fn: the same
+        launches, every block's relu(h) and net kept for the backward (pointnet_grad.PointnetFunction).  Every other call: the ping-pong route."""
         if not p.is_cuda:
             raise _lib.EgoHMRHipError("ResnetPointnet runs on the HIP kernels only (got a CPU tensor); there is no CPU path")
-        with _lib.on_device(p.device):                                                   # the library launches on the CURRENT device's stream
+        if self._wants_grad(p):
+            if self.hi_only:
+                raise _lib.EgoHMRHipError(self.GRAD_HI_ONLY)
+            from . import pointnet_grad
+            return pointnet_grad.PointnetFunction.apply(self, p, *(self.grad_parameters() if self.grad_params else ()))
+        with torch.no_grad(), _lib.on_device(p.device):                                  # the library launches on the CURRENT device's stream
             return self._forward_on_device(p)
 
-    def _forward_on_device(self, p):
+    def _forward_on_device(self, p, save=False):
+        """save: keep what the backward reads instead of ping-ponging it - every block's relu(h) and net (the last block's net is stored too) - and
+        return (out, saved).  The launches and their descriptors are the same otherwise: the output has the same bits."""
         A, P_, dev, H = _lib.api(), _lib.ptr, p.device, self.hidden_dim
         P = self._prepare(dev)
         p = _lib.f32(p)
@@ -346,7 +368,9 @@ class ResnetPointnet(nn.Module):
         M = B * Np
         st = _lib.stream_ptr()
         f32buf = lambda cols: torch.empty(M, cols, dtype=torch.float32, device=dev)      # X2 buffers (same bytes as float32)
-        P32, Hb, netA, netB = f32buf(32), f32buf(H), f32buf(H), f32buf(H)
+        P32, Hb, netA = f32buf(32), f32buf(H), f32buf(H)
+        netB = f32buf(H) if not save else None
+        rhs, nets = [Hb], [netA]                                                         # (save) the blocks' relu(h) and net
         p = p.contiguous()
         A.ehm_pointnet_lift(p, None, None, None, P32, B, N, Np, 2 * H, st)
 
@@ -379,9 +403,16 @@ class ResnetPointnet(nn.Module):
         for i in (1, 2, 3):
             # pooled halves of fc_0(relu(cat[net, pooled])) and of shortcut(cat[net, pooled]): one launch, [B, 2H]
             vs = small(pooled, P[f"wvsT_{i}"], P[f"bvs_{i}"], relu_in_cols=H)
+            if save:
+                Hb, nxt = f32buf(H), f32buf(H)
+                rhs.append(Hb)
+                nets.append(nxt)
             gemm(cur, H, None, 0, P[f"g1_{i}"], None, (vs, 0), Hb, None, True, True)
             pooled = pooled_all[i]
-            gemm(Hb, H, cur, H, P[f"g3_{i}"], P[f"g3_{i}"][3], (vs, H), nxt if i < 3 else None, pooled, False, False)
+            gemm(Hb, H, cur, H, P[f"g3_{i}"], P[f"g3_{i}"][3], (vs, H), nxt if (i < 3 or save) else None, pooled, False, False)
             cur, nxt = nxt, cur
-        return small(pooled, P["fc_cT"], P["fc_cb"], relu_in_cols=P["fc_cT"].shape[1])
+        out = small(pooled, P["fc_cT"], P["fc_cb"], relu_in_cols=P["fc_cT"].shape[1])
+        if save:
+            return out, dict(p=p, B=B, N=N, Np=Np, rh=rhs, net=nets, pooled=pooled_all, arg=None)
+        return out
 

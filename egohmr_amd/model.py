@@ -1029,9 +1029,10 @@ class EgoHMR(nn.Module):
         }
 
     def training_step(self, *a, **k):
-        raise NotImplementedError("training_step is not built: compute_loss has a backward (the loss, SMPL.forward, rot6d_to_rotmat and ModulatedGCN.forward "
-                                  "are differentiable, ModulatedGCN.train_batchnorm runs BatchNorm in training mode; decode_output chains them), but the "
-                                  "conditioning encoders' backward and the non-local block's backward are missing")
+        raise NotImplementedError("training_step is not built: compute_loss has a backward (the loss, SMPL.forward, rot6d_to_rotmat, ModulatedGCN.forward "
+                                  "and ResnetPointnet.forward are differentiable, ModulatedGCN.train_batchnorm runs BatchNorm in training mode; decode_output "
+                                  "chains them), but the ResNet-50 trunk's backward, the non-local block's backward and the wiring of EgoHMR.forward "
+                                  "(FusedSampler.prepare carries no graph) are missing")
 
 
 class EgoHMRVolsmpl(EgoHMR):

@@ -1,5 +1,6 @@
 """Eager PyTorch (MIOpen / hipBLASLt) forward of the ResNet-50 trunk for the yardstick tools ONLY: the package's modules have no eager route
 (ResNet50Features.forward is the HIP path).  Works on the package's parameter containers."""
+import torch
 import torch.nn.functional as F
 
 
@@ -21,6 +22,17 @@ def resnet50_eager(net, x):
             s = x if b.downsample is None else _bn(_conv(x, b.downsample[0]), b.downsample[1])
             x = F.relu(y + s)
     return x.mean(dim=(2, 3))
+
+
+def resnet_pointnet_eager(net, p):
+    """respointnet.py:33-59 on the package's ResnetPointnet parameter container: eager float32 ops, differentiable through torch's own autograd."""
+    x = F.linear(p, net.fc_pos_0.weight, net.fc_pos_0.bias)
+    for i in range(4):
+        b = getattr(net, f"block_{i}")
+        if i:
+            x = torch.cat([x, x.max(dim=1, keepdim=True)[0].expand(x.size())], dim=2)
+        x = F.linear(F.relu(F.linear(F.relu(x), b.fc_0.weight, b.fc_0.bias)), b.fc_1.weight, b.fc_1.bias) + F.linear(x, b.shortcut.weight)
+    return F.linear(F.relu(x.max(dim=1)[0]), net.fc_c.weight, net.fc_c.bias)
 
 
 SMPL_TO_OPENPOSE = [24, 12, 17, 19, 21, 16, 18, 20, 0, 2, 5, 8, 1, 4, 7, 25, 26, 27, 28, 29, 30, 31, 32, 33, 34]
