@@ -16,6 +16,7 @@ import torch.nn as nn
 import torch.nn.functional as F
 
 from . import _lib
+from .split_gemm import weight_scale
 
 
 # measurement hook (tools/exp_encoder_precision.py): called with every X2 activation buffer an encoder kernel has just written, (buffer, channels).
@@ -110,7 +111,6 @@ class ResNet50Features(nn.Module):
         convolutions (ehm_conv_nhwc_split - the kernel the non-local GCN block also uses; kept as a second implementation the tests
         compare).  HIP tensors only: there is no eager / library-convolution route."""
         import ctypes as C
-        import math
 
         A, P = _lib.api(), _lib.ptr
 
@@ -139,8 +139,7 @@ class ResNet50Features(nn.Module):
             Co_pad = (Co + 127) // 128 * 128
             w2 = torch.zeros(Co_pad, K, device=w.device)
             w2[:Co] = w.permute(0, 2, 3, 1).reshape(Co, K)
-            amax = float(w2.abs().max())
-            scale = 2.0 ** math.floor(math.log2(2048.0 / amax)) if amax > 0 else 1.0
+            scale = weight_scale(float(w2.abs().max()))
             buf = torch.empty(Co_pad, K, device=w.device)              # X2 rows have the byte size of float rows
             A.ehm_split_pack(w2, buf, Co_pad, K, K, scale, _lib.stream_ptr())
             packed[id(w)] = (buf, scale, p[1].contiguous(), (Co, Ci, KH, KW), p[2][0], p[3][0])
@@ -189,8 +188,7 @@ class ResNet50Features(nn.Module):
             assert w.shape[2:] == (1, 1) and wd.shape[2:] == (1, 1) and wd.shape[0] == Co and Co % 128 == 0
             K = Ci + wd.shape[1]
             w2 = torch.cat([w.reshape(Co, Ci), wd.reshape(Co, -1)], dim=1).contiguous()
-            amax = float(w2.abs().max())
-            scale = 2.0 ** math.floor(math.log2(2048.0 / amax)) if amax > 0 else 1.0
+            scale = weight_scale(float(w2.abs().max()))
             buf = torch.empty(Co, K, device=w.device)
             A.ehm_split_pack(w2, buf, Co, K, K, scale, _lib.stream_ptr())
             packed[key] = (buf, scale, (p[1].double() + ds[1].double()).float().contiguous(), (Co, Ci, 1, 1), p[2][0], p[3][0], wd.shape[1], ds[2][0])
@@ -305,7 +303,8 @@ class ResnetPointnet(nn.Module):
     # ------------------------------------------------------------------ weight preparation (once per weight version)
     @staticmethod
     def _pack(w64: torch.Tensor, device):
-        """float64 [N,K] -> (X2 buffer, power-of-two scale); K padded to a multiple of 32."""
+        """float64 [N,K] -> (X2 buffer, power-of-two scale); K padded to a multiple of 32.  Its scale rule is not split_gemm.weight_scale (at
+        amax = 1.5 it gives 2048, that one 1024): unifying them would change the forward's bits."""
         w = w64.float().contiguous().to(device)
         N, K = w.shape
         Kp = (K + 31) // 32 * 32

@@ -138,9 +138,10 @@ class FusedSampler:
         if A.ehm_gcn_get_precision(self._gcn) != mode:
             A.ehm_gcn_set_precision(self._gcn, mode)
         if self.model.diffusion_model.nonlocal_layer:       # the one-call loop runs the block natively (ehm_gcn_set_nonlocal)
-            ((wq, sq, bq), (wo, so, bo)), nl_key = self.model.diffusion_model.nonlocal_packed()
+            (q, o), nl_key = self.model.diffusion_model.nonlocal_packed()
             if self._nl_set != (nl_key, self._gcn.serial):
-                p = _lib.NonlocalParams(_lib.ptr(wq), _lib.ptr(bq), sq, _lib.ptr(wo), _lib.ptr(bo), so, self.model.diffusion_model.non_local.inter_channels)
+                p = _lib.NonlocalParams(_lib.ptr(q.buf), _lib.ptr(q.bias), q.scale, _lib.ptr(o.buf), _lib.ptr(o.bias), o.scale,
+                                        self.model.diffusion_model.non_local.inter_channels)
                 A.ehm_gcn_set_nonlocal(self._gcn, C.byref(p))
                 self._nl_set = (nl_key, self._gcn.serial)
         return self._gcn

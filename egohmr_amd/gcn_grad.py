@@ -1,10 +1,10 @@
 """Backward of the Modulated-GCN denoiser's graph convs on libegohmr_hip (csrc/gcn_bwd.hip + the split-f16 GEMM engine), and the
-``torch.autograd.Function`` that ModulatedGCN.forward runs behind when a gradient is asked for (model.py).
+``torch.autograd.Function``s that ModulatedGCN.forward runs behind when a gradient is asked for (model.py), with their forwards.
 
 One conv (modulated_gcn_conv.py:39-50 + BatchNorm1d(eval) + ReLU + residual, modulated_gcn.py:21-28, :38-42), X [rows, K] -> out [rows, N]:
 
     G [rows, 2N] = [h0bar | h1bar]             ehm_gcn_bwd_epilogue          (gate, BatchNorm factor, transposed adjacency mix, modulation)
-    Xbar = G [W0; W1]^T                        ehm_conv_nhwc_split, H = W = 1 (float32 rows x ehm_split_pack'ed weights)
+    Xbar = G [W0; W1]^T                        ehm_conv_nhwc_split, H = W = 1 (split_gemm.gemm_rows: float32 rows x ehm_split_pack'ed weights)
     [W0bar | W1bar] = X^T G                    the same engine: X^T as the rows, G^T packed at run time as the weight operand
     pre = X [W0 | W1]                          the same engine (recomputed, not kept by the forward)
     Mbar, adj2bar, biasbar, gammabar, betabar  ehm_gcn_bwd_params            (fixed-order sums)
@@ -16,58 +16,25 @@ computed on the device: no host synchronisation.
 from __future__ import annotations
 
 import ctypes as C
-import math
 
 import torch
 
 from . import _lib
+from .fused import PRECISIONS
+from .split_gemm import Packed, gemm_rows, pack_weight, pad_cols, pow2_scale, round_up
 
 INPUT, OUTPUT = _lib.GCN_CONV_INPUT, _lib.GCN_CONV_OUTPUT
 
 
-def _up(n, m):
-    return (n + m - 1) // m * m
-
-
-def pack_weight(w2):
-    """float32 [Co, K] on a HIP device -> (ehm_split_pack'ed [Co padded to 128, K padded to 32], its power-of-two scale, Co rounded up to 8 = the
-    column count ehm_conv_nhwc_split writes for it)."""
-    Co, K = w2.shape
-    wp = torch.zeros(_up(Co, 128), _up(K, 32), device=w2.device)
-    wp[:Co, :K] = w2
-    amax = float(wp.abs().max())
-    scale = 2.0 ** math.floor(math.log2(2048.0 / amax)) if 0.0 < amax < float("inf") else 1.0
-    buf = torch.empty_like(wp)
-    _lib.api().ehm_split_pack(wp, buf, wp.shape[0], wp.shape[1], wp.shape[1], scale, _lib.stream_ptr())
-    return buf, scale, _up(Co, 8)
-
-
-def gemm_rows(x, packed, rows=None):
-    """x [M, Ci] float32 (Ci a multiple of 32, contiguous) times a pack_weight() operand -> [rows or M, Co8] float32 (ehm_conv_nhwc_split, H = W = 1)."""
-    buf, scale, co = packed
-    M = x.shape[0] if rows is None else rows
-    y = torch.empty(M, co, device=x.device)
-    d = _lib.ConvDesc(_lib.ptr(x), _lib.ptr(buf), None, None, _lib.ptr(y), M, 1, 1, x.shape[1], co, 1, 1, 1, 0, 0, scale)
-    _lib.api().ehm_conv_nhwc_split(C.byref(d), _lib.stream_ptr())
-    return y
-
-
-def pow2_scale(t, target=1024.0):
-    """0-d device tensor: the power of two that brings max|t| into [target/2, target]; 1 for an all-zero or non-finite t.  No host read-back."""
-    lo, hi = torch.aminmax(t)                                   # one pass, no |t| temporary
-    a = torch.maximum(-lo, hi)
-    s = torch.exp2(torch.floor(torch.log2(target / a)))
-    return torch.where((a > 0) & torch.isfinite(s) & (s > 0), s, torch.ones_like(s))
-
-
 class ConvWeights:
-    """The two packed GEMM operands of one conv's backward, made on first use from W [2, K, N] (the engine contracts over an operand's columns):
-    `bwd` = [W0 | W1] as [K, 2N] for Xbar = G [W0; W1]^T, `fwd` = its transpose [2N, K] for the recompute X [W0 | W1]."""
+    """The two packed GEMM operands of one conv, made on first use from W [2, K, N] (the engine contracts over an operand's columns):
+    `fwd` = [W0 | W1]^T as [2N, K] for X [W0 | W1] (the input conv's forward, the backward's recompute), `bwd` = its transpose [K, 2N] for
+    Xbar = G [W0; W1]^T."""
 
     def __init__(self, W):
         self.W = W.detach()
         self.K, self.N = W.shape[1], W.shape[2]
-        self.ldg = _up(2 * self.N, 32)          # row length of G: the K granule of the engine
+        self.ldg = round_up(2 * self.N, 32)          # row length of G: the K granule of the engine
         self._fwd = self._bwd = None
 
     @property
@@ -83,13 +50,12 @@ class ConvWeights:
         return self._bwd
 
 
-def _new_G(rows, cw, dev):
-    return torch.empty(rows, cw.ldg, device=dev) if cw.ldg == 2 * cw.N else torch.zeros(rows, cw.ldg, device=dev)
-
-
-def _gemm_grads(G, cw, X, rows, need_x, need_w, out, res):
-    """The two GEMMs behind a backward epilogue's G = [h0bar | h1bar]: res['x'] = G [W0; W1]^T (need_x), res['W'] = X^T G (need_w)."""
-    A, s, N, K, dev = _lib.api(), _lib.stream_ptr(), cw.N, cw.K, G.device
+def _gemm_grads(epilogue, cw, X, rows, need_x, need_w, out, res):
+    """epilogue(G) writes a conv's G = [h0bar | h1bar] [rows, cw.ldg]; then the two GEMMs behind it: res['x'] = G [W0; W1]^T (need_x),
+    res['W'] = X^T G (need_w)."""
+    A, s, N, K, dev = _lib.api(), _lib.stream_ptr(), cw.N, cw.K, X.device
+    G = torch.empty(rows, cw.ldg, device=dev) if cw.ldg == 2 * N else torch.zeros(rows, cw.ldg, device=dev)
+    epilogue(G)
     sc = pow2_scale(G)
     G.mul_(sc)
     inv = 1.0 / sc
@@ -97,20 +63,34 @@ def _gemm_grads(G, cw, X, rows, need_x, need_w, out, res):
         xb = gemm_rows(G, cw.bwd).mul_(inv)        # [rows, K rounded up to the engine's 8-column granule]
         res["x"] = xb if xb.shape[1] == K else xb[:, :K].contiguous()
     if need_w:
-        rp = _up(rows, 32)                         # the contraction runs over the rows: padded to the engine's K granule with zeros
+        rp = round_up(rows, 32)                         # the contraction runs over the rows: padded to the engine's K granule with zeros
         alloc = lambda r: torch.empty(r, rp, device=dev) if rp == rows else torch.zeros(r, rp, device=dev)
         Xt = alloc(X.shape[1])
         Xt[:, :rows] = X[:rows].t()
-        Gt = alloc(2 * N) if 2 * N % 128 == 0 else torch.zeros(_up(2 * N, 128), rp, device=dev)
+        Gt = alloc(2 * N) if 2 * N % 128 == 0 else torch.zeros(round_up(2 * N, 128), rp, device=dev)
         Gt[:2 * N, :rows] = G[:, :2 * N].t()
         Gp = torch.empty_like(Gt)
         A.ehm_split_pack(Gt, Gp, Gt.shape[0], rp, rp, 1.0, s)
-        Wg = gemm_rows(Xt, (Gp, 1.0, _up(2 * N, 8)))[:K, :2 * N].mul_(inv)          # [K, 2N]
+        Wg = gemm_rows(Xt, Packed(Gp, 1.0, round_up(2 * N, 8), None))[:K, :2 * N].mul_(inv)          # [K, 2N]
         gW = out.get("W")
         if gW is None:
             gW = torch.empty(2, K, N, device=dev)
         gW.copy_(Wg.reshape(K, 2, N).permute(1, 0, 2))
         res["W"] = gW
+
+
+def _param_bufs(names, N, out, dev):
+    """The named parameter gradients' tensors: those preallocated in `out`, else new ones."""
+    shapes = dict(M=(24, N), adj2=(24, 24), bias=(N,), bn_weight=(N,), bn_bias=(N,))
+    return {k: out[k] if out.get(k) is not None else torch.empty(shapes[k], device=dev) for k in names}
+
+
+def _recompute(query, h, conv, cw, X, bodies):
+    """(pre = X [W0 | W1], float32 workspace of a parameter-gradient kernel, its byte size as `query` gives it)"""
+    pre = gemm_rows(X, cw.fwd, bodies * 24)
+    nb = C.c_int64(0)
+    query(h, conv, bodies, C.byref(nb))
+    return pre, torch.empty(nb.value // 4, device=X.device), nb.value
 
 
 def conv_backward(h, conv, cw, X, gate, gout, bodies, need_x=True, need_w=False, need_params=False, has_bn=True, out=None):
@@ -121,88 +101,19 @@ def conv_backward(h, conv, cw, X, gate, gout, bodies, need_x=True, need_w=False,
     'W' [2, K, N] (need_w) and 'M', 'adj2', 'bias' (+ 'bn_weight', 'bn_bias' when has_bn) (need_params).  `out` may hold preallocated tensors for
     the parameter gradients under those names; what is not asked for is neither computed nor written.  The residual's gradient is gout itself."""
     A, s = _lib.api(), _lib.stream_ptr()
-    rows, N, K, dev = bodies * 24, cw.N, cw.K, gout.device
     out = {} if out is None else out
     res = {}
     if need_x or need_w:
-        G = _new_G(rows, cw, dev)
-        A.ehm_gcn_bwd_epilogue(h, conv, gout, gate, G, cw.ldg, bodies, s)
-        _gemm_grads(G, cw, X, rows, need_x, need_w, out, res)
+        _gemm_grads(lambda G: A.ehm_gcn_bwd_epilogue(h, conv, gout, gate, G, cw.ldg, bodies, s), cw, X, bodies * 24, need_x, need_w, out, res)
     if need_params:
-        pre = gemm_rows(X, cw.fwd, rows)
-        nb = C.c_int64(0)
-        A.ehm_gcn_bwd_params_workspace_bytes(h, conv, bodies, C.byref(nb))
-        ws = torch.empty(nb.value // 4, device=dev)
-        names = ("M", "adj2", "bias") + (("bn_weight", "bn_bias") if has_bn else ())
-        shapes = dict(M=(24, N), adj2=(24, 24), bias=(N,), bn_weight=(N,), bn_bias=(N,))
-        g = {k: out[k] if out.get(k) is not None else torch.empty(shapes[k], device=dev) for k in names}
-        A.ehm_gcn_bwd_params(h, conv, gout, gate, pre, pre.shape[1], bodies, g["M"], g["adj2"], g["bias"], g.get("bn_weight"), g.get("bn_bias"),
-                             ws, nb.value, s)
+        pre, ws, nb = _recompute(A.ehm_gcn_bwd_params_workspace_bytes, h, conv, cw, X, bodies)
+        g = _param_bufs(("M", "adj2", "bias") + (("bn_weight", "bn_bias") if has_bn else ()), cw.N, out, gout.device)
+        A.ehm_gcn_bwd_params(h, conv, gout, gate, pre, pre.shape[1], bodies, g["M"], g["adj2"], g["bias"], g.get("bn_weight"), g.get("bn_bias"), ws, nb, s)
         res.update(g)
     return res
 
 
 PARAMS_PER_CONV = ("W", "M", "adj2", "bias", "bn_weight", "bn_bias")
-
-
-class GCNFunction(torch.autograd.Function):
-    """ModulatedGCN.forward (modulated_gcn.py:99-116, eval mode) with a backward: forward(module, x, *params) -> [B, 24, 6].  `params` is empty (gradient
-    to x only) or ModulatedGCN.grad_parameters(): W, M, adj2, bias, bn.weight, bn.bias of the input conv and every hidden conv, then W, M, adj2, bias
-    of the output conv."""
-
-    @staticmethod
-    def forward(ctx, module, x, *params):
-        out, saved = module._forward_saving(x)
-        ctx.module, ctx.saved, ctx.n_params = module, saved, len(params)
-        return out
-
-    @staticmethod
-    @torch.autograd.function.once_differentiable
-    def backward(ctx, gout):
-        m, sv = ctx.module, ctx.saved
-        need = ctx.needs_input_grad
-        need_x, pneed = need[1], need[2:]
-        dev = gout.device
-        B, hid, nh = sv["B"], m.hid_dim, 2 * m.num_layers
-        grads = [None] * ctx.n_params
-
-        def wants(ci, nparams=6):          # (need_w, need_params) of conv number ci in the parameter list
-            if not pneed:
-                return False, False
-            f = pneed[6 * ci: 6 * ci + nparams]
-            return bool(f[0]), any(f[1:])
-
-        def put(ci, r, has_bn):
-            for k, name in enumerate(PARAMS_PER_CONV if has_bn else PARAMS_PER_CONV[:4]):
-                if name in r and pneed[6 * ci + k]:
-                    grads[6 * ci + k] = r[name]
-
-        with _lib.on_device(dev):
-            h, cws = sv["h"], m._conv_weights(dev)
-            g = _lib.f32(gout, dev).reshape(B * 24, 6)
-            # the output conv
-            nw, npar = wants(nh + 1, 4)
-            r = conv_backward(h, OUTPUT, cws[nh + 1], sv["acts"][nh], None, g, B, True, nw, npar, has_bn=False)
-            put(nh + 1, r, False)
-            g = r["x"]
-            # the residual blocks, last first: out = y2 + block input, y2 = gconv2(y1), y1 = gconv1(block input)
-            for blk in reversed(range(m.num_layers)):
-                l1, l2 = 2 * blk, 2 * blk + 1
-                nw, npar = wants(l2 + 1)
-                r2 = conv_backward(h, l2, cws[l2 + 1], sv["ys"][l1 + 1], sv["ys"][l2 + 1], g, B, True, nw, npar)
-                put(l2 + 1, r2, True)
-                nw, npar = wants(l1 + 1)
-                r1 = conv_backward(h, l1, cws[l1 + 1], sv["acts"][l1], sv["ys"][l1 + 1], r2["x"], B, True, nw, npar)
-                put(l1 + 1, r1, True)
-                g = r1["x"].add_(g)                         # + the residual's gradient
-            nw, npar = wants(0)
-            gx = None
-            if need_x or nw or npar:
-                r = conv_backward(h, INPUT, cws[0], sv["xp"], sv["ys"][0], g, B, need_x, nw, npar)
-                put(0, r, True)
-                if need_x:
-                    gx = r["x"].reshape(B, 24, m.in_dim).to(sv["x_dtype"])
-        return (None, gx, *grads)
 
 
 # ---------------------------------------------------------------------------------------------- train-mode BatchNorm (csrc/gcn_train.hip)
@@ -241,76 +152,190 @@ def train_conv_backward(h, conv, cw, X, st, gate, gout, bodies, need_x=True, nee
     res = {}
     ws, nb = _train_ws(h, conv, bodies, dev)
     zbar = torch.empty(rows, N, device=dev)
-    g = {}
-    if need_params:
-        g = {k: out[k] if out.get(k) is not None else torch.empty(shp, device=dev)
-             for k, shp in (("M", (24, N)), ("adj2", (24, 24)), ("bn_weight", (N,)), ("bn_bias", (N,)))}
+    g = _param_bufs(("M", "adj2", "bn_weight", "bn_bias"), N, out, dev) if need_params else {}
     A.ehm_gcn_train_bn_backward(h, conv, gout, gate, st["z"], st["mean"], st["invstd"], bodies, zbar, g.get("bn_weight"), g.get("bn_bias"), ws, nb, s)
     if need_x or need_w:
-        G = _new_G(rows, cw, dev)
-        A.ehm_gcn_train_bwd_epilogue(h, conv, zbar, st["A"], G, cw.ldg, bodies, s)
-        _gemm_grads(G, cw, X, rows, need_x, need_w, out, res)
+        _gemm_grads(lambda G: A.ehm_gcn_train_bwd_epilogue(h, conv, zbar, st["A"], G, cw.ldg, bodies, s), cw, X, rows, need_x, need_w, out, res)
     if need_params:
-        pre = gemm_rows(X, cw.fwd, rows)
-        pb = C.c_int64(0)
-        A.ehm_gcn_train_bwd_params_workspace_bytes(h, conv, bodies, C.byref(pb))
-        A.ehm_gcn_train_bwd_params(h, conv, zbar, st["A"], pre, pre.shape[1], bodies, g["M"], g["adj2"], torch.empty(pb.value // 4, device=dev), pb.value, s)
+        pre, pws, pb = _recompute(A.ehm_gcn_train_bwd_params_workspace_bytes, h, conv, cw, X, bodies)
+        A.ehm_gcn_train_bwd_params(h, conv, zbar, st["A"], pre, pre.shape[1], bodies, g["M"], g["adj2"], pws, pb, s)
         bias = out["bias"].zero_() if out.get("bias") is not None else torch.zeros(N, device=dev)
         res.update(g, bias=bias)
     return res
 
 
-class GCNTrainFunction(torch.autograd.Function):
-    """ModulatedGCN.forward in training mode (ModulatedGCN.train_batchnorm): batch statistics in every BatchNorm, the running statistics updated in the
-    forward, and a backward through the mean and the variance.  Arguments and gradient order as GCNFunction."""
+# ---------------------------------------------------------------------------------------------- ModulatedGCN.forward with a backward
+# What a forward below keeps for the backward: dict(h, cws, B, x_dtype, convs): the handle and the ConvWeights it ran on, and one record (X, gate, st) per conv
+# in the handle's order (input conv, hidden convs, output conv) - X [>= rows, Kp] the conv's float32 input, gate its activation before the residual add
+# (None for the output conv), st what train_conv_forward returned (None: eval-mode BatchNorm)
+
+def _geometry(x):
+    """(B, rows, rows rounded up to the hidden convs' row tile)"""
+    rows, tile = x.shape[0] * 24, _lib.api().ehm_gcn_row_tile()
+    return x.shape[0], rows, (rows + tile - 1) // tile * tile
+
+
+@torch.no_grad()
+def forward_saving(m, x):
+    """ModulatedGCN.forward for GCNFunction: the same input conv, then the hidden convs ONE launch each (ehm_gcn_hidden_layer, no residual inside: the add
+    happens on the float32 copies, so that every conv's ReLU output - its gate - exists on its own), then gconv_output.  Returns (out [B, 24, 6], saved)."""
+    if m.precision == "f16":
+        raise _lib.EgoHMRHipError(m.GRAD_F16)
+    if m.nonlocal_layer:
+        raise NotImplementedError("ModulatedGCN.forward: the non-local block has no backward; the autograd route needs nonlocal_layer=False")
+    A = _lib.api()
+    dev = x.device
+    hid, nh = m.hid_dim, 2 * m.num_layers
+    with _lib.on_device(dev):
+        h, cws = m._native(dev)
+        xp, pre = m._input_gemm(x, cws[0])
+        s = _lib.stream_ptr()
+        B, rows, rows_pad = _geometry(x)
+        split = m.precision == "f16x3"                       # activations between the convs in the X2 split format (the last hidden conv writes float32)
+
+        def to_f32(buf, is_f32):
+            if is_f32:
+                return buf
+            out = torch.empty(rows_pad, hid, device=dev)
+            A.ehm_gcn_unpack_activations(buf, out, rows_pad, hid, 32, s)
+            return out
+
+        def to_mode(f):
+            if not split:
+                return f
+            out = torch.zeros(rows_pad, hid, device=dev)
+            A.ehm_gcn_pack_activations_checked(h, f, out, rows, s)
+            return out
+
+        cur = torch.zeros(rows_pad, hid, device=dev)
+        A.ehm_gcn_input_layer_rows(h, pre, cur, B, s)
+        cur_f = to_f32(cur, not split or nh == 0)
+        convs = [(xp, cur_f, None)]
+        for l in range(0, nh, 2):
+            y1 = torch.zeros(rows_pad, hid, device=dev)
+            A.ehm_gcn_hidden_layer(h, l, cur, None, y1, rows_pad, s)
+            y1_f = to_f32(y1, not split)
+            y2 = torch.zeros(rows_pad, hid, device=dev)
+            A.ehm_gcn_hidden_layer(h, l + 1, y1, None, y2, rows_pad, s)
+            y2_f = to_f32(y2, not split or l + 2 == nh)
+            convs += [(cur_f, y1_f, None), (y1_f, y2_f, None)]
+            cur_f = y2_f + cur_f                              # modulated_gcn.py:42
+            cur = to_mode(cur_f) if l + 2 < nh else cur_f
+        convs.append((cur_f, None, None))
+        x0 = torch.empty(B, 144, device=dev)
+        A.ehm_gcn_output_layer(h, cur_f, None, x0, B, 1, s)
+        A.ehm_gcn_stack_status(h, s)
+    return x0.view(B, 24, 6), dict(h=h, cws=cws, B=B, x_dtype=x.dtype, convs=convs)
+
+
+@torch.no_grad()
+def forward_train(m, x, save):
+    """ModulatedGCN.forward under .train() with `train_batchnorm`: per BatchNorm'd conv the split-f16 GEMM X [W0 | W1], then ehm_gcn_train_preact (modulation,
+    adjacency mix, bias), ehm_gcn_train_stats (batch mean / biased variance, running statistics) and ehm_gcn_train_normalize (BatchNorm, ReLU,
+    residual) on float32 activations; gconv_output as in eval mode.  The handle is this call's own: the running statistics change here, so the
+    eval-mode one (ModulatedGCN._native) is rebuilt by the next eval() call through its TensorKey.  Returns (out [B, 24, 6], saved or None)."""
+    A = _lib.api()
+    dev = x.device
+    hid, nh = m.hid_dim, 2 * m.num_layers
+    mods = m._convs()
+    with _lib.on_device(dev):
+        h, keep = m.create_native_handle(dev)
+        h = _lib.Handle(h, A.ehm_gcn_destroy, keep)
+        A.ehm_gcn_set_precision(h, PRECISIONS[m.precision])
+        cws = [ConvWeights(_lib.f32(gc.W, dev)) for gc, _ in mods]
+        s = _lib.stream_ptr()
+        B, rows, rows_pad = _geometry(x)
+        convs = []
+
+        def conv(idx, X, res, last):
+            """the handle's conv idx on X; the result (the output conv reads whole row tiles: zeros behind the last one's rows)"""
+            ci = len(convs)
+            bn = mods[ci][1]
+            running = (_lib.f32(bn.running_mean, dev).clone(), _lib.f32(bn.running_var, dev).clone())
+            if res is None:                               # the result is y itself
+                y, out = (None, torch.zeros(rows_pad, hid, device=dev)) if last else (torch.empty(rows, hid, device=dev), None)
+            else:                                         # y is kept for the backward only: its gate
+                y = torch.empty(rows, hid, device=dev) if save else None
+                out = torch.zeros(rows_pad, hid, device=dev) if last else torch.empty(rows, hid, device=dev)
+            st = train_conv_forward(h, idx, cws[ci], X, B, bn.eps, bn.momentum, running, res, y, out)
+            bn.running_mean.copy_(running[0])             # (copy_: the buffers' _version moves, which the eval-mode handle's key sees)
+            bn.running_var.copy_(running[1])
+            bn.num_batches_tracked.add_(1)
+            result = out if out is not None else y
+            convs.append((X, y if y is not None else result, st))
+            return result
+
+        # (the input GEMM runs inside train_conv_forward, like every conv's: only the padding of ModulatedGCN._input_gemm is needed here)
+        cur = conv(INPUT, pad_cols(_lib.f32(x).reshape(rows, m.in_dim), round_up(m.in_dim, 32)), None, nh == 0)
+        for l in range(0, nh, 2):
+            y1 = conv(l, cur, None, False)
+            cur = conv(l + 1, y1, cur, l + 2 == nh)
+        convs.append((cur, None, None))
+        x0 = torch.empty(B, 144, device=dev)
+        A.ehm_gcn_output_layer(h, cur, None, x0, B, 1, s)
+        A.ehm_gcn_stack_status(h, s)
+    return x0.view(B, 24, 6), dict(h=h, cws=cws, B=B, x_dtype=x.dtype, convs=convs) if save else None
+
+
+class GCNFunction(torch.autograd.Function):
+    """ModulatedGCN.forward (modulated_gcn.py:99-116, eval mode) with a backward: forward(module, x, *params) -> [B, 24, 6].  `params` is empty (gradient
+    to x only) or ModulatedGCN.grad_parameters(): W, M, adj2, bias, bn.weight, bn.bias of the input conv and every hidden conv, then W, M, adj2, bias
+    of the output conv."""
 
     @staticmethod
     def forward(ctx, module, x, *params):
-        out, saved = module._forward_train(x, save=True)
-        ctx.module, ctx.saved, ctx.n_params = module, saved, len(params)
+        out, ctx.saved = forward_saving(module, x)
+        ctx.n_params = len(params)
         return out
 
     @staticmethod
     @torch.autograd.function.once_differentiable
     def backward(ctx, gout):
-        m, sv = ctx.module, ctx.saved
-        need = ctx.needs_input_grad
-        need_x, pneed = need[1], need[2:]
-        dev = gout.device
-        B, nh = sv["B"], 2 * m.num_layers
+        sv = ctx.saved
+        need_x, pneed = ctx.needs_input_grad[1], ctx.needs_input_grad[2:]
+        h, cws, B, convs = sv["h"], sv["cws"], sv["B"], sv["convs"]
+        last = len(convs) - 1                       # the output conv's number in the parameter list
         grads = [None] * ctx.n_params
 
-        def wants(ci, nparams=6):
+        def wants(ci, nparams):                     # (need_w, need_params) of conv number ci in the parameter list
             if not pneed:
                 return False, False
             f = pneed[6 * ci: 6 * ci + nparams]
             return bool(f[0]), any(f[1:])
 
-        def put(ci, r, has_bn):
-            for k, name in enumerate(PARAMS_PER_CONV if has_bn else PARAMS_PER_CONV[:4]):
-                if name in r and pneed[6 * ci + k]:
-                    grads[6 * ci + k] = r[name]
-
-        def bn_conv(ci, conv, g, need_x=True):            # conv number ci of the parameter list = the handle's conv `conv`
-            nw, npar = wants(ci)
+        def conv(ci, g, need_x=True):               # conv number ci: its input's gradient from g, its parameters' gradients into grads
+            names = PARAMS_PER_CONV if ci < last else PARAMS_PER_CONV[:4]
+            nw, npar = wants(ci, len(names))
             if not (need_x or nw or npar):
                 return None
-            r = train_conv_backward(h, conv, cws[ci], sv["X"][ci], sv["st"][ci], sv["y"][ci], g, B, need_x, nw, npar)
-            put(ci, r, True)
+            X, gate, st = convs[ci]
+            idx = INPUT if ci == 0 else OUTPUT if ci == last else ci - 1
+            if st is not None:
+                r = train_conv_backward(h, idx, cws[ci], X, st, gate, g, B, need_x, nw, npar)
+            else:
+                r = conv_backward(h, idx, cws[ci], X, gate, g, B, need_x, nw, npar, has_bn=ci < last)
+            for k, name in enumerate(names):
+                if name in r and pneed[6 * ci + k]:
+                    grads[6 * ci + k] = r[name]
             return r.get("x")
 
-        with _lib.on_device(dev):
-            h, cws = sv["h"], sv["cws"]
-            g = _lib.f32(gout, dev).reshape(B * 24, 6)
-            nw, npar = wants(nh + 1, 4)
-            r = conv_backward(h, OUTPUT, cws[nh + 1], sv["X"][nh + 1], None, g, B, True, nw, npar, has_bn=False)
-            put(nh + 1, r, False)
-            g = r["x"]
-            for blk in reversed(range(m.num_layers)):
-                l1, l2 = 2 * blk, 2 * blk + 1
-                g1 = bn_conv(l1 + 1, l1, bn_conv(l2 + 1, l2, g))
-                g = g1.add_(g)                              # + the residual's gradient
-            gx = bn_conv(0, INPUT, g, need_x)
+        with _lib.on_device(gout.device):
+            g = conv(last, _lib.f32(gout, gout.device).reshape(B * 24, 6))
+            # the residual blocks, last first: out = y2 + block input, y2 = gconv2(y1), y1 = gconv1(block input)
+            for c2 in range(last - 1, 1, -2):
+                g = conv(c2 - 1, conv(c2, g)).add_(g)           # + the residual's gradient
+            gx = conv(0, g, need_x)
             if gx is not None:
-                gx = gx.reshape(B, 24, m.in_dim).to(sv["x_dtype"])
+                gx = gx.reshape(B, 24, cws[0].K).to(sv["x_dtype"])
         return (None, gx, *grads)
+
+
+class GCNTrainFunction(GCNFunction):
+    """ModulatedGCN.forward in training mode (ModulatedGCN.train_batchnorm): batch statistics in every BatchNorm, the running statistics updated in the
+    forward, and a backward through the mean and the variance.  Arguments, gradient order and the backward's walk as GCNFunction."""
+
+    @staticmethod
+    def forward(ctx, module, x, *params):
+        out, ctx.saved = forward_train(module, x, save=True)
+        ctx.n_params = len(params)
+        return out

@@ -6,7 +6,7 @@ pooled' = max over the N points of a body; gnet' / gpool' = the gradients arrivi
 
     arg [B,H]                                  ehm_pointnet_pool_argmax      (lowest maximising row of the SAVED net', NaN = maximum)
     G = gnet' + one-hot(arg) gpool'            ehm_pointnet_bwd_scatter      (+ its column sums: fc_1.bias grad, per-body sG)
-    dh = (G W1) (.) [relu(h) > 0]              ehm_conv_nhwc_split, H = W = 1 (gcn_grad.gemm_rows) + ehm_pointnet_bwd_gate (+ sums: fc_0.bias grad, sdh)
+    dh = (G W1) (.) [relu(h) > 0]              ehm_conv_nhwc_split, H = W = 1 (split_gemm.gemm_rows) + ehm_pointnet_bwd_gate (+ sums: fc_0.bias grad, sdh)
     dxa = (dh W0[:, :H]) (.) [net > 0] + G S[:, :H]          two GEMMs + ehm_pointnet_bwd_gate with `add`    -> gnet of the block before
     gpool = (sdh W0[:, H:]) (.) [pooled > 0] + sG S[:, H:]   ehm_skinny_gemm_f32: the pooled half is constant over a body, [B,H] products only
     fc_1.weight grad = G^T relu(h),  fc_0.weight grad = [dh^T relu(net) | sdh^T relu(pooled)],  shortcut.weight grad = [G^T net | sG^T pooled]
@@ -27,7 +27,7 @@ import ctypes as C
 import torch
 
 from . import _lib
-from .gcn_grad import gemm_rows, pack_weight, pow2_scale
+from .split_gemm import gemm_rows, pack_weight, pow2_scale
 
 # the order of the parameter gradients (ResnetPointnet.grad_parameters)
 PARAM_NAMES = (("fc_pos_0.weight", "fc_pos_0.bias") +

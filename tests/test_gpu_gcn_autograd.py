@@ -376,3 +376,37 @@ def test_module_behaviour(dev, module_case):
     with pytest.raises(NotImplementedError, match="non-local"):
         nl(x)
     assert nl(xs).grad_fn is None
+
+
+def test_in_place_update_rebuilds_the_packed_operands(dev, module_case):
+    """Parameters updated in place between two calls: the one cached (handle, packed GEMM operands) pair is rebuilt - output and every gradient equal, bit
+    for bit, those of a fresh module that loaded the updated weights, and so does the no-grad forward (its input GEMM reads the same packed operand)."""
+    from egohmr_amd.model import ModulatedGCN, smpl_tree_adjacency
+    xs, cot = module_case["x"].float().to(dev), module_case["cot"].float().to(dev)
+
+    def make(sd):
+        m = ModulatedGCN(smpl_tree_adjacency(), in_dim=70, hid_dim=64, num_layers=1)
+        m.load_state_dict({k: v.float() for k, v in sd.items()}, strict=False)
+        m.grad_params = True
+        return m.to(dev).eval()
+
+    def run(m):
+        m.zero_grad(set_to_none=True)
+        x = xs.clone().requires_grad_()
+        out = m(x)
+        out.backward(cot)
+        return [out.detach(), x.grad] + [p.grad for p in m.grad_parameters()]
+
+    old = make(module_case["sd"])
+    before = run(old)
+    with torch.no_grad():
+        old.gconv_layers[0].gconv1.gconv.W.mul_(0.5)
+        old.gconv_input[0].gconv.W.add_(0.01)
+    got = run(old)
+    assert not torch.equal(got[0], before[0])
+    fresh = make(old.state_dict())
+    want = run(fresh)
+    for i, (a, b) in enumerate(zip(got, want)):
+        assert a is not None and torch.equal(a, b), i
+    with torch.no_grad():
+        assert torch.equal(fresh(xs), old(xs))

@@ -445,3 +445,26 @@ def test_two_backward_calls_give_the_same_bits():
     torch.cuda.synchronize()
     for a, b in zip(*runs):
         assert torch.equal(a, b)
+
+
+# ---------------------------------------------------------------------------------------------- 6. the packed operands follow an in-place update
+def test_in_place_update_repacks_both_routes_operands():
+    """A weight updated in place between two calls: the one cache key invalidates the forward's packed operands and the backward's - output, p.grad and the
+    24 gradients equal, bit for bit, those of a fresh module that loaded the updated weights."""
+    B, N = 2, 3
+    sd, p, gout, out, it, pbar, grads = reference(B, N, E2E_SEED[(B, N)], False, 1.0)
+
+    def run(m):
+        c, pt = run_module(m, p, gout)
+        return [c.detach(), pt.grad] + [q.grad for q in m.grad_parameters()]
+
+    m = make_module(sd)
+    before = run(m)
+    with torch.no_grad():
+        m.block_1.fc_1.weight.mul_(0.5)
+    got = run(m)
+    assert not torch.equal(got[0], before[0])
+    fresh = make_module({R.PREFIX + k: v for k, v in m.state_dict().items()})
+    want = run(fresh)
+    for i, (a, b) in enumerate(zip(got, want)):
+        assert a is not None and torch.equal(a, b), i

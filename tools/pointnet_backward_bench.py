@@ -113,7 +113,7 @@ def main():
 def profile_backward(m, p, cot):
     """HIP-event time of every native entry and torch op family inside one backward: the entries of _lib.api() and the helpers of pointnet_grad are
     wrapped for this one call (a synchronise after each, so the sum exceeds the asynchronous backward)."""
-    from egohmr_amd import _lib, gcn_grad
+    from egohmr_amd import _lib
     acc = {}
 
     def wrap(name, fn):
@@ -138,7 +138,7 @@ def profile_backward(m, p, cot):
     try:
         for n in names:
             setattr(api, n, wrap(n, keep[n]))
-        pointnet_grad.gemm_rows = wrap("gemm_rows (ehm_conv_nhwc_split)", gcn_grad.gemm_rows)
+        pointnet_grad.gemm_rows = wrap("gemm_rows (ehm_conv_nhwc_split)", keep_rows)
         pointnet_grad.pow2_scale = wrap("pow2_scale", keep_scale)
         total = timed(lambda: out.backward(cot))
     finally:
