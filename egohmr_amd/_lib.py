@@ -29,7 +29,7 @@ _HERE = os.path.dirname(os.path.abspath(__file__))
 LIB_PATH = os.environ.get("EHM_LIB_PATH") or os.path.join(_HERE, "libegohmr_hip.so")   # EHM_LIB_PATH: A/B a second build (experiments)
 CSRC = os.path.join(_HERE, "csrc")
 INCLUDE = os.path.join(os.path.dirname(_HERE), "include")
-SOURCES = ["gcn.hip", "gcn_tile.hip", "linear.hip", "conv.hip", "stem.hip", "metrics.hip", "smpl.hip", "sampler.hip", "guidance.hip", "prep.hip", "step.hip", "eval.hip", "stage1.hip", "scene.hip", "loss.hip", "gcn_bwd.hip", "gcn_train.hip", "pointnet_bwd.hip"]
+SOURCES = ["gcn.hip", "gcn_tile.hip", "linear.hip", "conv.hip", "stem.hip", "metrics.hip", "smpl.hip", "sampler.hip", "guidance.hip", "prep.hip", "step.hip", "eval.hip", "stage1.hip", "scene.hip", "loss.hip", "gcn_bwd.hip", "gcn_train.hip", "pointnet_bwd.hip", "train.hip"]
 
 
 class EgoHMRHipError(RuntimeError):
@@ -323,6 +323,8 @@ PROTOTYPES = {
     "ehm_val_losses_backward_workspace_bytes": (_I, [_I, _I, C.POINTER(C.c_int64)]),
     "ehm_val_losses_backward": (_I, [C.POINTER(ValLossesBwdDesc), _P]),
     "ehm_scene_cap_points": (_I, [_P, _P, _P, _P, _I, _I, _I, _I, _P]),
+    "ehm_cond_assemble": (_I, [_P, _P, _P, _P, _I, _I, _P, _P, _I, _P, _I, _I, _I, _P]),
+    "ehm_cond_assemble_backward": (_I, [_P, _P, _P, _I, _I, _P, _P, _P, _P, _I, _I, _I, _P]),
     "ehm_profile_begin": (_I, []),
     "ehm_profile_end": (_I, [C.POINTER(C.c_double), C.POINTER(C.c_int64), _I]),
 }

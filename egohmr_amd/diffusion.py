@@ -325,10 +325,27 @@ class GaussianDiffusion:
         return final
 
     def training_losses(self, model, batch, t, cur_epoch=0, noise=None):
-        raise NotImplementedError("training_losses (gaussian_diffusion.py:721-746) is not built: EgoHMR.compute_loss has a backward and EgoHMR.decode_output "
-                                  "chains x_0 -> SMPL -> loss, but model(batch, t) itself carries no graph (the ResNet-50 trunk's backward, the non-local block's "
-                                  "backward and the wiring of EgoHMR.forward are missing; the scene PointNet and ModulatedGCN have theirs, train-mode "
-                                  "BatchNorm exists behind ModulatedGCN.train_batchnorm)")
+        """gaussian_diffusion.py:721-746 behind EgoHMR.frozen_trunk_training (else NotImplementedError): x_start from the ground-truth axis-angle pose,
+        q_sample at `t` [B], batch['x_t'], then model.training_step - forward, loss, backward and one optimizer step (`model` is the EgoHMR itself, as in
+        val_losses); returns its output dict."""
+        if not getattr(model, "frozen_trunk_training", False):
+            from .model import EgoHMR
+            raise NotImplementedError("training_losses (gaussian_diffusion.py:721-746) is not built: " + EgoHMR.NOT_BUILT)
+        from . import geometry
+        model._check_trainable()
+        sp = batch["smpl_params"]
+        B = batch["img"].shape[0]
+        dev = model.device
+        aa = th.cat([_lib.f32(sp["global_orient"], dev).reshape(B, -1), _lib.f32(sp["body_pose"], dev).reshape(B, -1)], dim=1).reshape(-1, 3)   # :732-733
+        rot6d = geometry.rotmat_to_rot6d(geometry.aa_to_rotmat(aa).reshape(-1, 3, 3), rot6d_mode="diffusion").reshape(B, -1)                    # :734-736
+        mean, std = model._std_mean()                       # the diffusion's own statistics where it was given some (gaussian_diffusion.py:737)
+        if self.body_rep_mean is not None and self.body_rep_std is not None:
+            mean, std = (th.as_tensor(np.asarray(v), dtype=th.float32).reshape(144).to(dev) for v in (self.body_rep_mean, self.body_rep_std))
+        x_start = (rot6d - mean) / std                                                                                                        # :737
+        if noise is None:
+            noise = th.randn_like(x_start)                                                                                                    # :741
+        batch["x_t"] = self.q_sample(x_start, t, noise=_lib.f32(noise, dev))                                                                  # :742-743
+        return model.training_step(batch=batch, timesteps=self._scale_timesteps(t), cur_epoch=cur_epoch)                                       # :745
 
     def val_losses(self, model, batch, shape, clip_denoised=True, progress=False, cond_fn_with_grad=False, cond_grad_weight=1.0,
                    cur_epoch=0, timestep_respacing="", compute_loss=True, noise_stack=None):

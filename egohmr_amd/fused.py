@@ -78,6 +78,13 @@ class _Prepared:
             num_masked=S * self.num_masked if self.num_masked >= 0 else self.num_masked, **tiled)
 
 
+@dataclasses.dataclass
+class _PreparedConstants(_Prepared):
+    """prepare(_constants_only=True): what the training route of EgoHMR.forward keeps constant.  h_img, h_oth, betas and scene_feats are None and there
+    is no pass map, so take() / tile() do not apply."""
+    other: torch.Tensor = None          # the padded [scene (unwritten) | transl | cam] operand ehm_item_prep filled
+
+
 class FusedSampler:
     """Owns the native denoiser handle and runs sampling loops through ehm_sample_loop."""
 
@@ -152,12 +159,15 @@ class FusedSampler:
 
     # ------------------------------------------------------------------ step-invariant conditioning
     @torch.no_grad()
-    def prepare(self, batch) -> _Prepared:
-        """Everything in EgoHMR.forward that does not depend on x_t / t (egohmr.py:182-223, :263-265)."""
+    def prepare(self, batch, _constants_only=False) -> _Prepared:
+        """Everything in EgoHMR.forward that does not depend on x_t / t (egohmr.py:182-223, :263-265).
+        _constants_only (the training route of EgoHMR.forward): only what stays constant with the trunk frozen - trunk, visibility, camera columns, scene,
+        translation; the PointNet, the projections, the beta head and the native handle are left out (h_img, h_oth, betas, scene_feats = None, no pass map,
+        no host read-back; `other` holds ehm_item_prep's operand).  Such an entry is cached under a key of its own: no other caller ever sees it."""
         with _lib.on_device(self.model.device):          # every native call below launches on the CURRENT device's stream
-            return self._prepare_on_device(batch)
+            return self._prepare_on_device(batch, _constants_only)
 
-    def _prepare_on_device(self, batch) -> _Prepared:
+    def _prepare_on_device(self, batch, constants_only=False) -> _Prepared:
         m = self.model
         # Cache key = identity AND version of every tensor the conditioning is computed from, and of every weight it passes
         # through.  The cached entry keeps strong references to those input tensors, so neither their id() nor their storage can be
@@ -173,9 +183,12 @@ class FusedSampler:
         m.backbone.hi_only = m.scene_enc.hi_only = m.encoder_precision == "f16"
         switches = (bool(m.with_bbox_info), bool(m.with_cam_center), bool(m.scene_cano), tuple(m.openpose_to_smpl), m.encoder_precision)
         key = tuple((id(t), t._version, t.data_ptr()) for t in ins) + self._param_key() + self._cond_param_key() + (switches,)
+        if constants_only:
+            key += ("constants_only",)
         if self._prep is not None and self._prep_key == key:
             return self._prep
-        self.gcn()
+        if not constants_only:
+            self.gcn()
         dev = m.device
         g = lambda k: _lib.f32(batch[k], dev)
         transl = _lib.f32(batch["smpl_params"]["transl"], dev)
@@ -184,7 +197,7 @@ class FusedSampler:
             scene = scene - transl.unsqueeze(1)                                        # :211
         scene = scene.contiguous()
         img = g("img")
-        B, f, st = img.shape[0], self._folded, _lib.stream_ptr()
+        B, st = img.shape[0], _lib.stream_ptr()
         # ---- per-item scalars in two launches (csrc/prep.hip): joint visibility (:186-188), the pass-pruning map (ehm_gcn_set_pass_map: items
         # with an invisible joint need the second pass), TranslEnc (:217) and the camera features (:195-205) written straight into the padded
         # [scene | transl | cam] operand of the projections, and the per-item "inputs are finite" flag.  The reference's float32 graph carries a
@@ -200,13 +213,14 @@ class FusedSampler:
         tw = [_lib.f32(te[0].weight, dev), _lib.f32(te[0].bias, dev), _lib.f32(te[2].weight, dev), _lib.f32(te[2].bias, dev)]
         n_scene, n_tr = m.scene_enc.fc_c.out_features, te[2].out_features
         n_other = n_scene + n_tr + 1 + (3 if m.with_bbox_info else 0) + (2 if m.with_cam_center else 0)
+        k_oth = (n_other + 31) // 32 * 32                                              # (= _folded.k_oth: the projections' K granule)
         jm = self._joint_map
         if kp.dim() != 3 or kp.shape[2] != 3 or not all(0 <= int(k) < kp.shape[1] for k in m.openpose_to_smpl):
             # (item_prep_kernel indexes keypoints_2d[b, joint_map[t], 2]: checked here, once per batch, instead of on the device)
             raise ValueError(f"orig_keypoints_2d must be [B, NK, 3] with NK > max(openpose_to_smpl) = {max(m.openpose_to_smpl)}; got {tuple(kp.shape)}")
         if jm is None or jm[0] != (tuple(m.openpose_to_smpl), str(dev)):
             jm = self._joint_map = ((tuple(m.openpose_to_smpl), str(dev)), torch.tensor(m.openpose_to_smpl, dtype=torch.int32, device=dev))
-        oth = torch.empty(B, f.k_oth, device=dev)
+        oth = torch.empty(B, k_oth, device=dev)
         vis = torch.empty(B, 24, dtype=torch.uint8, device=dev)
         flags = torch.empty(2, B, dtype=torch.uint8, device=dev)                       # finite | need (scratch)
         maps = torch.empty(2 * B + 1, dtype=torch.int32, device=dev)                   # mask_slot | mask_items | count
@@ -216,7 +230,7 @@ class FusedSampler:
                               cy=P(cy), box_center=P(bc), box_size=P(bs), transl=P(transl), fx_norm=m.cfg.CAM.FX_NORM_COEFF,
                               with_bbox=int(m.with_bbox_info), with_cam_center=int(m.with_cam_center), tW1=P(tw[0]), tb1=P(tw[1]),
                               tW2=P(tw[2]), tb2=P(tw[3]), t_hidden=te[0].out_features, t_out=n_tr, img_rowsum=P(sums[0]),
-                              scene_rowsum=P(sums[1]), other=P(oth), other_ld=f.k_oth, other_col0=n_scene, vis=P(vis),
+                              scene_rowsum=P(sums[1]), other=P(oth), other_ld=k_oth, other_col0=n_scene, vis=P(vis),
                               mask_slot=P(maps), mask_items=P(maps[B:]), count=P(maps[2 * B:]), finite=P(flags),
                               need_scratch=P(flags[1]), pass_group=1, B=B)
         _lib.api().ehm_item_prep(C.byref(d), st)
@@ -228,6 +242,12 @@ class FusedSampler:
         # The two encoders are independent, but each fills the chip on its own: one after the other on ONE stream (two streams measured
         # slower, docs/EXPERIMENTS.md)
         img_feats = self._backbone_fn()(img)                                           # :183 (BatchNorm folded into the convs)
+        if constants_only:
+            self._prep = _PreparedConstants(B=B, h_img=None, h_oth=None, vis=vis, vis_bool=vis.view(torch.bool), betas=None, scene=scene, transl=transl, fx=fx,
+                                   cam_cx=cx, cam_cy=cy, img_feats=img_feats.contiguous(), scene_feats=None,
+                                            finite=flags[0].view(torch.bool), mask_items=maps[B:B], mask_slot=maps[:B], num_masked=-1, inputs=ins, other=oth)
+            self._prep_key = key
+            return self._prep
         scene_feats = m.scene_enc(scene)                                               # :214
         oth[:, :n_scene].copy_(scene_feats)                                            # :220-221 [scene | transl | cam] (the rest was written by ehm_item_prep)
         h_img, h_oth, betas = self._project(img_feats.contiguous(), oth, n_other)

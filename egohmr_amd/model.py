@@ -22,7 +22,7 @@ import numpy as np
 import torch
 import torch.nn as nn
 
-from . import _lib, gcn_grad, geometry, loss_grad, split_gemm, synthetic
+from . import _lib, gcn_grad, geometry, loss_grad, split_gemm, synthetic, train_grad
 from . import smpl as smpl_mod
 from .encoders import ResnetPointnet, ResNet50Features
 from .fused import PRECISIONS, FusedSampler  # noqa: F401  (PRECISIONS re-exported)
@@ -403,7 +403,8 @@ class EgoHMR(nn.Module):
         self.with_focal_length, self.with_bbox_info, self.with_cam_center = True, bool(with_bbox_info), bool(with_cam_center)
         self.scene_type, self.scene_cano = scene_type, scene_cano
         self.only_mask_img_cond, self.diffuse_fuse = only_mask_img_cond, diffuse_fuse
-        # cond_mask_prob only acts under self.training (mask_cond, egohmr.py:159-168): the sampling path is eval-only, so it is kept and ignored
+        # cond_mask_prob only acts under self.training (mask_cond, egohmr.py:159-168): the sampling path ignores it; the training route of forward
+        # (frozen_trunk_training) draws the reference's per-item mask from it (cond_drop_mask) and applies it inside ehm_cond_assemble
         self.cond_mask_prob = float(cond_mask_prob)
         # egohmr.py:121-122, :130-137: read by compute_loss only
         self.weight_loss_v2v, self.weight_loss_keypoints_3d = weight_loss_v2v, weight_loss_keypoints_3d
@@ -500,10 +501,84 @@ class EgoHMR(nn.Module):
         vis[:, 8] = True                                                               # :187
         return vis[:, self.openpose_to_smpl]                                           # :188
 
+    # False: training_step / GaussianDiffusion.training_losses raise NotImplementedError and forward never carries a graph.  True: they run the reference's
+    # training loop (egohmr.py:453-472, gaussian_diffusion.py:721-746) with the image trunk FROZEN - a forward under self.training takes the training route
+    # (_forward_train): the folded ResNet-50 in eval mode under no_grad, everything else of init_optimizers' list (scene PointNet, transl_enc, beta_layer,
+    # the denoiser, embed_timestep, input_process) with a graph.  Calls with self.training False do not depend on it
+    frozen_trunk_training = False
+
     def forward(self, batch, timesteps, eval_with_uncond=True):
-        """One denoising evaluation (egohmr.py:173-303).  Conditioning is cached per batch object."""
+        """One denoising evaluation (egohmr.py:173-303).  Conditioning is cached per batch object.  Under self.training with frozen_trunk_training set: the
+        training route (_forward_train), one pass whatever eval_with_uncond says."""
         with _lib.on_device(self.device):                 # native calls launch on the CURRENT device's stream
+            if self.training and self.frozen_trunk_training:
+                return self._forward_train(batch, timesteps)
             return self._forward_on_device(batch, timesteps, eval_with_uncond)
+
+    def _check_trainable(self):
+        """What the training route cannot run, refused before any device call."""
+        dm = self.diffusion_model
+        if dm.nonlocal_layer:
+            raise NotImplementedError("EgoHMR.frozen_trunk_training: the non-local block has no backward; the training route needs gcn_nonlocal_layer=False")
+        if self.gcn_precision == "f16" or dm.precision == "f16":
+            raise _lib.EgoHMRHipError(dm.GRAD_F16)
+
+    def cond_drop_mask(self, B):
+        """mask_cond's per-item draw (egohmr.py:159-160): None when cond_mask_prob is 0, else [B] uint8 (1 = the item's conditioning is dropped) from the
+        reference's own call on torch's global generator."""
+        if not self.cond_mask_prob > 0.0:
+            return None
+        return torch.bernoulli(torch.ones(B, device=self.device) * self.cond_mask_prob).to(torch.uint8)
+
+    def _set_train_modes(self):
+        """egohmr.py:454-462 with the trunk frozen: the backbone stays in eval mode, and the denoiser trains its BatchNorm only behind
+        ModulatedGCN.train_batchnorm - without it the denoiser stays in eval mode and its statistics frozen (a deviation from the reference, which always
+        trains on batch statistics)."""
+        self.training = True
+        self.backbone.eval()
+        for m in (self.scene_enc, self.transl_enc, self.beta_layer, self.input_process, self.embed_timestep):
+            m.train()
+        self.diffusion_model.train(bool(self.diffusion_model.train_batchnorm))
+
+    def _forward_train(self, batch, timesteps):
+        """egohmr.py:173-303 under self.training, as an autograd graph, with the image trunk frozen (eval_with_uncond=False: one pass, also with
+        diffuse_fuse - training_step passes that, :465).
+
+        Constants, from the no-grad code of FusedSampler.prepare (run once per step, without its PointNet / projection part): img_feats (folded trunk, eval
+        mode), the joint visibility, the camera columns, the scene (after scene_cano), transl, fx, cam_cx, cam_cy.  With a graph: scene_enc (its HIP VJP,
+        grad_params set for the call), transl_enc, embed_timestep (one timestep per item, :178), input_process and beta_layer (plain torch modules), the
+        conditioning assembly with the cond_mask_prob draw (train_grad.CondAssemble: one launch each way), the denoiser (ModulatedGCN.forward with
+        grad_params set, in EgoHMR.gcn_precision: batch statistics behind ModulatedGCN.train_batchnorm, else eval-mode BatchNorm with frozen statistics -
+        the reference always trains on batch statistics) and decode_output.  Sets batch['vis_mask_smpl'], smpl_output, scene_pcd_verts, input_transl,
+        focal_length and camera_center_full like forward; like decode_output it does NOT apply the NaN rule of ehm_pack_outputs."""
+        self._check_trainable()
+        dm, dev = self.diffusion_model, self.device
+        x_t = _lib.f32(batch["x_t"], dev).reshape(-1, 144)
+        B = x_t.shape[0]
+        ts = torch.as_tensor(timesteps, device=dev).reshape(-1).long()
+        if ts.numel() not in (1, B):
+            raise ValueError(f"timesteps must hold one value per item: got {ts.numel()} for a batch of {B}")
+        st = self.fused_sampler.prepare(batch, _constants_only=True)
+        n_scene, n_other = self.scene_enc.fc_c.out_features, self.context_feats_dim - IMG_DIM
+        enc = self.scene_enc
+        keep = (enc.grad_params, dm.grad_params, dm.precision)
+        try:
+            enc.grad_params = dm.grad_params = True
+            dm.precision = self.gcn_precision
+            dm.train(bool(dm.train_batchnorm))
+            scene_feats = enc(st.scene)                                                                    # :214
+            transl_feat = self.transl_enc(st.transl)                                                       # :217
+            cam = st.other[:, n_scene + transl_feat.shape[1]:n_other]                                      # :195-205 (ehm_item_prep wrote them)
+            other = torch.cat([scene_feats, transl_feat, cam], dim=1)                                      # :220-221
+            temb = self.embed_timestep(ts.expand(B)).squeeze(0)                                            # :178
+            x_feat = self.input_process.poseEmbedding(x_t.reshape(B * 24, 6))                              # :234
+            X = train_grad.CondAssemble.apply(st.img_feats, st.vis, self.cond_drop_mask(B), other, x_feat, temb, self.only_mask_img_cond)   # :190-191, :222-236
+            x0 = dm(X).reshape(B, 144)                                                                     # :237, :256
+        finally:
+            enc.grad_params, dm.grad_params, dm.precision = keep
+        betas = self.beta_layer(torch.cat([st.img_feats, other], dim=1))                                   # :263-265
+        batch["vis_mask_smpl"] = st.vis_bool                                                               # :189
+        return self.decode_output(batch, x0, betas, _st=st)
 
     def _forward_on_device(self, batch, timesteps, eval_with_uncond):
         fs = self.fused_sampler
@@ -837,7 +912,7 @@ class EgoHMR(nn.Module):
                                    self.weight_loss_betas, self.weight_loss_body_pose, self.weight_loss_global_orient, self.weight_loss_pose_6d_ortho,
                                    self.weight_coap_penetration)]
 
-    def decode_output(self, batch, pred_x_start, betas=None):
+    def decode_output(self, batch, pred_x_start, betas=None, _st=None):
         """egohmr.py:256-303 as an autograd graph: a pred_x_start [B,144] (and optionally betas [B,10]; default: the prepared batch's, a constant) -> the
         output dict of `forward` - the same keys as _pack_output - through torch ops and the differentiable geometry.rot6d_to_rotmat, SMPL.forward and
         geometry.perspective_projection, so that `compute_loss(batch, decode_output(batch, x0))` backpropagates into x0 (and betas).  Sets smpl_output,
@@ -845,7 +920,7 @@ class EgoHMR(nn.Module):
         with a non-finite input is not blanked: values propagate as torch computes them)."""
         dev = self.device
         with _lib.on_device(dev):
-            st = self.fused_sampler.prepare(batch)
+            st = self.fused_sampler.prepare(batch) if _st is None else _st                                  # (_st: the training route's prepared constants)
             x0 = loss_grad.f32_graph(pred_x_start, dev).reshape(-1, 144)
             B = x0.shape[0]
             mean, std = self._std_mean()
@@ -871,11 +946,29 @@ class EgoHMR(nn.Module):
             "pred_keypoints_2d_full": kp2d,
         }
 
-    def training_step(self, *a, **k):
-        raise NotImplementedError("training_step is not built: compute_loss has a backward (the loss, SMPL.forward, rot6d_to_rotmat, ModulatedGCN.forward "
-                                  "and ResnetPointnet.forward are differentiable, ModulatedGCN.train_batchnorm runs BatchNorm in training mode; decode_output "
-                                  "chains them), but the ResNet-50 trunk's backward, the non-local block's backward and the wiring of EgoHMR.forward "
-                                  "(FusedSampler.prepare carries no graph) are missing")
+    NOT_BUILT = ("compute_loss has a backward (the loss, SMPL.forward, rot6d_to_rotmat, ModulatedGCN.forward and ResnetPointnet.forward are differentiable, "
+                 "ModulatedGCN.train_batchnorm runs BatchNorm in training mode; decode_output chains them), but the ResNet-50 trunk's backward and the non-local "
+                 "block's backward are missing; the training route of EgoHMR.forward runs with the trunk frozen once EgoHMR.frozen_trunk_training is set")
+
+    def init_optimizers(self):
+        """egohmr.py:140-147 with the trunk frozen: the reference's parameter list in its order, without `backbone`."""
+        self.opt_params = (list(self.scene_enc.parameters()) + list(self.transl_enc.parameters()) + list(self.beta_layer.parameters()) +
+                           list(self.diffusion_model.parameters()) + list(self.embed_timestep.parameters()) + list(self.input_process.parameters()))
+        self.optimizer = torch.optim.AdamW(params=self.opt_params, lr=self.cfg.TRAIN.LR, weight_decay=self.cfg.TRAIN.WEIGHT_DECAY)
+
+    def training_step(self, batch=None, timesteps=None, cur_epoch=0):
+        """egohmr.py:453-472 behind frozen_trunk_training (else NotImplementedError): the training modes (_set_train_modes; left as set, validation_setup
+        restores eval), forward, compute_loss, zero_grad, backward, one step of the optimizer of init_optimizers; returns the output dict."""
+        if not getattr(self, "frozen_trunk_training", False):
+            raise NotImplementedError("training_step is not built: " + EgoHMR.NOT_BUILT)
+        self._check_trainable()
+        self._set_train_modes()
+        output = self.forward(batch, timesteps, eval_with_uncond=False)                                    # :465
+        loss = self.compute_loss(batch, output, cur_epoch=cur_epoch)
+        self.optimizer.zero_grad()
+        loss.backward()
+        self.optimizer.step()
+        return output
 
 
 class EgoHMRVolsmpl(EgoHMR):

@@ -799,6 +799,21 @@ int ehm_sample_loop(ehm_gcn* gcn, ehm_smpl* smpl, const ehm_sample_desc* d, cons
                     float* x_final, float* x0_final, float* verts, float* joints, float* R, float* pose6d,
                     float* trace, void* workspace, int64_t workspace_bytes, void* stream);
 
+/* ---- the denoiser's input feature on the training route of EgoHMR.forward and its VJP (csrc/train.hip; egohmr.py:190-191, :220-236, mask_cond :150-169).
+ *   X [B,24,D], D = img_dim + n_other + 2 embed_dim, 16-byte aligned:
+ *     X[b,j,:] = [ vis[b,j] keep_img[b] img_feats[b] | keep_oth[b] other[b] | x_feat[24 b + j] | temb[b] ]
+ *   img_feats [B,img_dim]; vis [B,24] uint8; drop [B] uint8 or NULL (1 = the item's conditioning is dropped: keep_img = 1 - drop, keep_oth = 1 - drop or,
+ *   with only_mask_img = 1, always 1); other [B,other_ld] of which the first n_other columns are read (the padded [scene | transl | cam] operand of the
+ *   projections can be read in place); x_feat [24 B,embed_dim]; temb [B,embed_dim].  img_dim and embed_dim are multiples of 4, n_other is anything >= 1.
+ *   The masks are products with 0.0f / 1.0f.
+ * ehm_cond_assemble_backward: gX [B,24,D] -> g_img [B,img_dim] = keep_img sum_j vis gX, g_other [B,n_other] (contiguous) = keep_oth sum_j gX,
+ *   g_x_feat [24 B,embed_dim] (16-byte aligned) = its columns of gX, g_temb [B,embed_dim] = sum_j gX.  An output that is NULL is not computed and its
+ *   columns of gX are not read.  The sums over the joints run in index order in one thread (float32, no atomics): a call repeats bit for bit. */
+int ehm_cond_assemble(const float* img_feats, const uint8_t* vis, const uint8_t* drop, const float* other, int other_ld, int n_other,
+                      const float* x_feat, const float* temb, int only_mask_img, float* X, int B, int img_dim, int embed_dim, void* stream);
+int ehm_cond_assemble_backward(const float* gX, const uint8_t* vis, const uint8_t* drop, int n_other, int only_mask_img, float* g_img, float* g_other,
+                               float* g_x_feat, float* g_temb, int B, int img_dim, int embed_dim, void* stream);
+
 /* ---- measurement aid (bench.py's roofline objects; SURVEY.md 8d asks for per-kernel figures).  No reference counterpart.
  * Between ehm_profile_begin() and ehm_profile_end() every launch of ehm_sample_loop is bracketed by a pair of HIP events ON THE
  * LAUNCH STREAM, tagged with its class; ehm_profile_end waits for them and adds the elapsed times up per class
