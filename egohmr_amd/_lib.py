@@ -29,7 +29,7 @@ _HERE = os.path.dirname(os.path.abspath(__file__))
 LIB_PATH = os.environ.get("EHM_LIB_PATH") or os.path.join(_HERE, "libegohmr_hip.so")   # EHM_LIB_PATH: A/B a second build (experiments)
 CSRC = os.path.join(_HERE, "csrc")
 INCLUDE = os.path.join(os.path.dirname(_HERE), "include")
-SOURCES = ["gcn.hip", "gcn_tile.hip", "linear.hip", "conv.hip", "stem.hip", "metrics.hip", "smpl.hip", "sampler.hip", "guidance.hip", "prep.hip", "step.hip", "eval.hip", "stage1.hip", "scene.hip", "loss.hip", "gcn_bwd.hip", "gcn_train.hip", "pointnet_bwd.hip", "train.hip"]
+SOURCES = ["gcn.hip", "gcn_tile.hip", "linear.hip", "conv.hip", "stem.hip", "metrics.hip", "smpl.hip", "sampler.hip", "guidance.hip", "prep.hip", "step.hip", "eval.hip", "stage1.hip", "scene.hip", "loss.hip", "gcn_bwd.hip", "gcn_train.hip", "pointnet_bwd.hip", "train.hip", "conv_bwd.hip"]
 
 
 class EgoHMRHipError(RuntimeError):
@@ -298,6 +298,11 @@ PROTOTYPES = {
     "ehm_pointnet_bwd_lift": (_I, [_P, _P, _P, _P, _P, _P, _I, _I, _I, _I, _P, _L, _P]),
     "ehm_pointnet_bwd_wgrad_workspace_bytes": (_I, [_I, _I, _I, _I, C.POINTER(C.c_int64)]),
     "ehm_pointnet_bwd_wgrad": (_I, [_P, _P, _I, _I, _P, _I, _I, _I, _I, _I, _I, _P, _L, _P]),
+    "ehm_conv_bwd_gate": (_I, [_P, _I, _P, _P, _P, _I, _I, _I, _I, _I, _I, _P]),
+    "ehm_conv_bwd_wgrad_workspace_bytes": (_I, [_I, _I, _I, _I, _I, _I, _I, _I, C.POINTER(C.c_int64)]),
+    "ehm_conv_bwd_wgrad": (_I, [_P, _P, _L, _P, _P, _I, _I, _I, _I, _I, _I, _I, _I, _P, _L, _P]),
+    "ehm_resnet_stem_backward_workspace_bytes": (_I, [_I, _I, _I, C.POINTER(C.c_int64)]),
+    "ehm_resnet_stem_backward": (_I, [_P, _P, _P, _P, _P, _P, _P, _P, _I, _I, _I, _P, _L, _P]),
     "ehm_ddpm_step": (_I, [_P, _P, _P, _P, _P, _F, _F, _F, _F, _F, _L, _P]),
     "ehm_ddim_step": (_I, [_P, _P, _P, _P, _F, _F, _F, _F, _F, _F, _L, _P]),
     "ehm_collision_proxy": (_I, [_P, _P, _P, _P, _I, _I, _I, _F, _P]),
@@ -306,6 +311,8 @@ PROTOTYPES = {
     "ehm_guidance_grad_finish": (_I, [_P, _P, _P, _I, _F, _P]),
     "ehm_smpl_backward": (_I, [_P, _P, _P, _P, _P, _P, _P, _I, _P, _L, _P]),
     "ehm_smpl_backward_workspace_bytes": (_I, [_P, _I, C.POINTER(C.c_int64)]),
+    "ehm_smpl_backward_ordered": (_I, [_P, _P, _P, _P, _P, _P, _P, _I, _P, _L, _P]),
+    "ehm_smpl_backward_ordered_workspace_bytes": (_I, [_P, _I, C.POINTER(C.c_int64)]),
     "ehm_nn_dist2": (_I, [_P, _P, _P, _P, _I, _I, _I, _P]),
     "ehm_eval_point_errors": (_I, [C.POINTER(EvalPointsDesc), _P]),
     "ehm_eval_procrustes": (_I, [_P, _P, _P, _P, _P, _P, _P, _P, _I, _I, _I, _P]),

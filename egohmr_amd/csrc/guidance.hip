@@ -490,6 +490,113 @@ __global__ __launch_bounds__(kVT, 4) void skin_bwd_kernel(const float* __restric
   }
 }
 
+// skin_bwd_kernel's gA alone, in a FIXED order (ehm_smpl_backward_ordered): the same blocks (256 vertices x 8 bodies), the blended rest vertex
+// recomputed as there, but no atomics - a wave adds its 64 vertices with wave_sum, the block's four waves add into LDS one after the other, and the
+// block's sums go to part[vt][B][24][12] (cleared by the caller), which skin_gA_sum_kernel adds over the vertex tiles in index order.  Reads the
+// INCOMING vertex cotangent: it runs before skin_bwd_kernel overwrites it.  Bodies / joints that no lane of a wave touches are skipped.
+__global__ __launch_bounds__(kVT) void skin_gA_ordered_kernel(const float* __restrict__ betas, const float* __restrict__ Rws, SmplDev S,
+                                                              const float* __restrict__ gv_in, float* __restrict__ part, int B, int v_tiles,
+                                                              int b_groups) {
+  __shared__ float sG[kBG][kJ][12];
+  __shared__ float sPF[kBG][kPoseBasis + 1];
+  __shared__ float sBeta[kBG][10];
+  __shared__ int any_grad;
+  const int bid = blockIdx.x;
+  const int xcd = bid & 7, k = bid >> 3;
+  const int vt = (k / b_groups) * 8 + xcd, bg = k % b_groups;
+  if (vt >= v_tiles) return;
+  const int b0 = bg * kBG, nb = min(kBG, B - b0), tid = threadIdx.x;
+  const int v = vt * kVT + tid;
+  const bool vok = v < S.V;
+  float gv[kBG][3], vp[kBG][3];
+  bool mine = false;
+#pragma unroll
+  for (int bb = 0; bb < kBG; ++bb) {
+#pragma unroll
+    for (int c = 0; c < 3; ++c) {
+      gv[bb][c] = (vok && bb < nb) ? gv_in[((size_t)(b0 + bb) * S.V + v) * 3 + c] : 0.f;
+      vp[bb][c] = 0.f;
+      mine |= gv[bb][c] != 0.f;
+    }
+  }
+  if (tid == 0) any_grad = 0;
+  __syncthreads();
+  if (mine) any_grad = 1;
+  __syncthreads();
+  if (!any_grad) return;                                  // (block-uniform; the partial sums were cleared)
+  for (int i = tid; i < kBG * kJ * 12; i += kVT) (&sG[0][0][0])[i] = 0.f;
+  for (int i = tid; i < kBG * kPoseBasis; i += kVT) {
+    const int bb = i / kPoseBasis, p = i % kPoseBasis, e = p % 9;
+    sPF[bb][p] = bb < nb ? Rws[((size_t)(b0 + bb) * kJ + 1) * 9 + p] - ((e == 0 || e == 4 || e == 8) ? 1.f : 0.f) : 0.f;
+  }
+  if (tid < kBG * 10) sBeta[tid / 10][tid % 10] = (tid / 10) < nb ? betas[(size_t)b0 * 10 + tid] : 0.f;
+  __syncthreads();
+  if (mine) {                                             // the blended rest vertex, with skin_bwd_kernel's arithmetic
+    const int V3 = S.V * 3;
+    const float t0 = S.v_template[v * 3 + 0], t1 = S.v_template[v * 3 + 1], t2 = S.v_template[v * 3 + 2];
+#pragma unroll 2
+    for (int l = 0; l < 10; ++l) {
+      const float s0 = S.shape_t[(size_t)l * V3 + v * 3 + 0], s1 = S.shape_t[(size_t)l * V3 + v * 3 + 1], s2 = S.shape_t[(size_t)l * V3 + v * 3 + 2];
+#pragma unroll
+      for (int bb = 0; bb < kBG; ++bb) {
+        const float be = sBeta[bb][l];
+        vp[bb][0] = fmaf(be, s0, vp[bb][0]); vp[bb][1] = fmaf(be, s1, vp[bb][1]); vp[bb][2] = fmaf(be, s2, vp[bb][2]);
+      }
+    }
+#pragma unroll
+    for (int bb = 0; bb < kBG; ++bb) { vp[bb][0] += t0; vp[bb][1] += t1; vp[bb][2] += t2; }
+    const float* pd = S.posedirs + (size_t)v * 3;
+#pragma unroll 2
+    for (int p = 0; p < kPoseBasis; ++p) {
+      const float d0 = pd[(size_t)p * V3 + 0], d1 = pd[(size_t)p * V3 + 1], d2 = pd[(size_t)p * V3 + 2];
+#pragma unroll
+      for (int bb = 0; bb < kBG; ++bb) {
+        const float f = sPF[bb][p];
+        vp[bb][0] = fmaf(f, d0, vp[bb][0]); vp[bb][1] = fmaf(f, d1, vp[bb][1]); vp[bb][2] = fmaf(f, d2, vp[bb][2]);
+      }
+    }
+  }
+  // d/dA_j = sum_v w [gv (x) vp | gv]: lanes by wave_sum, waves one after the other (a thread without a gradient contributes zeros)
+  const int lane = tid & 63, wave = tid >> 6;
+  for (int w = 0; w < kVT / 64; ++w) {
+    __syncthreads();
+    if (wave != w) continue;
+#pragma unroll 1
+    for (int bb = 0; bb < nb; ++bb) {
+      float g0 = 0.f, g1 = 0.f, g2 = 0.f, p0 = 0.f, p1 = 0.f, p2 = 0.f;
+#pragma unroll
+      for (int q = 0; q < kBG; ++q)
+        if (q == bb) { g0 = gv[q][0]; g1 = gv[q][1]; g2 = gv[q][2]; p0 = vp[q][0]; p1 = vp[q][1]; p2 = vp[q][2]; }
+      const bool hot = g0 != 0.f || g1 != 0.f || g2 != 0.f;
+      if (__ballot(hot) == 0ull) continue;
+#pragma unroll 1
+      for (int j = 0; j < kJ; ++j) {
+        const float wj = hot ? S.w_t[(size_t)j * S.V + v] : 0.f;
+        if (__ballot(wj != 0.f) == 0ull) continue;
+        const float w0 = wj * g0, w1 = wj * g1, w2 = wj * g2;
+        const float c[12] = {w0 * p0, w0 * p1, w0 * p2, w0, w1 * p0, w1 * p1, w1 * p2, w1, w2 * p0, w2 * p1, w2 * p2, w2};
+#pragma unroll
+        for (int e = 0; e < 12; ++e) {
+          const float t = wave_sum(c[e]);
+          if (lane == 0) sG[bb][j][e] += t;
+        }
+      }
+    }
+  }
+  __syncthreads();
+  float* o = part + ((size_t)vt * B + b0) * kJ * 12;
+  for (int i = tid; i < nb * kJ * 12; i += kVT) o[i] = (&sG[0][0][0])[i];
+}
+
+// gA[i] = the vertex tiles' partial sums in index order
+__global__ __launch_bounds__(256) void skin_gA_sum_kernel(const float* __restrict__ part, float* __restrict__ gA, int n, int v_tiles) {
+  const int i = blockIdx.x * 256 + threadIdx.x;
+  if (i >= n) return;
+  float s = 0.f;
+  for (int t = 0; t < v_tiles; ++t) s += part[(size_t)t * n + i];
+  gA[i] = s;
+}
+
 // gpf[b][p] = sum_col posedirs[p][col] * gvp[b][col];  block = (joint-1: 9 basis rows) x (8 bodies)
 // The same contraction on the matrix cores in exact float32 (v_mfma_f32_32x32x2_f32): gpf[b][k] = sum_c gverts[b][c] * posedirs[k][c], a
 // [B, 3V] x [3V, 207] GEMM whose BOTH operands are k-contiguous rows - a lane (row / column = l & 31, h = l >> 5) loads 16 bytes of its row at
@@ -1115,12 +1222,16 @@ extern "C" int ehm_smpl_backward_workspace_bytes(const ehm_smpl* h, int B, int64
   return 0;
 }
 
-extern "C" int ehm_smpl_backward(ehm_smpl* h, const float* betas, const float* rotmats, const float* gverts, const float* gjoints, float* gbetas,
-                                 float* grotmats, int B, void* workspace, int64_t workspace_bytes, void* stream) {
+// the fixed-order route's extra workspace: the vertex tiles' partial gA
+static int64_t smpl_backward_ordered_extra(const ehm_smpl* h, int B) { return round_up(ceil_div(h->d.V, kVT) * (int64_t)B * kJ * 12 * 4, 256); }
+
+static int smpl_backward_impl(ehm_smpl* h, const float* betas, const float* rotmats, const float* gverts, const float* gjoints, float* gbetas,
+                              float* grotmats, int B, void* workspace, int64_t workspace_bytes, void* stream, bool ordered) {
   EHM_CHECK_ARG(h && betas && rotmats && B > 0);
   EHM_CHECK_ARG(gverts || gjoints);
   EHM_CHECK_ARG(gbetas || grotmats);
-  EHM_CHECK_ARG(workspace && ((uintptr_t)workspace & 15) == 0 && workspace_bytes >= smpl_backward_bytes(h, B));
+  EHM_CHECK_ARG(workspace && ((uintptr_t)workspace & 15) == 0 &&
+                workspace_bytes >= smpl_backward_bytes(h, B) + (ordered ? smpl_backward_ordered_extra(h, B) : 0));
   hipStream_t st = (hipStream_t)stream;
   const SmplDev& d = h->d;
   const int V = d.V;
@@ -1131,7 +1242,8 @@ extern "C" int ehm_smpl_backward(ehm_smpl* h, const float* betas, const float* r
   float* Aws = (float*)p;     p += round_up((int64_t)B * kJ * 12 * 4, 256);
   float* jws = (float*)p;     p += round_up((int64_t)B * (kJ + 64) * 3 * 4, 256);
   float* gcopy = (float*)p;   p += round_up((int64_t)B * V * 3 * 4, 256);
-  float* gbv = (float*)p;
+  float* gbv = (float*)p;     p += round_up((int64_t)B * 10 * 4, 256);
+  float* gA_part = (float*)p;                                 // (ordered only)
   if (gverts) EHM_HIP(hipMemcpyAsync(gcopy, gverts, (size_t)B * V * 3 * sizeof(float), hipMemcpyDeviceToDevice, st));
   else EHM_HIP(hipMemsetAsync(gcopy, 0, (size_t)B * V * 3 * sizeof(float), st));
   if (gjoints && d.n_extra)
@@ -1139,13 +1251,37 @@ extern "C" int ehm_smpl_backward(ehm_smpl* h, const float* betas, const float* r
                        d.n_extra);
   int rc = ehm_smpl_pose_rotmat_impl(h, betas, rotmats, Rws, Aws, jws, B, st);
   if (rc) return rc;
+  const int v_tiles = (int)ceil_div(V, kVT), b_groups = (int)ceil_div(B, kBG), nA = B * kJ * 12;
+  if (ordered) {                                              // gA in a fixed order, from the cotangent as it comes in
+    EHM_HIP(hipMemsetAsync(gA_part, 0, (size_t)v_tiles * nA * sizeof(float), st));
+    hipLaunchKernelGGL(skin_gA_ordered_kernel, dim3((unsigned)(round_up(v_tiles, 8) * b_groups)), dim3(kVT), 0, st, betas, (const float*)Rws, d,
+                       (const float*)gcopy, gA_part, B, v_tiles, b_groups);
+  }
   rc = skin_posefeat_bwd(h, betas, Rws, Aws, gcopy, B, s, st, nullptr, grotmats != nullptr);
   if (rc) return rc;
+  if (ordered)                                                // ... replaces the atomically accumulated one
+    hipLaunchKernelGGL(skin_gA_sum_kernel, dim3((unsigned)ceil_div(nA, 256)), dim3(256), 0, st, (const float*)gA_part, s.gA, nA, v_tiles);
   if (gbetas) hipLaunchKernelGGL(shape_bwd_kernel, dim3((unsigned)ceil_div(B, kSbB)), dim3(256), 0, st, gcopy, d.shape_t, gbv, B, V * 3);
   hipLaunchKernelGGL(chain_bwd_rotmat_kernel, dim3(B), dim3(64), 0, st, betas, rotmats, d, s.gA, s.gpf, gjoints, (kJ + d.n_extra) * 3, gbv, grotmats,
                      gbetas);
   EHM_LAUNCH_CHECK();
   return 0;
+}
+
+extern "C" int ehm_smpl_backward(ehm_smpl* h, const float* betas, const float* rotmats, const float* gverts, const float* gjoints, float* gbetas,
+                                 float* grotmats, int B, void* workspace, int64_t workspace_bytes, void* stream) {
+  return smpl_backward_impl(h, betas, rotmats, gverts, gjoints, gbetas, grotmats, B, workspace, workspace_bytes, stream, false);
+}
+
+extern "C" int ehm_smpl_backward_ordered_workspace_bytes(const ehm_smpl* h, int B, int64_t* bytes) {
+  EHM_CHECK_ARG(h && bytes && B > 0);
+  *bytes = smpl_backward_bytes(h, B) + smpl_backward_ordered_extra(h, B);
+  return 0;
+}
+
+extern "C" int ehm_smpl_backward_ordered(ehm_smpl* h, const float* betas, const float* rotmats, const float* gverts, const float* gjoints,
+                                         float* gbetas, float* grotmats, int B, void* workspace, int64_t workspace_bytes, void* stream) {
+  return smpl_backward_impl(h, betas, rotmats, gverts, gjoints, gbetas, grotmats, B, workspace, workspace_bytes, stream, true);
 }
 
 extern "C" int ehm_guidance_grad_finish(const float* gpose6d, const float* loss, float* grad, int B, float denom, void* stream) {

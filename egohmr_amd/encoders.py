@@ -46,6 +46,14 @@ class ResNet50Features(nn.Module):
     """models/resnet.py:139-150: ResNet-50 trunk, global average pool -> [B,2048]."""
 
     hi_only = False      # True: the plain-f16 tier of the trunk (ehm_conv_x2_desc.hi_only: hi halves only, one MFMA per product) - NOT parity grade
+    # True: a call with grad mode on and a parameter that requires grad runs behind trunk_grad.TrunkFunction - the same launches, every conv's X2 output
+    # kept for the backward (about 9 M values per 224 x 224 image) - and its backward fills the parameters' gradients (BatchNorm in eval mode: the
+    # statistics stay frozen, conv weights and affine parameters train).  False: every call is the no-graph route, whatever the parameters say
+    grad_params = False
+    GRAD_HI_ONLY = ("the autograd route of ResNet50Features keeps f32-grade activations for its backward; the plain-f16 tier "
+                    "(ResNet50Features.hi_only = True) stores none: set hi_only = False with it")
+    GRAD_IMAGE = ("ResNet50Features.grad_params differentiates the trunk with respect to its parameters only: the image gradient (the stem's data "
+                  "gradient) is not built, so the input must not require grad")
 
     def __init__(self):
         super().__init__()
@@ -71,7 +79,15 @@ class ResNet50Features(nn.Module):
         return self._fold_fn
 
     def forward(self, x):
-        """The module call IS the HIP path (models/resnet.py:139-150 in eval mode); there is no eager route."""
+        """The module call IS the HIP path (models/resnet.py:139-150 in eval mode); there is no eager route.  With `grad_params`, grad mode on and a
+        parameter that requires grad the result carries a grad_fn (trunk_grad.TrunkFunction: same launches, same bits, activations kept)."""
+        if self.grad_params and torch.is_grad_enabled() and any(p.requires_grad for p in self.parameters()):
+            if self.hi_only:
+                raise _lib.EgoHMRHipError(self.GRAD_HI_ONLY)
+            if x.requires_grad:
+                raise NotImplementedError(self.GRAD_IMAGE)
+            from . import trunk_grad
+            return trunk_grad.TrunkFunction.apply(self, x, *self.parameters())
         return self.current()(x)
 
     # ------------------------------------------------------------------ stream-K hand-off time-outs (csrc/conv.hip): made loud, never waited for
@@ -220,26 +236,32 @@ class ResNet50Features(nn.Module):
                 _x2_debug_hook(y, Co)
             return y, (N, Ho, Wo)
 
-        def run_x2(x):
-            """the whole trunk with the activations in the X2 split format between the layers (taps gathered by the LDS DMA)"""
+        def run_x2(x, saved=None):
+            """the whole trunk with the activations in the X2 split format between the layers (taps gathered by the LDS DMA).
+            saved: a list that receives (X2 buffer, (N, H, W)) of the stem's and of every conv's output in launch order instead of letting them go"""
             N = x.shape[0]
             shp = (N, x.shape[2] // 4, x.shape[3] // 4)
+            keep = (lambda *e: None) if saved is None else (lambda *e: saved.append(e))
             x = stem_mc(x, x2=True)
+            keep(x, shp)
             for c1, c2, c3, ds in blocks:
                 y, s1 = conv_x2(x, shp, c1)
+                keep(y, s1)
                 y, s2 = conv_x2(y, s1, c2)
+                keep(y, s2)
                 if ds is None:
                     x, shp = conv_x2(y, s2, c3, res=x)
                 elif fuse_shortcut:
                     x, shp = conv_x2(y, s2, c3, shortcut=(x, shp, ds))          # out = conv3(.) + downsample(x) in one launch: no shortcut tensor
                 else:
                     x, shp = conv_x2(y, s2, c3, res=conv_x2(x, shp, ds, relu=False)[0])
+                keep(x, shp)
             out = torch.empty(N, x.shape[1], device=x.device)
             A.ehm_x2_group_mean(x, out, N, shp[1] * shp[2], x.shape[1], int(bool(self.hi_only)), _lib.stream_ptr())
             self._sk_status_async(sk_ws.get(str(x.device)))
             return out
 
-        def run(x):
+        def run(x, saved=None):
             if not x.is_cuda:
                 raise _lib.EgoHMRHipError("the ResNet-50 backbone needs its input on a HIP device; egohmr_amd has no CPU path")
             x = _lib.f32(x)
@@ -247,13 +269,14 @@ class ResNet50Features(nn.Module):
                 raise _lib.EgoHMRHipError(f"the fused stem needs [N,3,H,W] images with H, W multiples of 32 (the reference feeds 224 x 224 crops); got {tuple(x.shape)}")
             with _lib.on_device(x.device):                                          # the library launches on the CURRENT device's stream
                 if x2_activations:
-                    return run_x2(x)
+                    return run_x2(x, saved)
                 x = stem_mc(x)                                                      # NHWC float32 from here on
                 for c1, c2, c3, ds in blocks:
                     y = conv_mc(conv_mc(x, c1), c2)
                     x = conv_mc(y, c3, res=x if ds is None else conv_mc(x, ds, relu=False))
                 return x.mean(dim=(1, 2))
 
+        run.stem, run.blocks, run.stem_wt, run.stem_b = stem, blocks, stem_wt, stem_b         # the folded parameters (trunk_grad reads them)
         return run
 
 

@@ -159,15 +159,17 @@ class FusedSampler:
 
     # ------------------------------------------------------------------ step-invariant conditioning
     @torch.no_grad()
-    def prepare(self, batch, _constants_only=False) -> _Prepared:
+    def prepare(self, batch, _constants_only=False, _no_trunk=False) -> _Prepared:
         """Everything in EgoHMR.forward that does not depend on x_t / t (egohmr.py:182-223, :263-265).
         _constants_only (the training route of EgoHMR.forward): only what stays constant with the trunk frozen - trunk, visibility, camera columns, scene,
         translation; the PointNet, the projections, the beta head and the native handle are left out (h_img, h_oth, betas, scene_feats = None, no pass map,
-        no host read-back; `other` holds ehm_item_prep's operand).  Such an entry is cached under a key of its own: no other caller ever sees it."""
+        no host read-back; `other` holds ehm_item_prep's operand).  Such an entry is cached under a key of its own: no other caller ever sees it.
+        _no_trunk (with _constants_only, behind EgoHMR.trunk_grad): the trunk is left out too - img_feats = None, the caller runs it with a graph -
+        again under a key of its own."""
         with _lib.on_device(self.model.device):          # every native call below launches on the CURRENT device's stream
-            return self._prepare_on_device(batch, _constants_only)
+            return self._prepare_on_device(batch, _constants_only, _constants_only and _no_trunk)
 
-    def _prepare_on_device(self, batch, constants_only=False) -> _Prepared:
+    def _prepare_on_device(self, batch, constants_only=False, no_trunk=False) -> _Prepared:
         m = self.model
         # Cache key = identity AND version of every tensor the conditioning is computed from, and of every weight it passes
         # through.  The cached entry keeps strong references to those input tensors, so neither their id() nor their storage can be
@@ -185,6 +187,8 @@ class FusedSampler:
         key = tuple((id(t), t._version, t.data_ptr()) for t in ins) + self._param_key() + self._cond_param_key() + (switches,)
         if constants_only:
             key += ("constants_only",)
+        if no_trunk:
+            key += ("no_trunk",)
         if self._prep is not None and self._prep_key == key:
             return self._prep
         if not constants_only:
@@ -241,10 +245,10 @@ class FusedSampler:
         count_ready.record(torch.cuda.current_stream(dev))
         # The two encoders are independent, but each fills the chip on its own: one after the other on ONE stream (two streams measured
         # slower, docs/EXPERIMENTS.md)
-        img_feats = self._backbone_fn()(img)                                           # :183 (BatchNorm folded into the convs)
+        img_feats = None if no_trunk else self._backbone_fn()(img)                     # :183 (BatchNorm folded into the convs)
         if constants_only:
             self._prep = _PreparedConstants(B=B, h_img=None, h_oth=None, vis=vis, vis_bool=vis.view(torch.bool), betas=None, scene=scene, transl=transl, fx=fx,
-                                   cam_cx=cx, cam_cy=cy, img_feats=img_feats.contiguous(), scene_feats=None,
+                                   cam_cx=cx, cam_cy=cy, img_feats=None if no_trunk else img_feats.contiguous(), scene_feats=None,
                                             finite=flags[0].view(torch.bool), mask_items=maps[B:B], mask_slot=maps[:B], num_masked=-1, inputs=ins, other=oth)
             self._prep_key = key
             return self._prep

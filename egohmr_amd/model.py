@@ -506,6 +506,10 @@ class EgoHMR(nn.Module):
     # (_forward_train): the folded ResNet-50 in eval mode under no_grad, everything else of init_optimizers' list (scene PointNet, transl_enc, beta_layer,
     # the denoiser, embed_timestep, input_process) with a graph.  Calls with self.training False do not depend on it
     frozen_trunk_training = False
+    # Consulted on the training route only (behind frozen_trunk_training, whose name stays): True unfreezes the trunk's WEIGHTS - img_feats comes from the
+    # backbone's autograd route (ResNet50Features.grad_params; BatchNorm in eval mode, the statistics stay frozen) and init_optimizers puts
+    # backbone.parameters() in front, which is the reference's list (egohmr.py:140-147)
+    trunk_grad = False
 
     def forward(self, batch, timesteps, eval_with_uncond=True):
         """One denoising evaluation (egohmr.py:173-303).  Conditioning is cached per batch object.  Under self.training with frozen_trunk_training set: the
@@ -550,7 +554,10 @@ class EgoHMR(nn.Module):
         conditioning assembly with the cond_mask_prob draw (train_grad.CondAssemble: one launch each way), the denoiser (ModulatedGCN.forward with
         grad_params set, in EgoHMR.gcn_precision: batch statistics behind ModulatedGCN.train_batchnorm, else eval-mode BatchNorm with frozen statistics -
         the reference always trains on batch statistics) and decode_output.  Sets batch['vis_mask_smpl'], smpl_output, scene_pcd_verts, input_transl,
-        focal_length and camera_center_full like forward; like decode_output it does NOT apply the NaN rule of ehm_pack_outputs."""
+        focal_length and camera_center_full like forward; like decode_output it does NOT apply the NaN rule of ehm_pack_outputs.
+        With EgoHMR.trunk_grad, img_feats is not a constant: prepare leaves the trunk out and the backbone runs here behind its autograd route
+        (ResNet50Features.grad_params set for the call; eval-mode BatchNorm, the statistics stay frozen).
+        SMPL.ordered_backward is set for the decode: the route has no order-dependent sum, so two steps on the same inputs give the same gradient bits."""
         self._check_trainable()
         dm, dev = self.diffusion_model, self.device
         x_t = _lib.f32(batch["x_t"], dev).reshape(-1, 144)
@@ -558,27 +565,38 @@ class EgoHMR(nn.Module):
         ts = torch.as_tensor(timesteps, device=dev).reshape(-1).long()
         if ts.numel() not in (1, B):
             raise ValueError(f"timesteps must hold one value per item: got {ts.numel()} for a batch of {B}")
-        st = self.fused_sampler.prepare(batch, _constants_only=True)
+        st = self.fused_sampler.prepare(batch, _constants_only=True, _no_trunk=bool(self.trunk_grad))
         n_scene, n_other = self.scene_enc.fc_c.out_features, self.context_feats_dim - IMG_DIM
-        enc = self.scene_enc
+        enc, bb = self.scene_enc, self.backbone
         keep = (enc.grad_params, dm.grad_params, dm.precision)
+        keep_bb = bb.grad_params
         try:
             enc.grad_params = dm.grad_params = True
             dm.precision = self.gcn_precision
             dm.train(bool(dm.train_batchnorm))
+            img_feats = st.img_feats
+            if self.trunk_grad:                                                                            # :183 with a graph (eval-mode BatchNorm)
+                bb.grad_params = True
+                img_feats = bb(_lib.f32(batch["img"], dev))
             scene_feats = enc(st.scene)                                                                    # :214
             transl_feat = self.transl_enc(st.transl)                                                       # :217
             cam = st.other[:, n_scene + transl_feat.shape[1]:n_other]                                      # :195-205 (ehm_item_prep wrote them)
             other = torch.cat([scene_feats, transl_feat, cam], dim=1)                                      # :220-221
             temb = self.embed_timestep(ts.expand(B)).squeeze(0)                                            # :178
             x_feat = self.input_process.poseEmbedding(x_t.reshape(B * 24, 6))                              # :234
-            X = train_grad.CondAssemble.apply(st.img_feats, st.vis, self.cond_drop_mask(B), other, x_feat, temb, self.only_mask_img_cond)   # :190-191, :222-236
+            X = train_grad.CondAssemble.apply(img_feats, st.vis, self.cond_drop_mask(B), other, x_feat, temb, self.only_mask_img_cond)   # :190-191, :222-236
             x0 = dm(X).reshape(B, 144)                                                                     # :237, :256
         finally:
             enc.grad_params, dm.grad_params, dm.precision = keep
-        betas = self.beta_layer(torch.cat([st.img_feats, other], dim=1))                                   # :263-265
+            bb.grad_params = keep_bb
+        betas = self.beta_layer(torch.cat([img_feats, other], dim=1))                                   # :263-265
         batch["vis_mask_smpl"] = st.vis_bool                                                               # :189
-        return self.decode_output(batch, x0, betas, _st=st)
+        keep_ordered = self.smpl.ordered_backward
+        try:
+            self.smpl.ordered_backward = True                                                              # a step's gradients repeat their bits
+            return self.decode_output(batch, x0, betas, _st=st)
+        finally:
+            self.smpl.ordered_backward = keep_ordered
 
     def _forward_on_device(self, batch, timesteps, eval_with_uncond):
         fs = self.fused_sampler
@@ -946,13 +964,16 @@ class EgoHMR(nn.Module):
             "pred_keypoints_2d_full": kp2d,
         }
 
-    NOT_BUILT = ("compute_loss has a backward (the loss, SMPL.forward, rot6d_to_rotmat, ModulatedGCN.forward and ResnetPointnet.forward are differentiable, "
-                 "ModulatedGCN.train_batchnorm runs BatchNorm in training mode; decode_output chains them), but the ResNet-50 trunk's backward and the non-local "
-                 "block's backward are missing; the training route of EgoHMR.forward runs with the trunk frozen once EgoHMR.frozen_trunk_training is set")
+    NOT_BUILT = ("compute_loss has a backward (the loss, SMPL.forward, rot6d_to_rotmat, ModulatedGCN.forward, ResnetPointnet.forward and the ResNet-50 trunk "
+                 "in eval mode are differentiable, ModulatedGCN.train_batchnorm runs BatchNorm in training mode; decode_output chains them), but train-mode "
+                 "BatchNorm2d for the ResNet-50 trunk, the image gradient and the non-local block's backward are missing; the training route of "
+                 "EgoHMR.forward runs once EgoHMR.frozen_trunk_training is set - with the trunk's statistics frozen, and its weights too unless "
+                 "EgoHMR.trunk_grad is set")
 
     def init_optimizers(self):
-        """egohmr.py:140-147 with the trunk frozen: the reference's parameter list in its order, without `backbone`."""
-        self.opt_params = (list(self.scene_enc.parameters()) + list(self.transl_enc.parameters()) + list(self.beta_layer.parameters()) +
+        """egohmr.py:140-147: the reference's parameter list in its order - without `backbone` while the trunk is frozen, with it in front behind
+        EgoHMR.trunk_grad."""
+        self.opt_params = ((list(self.backbone.parameters()) if self.trunk_grad else []) + list(self.scene_enc.parameters()) + list(self.transl_enc.parameters()) + list(self.beta_layer.parameters()) +
                            list(self.diffusion_model.parameters()) + list(self.embed_timestep.parameters()) + list(self.input_process.parameters()))
         self.optimizer = torch.optim.AdamW(params=self.opt_params, lr=self.cfg.TRAIN.LR, weight_decay=self.cfg.TRAIN.WEIGHT_DECAY)
 

@@ -51,7 +51,7 @@ class _SMPLForward(torch.autograd.Function):
         joints = torch.empty(B, model.num_joints_out, 3, device=dev, dtype=torch.float32)
         with torch.cuda.device(dev):
             _lib.api().ehm_smpl_forward(model.handle(), betas, full, verts, joints, None, B, _lib.stream_ptr())
-        ctx.model = model
+        ctx.model, ctx.ordered = model, bool(model.ordered_backward)
         ctx.save_for_backward(betas, full)
         ctx.set_materialize_grads(False)            # an unused output reaches the kernel as NULL, not as a zero tensor
         return verts, joints
@@ -70,16 +70,21 @@ class _SMPLForward(torch.autograd.Function):
         grot = torch.empty_like(full) if need_rot else None
         A, h = _lib.api(), ctx.model.handle()
         nb = C.c_int64()
-        A.ehm_smpl_backward_workspace_bytes(h, B, C.byref(nb))
+        size_fn, bwd_fn = ((A.ehm_smpl_backward_ordered_workspace_bytes, A.ehm_smpl_backward_ordered) if ctx.ordered else
+                           (A.ehm_smpl_backward_workspace_bytes, A.ehm_smpl_backward))
+        size_fn(h, B, C.byref(nb))
         ws = torch.empty(nb.value, device=dev, dtype=torch.uint8)
         with torch.cuda.device(dev):
-            A.ehm_smpl_backward(h, betas, full, gverts, gjoints, gbetas, grot, B, ws, nb.value, _lib.stream_ptr())
+            bwd_fn(h, betas, full, gverts, gjoints, gbetas, grot, B, ws, nb.value, _lib.stream_ptr())
         return None, gbetas, grot
 
 
 class SMPL(nn.Module):
     NUM_JOINTS = 23
     NUM_BODY_JOINTS = 23
+    # Read when a differentiable forward runs: True = its backward is ehm_smpl_backward_ordered (every sum in a fixed order: two calls give the same
+    # bits; two launches more).  False, the default: ehm_smpl_backward as it always was.  The training route of EgoHMR.forward sets it for its call
+    ordered_backward = False
 
     def __init__(self, asset: dict, gender: str = "neutral", batch_size: int = 1, create_transl: bool = True, **_):
         super().__init__()

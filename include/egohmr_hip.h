@@ -368,6 +368,35 @@ size_t ehm_resnet_stem_scratch_bytes(int N, int H, int W);
 int ehm_resnet_stem(const float* img, const float* Wt, const float* bias, float* scratch, float* y, int N, int H, int W,
                     int out_x2, void* stream);
 
+/* ------------------------------------------------------------------ ResNet-50 trunk: backward (eval-mode BatchNorm, folded) ---- */
+/* First derivatives of the folded trunk around its data-gradient convolutions, which are ehm_conv_nhwc_split calls of the caller
+ * (egohmr_amd/trunk_grad.py).  Per conv y = relu(conv(x, w') + b' (+ res)), g = dL/dy:  G = g (.) [y > 0],  b'bar = sum_p G,
+ * w'bar[co,kh,kw,ci] = sum_p G[p,co] x[tap(p),ci].  "X2" is the split format ehm_conv_x2 / ehm_resnet_stem write (rows of ehm_conv_x2_rows).
+ * No allocation, no host synchronisation, no atomics: every sum over pixels is a fixed-order reduction (two calls on the same inputs give the same bits).
+ *
+ * out[n,h,w,c] = *scale * g * [y > 0] as float32 NHWC.  y_x2: the conv's saved X2 output [N*Ho*Wo rows, C] (only its sign is used; a NaN in g behind
+ * a closed gate does not pass).  g: [N,Ho,Wo,C] float32, or with g_per_image [N,C] read as g[n,c] / (Ho*Wo) (the average pool).  (H, W) == (Ho, Wo):
+ * dense.  Otherwise (H-1)/2+1 == Ho and (W-1)/2+1 == Wo: zero-dilated - the value of (ho, wo) at (2 ho, 2 wo), zeros elsewhere - so that the data
+ * gradient of a stride-2 conv is a stride-1 conv.  scale: a float on the DEVICE, or NULL for 1.  C % 32 == 0, 16-byte aligned pointers. */
+int ehm_conv_bwd_gate(const float* g, int g_per_image, const void* y_x2, const float* scale, float* out, int N, int Ho, int Wo, int C, int H, int W,
+                      void* stream);
+/* gw [Co][K*K*Ci] (tap-major, like the forward's packed weights) = sum over the output pixels of G[p,co] x[tap(p),ci] and gbias [Co] = sum_p G[p,co]
+ * (either may be NULL, not both).  G float32 [N,Ho,Wo,Co] (dense), x_x2 the conv's saved X2 input [x_rows >= N*H*W, Ci]; K in {1, 3}, stride in {1, 2},
+ * any pad (a tap outside the image counts as zero and is never loaded); Ci % 64 == 0, Co % 64 == 0.  Exact float32 products on the matrix cores
+ * (v_mfma_f32_32x32x2_f32 with k = the pixel), split over at most 256 runs of pixels whose partial tiles are added in index order.
+ * workspace: *bytes of ehm_conv_bwd_wgrad_workspace_bytes, 16-byte aligned. */
+int ehm_conv_bwd_wgrad_workspace_bytes(int N, int H, int W, int Ci, int Co, int K, int stride, int pad, int64_t* bytes);
+int ehm_conv_bwd_wgrad(const float* G, const void* x_x2, int64_t x_rows, float* gw, float* gbias, int N, int H, int W, int Ci, int Co, int K, int stride,
+                       int pad, void* workspace, int64_t workspace_bytes, void* stream);
+/* Weight and bias gradient of the stem (ehm_resnet_stem): gW [64][147] (k = (ci*7 + kh)*7 + kw), gb [64] (either may be NULL, not both) from
+ * gpool [N,H/4,W/4,64] float32, the cotangent of the pooled output ALREADY gated by [pooled > 0].  The 7x7 / 2 pre-pool activation is recomputed in
+ * float32 per chunk of images into the workspace and the pooled cotangent routed by gather: a pre-pool pixel takes the cotangent of each of the (at
+ * most four) 3x3 / 2 windows whose arg-max it is (lowest row-major index among equals, NaN = maximum).  z_out / gz_out: optional [N,H/2,W/2,64]
+ * float32 copies of the pre-pool activation and of its cotangent (tests).  img [N,3,H,W], Wt [147][64], bias [64] as for ehm_resnet_stem. */
+int ehm_resnet_stem_backward_workspace_bytes(int N, int H, int W, int64_t* bytes);
+int ehm_resnet_stem_backward(const float* img, const float* Wt, const float* bias, const float* gpool, float* gW, float* gb, float* z_out, float* gz_out,
+                             int N, int H, int W, void* workspace, int64_t workspace_bytes, void* stream);
+
 /* NHWC convolution + bias (+ identity) + ReLU as an implicit GEMM on the f16 matrix cores with f32-grade accuracy (hi/lo split
  * operands, f32 accumulate): y[n,ho,wo,co] = act(sum x[n, ho*s-p+kh, wo*s-p+kw, ci] w[co,kh,kw,ci] + bias[co] (+ residual)).
  * Stands in for torchvision's Bottleneck conv1/conv2/conv3/downsample + BatchNorm(eval, folded by the caller) + ReLU of the
@@ -480,11 +509,20 @@ int ehm_smpl_backward_rot6d(ehm_smpl* h, const float* betas, const float* x, con
  * betas / rotmats: the forward's inputs (the chain is recomputed).  Reproducibility: the pose-blend and shape contractions, the extra-joint
  * scatter and the chain pass sum in a fixed order, but the skinning VJP they share with ehm_smpl_backward_rot6d accumulates the per-joint
  * transform gradients with float atomics, and both outputs are derived from those: with more than two contributing vertices per joint,
- * grotmats and gbetas are reproducible from call to call only up to the last bits (order of float32 additions).  Launches on `stream`
+ * grotmats and gbetas are reproducible from call to call only up to the last bits (order of float32 additions) - ehm_smpl_backward_ordered
+ * below is the variant that repeats its bits.  Launches on `stream`
  * out of `workspace` (16-byte aligned, at least *bytes of ehm_smpl_backward_workspace_bytes(h, B, &bytes)): no allocation, no host
  * synchronisation.  Bad arguments are refused with EINVAL before anything is launched. */
 int ehm_smpl_backward(ehm_smpl* h, const float* betas, const float* rotmats, const float* gverts, const float* gjoints, float* gbetas,
                       float* grotmats, int B, void* workspace, int64_t workspace_bytes, void* stream);
+/* ehm_smpl_backward with EVERY sum in a fixed order (the training route of EgoHMR.forward: a step's gradients repeat their bits).  The same
+ * launches plus two: before the skinning VJP a kernel of its own sums the per-joint transform gradients without atomics (a wave adds its 64
+ * vertices by lane, a block its four waves one after the other, per vertex tile), behind it a finish kernel adds the tiles in index order and
+ * replaces the atomically accumulated values.  Same arguments; workspace: *bytes of ehm_smpl_backward_ordered_workspace_bytes (larger by the
+ * tiles' partial sums).  ehm_smpl_backward and its callers are unchanged. */
+int ehm_smpl_backward_ordered_workspace_bytes(const ehm_smpl* h, int B, int64_t* bytes);
+int ehm_smpl_backward_ordered(ehm_smpl* h, const float* betas, const float* rotmats, const float* gverts, const float* gjoints, float* gbetas,
+                              float* grotmats, int B, void* workspace, int64_t workspace_bytes, void* stream);
 int ehm_smpl_backward_workspace_bytes(const ehm_smpl* h, int B, int64_t* bytes);
 
 /* egohmr.py:561-570: g = -(1/denom) * gpose6d (denom = B for loss.mean(), 1 for loss.sum()),

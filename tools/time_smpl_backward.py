@@ -1,5 +1,5 @@
 """One SMPL backward at 1280 bodies with a dense vertex cotangent: the general VJP (ehm_smpl_backward) next to the 6-D one (ehm_smpl_backward_rot6d:
-skin_bwd + posefeat_bwd + chain_bwd).  HIP events around each entry point; for per-kernel times run it under
+skin_bwd + posefeat_bwd + chain_bwd) and to the fixed-order variant of the general one (ehm_smpl_backward_ordered), in one run.  HIP events around each entry point; for per-kernel times run it under
 `rocprofv3 --kernel-trace --stats --output-format csv -d <dir> -- python tools/time_smpl_backward.py` (a run of its own).  Run from the repository root."""
 import ctypes as C
 import os
@@ -27,6 +27,9 @@ A, h, s = _lib.api(), smpl.handle(), _lib.stream_ptr()
 nb = C.c_int64()
 A.ehm_smpl_backward_workspace_bytes(h, B, C.byref(nb))
 ws = torch.empty(nb.value, device=dev, dtype=torch.uint8)
+nbo = C.c_int64()
+A.ehm_smpl_backward_ordered_workspace_bytes(h, B, C.byref(nbo))
+wso = torch.empty(nbo.value, device=dev, dtype=torch.uint8)
 gb, gr, gp = torch.empty(B, 10, device=dev), torch.empty(B, 24, 3, 3, device=dev), torch.empty(B, 144, device=dev)
 
 
@@ -49,6 +52,9 @@ cases = {
     "general: verts -> rotmats + betas": lambda: A.ehm_smpl_backward(h, betas, R, gv, None, gb, gr, B, ws, nb.value, s),
     "general: verts -> rotmats": lambda: A.ehm_smpl_backward(h, betas, R, gv, None, None, gr, B, ws, nb.value, s),
     "general: verts + joints -> rotmats + betas": lambda: A.ehm_smpl_backward(h, betas, R, gv, gj, gb, gr, B, ws, nb.value, s),
+    "general, fixed order (ehm_smpl_backward_ordered): verts + joints -> rotmats + betas":
+        lambda: A.ehm_smpl_backward_ordered(h, betas, R, gv, gj, gb, gr, B, wso, nbo.value, s),
+    "general again: verts + joints -> rotmats + betas": lambda: A.ehm_smpl_backward(h, betas, R, gv, gj, gb, gr, B, ws, nb.value, s),
 }
 for k, fn in cases.items():
     med, lo, hi = timed(fn)

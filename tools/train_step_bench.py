@@ -4,7 +4,8 @@ model, B = 64 items with N = 4096 scene points, batch-statistics BatchNorm: the 
 device events recorded on the launch stream around each phase (everything runs on one stream, so a phase's events bracket its kernels):
   trunk | PointNet fwd + bwd | assembly fwd + bwd | denoiser fwd + bwd | decode + loss fwd + bwd | optimiser | rest (the small torch modules, host gaps)
 A record, not a bar: the parent commit has no training step.  Prints one JSON line.
-    python tools/train_step_bench.py [--batch 64] [--points 4096] [--warmup 3] [--calls 12]"""
+--trunk-grad: with EgoHMR.trunk_grad (the trunk's weights train: its autograd forward is the "trunk" phase, its backward "trunk_bwd").
+    python tools/train_step_bench.py [--batch 64] [--points 4096] [--warmup 3] [--calls 12] [--trunk-grad]"""
 import argparse
 import json
 import os
@@ -15,7 +16,7 @@ import numpy as np
 import torch
 
 sys.path.insert(0, os.path.dirname(os.path.dirname(os.path.abspath(__file__))))
-from egohmr_amd import gcn_grad, pointnet_grad, train_grad  # noqa: E402
+from egohmr_amd import gcn_grad, pointnet_grad, train_grad, trunk_grad  # noqa: E402
 from egohmr_amd import synthetic as syn  # noqa: E402
 from egohmr_amd.diffusion import create_gaussian_diffusion  # noqa: E402
 from egohmr_amd.factory import batch_to_device, build_synthetic_model  # noqa: E402
@@ -25,6 +26,7 @@ ap.add_argument("--batch", type=int, default=64)
 ap.add_argument("--points", type=int, default=4096)
 ap.add_argument("--warmup", type=int, default=3)
 ap.add_argument("--calls", type=int, default=12)
+ap.add_argument("--trunk-grad", action="store_true")
 args = ap.parse_args()
 assert args.calls >= 10, "the median is taken over at least 10 calls"
 assert torch.cuda.is_available(), "this measurement needs the GPU; there is no CPU fallback"
@@ -37,6 +39,7 @@ weights = dict(weight_loss_v2v=0.5, weight_loss_keypoints_3d=0.05, weight_loss_k
 model = build_synthetic_model(dev, 0, smpl_asset_male=syn.make_smpl_asset(1), smpl_asset_female=syn.make_smpl_asset(2), **weights)
 model.frozen_trunk_training = True
 model.diffusion_model.train_batchnorm = True
+model.trunk_grad = bool(args.trunk_grad)
 model.init_optimizers()
 g = np.random.default_rng(1)
 b = syn.make_batch(B, args.points, seed=1)
@@ -84,6 +87,9 @@ def mark(fn, name, before):
 fs = model.fused_sampler
 backbone_fn = fs._backbone_fn
 fs._backbone_fn = lambda: timed(backbone_fn(), "trunk")
+if args.trunk_grad:
+    model.backbone.forward = timed(model.backbone.forward, "trunk")
+    trunk_grad.TrunkFunction.backward = staticmethod(timed(trunk_grad.TrunkFunction.backward, "trunk_bwd"))
 model.scene_enc.forward = timed(model.scene_enc.forward, "pointnet_fwd")
 pointnet_grad.PointnetFunction.backward = staticmethod(timed(pointnet_grad.PointnetFunction.backward, "pointnet_bwd"))
 train_grad.cond_assemble_native = timed(train_grad.cond_assemble_native, "assembly_fwd")
@@ -121,9 +127,10 @@ for _ in range(args.calls):
     losses.append(loss)
 med = {k: statistics.median(r[k] for r in runs) for k in runs[0]}
 pair = lambda a, b_: round(med[a] + med[b_], 3)
-print(json.dumps({"what": "one training_losses call, frozen trunk", "batch": B, "scene_points": args.points, "warmup": args.warmup, "calls": args.calls,
+med.setdefault("trunk_bwd", 0.0)
+print(json.dumps({"what": "one training_losses call, " + ("trunk_grad" if args.trunk_grad else "frozen trunk"), "batch": B, "scene_points": args.points, "warmup": args.warmup, "calls": args.calls,
                   "median_ms": round(med["total"], 3), "min_ms": round(min(r["total"] for r in runs), 3), "max_ms": round(max(r["total"] for r in runs), 3),
-                  "phases_median_ms": {"trunk": round(med["trunk"], 3), "pointnet_fwd_bwd": pair("pointnet_fwd", "pointnet_bwd"),
+                  "phases_median_ms": {"trunk": round(med["trunk"], 3), "trunk_bwd": round(med["trunk_bwd"], 3), "pointnet_fwd_bwd": pair("pointnet_fwd", "pointnet_bwd"),
                                        "assembly_fwd_bwd": pair("assembly_fwd", "assembly_bwd"), "denoiser_fwd_bwd": pair("denoiser_fwd", "denoiser_bwd"),
                                        "decode_loss_fwd_bwd": pair("decode_loss_fwd", "decode_loss_bwd"), "optimiser": round(med["optimiser"], 3),
                                        "rest": round(med["rest"], 3)},
