@@ -29,7 +29,7 @@ _HERE = os.path.dirname(os.path.abspath(__file__))
 LIB_PATH = os.environ.get("EHM_LIB_PATH") or os.path.join(_HERE, "libegohmr_hip.so")   # EHM_LIB_PATH: A/B a second build (experiments)
 CSRC = os.path.join(_HERE, "csrc")
 INCLUDE = os.path.join(os.path.dirname(_HERE), "include")
-SOURCES = ["gcn.hip", "gcn_tile.hip", "linear.hip", "conv.hip", "stem.hip", "metrics.hip", "smpl.hip", "sampler.hip", "guidance.hip", "prep.hip", "step.hip", "eval.hip", "stage1.hip", "scene.hip", "loss.hip", "gcn_bwd.hip", "gcn_train.hip", "pointnet_bwd.hip", "train.hip", "conv_bwd.hip"]
+SOURCES = ["gcn.hip", "gcn_tile.hip", "linear.hip", "conv.hip", "stem.hip", "metrics.hip", "smpl.hip", "sampler.hip", "guidance.hip", "prep.hip", "step.hip", "eval.hip", "stage1.hip", "scene.hip", "loss.hip", "gcn_bwd.hip", "gcn_train.hip", "pointnet_bwd.hip", "train.hip", "conv_bwd.hip", "bn2d_train.hip"]
 
 
 class EgoHMRHipError(RuntimeError):
@@ -303,6 +303,13 @@ PROTOTYPES = {
     "ehm_conv_bwd_wgrad": (_I, [_P, _P, _L, _P, _P, _I, _I, _I, _I, _I, _I, _I, _I, _P, _L, _P]),
     "ehm_resnet_stem_backward_workspace_bytes": (_I, [_I, _I, _I, C.POINTER(C.c_int64)]),
     "ehm_resnet_stem_backward": (_I, [_P, _P, _P, _P, _P, _P, _P, _P, _I, _I, _I, _P, _L, _P]),
+    "ehm_resnet_stem_preact": (_I, [_P, _P, _P, _P, _I, _I, _I, _P]),
+    "ehm_resnet_stem_route": (_I, [_P, _P, _P, _I, _I, _I, _P]),
+    "ehm_resnet_stem_wgrad": (_I, [_P, _P, _P, _P, _I, _I, _I, _P, _L, _P]),
+    "ehm_bn2d_train_workspace_bytes": (_I, [_L, _I, C.POINTER(C.c_int64)]),
+    "ehm_bn2d_train_stats": (_I, [_P, _I, _L, _L, _I, C.c_double, C.c_double, _P, _P, _P, _P, _P, _P, _P, _L, _P]),
+    "ehm_bn2d_train_bwd_sums": (_I, [_P, _P, _I, _L, _L, _I, _P, _P, _P, _P, _P, _L, _P]),
+    "ehm_bn2d_train_bwd_zbar": (_I, [_P, _P, _I, _L, _P, _P, _P, _P, _P, _P, _P, _I, _I, _I, _I, _I, _I, _P]),
     "ehm_ddpm_step": (_I, [_P, _P, _P, _P, _P, _F, _F, _F, _F, _F, _L, _P]),
     "ehm_ddim_step": (_I, [_P, _P, _P, _P, _F, _F, _F, _F, _F, _F, _L, _P]),
     "ehm_collision_proxy": (_I, [_P, _P, _P, _P, _I, _I, _I, _F, _P]),

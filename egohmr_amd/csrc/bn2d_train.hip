@@ -1,0 +1,277 @@
+// Train-mode BatchNorm2d of the ResNet-50 trunk (egohmr_amd/encoders.py ResNet50Features.train_batchnorm, egohmr_amd/trunk_grad.py) for gfx950 (MI355X):
+// what batch statistics add to the folded trunk and to its backward (csrc/conv_bwd.hip), in the pattern of csrc/gcn_train.hip.  z [pixels, C] is a
+// conv's RAW output (no BatchNorm, no bias), either the X2 buffer ehm_conv_x2 wrote (only its first `pixels` rows count: the tile padding and the
+// trailing zero row are never read) or float32 rows (the stem's pre-pool activation).
+//   forward:   mu = mean_p z,  var = mean_p (z - mu)^2 (biased),  invstd = 1 / sqrt(var + eps)          bn2d_sum_kernel x 2 + bn2d_stats_finish_kernel
+//              running_mean / running_var (unbiased) / num_batches_tracked as nn.BatchNorm2d updates them, in the same launch sequence.
+//              Two passes (the mean first, then the centred squares), float64 accumulators: correct to float32 rounding at |mu| / sigma = 1e3.
+//   backward:  with G = g (.) [y > 0] (ehm_conv_bwd_gate) and xhat = (z - mu) invstd:
+//              betabar = sum_p G,  gammabar = sum_p G xhat                                                  bn2d_sum_kernel + bn2d_bwd_finish_kernel
+//              zbar = *scale gamma invstd (G - betabar / R - xhat gammabar / R)                             bn2d_zbar_kernel (dense, or zero-dilated)
+// No atomics: a block owns a run of pixels that is a function of the shape alone, a lane adds its rows in row order, the row lanes and then the runs
+// are added in index order - two calls on the same inputs give the same bits.
+#include "common.h"
+#include "egohmr_hip.h"
+#include "gcn_dev.h"
+
+namespace {
+
+inline bool al16(const void* p) { return ((uintptr_t)p & 15) == 0; }
+
+constexpr int BN_ROWL = 16;        // row lanes of a bn2d_sum_kernel block (x 16 column lanes of 8 channels = 128 columns)
+constexpr int BN_MAX_RUNS = 256;
+
+// 8 consecutive channels (c % 8 == 0) of row `row`: X2 (32 hi halves | 32 lo halves per 32 channels, value = hi + lo) or float32
+template <bool X2IN>
+__device__ __forceinline__ void load8(const void* __restrict__ z, size_t row, int c, int C, float (&v)[8]) {
+  if (X2IN) {
+    const half_t* p = (const half_t*)z + split_off<32>(row, c, C);
+    const half8 hi = *(const half8*)p, lo = *(const half8*)(p + 32);
+#pragma unroll
+    for (int q = 0; q < 8; ++q) v[q] = (float)hi[q] + (float)lo[q];
+  } else {
+    const float* p = (const float*)z + row * (size_t)C + c;
+    const f32x4 a = *(const f32x4*)p, b = *(const f32x4*)(p + 4);
+#pragma unroll
+    for (int q = 0; q < 4; ++q) { v[q] = a[q]; v[4 + q] = b[q]; }
+  }
+}
+
+// MODE 0: part[run][0][c] = sum z                       (A unused)
+// MODE 1: part[run][0][c] = sum (z - mean_d)^2          (mean_d: float64 [C])
+// MODE 2: part[run][0][c] = sum G, part[run][1][c] = sum G (z - mean) invstd      (mean, invstd float32 [C]; G float32 [P, C])
+// grid (runs, ceil(C / 128)); thread = 8 channels x one of 16 row lanes
+template <bool X2IN, int MODE>
+__global__ __launch_bounds__(256) void bn2d_sum_kernel(const void* __restrict__ z, const float* __restrict__ G, const double* __restrict__ mean_d,
+                                                       const float* __restrict__ mean, const float* __restrict__ invstd, double* __restrict__ part,
+                                                       long long P, int C, int run) {
+  constexpr int NS = MODE == 2 ? 2 : 1;
+  __shared__ double red[BN_ROWL][NS][128];
+  const int cl = threadIdx.x & 15, rl = threadIdx.x >> 4;
+  const int c = blockIdx.y * 128 + 8 * cl;
+  const long long p0 = (long long)blockIdx.x * run;
+  double acc[NS][8];
+#pragma unroll
+  for (int s = 0; s < NS; ++s)
+#pragma unroll
+    for (int q = 0; q < 8; ++q) acc[s][q] = 0.0;
+  if (c < C) {
+    double m[8];
+    float is[8];
+#pragma unroll
+    for (int q = 0; q < 8; ++q) {
+      m[q] = MODE == 1 ? mean_d[c + q] : (MODE == 2 ? (double)mean[c + q] : 0.0);
+      is[q] = MODE == 2 ? invstd[c + q] : 0.f;
+    }
+    for (long long r = p0 + rl; r < p0 + run && r < P; r += BN_ROWL) {
+      float v[8];
+      load8<X2IN>(z, (size_t)r, c, C, v);
+      if (MODE == 0) {
+#pragma unroll
+        for (int q = 0; q < 8; ++q) acc[0][q] += (double)v[q];
+      } else if (MODE == 1) {
+#pragma unroll
+        for (int q = 0; q < 8; ++q) {
+          const double d = (double)v[q] - m[q];
+          acc[0][q] += d * d;
+        }
+      } else {
+        const float* gp = G + (size_t)r * C + c;
+        const f32x4 g0 = *(const f32x4*)gp, g1 = *(const f32x4*)(gp + 4);
+#pragma unroll
+        for (int q = 0; q < 8; ++q) {
+          const double g = (double)(q < 4 ? g0[q & 3] : g1[q & 3]);
+          acc[0][q] += g;
+          acc[1][q] += g * (((double)v[q] - m[q]) * (double)is[q]);
+        }
+      }
+    }
+  }
+#pragma unroll
+  for (int s = 0; s < NS; ++s)
+#pragma unroll
+    for (int q = 0; q < 8; ++q) red[rl][s][8 * cl + q] = acc[s][q];
+  __syncthreads();
+  for (int t = threadIdx.x; t < NS * 128; t += 256) {
+    const int s = t / 128, j = t - 128 * s;
+    if (blockIdx.y * 128 + j >= C) continue;
+    double sum = red[0][s][j];
+#pragma unroll
+    for (int r = 1; r < BN_ROWL; ++r) sum += red[r][s][j];
+    part[((size_t)blockIdx.x * NS + s) * C + blockIdx.y * 128 + j] = sum;
+  }
+}
+
+__device__ __forceinline__ double runs_sum(const double* __restrict__ p, size_t stride, int n) {
+  double s = 0.0;
+  for (int k = 0; k < n; ++k) s += p[(size_t)k * stride];
+  return s;
+}
+
+__global__ __launch_bounds__(256) void bn2d_mean_finish_kernel(const double* __restrict__ part, double* __restrict__ mean_d, int C, int runs, double R) {
+  const int t = blockIdx.x * 256 + threadIdx.x;
+  if (t >= C) return;
+  mean_d[t] = runs_sum(part + t, (size_t)C, runs) / R;
+}
+
+__global__ __launch_bounds__(256) void bn2d_stats_finish_kernel(const double* __restrict__ part, const double* __restrict__ mean_d, float* __restrict__ mean,
+                                                                float* __restrict__ var, float* __restrict__ invstd, float* __restrict__ running_mean,
+                                                                float* __restrict__ running_var, long long* __restrict__ tracked, int C, int runs,
+                                                                double R, double eps, double momentum) {
+  const int t = blockIdx.x * 256 + threadIdx.x;
+  if (t == 0 && tracked) *tracked += 1;
+  if (t >= C) return;
+  const double mu = mean_d[t], v = runs_sum(part + t, (size_t)C, runs) / R;
+  mean[t] = (float)mu;
+  var[t] = (float)v;
+  invstd[t] = (float)(1.0 / sqrt(v + eps));
+  if (running_mean) running_mean[t] = (float)((1.0 - momentum) * (double)running_mean[t] + momentum * mu);
+  if (running_var) running_var[t] = (float)((1.0 - momentum) * (double)running_var[t] + momentum * (v * R / (R - 1.0)));
+}
+
+__global__ __launch_bounds__(256) void bn2d_bwd_finish_kernel(const double* __restrict__ part, float* __restrict__ gbeta, float* __restrict__ ggamma, int C,
+                                                              int runs) {
+  const int t = blockIdx.x * 256 + threadIdx.x;
+  if (t >= C) return;
+  gbeta[t] = (float)runs_sum(part + t, (size_t)2 * C, runs);
+  ggamma[t] = (float)runs_sum(part + C + t, (size_t)2 * C, runs);
+}
+
+struct ZbarArgs {
+  const float* G; const void* z; const float *mean, *invstd, *gamma, *gbeta, *ggamma, *scale;
+  float* out;
+  int Ho, Wo, C, H, W, dil;
+  float invR;
+  long long total8;
+};
+
+// one thread = 8 consecutive channels of one OUTPUT pixel (h, w) of [N, H, W, C] (the form of conv_bwd_gate_kernel): one pass over G and z, 16-byte accesses
+template <bool X2IN>
+__global__ __launch_bounds__(256) void bn2d_zbar_kernel(ZbarArgs a) {
+  const long long t = (long long)blockIdx.x * 256 + threadIdx.x;
+  if (t >= a.total8) return;
+  const int c8 = a.C / 8;
+  const int c = 8 * (int)(t % c8);
+  long long pix = t / c8;
+  const int w = (int)(pix % a.W);
+  pix /= a.W;
+  const int h = (int)(pix % a.H);
+  const long long n = pix / a.H;
+  int ho = h, wo = w;
+  bool live = true;
+  if (a.dil == 2) {
+    ho = h >> 1;
+    wo = w >> 1;
+    live = !(h & 1) && !(w & 1) && ho < a.Ho && wo < a.Wo;
+  }
+  f32x4 v0 = {0.f, 0.f, 0.f, 0.f}, v1 = {0.f, 0.f, 0.f, 0.f};
+  if (live) {
+    const size_t row = ((size_t)n * a.Ho + ho) * a.Wo + wo;
+    float zv[8];
+    load8<X2IN>(a.z, row, c, a.C, zv);
+    const float* gp = a.G + row * (size_t)a.C + c;
+    const f32x4 g0 = *(const f32x4*)gp, g1 = *(const f32x4*)(gp + 4);
+    const float s = a.scale ? *a.scale : 1.f;
+#pragma unroll
+    for (int q = 0; q < 8; ++q) {
+      const float is = a.invstd[c + q];
+      const float xh = (zv[q] - a.mean[c + q]) * is;
+      const float g = q < 4 ? g0[q & 3] : g1[q & 3];
+      const float r = s * (a.gamma[c + q] * is) * (g - a.gbeta[c + q] * a.invR - xh * (a.ggamma[c + q] * a.invR));
+      if (q < 4) v0[q & 3] = r; else v1[q & 3] = r;
+    }
+  }
+  float* o = a.out + (size_t)(t / c8) * a.C + c;
+  *(f32x4*)o = v0;
+  *(f32x4*)(o + 4) = v1;
+}
+
+struct BnPlan { int run, runs, cblocks; };
+
+// runs of whole 16-row groups, at most BN_MAX_RUNS of them: a function of the shape alone
+int bn_plan(int64_t pixels, int64_t z_rows, int C, BnPlan* pl) {
+  EHM_CHECK_ARG(pixels >= 2 && pixels < (1ll << 31) && z_rows >= pixels && C > 0 && C % 32 == 0 && pixels * C < (1ll << 40));
+  pl->run = (int)round_up(ceil_div(pixels, BN_MAX_RUNS), BN_ROWL);
+  pl->runs = (int)ceil_div(pixels, pl->run);
+  pl->cblocks = (int)ceil_div(C, 128);
+  return 0;
+}
+
+int64_t bn_ws_doubles(const BnPlan& pl, int C) { return (int64_t)pl.runs * 2 * C + C; }
+
+template <int MODE>
+void launch_sum(bool x2, const BnPlan& pl, hipStream_t st, const void* z, const float* G, const double* mean_d, const float* mean, const float* invstd,
+                double* part, long long P, int C) {
+  const dim3 grid((unsigned)pl.runs, (unsigned)pl.cblocks);
+  if (x2) hipLaunchKernelGGL((bn2d_sum_kernel<true, MODE>), grid, dim3(256), 0, st, z, G, mean_d, mean, invstd, part, P, C, pl.run);
+  else hipLaunchKernelGGL((bn2d_sum_kernel<false, MODE>), grid, dim3(256), 0, st, z, G, mean_d, mean, invstd, part, P, C, pl.run);
+}
+
+}  // namespace
+
+extern "C" int ehm_bn2d_train_workspace_bytes(int64_t pixels, int C, int64_t* bytes) {
+  EHM_CHECK_ARG(bytes != nullptr);
+  BnPlan pl;
+  const int rc = bn_plan(pixels, pixels, C, &pl);
+  if (rc != 0) return rc;
+  *bytes = bn_ws_doubles(pl, C) * (int64_t)sizeof(double);
+  return 0;
+}
+
+extern "C" int ehm_bn2d_train_stats(const void* z, int z_is_x2, int64_t z_rows, int64_t pixels, int C, double eps, double momentum, float* mean, float* var,
+                                    float* invstd, float* running_mean, float* running_var, int64_t* num_batches_tracked, void* workspace,
+                                    int64_t workspace_bytes, void* stream) {
+  BnPlan pl;
+  const int rc = bn_plan(pixels, z_rows, C, &pl);
+  if (rc != 0) return rc;
+  EHM_CHECK_ARG(z && mean && var && invstd && al16(z) && (z_is_x2 == 0 || z_is_x2 == 1) && eps >= 0.0 && momentum >= 0.0 && momentum <= 1.0);
+  EHM_CHECK_ARG(workspace && al16(workspace) && workspace_bytes >= bn_ws_doubles(pl, C) * (int64_t)sizeof(double));
+  hipStream_t st = (hipStream_t)stream;
+  double* part = (double*)workspace;
+  double* mean_d = part + (size_t)pl.runs * 2 * C;
+  const unsigned cb = (unsigned)ceil_div(C, 256);
+  launch_sum<0>(z_is_x2 != 0, pl, st, z, nullptr, nullptr, nullptr, nullptr, part, pixels, C);
+  hipLaunchKernelGGL(bn2d_mean_finish_kernel, dim3(cb), dim3(256), 0, st, (const double*)part, mean_d, C, pl.runs, (double)pixels);
+  launch_sum<1>(z_is_x2 != 0, pl, st, z, nullptr, (const double*)mean_d, nullptr, nullptr, part, pixels, C);
+  hipLaunchKernelGGL(bn2d_stats_finish_kernel, dim3(cb), dim3(256), 0, st, (const double*)part, (const double*)mean_d, mean, var, invstd, running_mean,
+                     running_var, (long long*)num_batches_tracked, C, pl.runs, (double)pixels, eps, momentum);
+  EHM_LAUNCH_CHECK();
+  return 0;
+}
+
+extern "C" int ehm_bn2d_train_bwd_sums(const float* G, const void* z, int z_is_x2, int64_t z_rows, int64_t pixels, int C, const float* mean,
+                                       const float* invstd, float* gbeta, float* ggamma, void* workspace, int64_t workspace_bytes, void* stream) {
+  BnPlan pl;
+  const int rc = bn_plan(pixels, z_rows, C, &pl);
+  if (rc != 0) return rc;
+  EHM_CHECK_ARG(G && z && mean && invstd && gbeta && ggamma && al16(G) && al16(z) && (z_is_x2 == 0 || z_is_x2 == 1));
+  EHM_CHECK_ARG(workspace && al16(workspace) && workspace_bytes >= bn_ws_doubles(pl, C) * (int64_t)sizeof(double));
+  hipStream_t st = (hipStream_t)stream;
+  double* part = (double*)workspace;
+  launch_sum<2>(z_is_x2 != 0, pl, st, z, G, nullptr, mean, invstd, part, pixels, C);
+  hipLaunchKernelGGL(bn2d_bwd_finish_kernel, dim3((unsigned)ceil_div(C, 256)), dim3(256), 0, st, (const double*)part, gbeta, ggamma, C, pl.runs);
+  EHM_LAUNCH_CHECK();
+  return 0;
+}
+
+extern "C" int ehm_bn2d_train_bwd_zbar(const float* G, const void* z, int z_is_x2, int64_t z_rows, const float* mean, const float* invstd, const float* gamma,
+                                       const float* gbeta, const float* ggamma, const float* scale, float* out, int N, int Ho, int Wo, int C, int H, int W,
+                                       void* stream) {
+  EHM_CHECK_ARG(G && z && mean && invstd && gamma && gbeta && ggamma && out && al16(G) && al16(z) && al16(out) && (z_is_x2 == 0 || z_is_x2 == 1));
+  EHM_CHECK_ARG(N > 0 && Ho > 0 && Wo > 0 && H > 0 && W > 0 && C > 0 && C % 32 == 0);
+  const bool dense = H == Ho && W == Wo;
+  EHM_CHECK_ARG(dense || ((H - 1) / 2 + 1 == Ho && (W - 1) / 2 + 1 == Wo));
+  const long long R = (long long)N * Ho * Wo;
+  EHM_CHECK_ARG(R >= 2 && z_rows >= R && (long long)N * H * W * C < (1ll << 40) && (const void*)G != (const void*)out);
+  ZbarArgs a;
+  a.G = G; a.z = z; a.mean = mean; a.invstd = invstd; a.gamma = gamma; a.gbeta = gbeta; a.ggamma = ggamma; a.scale = scale; a.out = out;
+  a.Ho = Ho; a.Wo = Wo; a.C = C; a.H = H; a.W = W; a.dil = dense ? 1 : 2;
+  a.invR = (float)(1.0 / (double)R);
+  a.total8 = (long long)N * H * W * (C / 8);
+  const long long blocks = ceil_div(a.total8, 256);
+  EHM_CHECK_ARG(blocks < (1ll << 31));
+  if (z_is_x2) hipLaunchKernelGGL(bn2d_zbar_kernel<true>, dim3((unsigned)blocks), dim3(256), 0, (hipStream_t)stream, a);
+  else hipLaunchKernelGGL(bn2d_zbar_kernel<false>, dim3((unsigned)blocks), dim3(256), 0, (hipStream_t)stream, a);
+  EHM_LAUNCH_CHECK();
+  return 0;
+}

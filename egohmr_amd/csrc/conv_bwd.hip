@@ -430,3 +430,42 @@ extern "C" int ehm_resnet_stem_backward(const float* img, const float* Wt, const
   EHM_LAUNCH_CHECK();
   return 0;
 }
+
+// The stem backward's three steps on their own, for the train-mode BatchNorm route (csrc/bn2d_train.hip, egohmr_amd/trunk_grad.py), which needs the batch
+// sums over ALL pre-pool pixels between them: whole-batch tensors, no chunks.
+extern "C" int ehm_resnet_stem_preact(const float* img, const float* Wt, const float* bias, float* z, int N, int H, int W, void* stream) {
+  StemPlan pl;
+  const int rc = stem_plan(N, H, W, &pl);
+  if (rc != 0) return rc;
+  EHM_CHECK_ARG(img && Wt && bias && z);
+  const long long pixels = (long long)N * (H / 2) * (W / 2);
+  hipLaunchKernelGGL(stem_bwd_preact_kernel, dim3((unsigned)ceil_div(pixels, 4)), dim3(256), 0, (hipStream_t)stream, img, Wt, bias, z, H, W, pixels);
+  EHM_LAUNCH_CHECK();
+  return 0;
+}
+
+extern "C" int ehm_resnet_stem_route(const float* z, const float* gpool, float* gz, int N, int H, int W, void* stream) {
+  StemPlan pl;
+  const int rc = stem_plan(N, H, W, &pl);
+  if (rc != 0) return rc;
+  EHM_CHECK_ARG(z && gpool && gz && (const void*)z != (const void*)gz);
+  const long long pixels = (long long)N * (H / 2) * (W / 2);
+  hipLaunchKernelGGL(stem_bwd_route_kernel, dim3((unsigned)ceil_div(pixels, 4)), dim3(256), 0, (hipStream_t)stream, z, gpool, gz, H / 2, W / 2, pixels);
+  EHM_LAUNCH_CHECK();
+  return 0;
+}
+
+extern "C" int ehm_resnet_stem_wgrad(const float* img, const float* gz, float* gW, float* gb, int N, int H, int W, void* workspace, int64_t workspace_bytes,
+                                     void* stream) {
+  StemPlan pl;
+  const int rc = stem_plan(N, H, W, &pl);
+  if (rc != 0) return rc;
+  EHM_CHECK_ARG(img && gz && (gW || gb));
+  EHM_CHECK_ARG(workspace && al16(workspace) && workspace_bytes >= (int64_t)SB_BLOCKS * SB_K * 64 * (int64_t)sizeof(float));
+  hipStream_t st = (hipStream_t)stream;
+  float* part = (float*)workspace;
+  hipLaunchKernelGGL(stem_bwd_wgrad_kernel, dim3(SB_BLOCKS), dim3(256), 0, st, img, gz, part, H, W, N * (H / 2), 0);
+  hipLaunchKernelGGL(stem_bwd_finish_kernel, dim3((unsigned)ceil_div(SB_K * 64, 256)), dim3(256), 0, st, (const float*)part, gW, gb);
+  EHM_LAUNCH_CHECK();
+  return 0;
+}

@@ -50,6 +50,11 @@ class ResNet50Features(nn.Module):
     # kept for the backward (about 9 M values per 224 x 224 image) - and its backward fills the parameters' gradients (BatchNorm in eval mode: the
     # statistics stay frozen, conv weights and affine parameters train).  False: every call is the no-graph route, whatever the parameters say
     grad_params = False
+    # True: a call under .train() (self.training) runs every BatchNorm2d on BATCH statistics (csrc/bn2d_train.hip): mean and biased variance over the
+    # N H W rows of the conv's raw output, the running statistics updated in place as nn.BatchNorm2d updates them, and - behind grad_params, with a
+    # graph - trunk_grad.TrunkTrainFunction, whose backward differentiates through the mean and the variance.  False: .train() is ignored, every call
+    # folds the frozen running statistics
+    train_batchnorm = False
     GRAD_HI_ONLY = ("the autograd route of ResNet50Features keeps f32-grade activations for its backward; the plain-f16 tier "
                     "(ResNet50Features.hi_only = True) stores none: set hi_only = False with it")
     GRAD_IMAGE = ("ResNet50Features.grad_params differentiates the trunk with respect to its parameters only: the image gradient (the stem's data "
@@ -81,14 +86,33 @@ class ResNet50Features(nn.Module):
     def forward(self, x):
         """The module call IS the HIP path (models/resnet.py:139-150 in eval mode); there is no eager route.  With `grad_params`, grad mode on and a
         parameter that requires grad the result carries a grad_fn (trunk_grad.TrunkFunction: same launches, same bits, activations kept)."""
+        train = self.train_batchnorm and self.training
         if self.grad_params and torch.is_grad_enabled() and any(p.requires_grad for p in self.parameters()):
             if self.hi_only:
                 raise _lib.EgoHMRHipError(self.GRAD_HI_ONLY)
             if x.requires_grad:
                 raise NotImplementedError(self.GRAD_IMAGE)
             from . import trunk_grad
+            if train:
+                self._check_train(x)
+                return trunk_grad.TrunkTrainFunction.apply(self, x, *self.parameters())
             return trunk_grad.TrunkFunction.apply(self, x, *self.parameters())
+        if train:
+            self._check_train(x)
+            return self.folded(train=True)(x)
         return self.current()(x)
+
+    def _check_train(self, x):
+        """What the train-mode BatchNorm route cannot run, refused before any device call: a BatchNorm2d without a fixed momentum or without running
+        statistics (NotImplementedError, as ModulatedGCN refuses them) and a batch that leaves a BatchNorm2d fewer than two values per channel
+        (ValueError, as torch raises it: layer4 has N * H/32 * W/32 rows)."""
+        for bn in self.modules():
+            if isinstance(bn, nn.BatchNorm2d) and (bn.momentum is None or not bn.track_running_stats):
+                raise NotImplementedError("ResNet50Features: the train-mode route updates the running statistics with a fixed momentum; "
+                                          "BatchNorm2d(momentum=None) and track_running_stats=False are not built")
+        if x.dim() == 4 and x.shape[0] * (x.shape[2] // 32) * (x.shape[3] // 32) < 2:
+            raise ValueError(f"Expected more than 1 value per channel when training, got input size {tuple(x.shape)} "
+                             "(layer4 of the trunk has N * H/32 * W/32 values per channel)")
 
     # ------------------------------------------------------------------ stream-K hand-off time-outs (csrc/conv.hip): made loud, never waited for
     def _sk_status_async(self, ws):
@@ -120,28 +144,33 @@ class ResNet50Features(nn.Module):
 
     # ------------------------------------------------------------------ inference form: BatchNorm folded into the convolutions
     @torch.no_grad()
-    def folded(self, x2_activations: bool = True, fuse_shortcut: bool = True):
+    def folded(self, x2_activations: bool = True, fuse_shortcut: bool = True, train: bool = False):
         """Eval-mode ResNet-50 on the matrix cores with every BatchNorm2d folded into its convolution (w' = w * g/sqrt(v+eps),
         b' = beta - mean * g/sqrt(v+eps); exact up to float re-association).  x2_activations=True (the product path): the activations
         stay in the X2 split format from the stem to the average pool (ehm_conv_x2); False: float32 NHWC activations between the
         convolutions (ehm_conv_nhwc_split - the kernel the non-local GCN block also uses; kept as a second implementation the tests
-        compare).  HIP tensors only: there is no eager / library-convolution route."""
+        compare).  HIP tensors only: there is no eager / library-convolution route.
+        train=True (the X2 route only; ResNet50Features.train_batchnorm): nothing is folded here; the returned run(x, rec=None) folds each BatchNorm2d on
+        the statistics of the batch it is given and updates the running ones (run_x2_train below)."""
         import ctypes as C
 
         A, P = _lib.api(), _lib.ptr
 
-        def fold(conv, bn):
-            scale = (bn.weight.double() / torch.sqrt(bn.running_var.double() + bn.eps))
+        def fold(conv, bn, stats=None):
+            """stats: (mean, biased variance) that stand in for the running ones - the train-mode route's float32 batch statistics"""
+            mean, var = (bn.running_mean, bn.running_var) if stats is None else stats
+            scale = (bn.weight.double() / torch.sqrt(var.double() + bn.eps))
             w = (conv.weight.double() * scale.view(-1, 1, 1, 1)).float()
-            b = (bn.bias.double() - bn.running_mean.double() * scale).float()
+            b = (bn.bias.double() - mean.double() * scale).float()
             return w, b, conv.stride, conv.padding
 
-        stem = fold(self.conv1, self.bn1)
-        blocks = []
-        for layer in (self.layer1, self.layer2, self.layer3, self.layer4):
-            for blk in layer:
-                blocks.append((fold(blk.conv1, blk.bn1), fold(blk.conv2, blk.bn2), fold(blk.conv3, blk.bn3),
-                               fold(blk.downsample[0], blk.downsample[1]) if blk.downsample is not None else None))
+        stem, blocks = None, []
+        if not train:
+            stem = fold(self.conv1, self.bn1)
+            for layer in (self.layer1, self.layer2, self.layer3, self.layer4):
+                for blk in layer:
+                    blocks.append((fold(blk.conv1, blk.bn1), fold(blk.conv2, blk.bn2), fold(blk.conv3, blk.bn3),
+                                   fold(blk.downsample[0], blk.downsample[1]) if blk.downsample is not None else None))
         packed = {}
         sk_ws = {}                                         # device -> scratch of the stream-K convs (one conv at a time on a stream)
 
@@ -170,8 +199,10 @@ class ResNet50Features(nn.Module):
             A.ehm_conv_nhwc_split(C.byref(d), _lib.stream_ptr())
             return y
 
-        stem_wt = stem[0].reshape(64, 147).t().contiguous()                        # [147][64], k = (ci*7 + kh)*7 + kw
-        stem_b = stem[1].contiguous()
+        def stem_operands(w, b):
+            return w.reshape(64, 147).t().contiguous(), b.contiguous()             # [147][64], k = (ci*7 + kh)*7 + kw
+
+        stem_wt, stem_b = (None, None) if train else stem_operands(*stem[:2])
 
         def x2_buffer(pixels, ch, dev, clear_last=False):
             """X2 activation matrix for ehm_conv_x2: pixels rounded up to the row tile + one all-zero row (out-of-image taps read it;
@@ -182,7 +213,7 @@ class ResNet50Features(nn.Module):
                 buf[rows - 1].zero_()
             return buf
 
-        def stem_mc(x, x2=False):
+        def stem_mc(x, x2=False, stem_wt=stem_wt, stem_b=stem_b):
             """conv1 + bn1 + relu + maxpool in one pass, NCHW in -> NHWC out (csrc/stem.hip); x2: output in the X2 split format"""
             N, _, H, W = x.shape
             if stem_wt.device != x.device:
@@ -261,6 +292,70 @@ class ResNet50Features(nn.Module):
             self._sk_status_async(sk_ws.get(str(x.device)))
             return out
 
+        def run_x2_train(x, rec=None):
+            """run_x2 on batch statistics.  Per (conv, BatchNorm2d) unit: the RAW conv output z on the same launch (unfolded weight through the same
+            pack, zero bias, no ReLU, no residual; a projection block's conv3 and downsample apart - each BatchNorm has its own statistics), its mean /
+            biased variance / invstd and the running-statistics update (ehm_bn2d_train_stats), then the folded launch of run_x2 unchanged, folded by the
+            same `fold` on the float32 batch statistics: the output has the bits of an eval-mode call whose running statistics are that batch's.
+            rec: a trunk_grad.TrainRecord that receives what the backward needs (acts: run_x2's `saved`; bn: per unit of trunk_grad.units
+            (z or None, z's shape, mean, var, invstd), None for an identity block's absent downsample)."""
+            from . import trunk_grad
+            N, _, H, W = x.shape
+            dev = x.device
+            keep = (lambda *e: None) if rec is None else (lambda *e: rec.acts.append(e))
+            note = (lambda e: None) if rec is None else rec.bn.append
+            zero = torch.zeros(2048, device=dev)
+            bumped = []
+
+            def unit(x, shp, conv, bn):
+                """-> the unit's (w', b', stride, padding) folded on the statistics of this batch"""
+                Co = conv.out_channels
+                packed.clear()                                  # per-call operands: nothing to reuse, and an id must not outlive its tensor
+                z, zs = conv_x2(x, shp, (conv.weight.detach().float(), zero[:Co], conv.stride, conv.padding), relu=False)
+                mean, var, invstd = trunk_grad.bn_stats(z, zs[0] * zs[1] * zs[2], Co, bn)
+                bumped.append(bn)
+                note((z if rec is not None and rec.keep_z else None, zs, mean, var, invstd))
+                packed.clear()
+                return fold(conv, bn, (mean, var))
+
+            raw_wt, _ = stem_operands(self.conv1.weight.detach().float(), zero[:64])
+            z = trunk_grad.stem_preact(x, raw_wt, zero[:64])
+            mean, var, invstd = trunk_grad.bn_stats(z, N * (H // 2) * (W // 2), 64, self.bn1, x2=False)
+            bumped.append(self.bn1)
+            del z                                                                   # (recomputed by the backward, like the eval route's)
+            wt, b = stem_operands(*fold(self.conv1, self.bn1, (mean, var))[:2])
+            note((None, (N, H // 2, W // 2), mean, var, invstd))
+            if rec is not None:
+                rec.stem_wt, rec.stem_b = wt, b
+            shp = (N, H // 4, W // 4)
+            x = stem_mc(x, x2=True, stem_wt=wt, stem_b=b)
+            keep(x, shp)
+            for layer in (self.layer1, self.layer2, self.layer3, self.layer4):
+                for blk in layer:
+                    y, s1 = conv_x2(x, shp, unit(x, shp, blk.conv1, blk.bn1))
+                    keep(y, s1)
+                    y2, s2 = conv_x2(y, s1, unit(y, s1, blk.conv2, blk.bn2))
+                    keep(y2, s2)
+                    p3 = unit(y2, s2, blk.conv3, blk.bn3)
+                    if blk.downsample is None:
+                        note(None)
+                        x, shp = conv_x2(y2, s2, p3, res=x)
+                    else:
+                        pd = unit(x, shp, blk.downsample[0], blk.downsample[1])
+                        if fuse_shortcut:
+                            x, shp = conv_x2(y2, s2, p3, shortcut=(x, shp, pd))
+                        else:
+                            x, shp = conv_x2(y2, s2, p3, res=conv_x2(x, shp, pd, relu=False)[0])
+                    keep(x, shp)
+            packed.clear()
+            out = torch.empty(N, x.shape[1], device=dev)
+            A.ehm_x2_group_mean(x, out, N, shp[1] * shp[2], x.shape[1], int(bool(self.hi_only)), _lib.stream_ptr())
+            self._sk_status_async(sk_ws.get(str(dev)))
+            for bn in bumped:                    # the kernels wrote the buffers through their pointers: tell torch (current() refolds on the next eval call)
+                for t in (bn.running_mean, bn.running_var, bn.num_batches_tracked):
+                    torch.autograd.graph.increment_version(t)
+            return out
+
         def run(x, saved=None):
             if not x.is_cuda:
                 raise _lib.EgoHMRHipError("the ResNet-50 backbone needs its input on a HIP device; egohmr_amd has no CPU path")
@@ -268,6 +363,9 @@ class ResNet50Features(nn.Module):
             if x.shape[1] != 3 or x.shape[2] % 32 or x.shape[3] % 32:
                 raise _lib.EgoHMRHipError(f"the fused stem needs [N,3,H,W] images with H, W multiples of 32 (the reference feeds 224 x 224 crops); got {tuple(x.shape)}")
             with _lib.on_device(x.device):                                          # the library launches on the CURRENT device's stream
+                if train:
+                    with torch.no_grad():
+                        return run_x2_train(x, saved)
                 if x2_activations:
                     return run_x2(x, saved)
                 x = stem_mc(x)                                                      # NHWC float32 from here on

@@ -507,8 +507,9 @@ class EgoHMR(nn.Module):
     # the denoiser, embed_timestep, input_process) with a graph.  Calls with self.training False do not depend on it
     frozen_trunk_training = False
     # Consulted on the training route only (behind frozen_trunk_training, whose name stays): True unfreezes the trunk's WEIGHTS - img_feats comes from the
-    # backbone's autograd route (ResNet50Features.grad_params; BatchNorm in eval mode, the statistics stay frozen) and init_optimizers puts
-    # backbone.parameters() in front, which is the reference's list (egohmr.py:140-147)
+    # backbone's autograd route (ResNet50Features.grad_params; BatchNorm in eval mode with frozen statistics, or - backbone.train_batchnorm = True - in
+    # .train() on batch statistics as the reference's backbone.train(), egohmr.py:455) and init_optimizers puts backbone.parameters() in front, which
+    # is the reference's list (egohmr.py:140-147)
     trunk_grad = False
 
     def forward(self, batch, timesteps, eval_with_uncond=True):
@@ -535,11 +536,12 @@ class EgoHMR(nn.Module):
         return torch.bernoulli(torch.ones(B, device=self.device) * self.cond_mask_prob).to(torch.uint8)
 
     def _set_train_modes(self):
-        """egohmr.py:454-462 with the trunk frozen: the backbone stays in eval mode, and the denoiser trains its BatchNorm only behind
+        """egohmr.py:454-462: the backbone goes into .train() (:455, batch statistics) exactly when EgoHMR.trunk_grad and
+        ResNet50Features.train_batchnorm are both set, else it stays in eval mode; the denoiser trains its BatchNorm only behind
         ModulatedGCN.train_batchnorm - without it the denoiser stays in eval mode and its statistics frozen (a deviation from the reference, which always
         trains on batch statistics)."""
         self.training = True
-        self.backbone.eval()
+        self.backbone.train(bool(self.trunk_grad and self.backbone.train_batchnorm))
         for m in (self.scene_enc, self.transl_enc, self.beta_layer, self.input_process, self.embed_timestep):
             m.train()
         self.diffusion_model.train(bool(self.diffusion_model.train_batchnorm))
@@ -556,7 +558,8 @@ class EgoHMR(nn.Module):
         the reference always trains on batch statistics) and decode_output.  Sets batch['vis_mask_smpl'], smpl_output, scene_pcd_verts, input_transl,
         focal_length and camera_center_full like forward; like decode_output it does NOT apply the NaN rule of ehm_pack_outputs.
         With EgoHMR.trunk_grad, img_feats is not a constant: prepare leaves the trunk out and the backbone runs here behind its autograd route
-        (ResNet50Features.grad_params set for the call; eval-mode BatchNorm, the statistics stay frozen).
+        (ResNet50Features.grad_params set for the call; eval-mode BatchNorm with frozen statistics, or - ResNet50Features.train_batchnorm - the
+        backbone in .train() on batch statistics, :455).
         SMPL.ordered_backward is set for the decode: the route has no order-dependent sum, so two steps on the same inputs give the same gradient bits."""
         self._check_trainable()
         dm, dev = self.diffusion_model, self.device
@@ -575,8 +578,9 @@ class EgoHMR(nn.Module):
             dm.precision = self.gcn_precision
             dm.train(bool(dm.train_batchnorm))
             img_feats = st.img_feats
-            if self.trunk_grad:                                                                            # :183 with a graph (eval-mode BatchNorm)
+            if self.trunk_grad:                                                 # :183 with a graph (batch statistics behind backbone.train_batchnorm)
                 bb.grad_params = True
+                bb.train(bool(bb.train_batchnorm))
                 img_feats = bb(_lib.f32(batch["img"], dev))
             scene_feats = enc(st.scene)                                                                    # :214
             transl_feat = self.transl_enc(st.transl)                                                       # :217
@@ -965,10 +969,10 @@ class EgoHMR(nn.Module):
         }
 
     NOT_BUILT = ("compute_loss has a backward (the loss, SMPL.forward, rot6d_to_rotmat, ModulatedGCN.forward, ResnetPointnet.forward and the ResNet-50 trunk "
-                 "in eval mode are differentiable, ModulatedGCN.train_batchnorm runs BatchNorm in training mode; decode_output chains them), but train-mode "
-                 "BatchNorm2d for the ResNet-50 trunk, the image gradient and the non-local block's backward are missing; the training route of "
-                 "EgoHMR.forward runs once EgoHMR.frozen_trunk_training is set - with the trunk's statistics frozen, and its weights too unless "
-                 "EgoHMR.trunk_grad is set")
+                 "are differentiable, ModulatedGCN.train_batchnorm and ResNet50Features.train_batchnorm run BatchNorm in training mode; decode_output "
+                 "chains them), but the image gradient and the non-local block's backward are missing; the training route of "
+                 "EgoHMR.forward runs once EgoHMR.frozen_trunk_training is set - with the trunk's weights frozen unless EgoHMR.trunk_grad is set, and "
+                 "its statistics frozen unless ResNet50Features.train_batchnorm is set too")
 
     def init_optimizers(self):
         """egohmr.py:140-147: the reference's parameter list in its order - without `backbone` while the trunk is frozen, with it in front behind

@@ -396,6 +396,34 @@ int ehm_conv_bwd_wgrad(const float* G, const void* x_x2, int64_t x_rows, float* 
 int ehm_resnet_stem_backward_workspace_bytes(int N, int H, int W, int64_t* bytes);
 int ehm_resnet_stem_backward(const float* img, const float* Wt, const float* bias, const float* gpool, float* gW, float* gb, float* z_out, float* gz_out,
                              int N, int H, int W, void* workspace, int64_t workspace_bytes, void* stream);
+/* The three steps of ehm_resnet_stem_backward on their own, on whole-batch tensors (the train-mode BatchNorm route needs sums over all pre-pool pixels
+ * between them): z [N,H/2,W/2,64] = conv 7x7 / 2 / pad 3 of img + bias in float32;  gz = gpool routed to each window's arg-max of z (z != gz);
+ * gW [64][147], gb [64] (either may be NULL, not both) = sum over the pre-pool pixels of gz (x) the image taps, workspace: 256 * 148 * 64 floats. */
+int ehm_resnet_stem_preact(const float* img, const float* Wt, const float* bias, float* z, int N, int H, int W, void* stream);
+int ehm_resnet_stem_route(const float* z, const float* gpool, float* gz, int N, int H, int W, void* stream);
+int ehm_resnet_stem_wgrad(const float* img, const float* gz, float* gW, float* gb, int N, int H, int W, void* workspace, int64_t workspace_bytes,
+                          void* stream);
+
+/* ------------------------------------------------------------------ ResNet-50 trunk: train-mode BatchNorm2d (csrc/bn2d_train.hip) ---- */
+/* z [pixels, C]: a conv's RAW output, as the X2 buffer ehm_conv_x2 wrote (z_is_x2 = 1; z_rows >= pixels rows, only the first `pixels` are read) or as
+ * float32 rows (z_is_x2 = 0).  C % 32 == 0, pixels >= 2, 16-byte aligned pointers.  No allocation, no host synchronisation, no atomics: float64 partial
+ * sums over runs of pixels that depend on the shape alone, added in index order.  workspace: *bytes of ehm_bn2d_train_workspace_bytes.
+ *
+ * stats: mean[c], var[c] (biased) and invstd[c] = 1 / sqrt(var + eps) as float32, from two passes in float64 (the mean, then the centred squares).
+ * running_mean / running_var (may be NULL: left alone) <- (1 - momentum) old + momentum (mean | var pixels / (pixels - 1)); *num_batches_tracked
+ * (int64 on the device, may be NULL) += 1 - nn.BatchNorm2d's update.
+ * bwd_sums: gbeta[c] = sum_p G[p,c], ggamma[c] = sum_p G[p,c] (z[p,c] - mean[c]) invstd[c];  G float32 [pixels, C].
+ * bwd_zbar: out[n,h,w,c] = *scale gamma invstd (G - gbeta / R - xhat ggamma / R), R = N Ho Wo, as float32 NHWC; dense ((H, W) == (Ho, Wo)) or
+ * zero-dilated like ehm_conv_bwd_gate.  scale: a float on the DEVICE, or NULL for 1. */
+int ehm_bn2d_train_workspace_bytes(int64_t pixels, int C, int64_t* bytes);
+int ehm_bn2d_train_stats(const void* z, int z_is_x2, int64_t z_rows, int64_t pixels, int C, double eps, double momentum, float* mean, float* var,
+                         float* invstd, float* running_mean, float* running_var, int64_t* num_batches_tracked, void* workspace, int64_t workspace_bytes,
+                         void* stream);
+int ehm_bn2d_train_bwd_sums(const float* G, const void* z, int z_is_x2, int64_t z_rows, int64_t pixels, int C, const float* mean, const float* invstd,
+                            float* gbeta, float* ggamma, void* workspace, int64_t workspace_bytes, void* stream);
+int ehm_bn2d_train_bwd_zbar(const float* G, const void* z, int z_is_x2, int64_t z_rows, const float* mean, const float* invstd, const float* gamma,
+                            const float* gbeta, const float* ggamma, const float* scale, float* out, int N, int Ho, int Wo, int C, int H, int W,
+                            void* stream);
 
 /* NHWC convolution + bias (+ identity) + ReLU as an implicit GEMM on the f16 matrix cores with f32-grade accuracy (hi/lo split
  * operands, f32 accumulate): y[n,ho,wo,co] = act(sum x[n, ho*s-p+kh, wo*s-p+kw, ci] w[co,kh,kw,ci] + bias[co] (+ residual)).

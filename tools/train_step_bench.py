@@ -5,7 +5,8 @@ device events recorded on the launch stream around each phase (everything runs o
   trunk | PointNet fwd + bwd | assembly fwd + bwd | denoiser fwd + bwd | decode + loss fwd + bwd | optimiser | rest (the small torch modules, host gaps)
 A record, not a bar: the parent commit has no training step.  Prints one JSON line.
 --trunk-grad: with EgoHMR.trunk_grad (the trunk's weights train: its autograd forward is the "trunk" phase, its backward "trunk_bwd").
-    python tools/train_step_bench.py [--batch 64] [--points 4096] [--warmup 3] [--calls 12] [--trunk-grad]"""
+--train-bn (with --trunk-grad): ResNet50Features.train_batchnorm too - the backbone in .train() on batch statistics, as the reference trains it.
+    python tools/train_step_bench.py [--batch 64] [--points 4096] [--warmup 3] [--calls 12] [--trunk-grad] [--train-bn]"""
 import argparse
 import json
 import os
@@ -27,7 +28,9 @@ ap.add_argument("--points", type=int, default=4096)
 ap.add_argument("--warmup", type=int, default=3)
 ap.add_argument("--calls", type=int, default=12)
 ap.add_argument("--trunk-grad", action="store_true")
+ap.add_argument("--train-bn", action="store_true")
 args = ap.parse_args()
+assert args.trunk_grad or not args.train_bn, "--train-bn is consulted with --trunk-grad only"
 assert args.calls >= 10, "the median is taken over at least 10 calls"
 assert torch.cuda.is_available(), "this measurement needs the GPU; there is no CPU fallback"
 dev = torch.device("cuda:0")
@@ -40,6 +43,7 @@ model = build_synthetic_model(dev, 0, smpl_asset_male=syn.make_smpl_asset(1), sm
 model.frozen_trunk_training = True
 model.diffusion_model.train_batchnorm = True
 model.trunk_grad = bool(args.trunk_grad)
+model.backbone.train_batchnorm = bool(args.train_bn)
 model.init_optimizers()
 g = np.random.default_rng(1)
 b = syn.make_batch(B, args.points, seed=1)
@@ -90,6 +94,7 @@ fs._backbone_fn = lambda: timed(backbone_fn(), "trunk")
 if args.trunk_grad:
     model.backbone.forward = timed(model.backbone.forward, "trunk")
     trunk_grad.TrunkFunction.backward = staticmethod(timed(trunk_grad.TrunkFunction.backward, "trunk_bwd"))
+    trunk_grad.TrunkTrainFunction.backward = staticmethod(timed(trunk_grad.TrunkTrainFunction.backward, "trunk_bwd"))
 model.scene_enc.forward = timed(model.scene_enc.forward, "pointnet_fwd")
 pointnet_grad.PointnetFunction.backward = staticmethod(timed(pointnet_grad.PointnetFunction.backward, "pointnet_bwd"))
 train_grad.cond_assemble_native = timed(train_grad.cond_assemble_native, "assembly_fwd")
@@ -121,6 +126,7 @@ def one_call():
 for _ in range(args.warmup):
     one_call()
 runs, losses = [], []
+torch.cuda.reset_peak_memory_stats()
 for _ in range(args.calls):
     ms, loss = one_call()
     runs.append(ms)
@@ -128,11 +134,12 @@ for _ in range(args.calls):
 med = {k: statistics.median(r[k] for r in runs) for k in runs[0]}
 pair = lambda a, b_: round(med[a] + med[b_], 3)
 med.setdefault("trunk_bwd", 0.0)
-print(json.dumps({"what": "one training_losses call, " + ("trunk_grad" if args.trunk_grad else "frozen trunk"), "batch": B, "scene_points": args.points, "warmup": args.warmup, "calls": args.calls,
+print(json.dumps({"what": "one training_losses call, " + (("trunk_grad + train_batchnorm" if args.train_bn else "trunk_grad") if args.trunk_grad else "frozen trunk"), "batch": B, "scene_points": args.points, "warmup": args.warmup, "calls": args.calls,
                   "median_ms": round(med["total"], 3), "min_ms": round(min(r["total"] for r in runs), 3), "max_ms": round(max(r["total"] for r in runs), 3),
                   "phases_median_ms": {"trunk": round(med["trunk"], 3), "trunk_bwd": round(med["trunk_bwd"], 3), "pointnet_fwd_bwd": pair("pointnet_fwd", "pointnet_bwd"),
                                        "assembly_fwd_bwd": pair("assembly_fwd", "assembly_bwd"), "denoiser_fwd_bwd": pair("denoiser_fwd", "denoiser_bwd"),
                                        "decode_loss_fwd_bwd": pair("decode_loss_fwd", "decode_loss_bwd"), "optimiser": round(med["optimiser"], 3),
                                        "rest": round(med["rest"], 3)},
                   "assembly_fwd_ms": round(med["assembly_fwd"], 4), "assembly_bwd_ms": round(med["assembly_bwd"], 4),
-                  "assembly_bytes": 4 * B * 24 * model.diffusion_model.in_dim, "loss_first": losses[0], "loss_last": losses[-1]}))
+                  "assembly_bytes": 4 * B * 24 * model.diffusion_model.in_dim, "loss_first": losses[0], "loss_last": losses[-1],
+                  "peak_allocated_gib": round(torch.cuda.max_memory_allocated() / 2 ** 30, 2)}))
