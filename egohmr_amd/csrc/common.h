@@ -41,6 +41,22 @@ constexpr int kPoseDim = 144;  // 24 x 6
 static inline int64_t ceil_div(int64_t a, int64_t b) { return (a + b - 1) / b; }
 static inline int64_t round_up(int64_t a, int64_t b) { return ceil_div(a, b) * b; }
 
+// ---- float32 chains that must round like the reference's separate torch ops: one correctly rounded operation each, never contracted.
+// HIP's __fmul_rn / __fadd_rn / __fsub_rn are the plain operators, which hipcc's default -ffp-contract=fast-honor-pragmas fuses across
+// statements: __fadd_rn(__fmul_rn(a, b), c) compiles to ONE v_fma_f32.  A product formed here carries no contract flag, so no sum can absorb it.
+static __device__ __forceinline__ float mul_rn(float a, float b) {
+#pragma clang fp contract(off)
+  return a * b;
+}
+static __device__ __forceinline__ float add_rn(float a, float b) {
+#pragma clang fp contract(off)
+  return a + b;
+}
+static __device__ __forceinline__ float sub_rn(float a, float b) {
+#pragma clang fp contract(off)
+  return a - b;
+}
+
 // ---- cross-lane helpers on the DPP path (hipcc lowers __shfl_xor to ds_bpermute_b32, an LDS-crossbar instruction) ----
 template <int CTRL>
 static __device__ __forceinline__ float dpp_move(float v) {

@@ -48,7 +48,8 @@ __global__ __launch_bounds__(kPrepThreads) void item_prep_kernel(ehm_item_prep_d
   if (t == 0) {
     const float fx = d.fx[b], ofx = __fmul_rn(fx, d.fx_norm);
     int c = d.other_col0 + d.t_out;
-    bool ok = isfinite(d.transl[3 * b] + d.transl[3 * b + 1] + d.transl[3 * b + 2]) && isfinite(fx);
+    // component by component: a sum of finite values can overflow float32
+    bool ok = isfinite(d.transl[3 * b]) && isfinite(d.transl[3 * b + 1]) && isfinite(d.transl[3 * b + 2]) && isfinite(fx);
     if (d.with_cam_center) {
       orow[c++] = __fdiv_rn(d.cx[b], ofx);
       orow[c++] = __fdiv_rn(d.cy[b], ofx);
@@ -58,7 +59,7 @@ __global__ __launch_bounds__(kPrepThreads) void item_prep_kernel(ehm_item_prep_d
       orow[c++] = __fdiv_rn(d.box_center[2 * b], ofx);
       orow[c++] = __fdiv_rn(d.box_center[2 * b + 1], ofx);
       orow[c++] = __fdiv_rn(d.box_size[b], ofx);
-      ok = ok && isfinite(d.box_center[2 * b] + d.box_center[2 * b + 1]) && isfinite(d.box_size[b]);
+      ok = ok && isfinite(d.box_center[2 * b]) && isfinite(d.box_center[2 * b + 1]) && isfinite(d.box_size[b]);
     }
     orow[c++] = fx;
     for (; c < d.other_ld; ++c) orow[c] = 0.f;
@@ -145,7 +146,7 @@ __global__ __launch_bounds__(kPackThreads) void pack_outputs_kernel(ehm_pack_des
   }
   for (int i = t; i < 10; i += kPackThreads) d.betas_out[(size_t)b * 10 + i] = bad ? nan : d.betas_in[(size_t)b * 10 + i];
   // egohmr.py:283-301 (float32 op for op: focal = fx * FX_NORM; p = joints + transl; p / p.z; u = f p.x + c p.z; u / 1920 - 0.5)
-  const float f = __fmul_rn(d.fx[b], d.fx_norm), ccx = d.cx[b], ccy = d.cy[b];
+  const float f = mul_rn(d.fx[b], d.fx_norm), ccx = d.cx[b], ccy = d.cy[b];      // (mul_rn / add_rn / sub_rn of common.h: never contracted into an FMA)
   if (t == 0) {
     d.focal[2 * b] = f; d.focal[2 * b + 1] = f;
     d.center[2 * b] = ccx; d.center[2 * b + 1] = ccy;
@@ -154,12 +155,12 @@ __global__ __launch_bounds__(kPackThreads) void pack_outputs_kernel(ehm_pack_des
   for (int j = t; j < d.J; j += kPackThreads) {
     const size_t o = ((size_t)b * d.J + j) * 3;
     const float jx = bad ? nan : d.joints[o], jy = bad ? nan : d.joints[o + 1], jz = bad ? nan : d.joints[o + 2];
-    const float px = __fadd_rn(jx, tx), py = __fadd_rn(jy, ty), pz = __fadd_rn(jz, tz);
+    const float px = add_rn(jx, tx), py = add_rn(jy, ty), pz = add_rn(jz, tz);
     d.kp3d_full[o] = px; d.kp3d_full[o + 1] = py; d.kp3d_full[o + 2] = pz;
     const float qx = __fdiv_rn(px, pz), qy = __fdiv_rn(py, pz), qz = __fdiv_rn(pz, pz);
-    const float u = __fadd_rn(__fmul_rn(f, qx), __fmul_rn(ccx, qz)), v = __fadd_rn(__fmul_rn(f, qy), __fmul_rn(ccy, qz));
-    d.kp2d_full[((size_t)b * d.J + j) * 2] = __fsub_rn(__fdiv_rn(u, 1920.f), 0.5f);
-    d.kp2d_full[((size_t)b * d.J + j) * 2 + 1] = __fsub_rn(__fdiv_rn(v, 1080.f), 0.5f);
+    const float u = add_rn(mul_rn(f, qx), mul_rn(ccx, qz)), v = add_rn(mul_rn(f, qy), mul_rn(ccy, qz));
+    d.kp2d_full[((size_t)b * d.J + j) * 2] = sub_rn(__fdiv_rn(u, 1920.f), 0.5f);
+    d.kp2d_full[((size_t)b * d.J + j) * 2 + 1] = sub_rn(__fdiv_rn(v, 1080.f), 0.5f);
   }
 }
 

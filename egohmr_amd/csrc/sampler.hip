@@ -101,16 +101,16 @@ extern "C" int ehm_profile_end(double* ms, int64_t* launches, int n) {
 
 namespace {
 
-// torch evaluates these chains as separate rounded float32 ops; keep the same roundings (no FMA contraction)
+// torch evaluates these chains as separate rounded float32 ops; keep the same roundings (no FMA contraction: mul_rn / add_rn of common.h)
 __global__ void ddpm_step_kernel(const float* __restrict__ x, const float* __restrict__ x0, const float* __restrict__ noise,
                                  const float* __restrict__ grad, float* __restrict__ out, float c1, float c2, float logvar,
                                  float nz, float gscale, int64_t n) {
   int64_t i = (int64_t)blockIdx.x * blockDim.x + threadIdx.x;
   if (i >= n) return;
-  float mean = __fadd_rn(__fmul_rn(c1, x0[i]), __fmul_rn(c2, x[i]));                 // :217-220
-  if (grad) mean = __fadd_rn(mean, __fmul_rn(gscale, grad[i]));                      // :381 / :385
-  const float sd = expf(__fmul_rn(0.5f, logvar));
-  out[i] = __fadd_rn(mean, __fmul_rn(__fmul_rn(nz, sd), noise[i]));                  // :336
+  float mean = add_rn(mul_rn(c1, x0[i]), mul_rn(c2, x[i]));                          // :217-220
+  if (grad) mean = add_rn(mean, mul_rn(gscale, grad[i]));                            // :381 / :385
+  const float sd = expf(mul_rn(0.5f, logvar));
+  out[i] = add_rn(mean, mul_rn(mul_rn(nz, sd), noise[i]));                           // :336
 }
 
 __global__ void ddim_step_kernel(const float* __restrict__ x, const float* __restrict__ x0, const float* __restrict__ noise,
@@ -118,9 +118,9 @@ __global__ void ddim_step_kernel(const float* __restrict__ x, const float* __res
                                  int64_t n) {
   int64_t i = (int64_t)blockIdx.x * blockDim.x + threadIdx.x;
   if (i >= n) return;
-  const float eps = __fdiv_rn(__fsub_rn(__fmul_rn(sr, x[i]), x0[i]), srm1);          // :286-290
-  const float mean = __fadd_rn(__fmul_rn(x0[i], sap), __fmul_rn(dir, eps));          // :548-551
-  out[i] = __fadd_rn(mean, __fmul_rn(__fmul_rn(nz, sigma), noise[i]));               // :555
+  const float eps = __fdiv_rn(sub_rn(mul_rn(sr, x[i]), x0[i]), srm1);                // :286-290
+  const float mean = add_rn(mul_rn(x0[i], sap), mul_rn(dir, eps));                   // :548-551
+  out[i] = add_rn(mean, mul_rn(mul_rn(nz, sigma), noise[i]));                        // :555
 }
 
 }  // namespace

@@ -683,7 +683,8 @@ int ehm_scene_select(const ehm_scene_desc* d, void* stream);
  *                       | camera features (:195-205: [cx, cy] / (fx*fx_norm), [box_center, box_size] / (fx*fx_norm), fx), zero-filled
  *                       up to other_ld (row stride of `other`; columns [0, other_col0) are the caller's: the scene features)
  *   finite [B] u8       0 when transl / fx / cx / cy / box / img_rowsum / scene_rowsum of the item hold a NaN or Inf (the float32
- *                       graph of the reference turns every output of such an item into NaN; see ehm_pack_outputs)
+ *                       graph of the reference turns every output of such an item into NaN; see ehm_pack_outputs).  Every component
+ *                       is tested on its own: finite components whose float32 sum would overflow are finite inputs
  * need_scratch: B bytes of device memory. */
 typedef struct ehm_item_prep_desc {
   const float* keypoints_2d; /* [B, NK, 3] */

@@ -53,12 +53,28 @@ def _same(a, b):
     (24, 50, "ddim5", True, "f32", None, False),          # float32 rows (the f32-input MFMA convs)
 ])
 def test_fused_step_launch_is_bit_equal_to_the_per_step_launches(dev, smpl_asset, B, n, respacing, ddim, precision, lowprec, all_visible):
+    _check_bit_equal(dev, smpl_asset, B, n, respacing, ddim, precision, lowprec, all_visible)
+
+
+@pytest.mark.parametrize("bodies_per_cu,n,respacing,ddim,precision,all_visible", [
+    (1, 100, "ddim5", True, "f16x3", False),              # B = CUs + 1: the 512-thread instantiation (two blocks per CU), mixed visibility
+    (2, 100, "ddim5", True, "f16x3", True),               # B = 2 CUs + 1: the 256-thread instantiation (the guided benchmark's), with pass pruning
+    (2, 4, "", False, "f16", False),                      # B = 2 CUs + 1: the 256-thread instantiation on plain-f16 rows, ancestral sampling
+])
+def test_fused_step_launch_block_shapes_of_larger_batches(dev, smpl_asset, bodies_per_cu, n, respacing, ddim, precision, all_visible):
+    """launch_fused (csrc/step.hip) picks 1024, 512 or 256 threads per body by the batch size against the CU count; the rows above stay within the
+    first.  The batch is sized from the device's own CU count, so that the rows reach the other two on any partitioning of the card."""
+    cus = torch.cuda.get_device_properties(dev).multi_processor_count
+    _check_bit_equal(dev, smpl_asset, bodies_per_cu * cus + 1, n, respacing, ddim, precision, None, all_visible, scene_points=256)
+
+
+def _check_bit_equal(dev, smpl_asset, B, n, respacing, ddim, precision, lowprec, all_visible, scene_points=512):
     from egohmr_amd.diffusion import create_gaussian_diffusion
     from egohmr_amd.factory import batch_to_device
     model = _model(dev, smpl_asset, diffuse_fuse=True)
     d = create_gaussian_diffusion(num_diffusion_timesteps=n, timestep_respacing=respacing)
     T = d.num_timesteps
-    b = syn.make_batch(B, 512, seed=21)
+    b = syn.make_batch(B, scene_points, seed=21)
     if all_visible:
         b["orig_keypoints_2d"][::2, :, 2] = 1.0
     batch = batch_to_device(b, dev)
