@@ -15,7 +15,7 @@ import torch
 import torch.nn as nn
 import torch.nn.functional as F
 
-from . import _lib
+from . import _lib, trunk_grad
 from .split_gemm import weight_scale
 
 
@@ -92,7 +92,6 @@ class ResNet50Features(nn.Module):
                 raise _lib.EgoHMRHipError(self.GRAD_HI_ONLY)
             if x.requires_grad:
                 raise NotImplementedError(self.GRAD_IMAGE)
-            from . import trunk_grad
             if train:
                 self._check_train(x)
                 return trunk_grad.TrunkTrainFunction.apply(self, x, *self.parameters())
@@ -145,40 +144,41 @@ class ResNet50Features(nn.Module):
     # ------------------------------------------------------------------ inference form: BatchNorm folded into the convolutions
     @torch.no_grad()
     def folded(self, x2_activations: bool = True, fuse_shortcut: bool = True, train: bool = False):
-        """Eval-mode ResNet-50 on the matrix cores with every BatchNorm2d folded into its convolution (w' = w * g/sqrt(v+eps),
+        """Eval-mode ResNet-50 on the matrix cores with every BatchNorm2d folded into its convolution (trunk_grad.fold: w' = w * g/sqrt(v+eps),
         b' = beta - mean * g/sqrt(v+eps); exact up to float re-association).  x2_activations=True (the product path): the activations
         stay in the X2 split format from the stem to the average pool (ehm_conv_x2); False: float32 NHWC activations between the
         convolutions (ehm_conv_nhwc_split - the kernel the non-local GCN block also uses; kept as a second implementation the tests
         compare).  HIP tensors only: there is no eager / library-convolution route.
-        train=True (the X2 route only; ResNet50Features.train_batchnorm): nothing is folded here; the returned run(x, rec=None) folds each BatchNorm2d on
-        the statistics of the batch it is given and updates the running ones (run_x2_train below)."""
+        The X2 route is ONE walk over trunk_grad.units (run_x2); where a unit's (w', b', stride, padding) come from is its operand provider.  Eval
+        (folded_units): folded here, once, and their packed form cached by unit index.  train=True (ResNet50Features.train_batchnorm; batch_units):
+        nothing is folded here; run(x, rec=None) folds each BatchNorm2d on the statistics of the batch it is given, updates the running ones, and packs
+        per call."""
         import ctypes as C
 
         A, P = _lib.api(), _lib.ptr
+        U = trunk_grad.units(self)
 
-        def fold(conv, bn, stats=None):
-            """stats: (mean, biased variance) that stand in for the running ones - the train-mode route's float32 batch statistics"""
-            mean, var = (bn.running_mean, bn.running_var) if stats is None else stats
-            scale = (bn.weight.double() / torch.sqrt(var.double() + bn.eps))
-            w = (conv.weight.double() * scale.view(-1, 1, 1, 1)).float()
-            b = (bn.bias.double() - mean.double() * scale).float()
-            return w, b, conv.stride, conv.padding
+        def operands(conv, bn, stats=None):
+            """a unit's launch operands: trunk_grad.fold's (w', b') in float32, the conv's stride and padding"""
+            w, b = trunk_grad.fold(conv, bn, stats)
+            return w.float(), b.float(), conv.stride, conv.padding
 
-        stem, blocks = None, []
-        if not train:
-            stem = fold(self.conv1, self.bn1)
-            for layer in (self.layer1, self.layer2, self.layer3, self.layer4):
-                for blk in layer:
-                    blocks.append((fold(blk.conv1, blk.bn1), fold(blk.conv2, blk.bn2), fold(blk.conv3, blk.bn3),
-                                   fold(blk.downsample[0], blk.downsample[1]) if blk.downsample is not None else None))
-        packed = {}
+        ops = [] if train else [None if u is None else operands(*u) for u in U]
+        stem, blocks = (ops[0], [tuple(ops[i:i + 4]) for i in range(1, len(U), 4)]) if ops else (None, [])
+        packs = {}                                         # the eval operands' packed form: unit index -> pack(), ("dual", conv3's index) -> pack_dual()
         sk_ws = {}                                         # device -> scratch of the stream-K convs (one conv at a time on a stream)
+
+        def cached(key, build, *args):
+            """build(*args), kept under `key`; key None (the train route's per-call operands): not kept"""
+            if key is None:
+                return build(*args)
+            if key not in packs:
+                packs[key] = build(*args)
+            return packs[key]
 
         def pack(p):
             """weights [Co,Ci,KH,KW] -> tap-major [Co_pad, KH*KW*Ci] X2 split format, scaled by a power of two"""
             w = p[0]
-            if id(w) in packed:
-                return packed[id(w)]
             Co, Ci, KH, KW = w.shape
             K = KH * KW * Ci
             Co_pad = (Co + 127) // 128 * 128
@@ -187,11 +187,10 @@ class ResNet50Features(nn.Module):
             scale = weight_scale(float(w2.abs().max()))
             buf = torch.empty(Co_pad, K, device=w.device)              # X2 rows have the byte size of float rows
             A.ehm_split_pack(w2, buf, Co_pad, K, K, scale, _lib.stream_ptr())
-            packed[id(w)] = (buf, scale, p[1].contiguous(), (Co, Ci, KH, KW), p[2][0], p[3][0])
-            return packed[id(w)]
+            return buf, scale, p[1].contiguous(), (Co, Ci, KH, KW), p[2][0], p[3][0]
 
-        def conv_mc(x, p, res=None, relu=True):
-            buf, scale, bias, (Co, Ci, KH, KW), stride, pad = pack(p)
+        def conv_mc(x, i, res=None, relu=True):
+            buf, scale, bias, (Co, Ci, KH, KW), stride, pad = cached(i, pack, ops[i])
             N, H, W, _ = x.shape
             Ho, Wo = (H + 2 * pad - KH) // stride + 1, (W + 2 * pad - KW) // stride + 1
             y = torch.empty(N, Ho, Wo, Co, device=x.device)
@@ -213,23 +212,20 @@ class ResNet50Features(nn.Module):
                 buf[rows - 1].zero_()
             return buf
 
-        def stem_mc(x, x2=False, stem_wt=stem_wt, stem_b=stem_b):
+        def stem_mc(x, wt, b, x2=False):
             """conv1 + bn1 + relu + maxpool in one pass, NCHW in -> NHWC out (csrc/stem.hip); x2: output in the X2 split format"""
             N, _, H, W = x.shape
-            if stem_wt.device != x.device:
+            if wt.device != x.device:
                 raise _lib.EgoHMRHipError("ResNet50Features.folded(): weights and input live on different devices")
             scratch = torch.empty(A.ehm_resnet_stem_scratch_bytes(N, H, W) // 4, device=x.device)
             y = x2_buffer(N * (H // 4) * (W // 4), 64, x.device, clear_last=True) if x2 else torch.empty(N, H // 4, W // 4, 64, device=x.device)
-            A.ehm_resnet_stem(x, stem_wt, stem_b, scratch, y, N, H, W, 1 if x2 else 0, _lib.stream_ptr())
+            A.ehm_resnet_stem(x, wt, b, scratch, y, N, H, W, 1 if x2 else 0, _lib.stream_ptr())
             if x2 and _x2_debug_hook is not None:
                 _x2_debug_hook(y, 64)
             return y
 
         def pack_dual(p, ds):
             """a bottleneck's last conv and its projection shortcut as ONE weight matrix [Co_pad, Ci + Ci_in] (both 1 x 1), common scale, summed bias"""
-            key = (id(p[0]), id(ds[0]))
-            if key in packed:
-                return packed[key]
             w, wd = p[0], ds[0]
             Co, Ci = w.shape[:2]
             assert w.shape[2:] == (1, 1) and wd.shape[2:] == (1, 1) and wd.shape[0] == Co and Co % 128 == 0
@@ -238,17 +234,17 @@ class ResNet50Features(nn.Module):
             scale = weight_scale(float(w2.abs().max()))
             buf = torch.empty(Co, K, device=w.device)
             A.ehm_split_pack(w2, buf, Co, K, K, scale, _lib.stream_ptr())
-            packed[key] = (buf, scale, (p[1].double() + ds[1].double()).float().contiguous(), (Co, Ci, 1, 1), p[2][0], p[3][0], wd.shape[1], ds[2][0])
-            return packed[key]
+            return buf, scale, (p[1].double() + ds[1].double()).float().contiguous(), (Co, Ci, 1, 1), p[2][0], p[3][0], wd.shape[1], ds[2][0]
 
-        def conv_x2(x, shape, p, res=None, relu=True, shortcut=None):
-            """one bottleneck conv on X2 activations (csrc/conv.hip conv_x2_tile_kernel); shape = (N, H, W) of x.
+        def conv_x2(x, shape, p, key, res=None, relu=True, shortcut=None):
+            """one bottleneck conv on X2 activations (csrc/conv.hip conv_x2_tile_kernel); shape = (N, H, W) of x; p: the unit's operands, key: what
+            their packed form is cached under (`cached`).
             shortcut = (block input, its shape, folded downsample): the projection shortcut accumulates inside this conv (second K segment)."""
             N, H, W = shape
             if shortcut is not None:
-                buf, scale, bias, (Co, Ci, KH, KW), stride, pad, Ci2, stride2 = pack_dual(p, shortcut[2])
+                buf, scale, bias, (Co, Ci, KH, KW), stride, pad, Ci2, stride2 = cached(None if key is None else ("dual", key), pack_dual, p, shortcut[2])
             else:
-                buf, scale, bias, (Co, Ci, KH, KW), stride, pad = pack(p)
+                buf, scale, bias, (Co, Ci, KH, KW), stride, pad = cached(key, pack, p)
             Ho, Wo = (H + 2 * pad - KH) // stride + 1, (W + 2 * pad - KW) // stride + 1
             y = x2_buffer(N * Ho * Wo, Co, x.device)
             d = _lib.ConvX2Desc(P(x), x.shape[0], P(buf), P(bias), P(res), P(y), N, H, W, Ci, Co, KH, KW, stride, pad, 1 if relu else 0, scale, None, 0)
@@ -267,93 +263,83 @@ class ResNet50Features(nn.Module):
                 _x2_debug_hook(y, Co)
             return y, (N, Ho, Wo)
 
-        def run_x2(x, saved=None):
-            """the whole trunk with the activations in the X2 split format between the layers (taps gathered by the LDS DMA).
-            saved: a list that receives (X2 buffer, (N, H, W)) of the stem's and of every conv's output in launch order instead of letting them go"""
-            N = x.shape[0]
-            shp = (N, x.shape[2] // 4, x.shape[3] // 4)
-            keep = (lambda *e: None) if saved is None else (lambda *e: saved.append(e))
-            x = stem_mc(x, x2=True)
-            keep(x, shp)
-            for c1, c2, c3, ds in blocks:
-                y, s1 = conv_x2(x, shp, c1)
-                keep(y, s1)
-                y, s2 = conv_x2(y, s1, c2)
-                keep(y, s2)
-                if ds is None:
-                    x, shp = conv_x2(y, s2, c3, res=x)
-                elif fuse_shortcut:
-                    x, shp = conv_x2(y, s2, c3, shortcut=(x, shp, ds))          # out = conv3(.) + downsample(x) in one launch: no shortcut tensor
-                else:
-                    x, shp = conv_x2(y, s2, c3, res=conv_x2(x, shp, ds, relu=False)[0])
-                keep(x, shp)
-            out = torch.empty(N, x.shape[1], device=x.device)
-            A.ehm_x2_group_mean(x, out, N, shp[1] * shp[2], x.shape[1], int(bool(self.hi_only)), _lib.stream_ptr())
-            self._sk_status_async(sk_ws.get(str(x.device)))
-            return out
+        def folded_units(x, rec):
+            """the eval provider: the operands folded above, packed once per closure"""
+            return (stem_wt, stem_b), (lambda i, x, shp: (ops[i], i)), (lambda: None)
 
-        def run_x2_train(x, rec=None):
-            """run_x2 on batch statistics.  Per (conv, BatchNorm2d) unit: the RAW conv output z on the same launch (unfolded weight through the same
-            pack, zero bias, no ReLU, no residual; a projection block's conv3 and downsample apart - each BatchNorm has its own statistics), its mean /
-            biased variance / invstd and the running-statistics update (ehm_bn2d_train_stats), then the folded launch of run_x2 unchanged, folded by the
-            same `fold` on the float32 batch statistics: the output has the bits of an eval-mode call whose running statistics are that batch's.
-            rec: a trunk_grad.TrainRecord that receives what the backward needs (acts: run_x2's `saved`; bn: per unit of trunk_grad.units
-            (z or None, z's shape, mean, var, invstd), None for an identity block's absent downsample)."""
-            from . import trunk_grad
+        def batch_units(x, rec):
+            """the train provider.  Per (conv, BatchNorm2d) unit: the RAW conv output z on the same launch (unfolded weight through the same pack, zero
+            bias, no ReLU, no residual; a projection block's conv3 and downsample apart - each BatchNorm has its own statistics), its mean / biased
+            variance / invstd and the running-statistics update (ehm_bn2d_train_stats), then the operands folded on the float32 batch statistics: the
+            output has the bits of an eval-mode call whose running statistics are that batch's.
+            rec: a trunk_grad.TrainRecord that receives what the backward needs (bn: per unit of trunk_grad.units (z or None, z's shape, mean, var,
+            invstd), None for an identity block's absent downsample; the stem's operands)."""
             N, _, H, W = x.shape
-            dev = x.device
-            keep = (lambda *e: None) if rec is None else (lambda *e: rec.acts.append(e))
-            note = (lambda e: None) if rec is None else rec.bn.append
-            zero = torch.zeros(2048, device=dev)
+            zero = torch.zeros(2048, device=x.device)
             bumped = []
+            if rec is not None:
+                rec.bn = [None] * len(U)
 
-            def unit(x, shp, conv, bn):
-                """-> the unit's (w', b', stride, padding) folded on the statistics of this batch"""
+            def note(i, *e):
+                bumped.append(U[i][1])
+                if rec is not None:
+                    rec.bn[i] = e
+
+            def unit(i, x, shp):
+                conv, bn = U[i]
                 Co = conv.out_channels
-                packed.clear()                                  # per-call operands: nothing to reuse, and an id must not outlive its tensor
-                z, zs = conv_x2(x, shp, (conv.weight.detach().float(), zero[:Co], conv.stride, conv.padding), relu=False)
+                z, zs = conv_x2(x, shp, (conv.weight.detach().float(), zero[:Co], conv.stride, conv.padding), None, relu=False)
                 mean, var, invstd = trunk_grad.bn_stats(z, zs[0] * zs[1] * zs[2], Co, bn)
-                bumped.append(bn)
-                note((z if rec is not None and rec.keep_z else None, zs, mean, var, invstd))
-                packed.clear()
-                return fold(conv, bn, (mean, var))
+                note(i, z if rec is not None and rec.keep_z else None, zs, mean, var, invstd)
+                return operands(conv, bn, (mean, var)), None
+
+            def finish():               # the kernels wrote the buffers through their pointers: tell torch (current() refolds on the next eval call)
+                for bn in bumped:
+                    for t in (bn.running_mean, bn.running_var, bn.num_batches_tracked):
+                        torch.autograd.graph.increment_version(t)
 
             raw_wt, _ = stem_operands(self.conv1.weight.detach().float(), zero[:64])
             z = trunk_grad.stem_preact(x, raw_wt, zero[:64])
             mean, var, invstd = trunk_grad.bn_stats(z, N * (H // 2) * (W // 2), 64, self.bn1, x2=False)
-            bumped.append(self.bn1)
             del z                                                                   # (recomputed by the backward, like the eval route's)
-            wt, b = stem_operands(*fold(self.conv1, self.bn1, (mean, var))[:2])
-            note((None, (N, H // 2, W // 2), mean, var, invstd))
+            note(0, None, (N, H // 2, W // 2), mean, var, invstd)
+            wt, b = stem_operands(*operands(self.conv1, self.bn1, (mean, var))[:2])
             if rec is not None:
                 rec.stem_wt, rec.stem_b = wt, b
-            shp = (N, H // 4, W // 4)
-            x = stem_mc(x, x2=True, stem_wt=wt, stem_b=b)
+            return (wt, b), unit, finish
+
+        def run_x2(x, saved=None, rec=None):
+            """the whole trunk with the activations in the X2 split format between the layers (taps gathered by the LDS DMA).
+            saved (train: rec.acts): a list that receives (X2 buffer, (N, H, W)) of the stem's and of every conv's output in launch order instead of
+            letting them go"""
+            N = x.shape[0]
+            shp = (N, x.shape[2] // 4, x.shape[3] // 4)
+            if rec is not None:
+                saved = rec.acts
+            keep = (lambda *e: None) if saved is None else (lambda *e: saved.append(e))
+            (wt, b), unit, finish = (batch_units if train else folded_units)(x, rec)
+            x = stem_mc(x, wt, b, x2=True)
             keep(x, shp)
-            for layer in (self.layer1, self.layer2, self.layer3, self.layer4):
-                for blk in layer:
-                    y, s1 = conv_x2(x, shp, unit(x, shp, blk.conv1, blk.bn1))
-                    keep(y, s1)
-                    y2, s2 = conv_x2(y, s1, unit(y, s1, blk.conv2, blk.bn2))
-                    keep(y2, s2)
-                    p3 = unit(y2, s2, blk.conv3, blk.bn3)
-                    if blk.downsample is None:
-                        note(None)
-                        x, shp = conv_x2(y2, s2, p3, res=x)
+            for i1 in range(1, len(U), 4):
+                i2, i3, id_ = i1 + 1, i1 + 2, i1 + 3
+                y, s1 = conv_x2(x, shp, *unit(i1, x, shp))
+                keep(y, s1)
+                y, s2 = conv_x2(y, s1, *unit(i2, y, s1))
+                keep(y, s2)
+                p3, k3 = unit(i3, y, s2)
+                if U[id_] is None:
+                    x, shp = conv_x2(y, s2, p3, k3, res=x)
+                else:
+                    pd, kd = unit(id_, x, shp)
+                    if fuse_shortcut:
+                        x, shp = conv_x2(y, s2, p3, k3, shortcut=(x, shp, pd))      # out = conv3(.) + downsample(x) in one launch: no shortcut tensor
                     else:
-                        pd = unit(x, shp, blk.downsample[0], blk.downsample[1])
-                        if fuse_shortcut:
-                            x, shp = conv_x2(y2, s2, p3, shortcut=(x, shp, pd))
-                        else:
-                            x, shp = conv_x2(y2, s2, p3, res=conv_x2(x, shp, pd, relu=False)[0])
-                    keep(x, shp)
-            packed.clear()
-            out = torch.empty(N, x.shape[1], device=dev)
+                        x, shp = conv_x2(y, s2, p3, k3, res=conv_x2(x, shp, pd, kd, relu=False)[0])
+                keep(x, shp)
+            out = torch.empty(N, x.shape[1], device=x.device)
             A.ehm_x2_group_mean(x, out, N, shp[1] * shp[2], x.shape[1], int(bool(self.hi_only)), _lib.stream_ptr())
-            self._sk_status_async(sk_ws.get(str(dev)))
-            for bn in bumped:                    # the kernels wrote the buffers through their pointers: tell torch (current() refolds on the next eval call)
-                for t in (bn.running_mean, bn.running_var, bn.num_batches_tracked):
-                    torch.autograd.graph.increment_version(t)
+            self._sk_status_async(sk_ws.get(str(x.device)))
+            finish()
             return out
 
         def run(x, saved=None):
@@ -365,13 +351,13 @@ class ResNet50Features(nn.Module):
             with _lib.on_device(x.device):                                          # the library launches on the CURRENT device's stream
                 if train:
                     with torch.no_grad():
-                        return run_x2_train(x, saved)
+                        return run_x2(x, rec=saved)
                 if x2_activations:
                     return run_x2(x, saved)
-                x = stem_mc(x)                                                      # NHWC float32 from here on
-                for c1, c2, c3, ds in blocks:
-                    y = conv_mc(conv_mc(x, c1), c2)
-                    x = conv_mc(y, c3, res=x if ds is None else conv_mc(x, ds, relu=False))
+                x = stem_mc(x, stem_wt, stem_b)                                     # NHWC float32 from here on
+                for i1 in range(1, len(U), 4):
+                    y = conv_mc(conv_mc(x, i1), i1 + 1)
+                    x = conv_mc(y, i1 + 2, res=x if U[i1 + 3] is None else conv_mc(x, i1 + 3, relu=False))
                 return x.mean(dim=(1, 2))
 
         run.stem, run.blocks, run.stem_wt, run.stem_b = stem, blocks, stem_wt, stem_b         # the folded parameters (trunk_grad reads them)

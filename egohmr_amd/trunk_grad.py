@@ -16,12 +16,17 @@ A fused projection block (y = relu(conv3(a) + downsample(x) + b3 + bd)) sends on
 The BatchNorm fold is undone in float64 by `unfold`.  running_mean / running_var / num_batches_tracked are never written.  The backward reads the
 parameters again (unfold), so one changed between forward and backward (TensorKey: storage or version counter) is refused, not silently mixed.
 
-Behind ResNet50Features.train_batchnorm (BatchNorm2d on batch statistics, csrc/bn2d_train.hip) the same walk runs with a BatchNorm backward per unit and
-no fold to undo: the second half of this file (TrunkTrainFunction).
+One function walks the blocks from the top for both routes (`_walk`): it owns the pruning, the three data gradients per block, the shortcut riding in as
+conv1's `residual`, the tensor lifetimes and the powers of two.  What a route does per unit is its step: `_eval_step` is the list above; `_train_step`
+(ResNet50Features.train_batchnorm: BatchNorm2d on batch statistics, csrc/bn2d_train.hip) runs a BatchNorm backward per unit on the raw weight, no fold to undo.
+`fold` and `units` are also what ResNet50Features.folded() builds its forward from.
 """
 from __future__ import annotations
 
 import ctypes as C
+from functools import reduce
+from operator import mul
+from types import SimpleNamespace
 
 import torch
 
@@ -29,10 +34,12 @@ from . import _lib
 from .split_gemm import pack_weight, pow2_scale
 
 
-def fold(conv, bn):
-    """(w', b') of ResNet50Features.folded() in float64: w' = w g / sqrt(v + eps), b' = beta - mean g / sqrt(v + eps)."""
-    scale = bn.weight.double() / torch.sqrt(bn.running_var.double() + bn.eps)
-    return conv.weight.double() * scale.view(-1, 1, 1, 1), bn.bias.double() - bn.running_mean.double() * scale
+def fold(conv, bn, stats=None):
+    """(w', b') of ResNet50Features.folded() in float64: w' = w g / sqrt(v + eps), b' = beta - mean g / sqrt(v + eps).  stats: (mean, biased variance)
+    that stand in for the running ones - the train-mode route's float32 batch statistics."""
+    mean, var = (bn.running_mean, bn.running_var) if stats is None else stats
+    scale = bn.weight.double() / torch.sqrt(var.double() + bn.eps)
+    return conv.weight.double() * scale.view(-1, 1, 1, 1), bn.bias.double() - mean.double() * scale
 
 
 def unfold(conv, bn, gw, gb):
@@ -60,6 +67,13 @@ def units(m):
     return out
 
 
+def _workspace(query, *dims, dtype=torch.float32, device=None):
+    """(scratch of the size `query(*dims, &bytes)` answers, that size in bytes)"""
+    nb = C.c_int64(0)
+    query(*dims, C.byref(nb))
+    return torch.empty(nb.value // dtype.itemsize, dtype=dtype, device=device), nb.value
+
+
 def dgrad_weight(wf):
     """Folded weight [Co,Ci,KH,KW] float32 -> the packed operand of its data gradient: taps flipped, Co <-> Ci transposed, [Ci][KH*KW*Co] tap-major."""
     Co, Ci, KH, KW = wf.shape
@@ -80,12 +94,10 @@ def wgrad(G, x_x2, in_shape, Ci, Co, K, stride, pad, want_w=True, want_b=True):
     """ehm_conv_bwd_wgrad: (w'bar [Co,Ci,K,K] as a view of the tap-major result, b'bar [Co]); G [N,Ho,Wo,Co] dense, x_x2 the conv's saved input."""
     A, dev = _lib.api(), G.device
     N, H, W = in_shape
-    nb = C.c_int64(0)
-    A.ehm_conv_bwd_wgrad_workspace_bytes(N, H, W, Ci, Co, K, stride, pad, C.byref(nb))
-    ws = torch.empty(nb.value // 4, device=dev)
+    ws, nb = _workspace(A.ehm_conv_bwd_wgrad_workspace_bytes, N, H, W, Ci, Co, K, stride, pad, device=dev)
     gw = torch.empty(Co, K * K * Ci, device=dev) if want_w else None
     gb = torch.empty(Co, device=dev) if want_b else None
-    A.ehm_conv_bwd_wgrad(G, x_x2 if want_w else None, x_x2.shape[0], gw, gb, N, H, W, Ci, Co, K, stride, pad, ws, nb.value, _lib.stream_ptr())
+    A.ehm_conv_bwd_wgrad(G, x_x2 if want_w else None, x_x2.shape[0], gw, gb, N, H, W, Ci, Co, K, stride, pad, ws, nb, _lib.stream_ptr())
     return (gw.view(Co, K, K, Ci).permute(0, 3, 1, 2) if want_w else None), gb
 
 
@@ -103,124 +115,165 @@ def stem_backward(img, stem_wt, stem_b, gpool, want_w=True, want_b=True, debug=F
     """ehm_resnet_stem_backward: (w'bar [64,3,7,7], b'bar [64]) from the gated pooled cotangent [N,H/4,W/4,64]; debug: also (z, gz) [N,H/2,W/2,64]."""
     A, dev = _lib.api(), img.device
     N, _, H, W = img.shape
-    nb = C.c_int64(0)
-    A.ehm_resnet_stem_backward_workspace_bytes(N, H, W, C.byref(nb))
-    ws = torch.empty(nb.value // 4, device=dev)
+    ws, nb = _workspace(A.ehm_resnet_stem_backward_workspace_bytes, N, H, W, device=dev)
     gw = torch.empty(64, 147, device=dev) if want_w else None
     gb = torch.empty(64, device=dev) if want_b else None
     z = torch.empty(N, H // 2, W // 2, 64, device=dev) if debug else None
     gz = torch.empty(N, H // 2, W // 2, 64, device=dev) if debug else None
-    A.ehm_resnet_stem_backward(img, stem_wt, stem_b, gpool, gw, gb, z, gz, N, H, W, ws, nb.value, _lib.stream_ptr())
+    A.ehm_resnet_stem_backward(img, stem_wt, stem_b, gpool, gw, gb, z, gz, N, H, W, ws, nb, _lib.stream_ptr())
     out = (gw.view(64, 3, 7, 7) if want_w else None), gb
     return out + (z, gz) if debug else out
 
 
-def _dgrad_weights(fn):
-    """The packed data-gradient operands of one folded() closure (rebuilt with it when a weight changes), built on first use."""
+def _walk(U, acts, gout, need, res, step):
+    """The backward of both routes, from the top block down to the stem.  U: units(m); acts: (X2 buffer, (N, H, W)) of the stem's pooled output and of
+    every conv's output; gout [N,2048]; need: per unit a tuple of flags or None; res: per unit what the step fills (returned).  No data gradient runs
+    below the lowest unit that wants something.  Per conv the route's `step` supplies
+        gate(g, y, shape, Cn, per_image) -> (gated, s)      the cotangent g behind the ReLU of the saved output y: a tuple, gated[0] the dense float32 tensor
+        head(i, gated, cum, x, x_shape, twin=None) -> state unit i's results into res[i] from its dense conv-output cotangent (which carries cum); x: the conv's
+                                                            saved input; twin: the unit that got the same gate before (a projection block's conv3)
+        operand(i, gated, state, out_hw, g) -> (T, s)       that cotangent as the data gradient's input, dense or (out_hw) zero-dilated to the conv's input size
+        weight(i)                                           unit i's packed flipped weight for dgrad
+        stem(g, cum, per_image)                             the stem's results into res[0]
+    s: the power of two (device scalar) the call multiplied in, or None.  `cum` collects them along the chain, `below` those a block's shortcut has yet to
+    be brought to.  The `del`s bound the peak: a cotangent goes as soon as the next one exists."""
+    def wants(i):
+        return need[i] is not None and any(need[i])
+
+    wanted = [i for i in range(len(U)) if wants(i)]
+    if not wanted:
+        return res
+    lowest = wanted[0]
+    below = []
+
+    def carried(c, s):
+        if s is None:
+            return c
+        below.append(s)
+        return c * s
+
+    g, per_image = _lib.f32(gout, gout.device), True
+    cum = torch.ones((), device=gout.device)
+    for b in range((len(U) - 1) // 4 - 1, -1, -1):
+        i1, i2, i3, id_ = 1 + 4 * b, 2 + 4 * b, 3 + 4 * b, 4 + 4 * b
+        if lowest > id_:
+            break
+        (xin, sh_in), (a1, sh1), (a2, sh2), (y, sh3) = acts[3 * b:3 * b + 4]
+        c1, c2, c3 = U[i1][0], U[i2][0], U[i3][0]
+        Cin, Wd, Cout, stride2 = c1.in_channels, c1.out_channels, c3.out_channels, c2.stride[0]
+        dilated = sh_in[1:] if stride2 == 2 else None              # (conv2 and the projection carry the block's stride; conv1 keeps the size: sh1 is sh_in)
+        project = U[id_] is not None
+        gt3, s = step.gate(g, y, sh3, Cout, per_image)
+        c = carried(cum, s)
+        del below[:]                                                                 # the shortcut leaves here: it carries c
+        st3 = std = None
+        if wants(i3) or lowest < i3:
+            st3 = step.head(i3, gt3, c, a2, sh2)
+        if project and (wants(id_) or lowest < i1):
+            std = step.head(id_, gt3, c, xin, sh_in, twin=i3)
+        if lowest >= i3:
+            break
+        T, s = step.operand(i3, gt3, st3, None, g)
+        del st3
+        c = carried(c, s)
+        ga2 = dgrad(T, step.weight(i3), Cout, Wd, 1, 0)
+        del T
+        gt2, s = step.gate(ga2, a2, sh2, Wd, False)
+        c = carried(c, s)
+        st2 = step.head(i2, gt2, c, a1, sh1)
+        if lowest >= i2:
+            break
+        T, s = step.operand(i2, gt2, st2, dilated, ga2)
+        del gt2, st2, ga2
+        c = carried(c, s)
+        ga1 = dgrad(T, step.weight(i2), Wd, Wd, 3, 1)
+        del T
+        gt1, s = step.gate(ga1, a1, sh1, Wd, False)
+        del ga1
+        c = carried(c, s)
+        st1 = step.head(i1, gt1, c, xin, sh_in)
+        if lowest >= i1:
+            break
+        T, s = step.operand(i1, gt1, st1, None, None)
+        del gt1, st1
+        c = carried(c, s)
+        # the shortcut's gradient, brought to the power of two conv1's data gradient carries, rides into it as its `residual`
+        if project:
+            short, sd = step.operand(id_, gt3, std, dilated, g)
+            del gt3, std
+            short = dgrad(short, step.weight(id_), Cout, Cin, 1, 0)
+        else:
+            short, sd = gt3[0], None
+            del gt3
+        short.mul_(reduce(mul, below) if sd is None else reduce(mul, below) / sd)
+        g = dgrad(T, step.weight(i1), Wd, Cin, 1, 0, res=short)
+        del T, short
+        cum, per_image = c, False
+    else:
+        if wants(0):
+            step.stem(g, cum, per_image)
+    return res
+
+
+def _eval_step(U, fn, img, acts, need, res):
+    """The eval-mode unit step of _walk: the gate scaled into the conv engine's range (dense for the weight gradient, gated again zero-dilated for a
+    stride-2 data gradient), (w'bar, b'bar) of the FOLDED weight into res[i], the data gradient on the folded weight's pack - kept on the folded()
+    closure `fn` (fn.dgrad), so rebuilt with it when a weight changes."""
+    ops = [fn.stem] + [p for blk in fn.blocks for p in blk]
     if getattr(fn, "dgrad", None) is None:
         fn.dgrad = {}
-    return fn.dgrad
+
+    def scaled(t, cum):
+        return None if t is None else t * (1.0 / cum)
+
+    def gate_(g, y, shape, Cn, per_image):
+        s = pow2_scale(g)
+        return (gate(g, y, shape, Cn, s, per_image=per_image), s, y, shape, Cn, per_image), s
+
+    def head(i, gated, cum, x, x_shape, twin=None):
+        n = need[i]
+        if n is None or not any(n):
+            return None
+        conv = U[i][0]
+        shared = res[twin][1] if twin is not None and n[1] else None                  # (the same column sum goes to both folded biases: once)
+        gw = gb = None
+        if n[0] or (n[1] and shared is None):
+            gw, gb = wgrad(gated[0], x, x_shape, conv.in_channels, conv.out_channels, conv.kernel_size[0], conv.stride[0], conv.padding[0],
+                           n[0], n[1] and shared is None)
+        res[i] = (scaled(gw, cum), scaled(gb, cum) if shared is None else shared)
+        return None
+
+    def operand(i, gated, state, out_hw, g):
+        G, s, y, shape, Cn, per_image = gated
+        return (G if out_hw is None else gate(g, y, shape, Cn, s, out_hw=out_hw, per_image=per_image)), None
+
+    def weight(i):
+        if i not in fn.dgrad:
+            fn.dgrad[i] = dgrad_weight(ops[i][0])
+        return fn.dgrad[i]
+
+    def stem(g, cum, per_image):
+        x0, sh0 = acts[0]
+        s0 = pow2_scale(g)
+        G0 = gate(g, x0, sh0, 64, s0, per_image=per_image)
+        gw0, gb0 = stem_backward(img, fn.stem_wt, fn.stem_b, G0, *need[0])
+        res[0] = (scaled(gw0, cum * s0), scaled(gb0, cum * s0))
+
+    return SimpleNamespace(gate=gate_, head=head, operand=operand, weight=weight, stem=stem)
 
 
 def trunk_backward(m, fn, img, acts, gout, need):
     """VJP of the folded trunk.  fn: the folded() closure the forward ran; img [N,3,H,W] float32; acts: what its `saved` list received; gout [N,2048];
     need: per unit of units(m) a pair (w' wanted, b' wanted) or None.  Returns per unit (w'bar [Co,Ci,KH,KW] float32 or None, b'bar or None): what is
     not asked for is neither computed nor written, and no data gradient runs below the lowest unit that wants something."""
-    dev = gout.device
     U = units(m)
     res = [(None, None)] * len(U)
-    wanted = [i for i, n in enumerate(need) if n is not None and (n[0] or n[1])]
-    if not wanted:
-        return res
-    lowest = wanted[0]
-    packs = _dgrad_weights(fn)
-
-    def packed(i, wf):
-        if i not in packs:
-            packs[i] = dgrad_weight(wf)
-        return packs[i]
-
-    def scaled(t, cum):
-        return None if t is None else t * (1.0 / cum)
-
-    g, per_image = _lib.f32(gout, dev), True
-    cum = torch.ones((), device=dev)
-    nblocks = len(fn.blocks)
-    for b in range(nblocks - 1, -1, -1):
-        i1, i2, i3, id_ = 1 + 4 * b, 2 + 4 * b, 3 + 4 * b, 4 + 4 * b
-        if lowest > id_:
-            break
-        c1, c2, c3, ds = fn.blocks[b]
-        (xin, sh_in), (a1, sh1), (a2, sh2), (y, sh3) = acts[3 * b], acts[3 * b + 1], acts[3 * b + 2], acts[3 * b + 3]
-        Cin, Wd, Cout = c1[0].shape[1], c1[0].shape[0], c3[0].shape[0]
-        s3 = pow2_scale(g)
-        G3 = gate(g, y, sh3, Cout, s3, per_image=per_image)
-        cum3 = cum * s3
-        n3, nd = need[i3], (need[id_] if ds is not None else None)
-        gb3 = None
-        if n3 is not None and (n3[0] or n3[1]):
-            gw3, gb3 = wgrad(G3, a2, sh2, Wd, Cout, 1, 1, 0, n3[0], n3[1])
-            res[i3] = (scaled(gw3, cum3), scaled(gb3, cum3))
-        if nd is not None and (nd[0] or nd[1]):
-            gwd = gbd = None
-            if nd[0] or (nd[1] and gb3 is None):                                         # (the same column sum goes to both folded biases: once)
-                gwd, gbd = wgrad(G3, xin, sh_in, Cin, Cout, 1, ds[2][0], 0, nd[0], nd[1] and gb3 is None)
-            gbd = res[i3][1] if (nd[1] and gb3 is not None) else scaled(gbd, cum3)
-            res[id_] = (scaled(gwd, cum3), gbd)
-        if lowest >= i3:
-            break
-        ga2 = dgrad(G3, packed(i3, c3[0]), Cout, Wd, 1, 0)
-        s2 = pow2_scale(ga2)
-        cum2 = cum3 * s2
-        G2 = gate(ga2, a2, sh2, Wd, s2)
-        n2 = need[i2]
-        stride2 = c2[2][0]
-        if n2 is not None and (n2[0] or n2[1]):
-            gw2, gb2 = wgrad(G2, a1, sh1, Wd, Wd, 3, stride2, 1, n2[0], n2[1])
-            res[i2] = (scaled(gw2, cum2), scaled(gb2, cum2))
-        if lowest >= i2:
-            break
-        if stride2 == 2:
-            G2 = gate(ga2, a2, sh2, Wd, s2, out_hw=sh1[1:])
-        del ga2
-        ga1 = dgrad(G2, packed(i2, c2[0]), Wd, Wd, 3, 1)
-        del G2
-        s1 = pow2_scale(ga1)
-        cum1 = cum2 * s1
-        G1 = gate(ga1, a1, sh1, Wd, s1)
-        del ga1
-        n1 = need[i1]
-        if n1 is not None and (n1[0] or n1[1]):
-            gw1, gb1 = wgrad(G1, xin, sh_in, Cin, Wd, 1, 1, 0, n1[0], n1[1])
-            res[i1] = (scaled(gw1, cum1), scaled(gb1, cum1))
-        if lowest >= i1:
-            break
-        # the shortcut's gradient, brought to conv1's power of two, rides into conv1's data gradient as its `residual`
-        if ds is None:
-            short = G3
-        else:
-            if ds[2][0] == 2:
-                G3 = gate(g, y, sh3, Cout, s3, out_hw=sh_in[1:], per_image=per_image)
-            short = dgrad(G3, packed(id_, ds[0]), Cout, Cin, 1, 0)
-        del G3
-        short.mul_(s2 * s1)
-        g = dgrad(G1, packed(i1, c1[0]), Wd, Cin, 1, 0, res=short)
-        del G1, short
-        cum, per_image = cum1, False
-    else:
-        n0 = need[0]
-        if n0 is not None and (n0[0] or n0[1]):
-            x0, sh0 = acts[0]
-            s0 = pow2_scale(g)
-            G0 = gate(g, x0, sh0, 64, s0, per_image=per_image)
-            gw0, gb0 = stem_backward(img, fn.stem_wt, fn.stem_b, G0, n0[0], n0[1])
-            res[0] = (scaled(gw0, cum * s0), scaled(gb0, cum * s0))
-    return res
+    return _walk(U, acts, gout, need, res, _eval_step(U, fn, img, acts, need, res))
 
 
 # ------------------------------------------------------------------------------------------------------------------ train-mode BatchNorm2d (csrc/bn2d_train.hip)
 # With ResNet50Features.train_batchnorm under .train() every BatchNorm2d normalises with the statistics of the batch.  Once (mu, var) are known that IS the
-# eval-mode fold with running_mean := mu, running_var := var, so the forward (encoders.py run_x2_train) is: raw conv z -> ehm_bn2d_train_stats -> the folded
+# eval-mode fold with running_mean := mu, running_var := var, so the forward (folded(train=True)'s unit provider) is: raw conv z -> ehm_bn2d_train_stats -> the folded
 # launch.  The backward differs per unit: with G = g (.) [y > 0], R = N H W rows, xhat = (z - mu) invstd:
 #     betabar = sum_p G,  gammabar = sum_p G xhat                   ehm_bn2d_train_bwd_sums  (float64 partial sums, fixed order)
 #     zbar = s gamma invstd (G - betabar / R - xhat gammabar / R)   ehm_bn2d_train_bwd_zbar  (dense for the weight gradient; s: pow2_scale of the dense result,
@@ -235,7 +288,7 @@ _train_debug_hook = None
 
 
 class TrainRecord:
-    """What run_x2_train leaves for the backward: acts (X2 buffer, (N, H, W)) of the stem's pooled output and of every conv's output; bn: per unit of
+    """What the train-mode forward leaves for the backward: acts (X2 buffer, (N, H, W)) of the stem's pooled output and of every conv's output; bn: per unit of
     units() (z X2 or None, (N, Ho, Wo), mean, var, invstd) float32, None where an identity block has no downsample; the stem's folded operands."""
 
     def __init__(self, keep_z=True):
@@ -244,9 +297,7 @@ class TrainRecord:
 
 
 def _bn_ws(pixels, Cn, dev):
-    nb = C.c_int64(0)
-    _lib.api().ehm_bn2d_train_workspace_bytes(pixels, Cn, C.byref(nb))
-    return torch.empty(nb.value // 8, dtype=torch.float64, device=dev), nb.value
+    return _workspace(_lib.api().ehm_bn2d_train_workspace_bytes, pixels, Cn, dtype=torch.float64, device=dev)
 
 
 def bn_stats(z, pixels, Cn, bn=None, x2=True, eps=1e-5, momentum=0.1):
@@ -302,133 +353,107 @@ def train_forward(m, img, keep_z=True):
     return m.folded(train=True)(img, rec), rec
 
 
-def trunk_backward_train(m, img, rec, gout, need):
-    """VJP of the train-mode trunk.  rec: the forward's TrainRecord; need: per unit of units(m) (weight wanted, gamma wanted, beta wanted) or None.
-    Returns per unit (wbar [Co,Ci,KH,KW], gammabar, betabar) float32, None where not asked for; no data gradient runs below the lowest unit that wants
-    something.  The running statistics are not read."""
-    dev = gout.device
-    U = units(m)
-    res = [(None, None, None)] * len(U)
-    wanted = [i for i, n in enumerate(need) if n is not None and any(n)]
-    if not wanted:
-        return res
-    lowest = wanted[0]
-    acts, hook = rec.acts, _train_debug_hook
+# ehm_resnet_stem_wgrad's scratch in floats (include/egohmr_hip.h: "workspace: 256 * 148 * 64 floats"; it has no size query)
+STEM_WGRAD_WS_FLOATS = 256 * 148 * 64
 
-    def raw_pack(i):
-        return dgrad_weight(U[i][0].weight.detach().float())
 
-    def unit_bwd(i, G, cum, x, x_shape, stride, pad, g_in=None):
-        """-> (the dense zbar of unit i, carrying cum like G; betabar; gammabar); fills res[i]"""
+def _train_step(U, img, rec, need, res):
+    """The train-mode unit step of _walk: the gate unscaled (it feeds no conv engine), per unit the BatchNorm backward (sums, zbar) and the RAW weight's
+    gradient - (wbar, gammabar, betabar) into res[i] -, zbar brought into the engine's range (dense in place, or made again zero-dilated) for the data
+    gradient on the raw weight's pack, built per call."""
+    hook = _train_debug_hook
+
+    def gate_(g, y, shape, Cn, per_image):
+        return (gate(g, y, shape, Cn, None, per_image=per_image), g if hook is not None else None), None
+
+    def head(i, gated, cum, x, x_shape, twin=None):
+        """-> (the dense zbar of unit i, carrying cum like the gate; betabar; gammabar)"""
         conv, bn = U[i]
+        G, g_in = gated
         z, zs, mean, _, invstd = rec.bn[i]
-        Co, Ci, K = conv.out_channels, conv.in_channels, conv.kernel_size[0]
+        Co = conv.out_channels
         gbeta, ggamma = bn_sums(G, z, zs[0] * zs[1] * zs[2], Co, mean, invstd)
         Z = bn_zbar(G, z, zs, Co, mean, invstd, _lib.f32(bn.weight), gbeta, ggamma)
         n = need[i] or (False, False, False)
-        gw = wgrad(Z, x, x_shape, Ci, Co, K, stride, pad, True, False)[0] if n[0] else None
+        gw = wgrad(Z, x, x_shape, conv.in_channels, Co, conv.kernel_size[0], conv.stride[0], conv.padding[0], True, False)[0] if n[0] else None
         inv = 1.0 / cum
         res[i] = (gw * inv if n[0] else None, ggamma * inv if n[1] else None, gbeta * inv if n[2] else None)
         if hook is not None:
-            hook.append((i, G if g_in is None else g_in, cum, Z.clone()))
+            hook.append((i, g_in, cum, Z.clone()))
         return Z, gbeta, ggamma
 
-    def scaled_for_dgrad(i, G, zb, out_hw):
-        """zbar brought into the conv engine's range by a power of two (pow2_scale of the dense zbar), dense in place or zero-dilated: (tensor, s)"""
-        Z, gbeta, ggamma = zb
+    def operand(i, gated, state, out_hw, g):
+        """zbar times s = pow2_scale of the dense zbar"""
+        Z, gbeta, ggamma = state
         s = pow2_scale(Z)
         if out_hw is None:
             return Z.mul_(s), s
         z, zs, mean, _, invstd = rec.bn[i]
-        return bn_zbar(G, z, zs, Z.shape[3], mean, invstd, _lib.f32(U[i][1].weight), gbeta, ggamma, scale=s, out_hw=out_hw), s
+        return bn_zbar(gated[0], z, zs, Z.shape[3], mean, invstd, _lib.f32(U[i][1].weight), gbeta, ggamma, scale=s, out_hw=out_hw), s
 
-    def wants(i):
-        return need[i] is not None and any(need[i])
+    def weight(i):
+        return dgrad_weight(U[i][0].weight.detach().float())
 
-    g, per_image = _lib.f32(gout, dev), True
-    cum = torch.ones((), device=dev)
-    nblocks = (len(U) - 1) // 4
-    for b in range(nblocks - 1, -1, -1):
-        i1, i2, i3, id_ = 1 + 4 * b, 2 + 4 * b, 3 + 4 * b, 4 + 4 * b
-        if lowest > id_:
-            break
-        (xin, sh_in), (a1, sh1), (a2, sh2), (y, sh3) = acts[3 * b], acts[3 * b + 1], acts[3 * b + 2], acts[3 * b + 3]
-        c1, c2, c3 = U[i1][0], U[i2][0], U[i3][0]
-        Cin, Wd, Cout = c1.in_channels, c1.out_channels, c3.out_channels
-        stride2 = c2.stride[0]
-        G3 = gate(g, y, sh3, Cout, None, per_image=per_image)
-        Z3 = Zd = None
-        if wants(i3) or lowest < i3:
-            Z3 = unit_bwd(i3, G3, cum, a2, sh2, 1, 0, g_in=g)
-        if U[id_] is not None and (wants(id_) or lowest < i1):
-            Zd = unit_bwd(id_, G3, cum, xin, sh_in, stride2, 0, g_in=g)
-        if lowest >= i3:
-            break
-        Z3, s3 = scaled_for_dgrad(i3, G3, Z3, None)
-        ga2 = dgrad(Z3, raw_pack(i3), Cout, Wd, 1, 0)
-        del Z3
-        cum2 = cum * s3
-        G2 = gate(ga2, a2, sh2, Wd, None)
-        Z2 = unit_bwd(i2, G2, cum2, a1, sh1, stride2, 1, g_in=ga2)
-        if lowest >= i2:
-            break
-        Z2, s2 = scaled_for_dgrad(i2, G2, Z2, sh1[1:] if stride2 == 2 else None)
-        del G2, ga2
-        ga1 = dgrad(Z2, raw_pack(i2), Wd, Wd, 3, 1)
-        del Z2
-        cum1 = cum2 * s2
-        G1 = gate(ga1, a1, sh1, Wd, None)
-        Z1 = unit_bwd(i1, G1, cum1, xin, sh_in, 1, 0, g_in=ga1)
-        if lowest >= i1:
-            break
-        Z1, s1 = scaled_for_dgrad(i1, G1, Z1, None)
-        del G1, ga1
-        cum_next = cum1 * s1
-        # the shortcut's gradient, brought to the power of two conv1's data gradient carries, rides in as its `residual`
-        if U[id_] is None:
-            short = G3.mul_(s3 * s2 * s1)
-        else:
-            Zd, sd = scaled_for_dgrad(id_, G3, Zd, sh_in[1:] if stride2 == 2 else None)
-            short = dgrad(Zd, raw_pack(id_), Cout, Cin, 1, 0)
-            short.mul_(s3 * s2 * s1 / sd)
-            del Zd
-        del G3
-        g = dgrad(Z1, raw_pack(i1), Wd, Cin, 1, 0, res=short)
-        del Z1, short
-        cum, per_image = cum_next, False
-    else:
-        n0 = need[0]
-        if n0 is not None and any(n0):
-            A = _lib.api()
-            x0, sh0 = acts[0]
-            N, _, H, W = img.shape
-            G0 = gate(g, x0, sh0, 64, None, per_image=per_image)                    # the pooled cotangent, gated by [pooled > 0]
-            zf = stem_preact(img, rec.stem_wt, rec.stem_b)                          # the folded pre-pool activation: its arg-max routes
-            gz = torch.empty_like(zf)
-            A.ehm_resnet_stem_route(zf, G0, gz, N, H, W, _lib.stream_ptr())
-            del zf, G0
-            conv, bn = U[0]
-            _, zs, mean, _, invstd = rec.bn[0]
-            pixels = zs[0] * zs[1] * zs[2]
-            wt = conv.weight.detach().float().reshape(64, 147).t().contiguous()
-            z = stem_preact(img, wt, torch.zeros(64, device=dev))                   # the raw one: the BatchNorm's input
-            gbeta, ggamma = bn_sums(gz, z, pixels, 64, mean, invstd, x2=False)
-            inv = 1.0 / cum
-            gw = None
-            if n0[0] or hook is not None:
-                Z0 = bn_zbar(gz, z, zs, 64, mean, invstd, _lib.f32(bn.weight), gbeta, ggamma, x2=False)
-                ws = torch.empty(256 * 148 * 64, device=dev)
-                gw = torch.empty(64, 147, device=dev)
-                A.ehm_resnet_stem_wgrad(img, Z0, gw, None, N, H, W, ws, ws.numel() * 4, _lib.stream_ptr())
-                gw = gw.view(64, 3, 7, 7) * inv
-                if hook is not None:
-                    hook.append((0, g, cum, Z0, gz))
-            res[0] = (gw if n0[0] else None, ggamma * inv if n0[1] else None, gbeta * inv if n0[2] else None)
-    return res
+    def stem(g, cum, per_image):
+        A, dev, n0 = _lib.api(), g.device, need[0]
+        x0, sh0 = rec.acts[0]
+        N, _, H, W = img.shape
+        G0 = gate(g, x0, sh0, 64, None, per_image=per_image)                        # the pooled cotangent, gated by [pooled > 0]
+        zf = stem_preact(img, rec.stem_wt, rec.stem_b)                              # the folded pre-pool activation: its arg-max routes
+        gz = torch.empty_like(zf)
+        A.ehm_resnet_stem_route(zf, G0, gz, N, H, W, _lib.stream_ptr())
+        del zf, G0
+        conv, bn = U[0]
+        _, zs, mean, _, invstd = rec.bn[0]
+        wt = conv.weight.detach().float().reshape(64, 147).t().contiguous()
+        z = stem_preact(img, wt, torch.zeros(64, device=dev))                       # the raw one: the BatchNorm's input
+        gbeta, ggamma = bn_sums(gz, z, zs[0] * zs[1] * zs[2], 64, mean, invstd, x2=False)
+        inv = 1.0 / cum
+        gw = None
+        if n0[0] or hook is not None:
+            Z0 = bn_zbar(gz, z, zs, 64, mean, invstd, _lib.f32(bn.weight), gbeta, ggamma, x2=False)
+            ws = torch.empty(STEM_WGRAD_WS_FLOATS, device=dev)
+            gw = torch.empty(64, 147, device=dev)
+            A.ehm_resnet_stem_wgrad(img, Z0, gw, None, N, H, W, ws, ws.numel() * 4, _lib.stream_ptr())
+            gw = gw.view(64, 3, 7, 7) * inv
+            if hook is not None:
+                hook.append((0, g, cum, Z0, gz))
+        res[0] = (gw if n0[0] else None, ggamma * inv if n0[1] else None, gbeta * inv if n0[2] else None)
+
+    return SimpleNamespace(gate=gate_, head=head, operand=operand, weight=weight, stem=stem)
+
+
+def trunk_backward_train(m, img, rec, gout, need):
+    """VJP of the train-mode trunk.  rec: the forward's TrainRecord; need: per unit of units(m) (weight wanted, gamma wanted, beta wanted) or None.
+    Returns per unit (wbar [Co,Ci,KH,KW], gammabar, betabar) float32, None where not asked for; no data gradient runs below the lowest unit that wants
+    something.  The running statistics are not read."""
+    U = units(m)
+    res = [(None, None, None)] * len(U)
+    return _walk(U, rec.acts, gout, need, res, _train_step(U, img, rec, need, res))
 
 
 def _param_key(m):
     return tuple((p.data_ptr(), p._version) for p in m.parameters())
+
+
+def _unit_flags(m, needs_input_grad):
+    """(per parameter id: does it want a gradient; per unit of units(m): that of (conv.weight, bn.weight, bn.bias), or None) from a backward's
+    ctx.needs_input_grad, whose entries behind (module, x) follow m.parameters()."""
+    flags = dict(zip((id(p) for p in m.parameters()), needs_input_grad[2:]))
+    return flags, [None if u is None else (flags[id(u[0].weight)], flags[id(u[1].weight)], flags[id(u[1].bias)]) for u in units(m)]
+
+
+def _backward_result(m, flags, grads):
+    """What a backward returns - None for (module, x), then one gradient or None per m.parameters() entry - from per unit of units(m) the gradients of
+    (conv.weight, bn.weight, bn.bias)."""
+    by_id = {}
+    for u, r in zip(units(m), grads):
+        if u is None:
+            continue
+        for p, gr in zip((u[0].weight, u[1].weight, u[1].bias), r):
+            if flags[id(p)] and gr is not None:
+                by_id[id(p)] = gr.to(p.dtype)
+    return (None, None, *[by_id.get(id(p)) for p in m.parameters()])
 
 
 class TrunkTrainFunction(torch.autograd.Function):
@@ -450,19 +475,10 @@ class TrunkTrainFunction(torch.autograd.Function):
         if _param_key(m) != ctx.key:
             raise _lib.EgoHMRHipError("a parameter of ResNet50Features changed (in place, or was replaced) between the forward and the backward "
                                       "of its autograd route; run the backward before the optimizer step")
-        flags = dict(zip((id(p) for p in m.parameters()), ctx.needs_input_grad[2:]))
-        U = units(m)
-        need = [None if u is None else (flags[id(u[0].weight)], flags[id(u[1].weight)], flags[id(u[1].bias)]) for u in U]
+        flags, need = _unit_flags(m, ctx.needs_input_grad)
         with _lib.on_device(gout.device):
             res = trunk_backward_train(m, ctx.img, ctx.rec, gout, need)
-        by_id = {}
-        for u, r in zip(U, res):
-            if u is None:
-                continue
-            for p, gr in zip((u[0].weight, u[1].weight, u[1].bias), r):
-                if flags[id(p)] and gr is not None:
-                    by_id[id(p)] = gr.to(p.dtype)
-        return (None, None, *[by_id.get(id(p)) for p in m.parameters()])
+        return _backward_result(m, flags, res)
 
 
 class TrunkFunction(torch.autograd.Function):
@@ -486,25 +502,9 @@ class TrunkFunction(torch.autograd.Function):
             # the folded weights and saved activations are the forward's, `unfold` reads the parameters as they are now: a mix of the two is no gradient
             raise _lib.EgoHMRHipError("a parameter or buffer of ResNet50Features changed (in place, or was replaced) between the forward and the backward "
                                       "of its autograd route; run the backward before the optimizer step")
-        flags = dict(zip((id(p) for p in m.parameters()), ctx.needs_input_grad[2:]))
-        U = units(m)
-        need = []
-        for u in U:
-            if u is None:
-                need.append(None)
-                continue
-            conv, bn = u
-            fw, fg, fb = flags[id(conv.weight)], flags[id(bn.weight)], flags[id(bn.bias)]
-            need.append((fw or fg, fg or fb))
+        flags, unit_flags = _unit_flags(m, ctx.needs_input_grad)
+        need = [None if f is None else (f[0] or f[1], f[1] or f[2]) for f in unit_flags]     # the folded (w', b') that unfold needs
         with _lib.on_device(gout.device):
             res = trunk_backward(m, ctx.fn, ctx.img, ctx.acts, gout, need)
-            by_id = {}
-            for u, (gw, gb) in zip(U, res):
-                if u is None:
-                    continue
-                conv, bn = u
-                g_w, g_gamma, g_beta = unfold(conv, bn, gw, gb)
-                for p, gr in ((conv.weight, g_w), (bn.weight, g_gamma), (bn.bias, g_beta)):
-                    if flags[id(p)] and gr is not None:
-                        by_id[id(p)] = gr.to(p.dtype)
-        return (None, None, *[by_id.get(id(p)) for p in m.parameters()])
+            # (a generator: one unit's float64 gradients at a time)
+            return _backward_result(m, flags, (None if u is None else unfold(*u, gw, gb) for u, (gw, gb) in zip(units(m), res)))
