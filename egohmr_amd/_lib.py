@@ -277,6 +277,10 @@ PROTOTYPES = {
     "ehm_gcn_train_bwd_epilogue": (_I, [_P, _I, _P, _P, _P, _I, _I, _P]),
     "ehm_gcn_train_bwd_params_workspace_bytes": (_I, [_P, _I, _I, C.POINTER(C.c_int64)]),
     "ehm_gcn_train_bwd_params": (_I, [_P, _I, _P, _P, _P, _I, _I, _P, _P, _P, _L, _P]),
+    "ehm_gcn_train_stats_local": (_I, [_P, _I, _P, _I, _I, _P, _P, _L, _P]),
+    "ehm_gcn_train_stats_merge": (_I, [_P, _I, _P, _P, _I, C.c_double, C.c_double, _P, _P, _P, _P, _P]),
+    "ehm_gcn_train_bwd_local": (_I, [_P, _I, _P, _P, _P, _P, _P, _I, _P, _P, _L, _P]),
+    "ehm_gcn_train_bwd_merge": (_I, [_P, _I, _P, _P, _I, _I, _P, _P, _P, _P, _P, _I, _P, _P, _P, _P, _L, _P]),
     "ehm_linear_split": (_I, [C.POINTER(LinearDesc), _P]),
     "ehm_split_pack": (_I, [_P, _P, _L, _I, _I, _F, _P]),
     "ehm_skinny_gemm_f32": (_I, [_P, _P, _P, _P, _I, _I, _I, _I, _P]),
@@ -310,6 +314,11 @@ PROTOTYPES = {
     "ehm_bn2d_train_stats": (_I, [_P, _I, _L, _L, _I, C.c_double, C.c_double, _P, _P, _P, _P, _P, _P, _P, _L, _P]),
     "ehm_bn2d_train_bwd_sums": (_I, [_P, _P, _I, _L, _L, _I, _P, _P, _P, _P, _P, _L, _P]),
     "ehm_bn2d_train_bwd_zbar": (_I, [_P, _P, _I, _L, _P, _P, _P, _P, _P, _P, _P, _I, _I, _I, _I, _I, _I, _P]),
+    "ehm_bn2d_train_stats_local": (_I, [_P, _I, _L, _L, _I, _P, _P, _L, _P]),
+    "ehm_bn2d_train_stats_merge": (_I, [_P, _P, _I, _I, C.c_double, C.c_double, _P, _P, _P, _P, _P, _P, _P]),
+    "ehm_bn2d_train_bwd_local": (_I, [_P, _P, _I, _L, _L, _I, _P, _P, _P, _P, _L, _P]),
+    "ehm_bn2d_train_bwd_merge": (_I, [_P, _I, _I, _I, _P, _P, _P, _P, _P]),
+    "ehm_bn2d_train_bwd_zbar_rows": (_I, [_P, _P, _I, _L, _P, _P, _P, _P, _P, _P, _P, _I, _I, _I, _I, _I, _I, _L, _P]),
     "ehm_ddpm_step": (_I, [_P, _P, _P, _P, _P, _F, _F, _F, _F, _F, _L, _P]),
     "ehm_ddim_step": (_I, [_P, _P, _P, _P, _F, _F, _F, _F, _F, _F, _L, _P]),
     "ehm_collision_proxy": (_I, [_P, _P, _P, _P, _I, _I, _I, _F, _P]),

@@ -8,6 +8,7 @@
 //   backward:  with G = g (.) [y > 0] (ehm_conv_bwd_gate) and xhat = (z - mu) invstd:
 //              betabar = sum_p G,  gammabar = sum_p G xhat                                                  bn2d_sum_kernel + bn2d_bwd_finish_kernel
 //              zbar = *scale gamma invstd (G - betabar / R - xhat gammabar / R)                             bn2d_zbar_kernel (dense, or zero-dilated)
+// Data parallel (the *_local / *_merge entries at the end): each rank stops at [2][C] float64, the caller all-gathers, every rank merges in rank order.
 // No atomics: a block owns a run of pixels that is a function of the shape alone, a lane adds its rows in row order, the row lanes and then the runs
 // are added in index order - two calls on the same inputs give the same bits.
 #include "common.h"
@@ -137,6 +138,52 @@ __global__ __launch_bounds__(256) void bn2d_bwd_finish_kernel(const double* __re
   ggamma[t] = (float)runs_sum(part + C + t, (size_t)2 * C, runs);
 }
 
+// a rank's own statistics: local[0][c] = its mean, local[1][c] = its sum of squares centred on that mean
+__global__ __launch_bounds__(256) void bn2d_local_stats_kernel(const double* __restrict__ part, const double* __restrict__ mean_d, double* __restrict__ local,
+                                                               int C, int runs) {
+  const int t = blockIdx.x * 256 + threadIdx.x;
+  if (t >= C) return;
+  local[t] = mean_d[t];
+  local[C + t] = runs_sum(part + t, (size_t)C, runs);
+}
+
+// every rank's (mean, M2) [world][2][C] -> what bn2d_stats_finish_kernel writes, for the whole batch's R rows
+__global__ __launch_bounds__(256) void bn2d_merge_stats_kernel(const double* __restrict__ gathered, RankRows rr, int world, float* __restrict__ mean,
+                                                               float* __restrict__ var, float* __restrict__ invstd, float* __restrict__ running_mean,
+                                                               float* __restrict__ running_var, long long* __restrict__ tracked, int C, double eps,
+                                                               double momentum) {
+  const int t = blockIdx.x * 256 + threadIdx.x;
+  if (t == 0 && tracked) *tracked += 1;
+  if (t >= C) return;
+  double mu, M2;
+  merge_moments(gathered + t, (size_t)2 * C, (size_t)C, rr, world, &mu, &M2);
+  const double R = rr.total, v = M2 / R;
+  mean[t] = (float)mu;
+  var[t] = (float)v;
+  invstd[t] = (float)(1.0 / sqrt(v + eps));
+  if (running_mean) running_mean[t] = (float)((1.0 - momentum) * (double)running_mean[t] + momentum * mu);
+  if (running_var) running_var[t] = (float)((1.0 - momentum) * (double)running_var[t] + momentum * (v * R / (R - 1.0)));
+}
+
+__global__ __launch_bounds__(256) void bn2d_local_bwd_kernel(const double* __restrict__ part, double* __restrict__ local, int C, int runs) {
+  const int t = blockIdx.x * 256 + threadIdx.x;
+  if (t >= C) return;
+  local[t] = runs_sum(part + t, (size_t)2 * C, runs);
+  local[C + t] = runs_sum(part + C + t, (size_t)2 * C, runs);
+}
+
+// the ranks' sums added in rank order -> the whole batch's (gbeta, ggamma) for the zbar launch; the rank's own -> the parameter gradients
+__global__ __launch_bounds__(256) void bn2d_merge_bwd_kernel(const double* __restrict__ gathered, int world, int rank, float* __restrict__ gbeta,
+                                                             float* __restrict__ ggamma, float* __restrict__ gbeta_own, float* __restrict__ ggamma_own,
+                                                             int C) {
+  const int t = blockIdx.x * 256 + threadIdx.x;
+  if (t >= C) return;
+  gbeta[t] = (float)runs_sum(gathered + t, (size_t)2 * C, world);
+  ggamma[t] = (float)runs_sum(gathered + C + t, (size_t)2 * C, world);
+  if (gbeta_own) gbeta_own[t] = (float)gathered[(size_t)rank * 2 * C + t];
+  if (ggamma_own) ggamma_own[t] = (float)gathered[(size_t)rank * 2 * C + C + t];
+}
+
 struct ZbarArgs {
   const float* G; const void* z; const float *mean, *invstd, *gamma, *gbeta, *ggamma, *scale;
   float* out;
@@ -189,8 +236,9 @@ __global__ __launch_bounds__(256) void bn2d_zbar_kernel(ZbarArgs a) {
 struct BnPlan { int run, runs, cblocks; };
 
 // runs of whole 16-row groups, at most BN_MAX_RUNS of them: a function of the shape alone
-int bn_plan(int64_t pixels, int64_t z_rows, int C, BnPlan* pl) {
-  EHM_CHECK_ARG(pixels >= 2 && pixels < (1ll << 31) && z_rows >= pixels && C > 0 && C % 32 == 0 && pixels * C < (1ll << 40));
+// (a rank's share of a data-parallel batch may be ONE row - min_pixels = 1 -, and float32 rows need whole 8-channel lanes only - cmult = 8)
+int bn_plan(int64_t pixels, int64_t z_rows, int C, BnPlan* pl, int64_t min_pixels = 2, int cmult = 32) {
+  EHM_CHECK_ARG(pixels >= min_pixels && pixels < (1ll << 31) && z_rows >= pixels && C > 0 && C % cmult == 0 && pixels * C < (1ll << 40));
   pl->run = (int)round_up(ceil_div(pixels, BN_MAX_RUNS), BN_ROWL);
   pl->runs = (int)ceil_div(pixels, pl->run);
   pl->cblocks = (int)ceil_div(C, 128);
@@ -254,15 +302,11 @@ extern "C" int ehm_bn2d_train_bwd_sums(const float* G, const void* z, int z_is_x
   return 0;
 }
 
-extern "C" int ehm_bn2d_train_bwd_zbar(const float* G, const void* z, int z_is_x2, int64_t z_rows, const float* mean, const float* invstd, const float* gamma,
-                                       const float* gbeta, const float* ggamma, const float* scale, float* out, int N, int Ho, int Wo, int C, int H, int W,
-                                       void* stream) {
-  EHM_CHECK_ARG(G && z && mean && invstd && gamma && gbeta && ggamma && out && al16(G) && al16(z) && al16(out) && (z_is_x2 == 0 || z_is_x2 == 1));
-  EHM_CHECK_ARG(N > 0 && Ho > 0 && Wo > 0 && H > 0 && W > 0 && C > 0 && C % 32 == 0);
+// zbar's launch for R rows in the batch statistics: the N Ho Wo rows of G (ehm_bn2d_train_bwd_zbar) or all ranks' (ehm_bn2d_train_bwd_zbar_rows)
+static int launch_zbar(const float* G, const void* z, int z_is_x2, int64_t z_rows, const float* mean, const float* invstd, const float* gamma,
+                       const float* gbeta, const float* ggamma, const float* scale, float* out, int N, int Ho, int Wo, int C, int H, int W, long long R,
+                       void* stream) {
   const bool dense = H == Ho && W == Wo;
-  EHM_CHECK_ARG(dense || ((H - 1) / 2 + 1 == Ho && (W - 1) / 2 + 1 == Wo));
-  const long long R = (long long)N * Ho * Wo;
-  EHM_CHECK_ARG(R >= 2 && z_rows >= R && (long long)N * H * W * C < (1ll << 40) && (const void*)G != (const void*)out);
   ZbarArgs a;
   a.G = G; a.z = z; a.mean = mean; a.invstd = invstd; a.gamma = gamma; a.gbeta = gbeta; a.ggamma = ggamma; a.scale = scale; a.out = out;
   a.Ho = Ho; a.Wo = Wo; a.C = C; a.H = H; a.W = W; a.dil = dense ? 1 : 2;
@@ -274,4 +318,94 @@ extern "C" int ehm_bn2d_train_bwd_zbar(const float* G, const void* z, int z_is_x
   else hipLaunchKernelGGL(bn2d_zbar_kernel<false>, dim3((unsigned)blocks), dim3(256), 0, (hipStream_t)stream, a);
   EHM_LAUNCH_CHECK();
   return 0;
+}
+
+extern "C" int ehm_bn2d_train_bwd_zbar(const float* G, const void* z, int z_is_x2, int64_t z_rows, const float* mean, const float* invstd, const float* gamma,
+                                       const float* gbeta, const float* ggamma, const float* scale, float* out, int N, int Ho, int Wo, int C, int H, int W,
+                                       void* stream) {
+  EHM_CHECK_ARG(G && z && mean && invstd && gamma && gbeta && ggamma && out && al16(G) && al16(z) && al16(out) && (z_is_x2 == 0 || z_is_x2 == 1));
+  EHM_CHECK_ARG(N > 0 && Ho > 0 && Wo > 0 && H > 0 && W > 0 && C > 0 && C % 32 == 0);
+  const bool dense = H == Ho && W == Wo;
+  EHM_CHECK_ARG(dense || ((H - 1) / 2 + 1 == Ho && (W - 1) / 2 + 1 == Wo));
+  const long long R = (long long)N * Ho * Wo;
+  EHM_CHECK_ARG(R >= 2 && z_rows >= R && (long long)N * H * W * C < (1ll << 40) && (const void*)G != (const void*)out);
+  return launch_zbar(G, z, z_is_x2, z_rows, mean, invstd, gamma, gbeta, ggamma, scale, out, N, Ho, Wo, C, H, W, R, stream);
+}
+
+// ---- data parallel: a rank's rows -> [2][C] float64, every rank's [world][2][C] (all-gathered by the caller, ONE collective per BatchNorm each way) -> the
+// batch's.  Every rank merges the same buffer in the same order: all ranks hold the same bits.  rows [world] on the host: each rank's pixel count R_r.
+// With world == 1 a local + merge pair gives the bits of ehm_bn2d_train_stats / ehm_bn2d_train_bwd_sums, and zbar_rows with total_rows = N Ho Wo those of
+// ehm_bn2d_train_bwd_zbar.  A rank may hold ONE row; float32 rows need C % 8 == 0 only (an X2 buffer C % 32 == 0, its format's granule).
+extern "C" int ehm_bn2d_train_stats_local(const void* z, int z_is_x2, int64_t z_rows, int64_t pixels, int C, double* local, void* workspace,
+                                          int64_t workspace_bytes, void* stream) {
+  BnPlan pl;
+  EHM_CHECK_ARG(z_is_x2 == 0 || z_is_x2 == 1);
+  const int rc = bn_plan(pixels, z_rows, C, &pl, 1, z_is_x2 ? 32 : 8);
+  if (rc != 0) return rc;
+  EHM_CHECK_ARG(z && local && al16(z) && (uintptr_t)local % 8 == 0);
+  EHM_CHECK_ARG(workspace && al16(workspace) && workspace_bytes >= bn_ws_doubles(pl, C) * (int64_t)sizeof(double));
+  hipStream_t st = (hipStream_t)stream;
+  double* part = (double*)workspace;
+  double* mean_d = part + (size_t)pl.runs * 2 * C;
+  const unsigned cb = (unsigned)ceil_div(C, 256);
+  launch_sum<0>(z_is_x2 != 0, pl, st, z, nullptr, nullptr, nullptr, nullptr, part, pixels, C);
+  hipLaunchKernelGGL(bn2d_mean_finish_kernel, dim3(cb), dim3(256), 0, st, (const double*)part, mean_d, C, pl.runs, (double)pixels);
+  launch_sum<1>(z_is_x2 != 0, pl, st, z, nullptr, (const double*)mean_d, nullptr, nullptr, part, pixels, C);
+  hipLaunchKernelGGL(bn2d_local_stats_kernel, dim3(cb), dim3(256), 0, st, (const double*)part, (const double*)mean_d, local, C, pl.runs);
+  EHM_LAUNCH_CHECK();
+  return 0;
+}
+
+extern "C" int ehm_bn2d_train_stats_merge(const double* gathered, const int64_t* rows, int world, int C, double eps, double momentum, float* mean, float* var,
+                                          float* invstd, float* running_mean, float* running_var, int64_t* num_batches_tracked, void* stream) {
+  RankRows rr;
+  const int rc = rank_rows_of(rows, world, &rr);
+  if (rc != 0) return rc;
+  EHM_CHECK_ARG(gathered && (uintptr_t)gathered % 8 == 0 && mean && var && invstd && C > 0 && C % 8 == 0 && eps >= 0.0 && momentum >= 0.0 && momentum <= 1.0);
+  hipLaunchKernelGGL(bn2d_merge_stats_kernel, dim3((unsigned)ceil_div(C, 256)), dim3(256), 0, (hipStream_t)stream, gathered, rr, world, mean, var, invstd,
+                     running_mean, running_var, (long long*)num_batches_tracked, C, eps, momentum);
+  EHM_LAUNCH_CHECK();
+  return 0;
+}
+
+extern "C" int ehm_bn2d_train_bwd_local(const float* G, const void* z, int z_is_x2, int64_t z_rows, int64_t pixels, int C, const float* mean,
+                                        const float* invstd, double* local, void* workspace, int64_t workspace_bytes, void* stream) {
+  BnPlan pl;
+  EHM_CHECK_ARG(z_is_x2 == 0 || z_is_x2 == 1);
+  const int rc = bn_plan(pixels, z_rows, C, &pl, 1, z_is_x2 ? 32 : 8);
+  if (rc != 0) return rc;
+  EHM_CHECK_ARG(G && z && mean && invstd && local && al16(G) && al16(z) && (uintptr_t)local % 8 == 0);
+  EHM_CHECK_ARG(workspace && al16(workspace) && workspace_bytes >= bn_ws_doubles(pl, C) * (int64_t)sizeof(double));
+  hipStream_t st = (hipStream_t)stream;
+  double* part = (double*)workspace;
+  launch_sum<2>(z_is_x2 != 0, pl, st, z, G, nullptr, mean, invstd, part, pixels, C);
+  hipLaunchKernelGGL(bn2d_local_bwd_kernel, dim3((unsigned)ceil_div(C, 256)), dim3(256), 0, st, (const double*)part, local, C, pl.runs);
+  EHM_LAUNCH_CHECK();
+  return 0;
+}
+
+// gbeta / ggamma: the whole batch's sums, for ehm_bn2d_train_bwd_zbar_rows; gbeta_own / ggamma_own (either may be NULL): float32 of rank `rank`'s own
+// float64 sums - the parameter gradients, which the caller's gradient all-reduce completes (the batch's sums there would count `world` times)
+extern "C" int ehm_bn2d_train_bwd_merge(const double* gathered, int world, int rank, int C, float* gbeta, float* ggamma, float* gbeta_own,
+                                        float* ggamma_own, void* stream) {
+  EHM_CHECK_ARG(gathered && (uintptr_t)gathered % 8 == 0 && world >= 1 && world <= kMaxRanks && rank >= 0 && rank < world && C > 0 && C % 8 == 0);
+  EHM_CHECK_ARG(gbeta && ggamma);
+  hipLaunchKernelGGL(bn2d_merge_bwd_kernel, dim3((unsigned)ceil_div(C, 256)), dim3(256), 0, (hipStream_t)stream, gathered, world, rank, gbeta, ggamma,
+                     gbeta_own, ggamma_own, C);
+  EHM_LAUNCH_CHECK();
+  return 0;
+}
+
+// ehm_bn2d_train_bwd_zbar with the batch statistics' row count given: total_rows = all ranks' rows (>= this rank's N Ho Wo, which may be one)
+extern "C" int ehm_bn2d_train_bwd_zbar_rows(const float* G, const void* z, int z_is_x2, int64_t z_rows, const float* mean, const float* invstd,
+                                            const float* gamma, const float* gbeta, const float* ggamma, const float* scale, float* out, int N, int Ho,
+                                            int Wo, int C, int H, int W, int64_t total_rows, void* stream) {
+  EHM_CHECK_ARG(G && z && mean && invstd && gamma && gbeta && ggamma && out && al16(G) && al16(z) && al16(out) && (z_is_x2 == 0 || z_is_x2 == 1));
+  EHM_CHECK_ARG(N > 0 && Ho > 0 && Wo > 0 && H > 0 && W > 0 && C > 0 && C % (z_is_x2 ? 32 : 8) == 0);
+  const bool dense = H == Ho && W == Wo;
+  EHM_CHECK_ARG(dense || ((H - 1) / 2 + 1 == Ho && (W - 1) / 2 + 1 == Wo));
+  const long long R = (long long)N * Ho * Wo;
+  EHM_CHECK_ARG(total_rows >= 2 && total_rows >= R && total_rows < (1ll << 40) && z_rows >= R && (long long)N * H * W * C < (1ll << 40) &&
+                (const void*)G != (const void*)out);
+  return launch_zbar(G, z, z_is_x2, z_rows, mean, invstd, gamma, gbeta, ggamma, scale, out, N, Ho, Wo, C, H, W, (long long)total_rows, stream);
 }

@@ -41,6 +41,44 @@ constexpr int kPoseDim = 144;  // 24 x 6
 static inline int64_t ceil_div(int64_t a, int64_t b) { return (a + b - 1) / b; }
 static inline int64_t round_up(int64_t a, int64_t b) { return ceil_div(a, b) * b; }
 
+// ---- data-parallel BatchNorm (csrc/gcn_train.hip, csrc/bn2d_train.hip): every rank's row count, handed to a merge kernel by value
+constexpr int kMaxRanks = 64;
+struct RankRows {
+  double r[kMaxRanks];
+  double total;
+};
+// rows [world] on the host -> RankRows: every rank has rows, all of them together at least two
+static inline int rank_rows_of(const int64_t* rows, int world, RankRows* rr) {
+  EHM_CHECK_ARG(rows && world >= 1 && world <= kMaxRanks);
+  int64_t total = 0;
+  for (int k = 0; k < world; ++k) {
+    EHM_CHECK_ARG(rows[k] >= 1 && rows[k] < (1ll << 40));
+    rr->r[k] = (double)rows[k];
+    total += rows[k];
+  }
+  EHM_CHECK_ARG(total >= 2);
+  rr->total = (double)total;
+  return 0;
+}
+// Chan et al.'s merge of the ranks' (mean, M2 = sum of squares centred on the rank's own mean) of one channel, in rank order; g: that channel's mean of
+// rank 0, rank k's at g[k * stride], its M2 at g[k * stride + m2].  The mean is taken relative to rank 0's and M2's correction on the merged mean, so
+// ranks whose means lie many sigma apart cancel nothing, and ONE rank gives back its own (mean, M2) bit for bit (mu_0 + 0, M2_0 + R_0 0).
+static __device__ __forceinline__ void merge_moments(const double* __restrict__ g, size_t stride, size_t m2, const RankRows& rr, int world, double* mu,
+                                                     double* M2) {
+  const double mu0 = g[0];
+  double d = 0.0;
+  for (int k = 1; k < world; ++k) d += rr.r[k] * (g[(size_t)k * stride] - mu0);
+  const double m = mu0 + d / rr.total;
+  double s = 0.0, c = 0.0;
+  for (int k = 0; k < world; ++k) {
+    const double dk = g[(size_t)k * stride] - m;
+    s += g[(size_t)k * stride + m2];
+    c += rr.r[k] * (dk * dk);
+  }
+  *mu = m;
+  *M2 = s + c;
+}
+
 // ---- float32 chains that must round like the reference's separate torch ops: one correctly rounded operation each, never contracted.
 // HIP's __fmul_rn / __fadd_rn / __fsub_rn are the plain operators, which hipcc's default -ffp-contract=fast-honor-pragmas fuses across
 // statements: __fadd_rn(__fmul_rn(a, b), c) compiles to ONE v_fma_f32.  A product formed here carries no contract flag, so no sum can absorb it.

@@ -21,9 +21,16 @@
 //   train_bnbwd_partial       g, gate, z -> partial sums of vbar and vbar xhat (float64).  12 N bytes read per row.
 //   train_bnbwd_finish        -> betabar, gammabar (float32) and betabar / R, gammabar / R in the workspace.
 //   train_zbar_kernel         g, gate, z -> zbar.  12 N bytes read and 4 N written per row.
+//   train_local_stats / train_local_bwd     a rank's (mean, M2) / (sum vbar, sum vbar xhat) [2][N] float64, for the data-parallel route below.
+//   train_merge_stats                       every rank's (mean, M2) -> the batch's mean, invstd and the running statistics (merge_moments, common.h).
+//   train_merge_bwd                         every rank's sums, added in rank order -> betabar / R, gammabar / R of the whole batch; the rank's own sums out.
 // The statistics are two-pass sums in float64 in a fixed order: exact to the float32 rounding of their results, whatever |mean| / std is.  No atomics
 // anywhere: two calls on the same inputs give the same bits.  The kernels read the raw parameter arrays the handle was created on, never its
 // BatchNorm-folded tables.
+//
+// Data parallel (ehm_gcn_train_stats_local / _stats_merge / _bwd_local / _bwd_merge): each rank runs the same passes on its own rows and stops at [2][N]
+// float64; the caller all-gathers them ([world][2][N], ONE collective per BatchNorm each way) and every rank merges the same buffer in the same order, so all
+// ranks hold the same bits.  With world == 1 a local + merge pair gives the bits of ehm_gcn_train_stats / ehm_gcn_train_bn_backward.
 #include "common.h"
 #include "egohmr_hip.h"
 #include "gcn_dev.h"
@@ -191,6 +198,50 @@ __global__ __launch_bounds__(256) void train_bnbwd_finish(const double* __restri
   gR[n] = (float)(sg / R);
 }
 
+// a rank's own statistics: local[0][n] = its mean, local[1][n] = its sum of squares centred on that mean
+__global__ __launch_bounds__(256) void train_local_stats(const double* __restrict__ part, const double* __restrict__ meand, int N, int groups,
+                                                         double* __restrict__ local) {
+  const int n = blockIdx.x * 256 + threadIdx.x;
+  if (n >= N) return;
+  local[n] = meand[n];
+  local[N + n] = ordered_sum(part + n, N, groups);
+}
+
+__global__ __launch_bounds__(256) void train_merge_stats(const double* __restrict__ gathered, RankRows rr, int world, int N, double eps, double momentum,
+                                                         float* __restrict__ mean, float* __restrict__ invstd, float* __restrict__ running_mean,
+                                                         float* __restrict__ running_var) {
+  const int n = blockIdx.x * 256 + threadIdx.x;
+  if (n >= N) return;
+  double mu, M2;
+  merge_moments(gathered + n, (size_t)2 * N, (size_t)N, rr, world, &mu, &M2);
+  const double R = rr.total, var = M2 / R;
+  mean[n] = (float)mu;
+  invstd[n] = (float)(1.0 / sqrt(var + eps));
+  if (running_mean) running_mean[n] = (float)((1.0 - momentum) * (double)running_mean[n] + momentum * mu);
+  if (running_var) running_var[n] = (float)((1.0 - momentum) * (double)running_var[n] + momentum * var * (R / (R - 1.0)));
+}
+
+__global__ __launch_bounds__(256) void train_local_bwd(const double* __restrict__ bpart, const double* __restrict__ gpart, int N, int groups,
+                                                       double* __restrict__ local) {
+  const int n = blockIdx.x * 256 + threadIdx.x;
+  if (n >= N) return;
+  local[n] = ordered_sum(bpart + n, N, groups);
+  local[N + n] = ordered_sum(gpart + n, N, groups);
+}
+
+// gbn_bias / gbn_weight: the rank's OWN sums (the caller's gradient all-reduce completes them); bR / gR: the whole batch's, over its row count R
+__global__ __launch_bounds__(256) void train_merge_bwd(const double* __restrict__ gathered, int world, int rank, int N, double R,
+                                                       float* __restrict__ gbn_weight, float* __restrict__ gbn_bias, float* __restrict__ bR,
+                                                       float* __restrict__ gR) {
+  const int n = blockIdx.x * 256 + threadIdx.x;
+  if (n >= N) return;
+  const double sb = ordered_sum(gathered + n, 2 * N, world), sg = ordered_sum(gathered + N + n, 2 * N, world);
+  if (gbn_bias) gbn_bias[n] = (float)gathered[(size_t)rank * 2 * N + n];
+  if (gbn_weight) gbn_weight[n] = (float)gathered[(size_t)rank * 2 * N + N + n];
+  bR[n] = (float)(sb / R);
+  gR[n] = (float)(sg / R);
+}
+
 __global__ __launch_bounds__(256) void train_zbar_kernel(const float* __restrict__ gout, const float* __restrict__ gate, const float* __restrict__ z,
                                                          const float* __restrict__ mean, const float* __restrict__ invstd, const float* __restrict__ gamma,
                                                          const float* __restrict__ bR, const float* __restrict__ gR, float* __restrict__ zbar, int N4,
@@ -341,6 +392,82 @@ extern "C" int ehm_gcn_train_bn_backward(const ehm_gcn* h, int conv, const float
   hipLaunchKernelGGL(train_bnbwd_partial, w.cgrid, dim3(NT), 0, st, gout, gate, z, mean, invstd, w.part0, w.part1, c.N, bodies, w.groups, w.chunks);
   hipLaunchKernelGGL(train_bnbwd_finish, w.ngrid, dim3(256), 0, st, (const double*)w.part0, (const double*)w.part1, c.N, w.groups, R, gbn_weight, gbn_bias,
                      w.bR, w.gR);
+  hipLaunchKernelGGL(train_zbar_kernel, dim3((unsigned)ceil_div(total4, 256)), dim3(256), 0, st, gout, gate, z, mean, invstd, c.raw.bn_weight,
+                     (const float*)w.bR, (const float*)w.gR, zbar, c.N / 4, total4);
+  EHM_LAUNCH_CHECK();
+  return 0;
+}
+
+// ---- data parallel: a rank's rows -> [2][N] float64, every rank's [world][2][N] -> the batch's.  rows [world] on the host: each rank's R_r = 24 bodies_r.
+extern "C" int ehm_gcn_train_stats_local(const ehm_gcn* h, int conv, const float* z, int bodies, int have_sums, double* local, void* workspace,
+                                         int64_t workspace_bytes, void* stream) {
+  TrainConv c;
+  const int rc = train_conv_of(h, conv, &c);
+  if (rc != 0) return rc;
+  EHM_CHECK_ARG(z && local && (uintptr_t)local % 8 == 0 && bodies > 0 && (have_sums == 0 || have_sums == 1));
+  EHM_CHECK_ARG(workspace_ok(workspace, workspace_bytes, c.N, bodies));
+  const TrainPlan w = plan_of(workspace, c.N, bodies);
+  hipStream_t st = (hipStream_t)stream;
+  const double R = (double)bodies * kJ;
+  if (!have_sums)
+    hipLaunchKernelGGL(train_colsum_kernel<false>, w.cgrid, dim3(NT), 0, st, z, (const double*)nullptr, w.part0, c.N, bodies, w.groups, w.chunks);
+  hipLaunchKernelGGL(train_mean_kernel, w.ngrid, dim3(256), 0, st, (const double*)w.part0, w.meand, c.N, w.groups, R);
+  hipLaunchKernelGGL(train_colsum_kernel<true>, w.cgrid, dim3(NT), 0, st, z, (const double*)w.meand, w.part1, c.N, bodies, w.groups, w.chunks);
+  hipLaunchKernelGGL(train_local_stats, w.ngrid, dim3(256), 0, st, (const double*)w.part1, (const double*)w.meand, c.N, w.groups, local);
+  EHM_LAUNCH_CHECK();
+  return 0;
+}
+
+extern "C" int ehm_gcn_train_stats_merge(const ehm_gcn* h, int conv, const double* gathered, const int64_t* rows, int world, double eps, double momentum,
+                                         float* mean, float* invstd, float* running_mean, float* running_var, void* stream) {
+  TrainConv c;
+  int rc = train_conv_of(h, conv, &c);
+  if (rc != 0) return rc;
+  RankRows rr;
+  if ((rc = rank_rows_of(rows, world, &rr)) != 0) return rc;
+  EHM_CHECK_ARG(gathered && (uintptr_t)gathered % 8 == 0 && mean && invstd && eps >= 0.0 && momentum >= 0.0 && momentum <= 1.0);
+  EHM_CHECK_ARG((running_mean == nullptr) == (running_var == nullptr));
+  for (int k = 0; k < world; ++k) EHM_CHECK_ARG(rows[k] % kJ == 0);
+  hipLaunchKernelGGL(train_merge_stats, dim3((unsigned)ceil_div(c.N, 256)), dim3(256), 0, (hipStream_t)stream, gathered, rr, world, c.N, eps, momentum, mean,
+                     invstd, running_mean, running_var);
+  EHM_LAUNCH_CHECK();
+  return 0;
+}
+
+extern "C" int ehm_gcn_train_bwd_local(const ehm_gcn* h, int conv, const float* gout, const float* gate, const float* z, const float* mean,
+                                       const float* invstd, int bodies, double* local, void* workspace, int64_t workspace_bytes, void* stream) {
+  TrainConv c;
+  const int rc = train_conv_of(h, conv, &c);
+  if (rc != 0) return rc;
+  EHM_CHECK_ARG(gout && gate && z && mean && invstd && local && (uintptr_t)local % 8 == 0 && bodies > 0);
+  EHM_CHECK_ARG(workspace_ok(workspace, workspace_bytes, c.N, bodies));
+  const TrainPlan w = plan_of(workspace, c.N, bodies);
+  hipStream_t st = (hipStream_t)stream;
+  hipLaunchKernelGGL(train_bnbwd_partial, w.cgrid, dim3(NT), 0, st, gout, gate, z, mean, invstd, w.part0, w.part1, c.N, bodies, w.groups, w.chunks);
+  hipLaunchKernelGGL(train_local_bwd, w.ngrid, dim3(256), 0, st, (const double*)w.part0, (const double*)w.part1, c.N, w.groups, local);
+  EHM_LAUNCH_CHECK();
+  return 0;
+}
+
+extern "C" int ehm_gcn_train_bwd_merge(const ehm_gcn* h, int conv, const double* gathered, const int64_t* rows, int world, int rank, const float* gout,
+                                       const float* gate, const float* z, const float* mean, const float* invstd, int bodies, float* zbar,
+                                       float* gbn_weight, float* gbn_bias, void* workspace, int64_t workspace_bytes, void* stream) {
+  TrainConv c;
+  int rc = train_conv_of(h, conv, &c);
+  if (rc != 0) return rc;
+  RankRows rr;
+  if ((rc = rank_rows_of(rows, world, &rr)) != 0) return rc;
+  EHM_CHECK_ARG(gathered && (uintptr_t)gathered % 8 == 0 && rank >= 0 && rank < world && bodies > 0 && rows[rank] == (int64_t)bodies * kJ);
+  EHM_CHECK_ARG(gout && gate && z && mean && invstd && zbar);
+  EHM_CHECK_ARG((const void*)zbar != (const void*)gate && (const void*)zbar != (const void*)z);
+  EHM_CHECK_ARG(((uintptr_t)gout | (uintptr_t)gate | (uintptr_t)z | (uintptr_t)mean | (uintptr_t)invstd | (uintptr_t)zbar |
+                 (uintptr_t)c.raw.bn_weight) % 16 == 0);
+  EHM_CHECK_ARG(workspace_ok(workspace, workspace_bytes, c.N, bodies));
+  const TrainPlan w = plan_of(workspace, c.N, bodies);
+  hipStream_t st = (hipStream_t)stream;
+  const long long total4 = (long long)bodies * kJ * (c.N / 4);
+  EHM_CHECK_ARG(ceil_div(total4, 256) < (1ll << 31));
+  hipLaunchKernelGGL(train_merge_bwd, w.ngrid, dim3(256), 0, st, gathered, world, rank, c.N, rr.total, gbn_weight, gbn_bias, w.bR, w.gR);
   hipLaunchKernelGGL(train_zbar_kernel, dim3((unsigned)ceil_div(total4, 256)), dim3(256), 0, st, gout, gate, z, mean, invstd, c.raw.bn_weight,
                      (const float*)w.bR, (const float*)w.gR, zbar, c.N / 4, total4);
   EHM_LAUNCH_CHECK();

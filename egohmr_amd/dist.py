@@ -93,6 +93,77 @@ def gather_floats(value: float, device) -> list:
     return [float(x.item()) for x in out]
 
 
+def _multi() -> bool:
+    return dist.is_available() and dist.is_initialized() and dist.get_world_size() > 1
+
+
+class StatSync:
+    """The collectives of ONE data-parallel training step (EgoHMR.data_parallel): the ranks' item counts B_r, and per BatchNorm and direction one all-gather
+    of the rank's float64 [2, C] (its mean and centred sum of squares forward, its two cotangent sums backward - csrc/gcn_train.hip, csrc/bn2d_train.hip)
+    into [world, 2, C], which every rank then merges in rank order.  Every rank must issue the same gathers in the same order: the BatchNorm routes do,
+    given the same module structure and requires_grad flags (EgoHMR.init_optimizers checks those once).
+
+    counts: every rank's item count, in rank order.  A process that is not part of a group is a world of one: gather() only adds the leading axis."""
+
+    def __init__(self, counts, rank: int = 0):
+        self.counts = [int(c) for c in counts]
+        self.world, self.rank = len(self.counts), int(rank)
+        if not 0 <= self.rank < self.world:
+            raise ValueError(f"StatSync: rank {rank} of a world of {self.world}")
+        if min(self.counts) < 1:
+            raise ValueError(f"StatSync: every rank needs at least one item of the batch, got the counts {self.counts}")
+        self.total = sum(self.counts)
+
+    @classmethod
+    def exchange(cls, items: int, device=None) -> "StatSync":
+        """The step's one count exchange: every rank's `items`.  A rank without items is refused here on EVERY rank (they all see the same counts), before
+        any other collective of the step."""
+        if not _multi():
+            return cls([items], 0)
+        dev = "cpu" if dist.get_backend() == "gloo" else device
+        mine = torch.tensor([int(items)], dtype=torch.int64, device=dev)
+        out = torch.empty(dist.get_world_size(), dtype=torch.int64, device=dev)
+        dist.all_gather_into_tensor(out, mine)
+        return cls(out.tolist(), dist.get_rank())
+
+    @property
+    def loss_weight(self) -> float:
+        """B_r / B: a rank's batch-mean loss times this, summed over the ranks, is the whole batch's mean loss - so with the loss scaled by it up front every
+        cotangent, BatchNorm sum and parameter gradient adds across the ranks unweighted."""
+        return self.counts[self.rank] / self.total
+
+    def rows(self, per_item: int = 1):
+        """The ranks' row counts R_r = per_item B_r as the int64 host array the merge entries read."""
+        import ctypes
+        return (ctypes.c_int64 * self.world)(*[c * int(per_item) for c in self.counts])
+
+    def gather(self, local: torch.Tensor) -> torch.Tensor:
+        """local [2, C] -> [world, 2, C] in rank order, on local's device (gloo with a device tensor: staged through the host, as gather_packed)."""
+        local = local.contiguous()
+        if self.world == 1:
+            return local.unsqueeze(0)
+        if not _multi() or dist.get_world_size() != self.world:
+            raise RuntimeError(f"StatSync.gather: counts for {self.world} ranks, but the process group has "
+                               f"{dist.get_world_size() if dist.is_initialized() else 'not been initialised'}")
+        if dist.get_backend() == "gloo" and local.is_cuda:
+            return self.gather(local.cpu()).to(local.device)
+        out = torch.empty((self.world * local.shape[0],) + tuple(local.shape[1:]), dtype=local.dtype, device=local.device)
+        dist.all_gather_into_tensor(out, local)                       # (the ranks' tensors along dim 0, the form every backend takes)
+        return out.view((self.world,) + tuple(local.shape))
+
+
+def all_reduce_sum_(flat: torch.Tensor) -> torch.Tensor:
+    """In-place SUM over the ranks of one flat tensor (the gradient bucket of EgoHMR.training_step); gloo with a device tensor goes through the host."""
+    if not _multi():
+        return flat
+    if dist.get_backend() == "gloo" and flat.is_cuda:
+        host = flat.cpu()
+        dist.all_reduce(host, op=dist.ReduceOp.SUM)
+        return flat.copy_(host)
+    dist.all_reduce(flat, op=dist.ReduceOp.SUM)
+    return flat
+
+
 def agree_schedule(fused_sampler, diffusion, batch, ddim=False, guided=False, cond_grad_weight=1.0, denom_items=None, **kw):
     """One precision-schedule calibration for the whole job: rank 0 measures k (and, in the same info dict, the two-term steps j) on ITS batch (FusedSampler.calibrate_schedule - with the
     contiguous sharding of `shard_range` these are the first items of the data set whatever the world size), every rank installs that k and j.

@@ -55,6 +55,10 @@ class ResNet50Features(nn.Module):
     # graph - trunk_grad.TrunkTrainFunction, whose backward differentiates through the mean and the variance.  False: .train() is ignored, every call
     # folds the frozen running statistics
     train_batchnorm = False
+    # A dist.StatSync, set for a call by EgoHMR.training_step behind EgoHMR.data_parallel: the train-mode route's BatchNorm2d statistics and their backward
+    # sums then run over ALL ranks' rows (one all-gather per BatchNorm each way, also under no_grad - the running statistics still move).  None: this
+    # process's rows, today's calls
+    stat_sync = None
     GRAD_HI_ONLY = ("the autograd route of ResNet50Features keeps f32-grade activations for its backward; the plain-f16 tier "
                     "(ResNet50Features.hi_only = True) stores none: set hi_only = False with it")
     GRAD_IMAGE = ("ResNet50Features.grad_params differentiates the trunk with respect to its parameters only: the image gradient (the stem's data "
@@ -109,7 +113,8 @@ class ResNet50Features(nn.Module):
             if isinstance(bn, nn.BatchNorm2d) and (bn.momentum is None or not bn.track_running_stats):
                 raise NotImplementedError("ResNet50Features: the train-mode route updates the running statistics with a fixed momentum; "
                                           "BatchNorm2d(momentum=None) and track_running_stats=False are not built")
-        if x.dim() == 4 and x.shape[0] * (x.shape[2] // 32) * (x.shape[3] // 32) < 2:
+        items = x.shape[0] if self.stat_sync is None else self.stat_sync.total             # (data parallel: the statistics see every rank's rows)
+        if x.dim() == 4 and items * (x.shape[2] // 32) * (x.shape[3] // 32) < 2:
             raise ValueError(f"Expected more than 1 value per channel when training, got input size {tuple(x.shape)} "
                              "(layer4 of the trunk has N * H/32 * W/32 values per channel)")
 
@@ -277,8 +282,12 @@ class ResNet50Features(nn.Module):
             N, _, H, W = x.shape
             zero = torch.zeros(2048, device=x.device)
             bumped = []
+            sync = self.stat_sync
+            if sync is not None and sync.counts[sync.rank] != N:
+                raise ValueError(f"ResNet50Features.stat_sync counts {sync.counts[sync.rank]} items for this rank, the input has {N}")
             if rec is not None:
                 rec.bn = [None] * len(U)
+                rec.sync = sync
 
             def note(i, *e):
                 bumped.append(U[i][1])
@@ -289,7 +298,7 @@ class ResNet50Features(nn.Module):
                 conv, bn = U[i]
                 Co = conv.out_channels
                 z, zs = conv_x2(x, shp, (conv.weight.detach().float(), zero[:Co], conv.stride, conv.padding), None, relu=False)
-                mean, var, invstd = trunk_grad.bn_stats(z, zs[0] * zs[1] * zs[2], Co, bn)
+                mean, var, invstd = trunk_grad.bn_stats(z, zs[0] * zs[1] * zs[2], Co, bn, sync=sync)
                 note(i, z if rec is not None and rec.keep_z else None, zs, mean, var, invstd)
                 return operands(conv, bn, (mean, var)), None
 
@@ -300,7 +309,7 @@ class ResNet50Features(nn.Module):
 
             raw_wt, _ = stem_operands(self.conv1.weight.detach().float(), zero[:64])
             z = trunk_grad.stem_preact(x, raw_wt, zero[:64])
-            mean, var, invstd = trunk_grad.bn_stats(z, N * (H // 2) * (W // 2), 64, self.bn1, x2=False)
+            mean, var, invstd = trunk_grad.bn_stats(z, N * (H // 2) * (W // 2), 64, self.bn1, x2=False, sync=sync)
             del z                                                                   # (recomputed by the backward, like the eval route's)
             note(0, None, (N, H // 2, W // 2), mean, var, invstd)
             wt, b = stem_operands(*operands(self.conv1, self.bn1, (mean, var))[:2])

@@ -123,8 +123,10 @@ def _train_ws(h, conv, bodies, dev):
     return torch.empty(nb.value // 8, device=dev, dtype=torch.float64), nb.value
 
 
-def train_conv_forward(h, conv, cw, X, bodies, eps, momentum, running=None, res=None, y=None, out=None):
+def train_conv_forward(h, conv, cw, X, bodies, eps, momentum, running=None, res=None, y=None, out=None, sync=None):
     """One BatchNorm'd conv (INPUT or a hidden conv's index) with batch statistics: X [>= rows, Kp] float32 (K padded to a multiple of 32 with zeros).
+    sync (a dist.StatSync, data parallel): the statistics are those of ALL ranks' rows - this rank's (mean, M2) in float64, one all-gather, the same merge
+    on every rank (ehm_gcn_train_stats_local / _merge); it rides in the result for the backward.
 
     running: (running_mean, running_var) float32 [N] on the device, updated in place, or None; res [rows, N] or None; y / out: float32 buffers of at
     least rows x N for relu(bn(z)) and for y + res (None: not written; with res, out is required).  Returns dict(z, mean, invstd): what the
@@ -138,9 +140,14 @@ def train_conv_forward(h, conv, cw, X, bodies, eps, momentum, running=None, res=
     A.ehm_gcn_train_adjacency(h, conv, adjm, s)
     A.ehm_gcn_train_preact(h, conv, pre, pre.shape[1], bodies, adjm, z, ws, nb, s)
     rm, rv = running if running is not None else (None, None)
-    A.ehm_gcn_train_stats(h, conv, z, bodies, 1, float(eps), float(momentum), mean, invstd, rm, rv, ws, nb, s)
+    if sync is None:
+        A.ehm_gcn_train_stats(h, conv, z, bodies, 1, float(eps), float(momentum), mean, invstd, rm, rv, ws, nb, s)
+    else:
+        local = torch.empty(2, N, device=dev, dtype=torch.float64)
+        A.ehm_gcn_train_stats_local(h, conv, z, bodies, 1, local, ws, nb, s)
+        A.ehm_gcn_train_stats_merge(h, conv, sync.gather(local), sync.rows(24), sync.world, float(eps), float(momentum), mean, invstd, rm, rv, s)
     A.ehm_gcn_train_normalize(h, conv, z, mean, invstd, res, y, out, bodies, s)
-    return dict(z=z, mean=mean, invstd=invstd, A=adjm)
+    return dict(z=z, mean=mean, invstd=invstd, A=adjm, sync=sync)
 
 
 def train_conv_backward(h, conv, cw, X, st, gate, gout, bodies, need_x=True, need_w=False, need_params=False, out=None):
@@ -153,7 +160,14 @@ def train_conv_backward(h, conv, cw, X, st, gate, gout, bodies, need_x=True, nee
     ws, nb = _train_ws(h, conv, bodies, dev)
     zbar = torch.empty(rows, N, device=dev)
     g = _param_bufs(("M", "adj2", "bn_weight", "bn_bias"), N, out, dev) if need_params else {}
-    A.ehm_gcn_train_bn_backward(h, conv, gout, gate, st["z"], st["mean"], st["invstd"], bodies, zbar, g.get("bn_weight"), g.get("bn_bias"), ws, nb, s)
+    sync = st.get("sync")
+    if sync is None:
+        A.ehm_gcn_train_bn_backward(h, conv, gout, gate, st["z"], st["mean"], st["invstd"], bodies, zbar, g.get("bn_weight"), g.get("bn_bias"), ws, nb, s)
+    else:                       # zbar on all ranks' sums; bn_weight / bn_bias receive this rank's own, which the caller's gradient sum completes
+        local = torch.empty(2, N, device=dev, dtype=torch.float64)
+        A.ehm_gcn_train_bwd_local(h, conv, gout, gate, st["z"], st["mean"], st["invstd"], bodies, local, ws, nb, s)
+        A.ehm_gcn_train_bwd_merge(h, conv, sync.gather(local), sync.rows(24), sync.world, sync.rank, gout, gate, st["z"], st["mean"], st["invstd"], bodies,
+                                  zbar, g.get("bn_weight"), g.get("bn_bias"), ws, nb, s)
     if need_x or need_w:
         _gemm_grads(lambda G: A.ehm_gcn_train_bwd_epilogue(h, conv, zbar, st["A"], G, cw.ldg, bodies, s), cw, X, rows, need_x, need_w, out, res)
     if need_params:
@@ -233,9 +247,14 @@ def forward_train(m, x, save):
     """ModulatedGCN.forward under .train() with `train_batchnorm`: per BatchNorm'd conv the split-f16 GEMM X [W0 | W1], then ehm_gcn_train_preact (modulation,
     adjacency mix, bias), ehm_gcn_train_stats (batch mean / biased variance, running statistics) and ehm_gcn_train_normalize (BatchNorm, ReLU,
     residual) on float32 activations; gconv_output as in eval mode.  The handle is this call's own: the running statistics change here, so the
-    eval-mode one (ModulatedGCN._native) is rebuilt by the next eval() call through its TensorKey.  Returns (out [B, 24, 6], saved or None)."""
+    eval-mode one (ModulatedGCN._native) is rebuilt by the next eval() call through its TensorKey.  Returns (out [B, 24, 6], saved or None).
+    With ModulatedGCN.stat_sync set (data parallel) every BatchNorm runs on all ranks' rows - also under no_grad, which still updates the running
+    statistics."""
     A = _lib.api()
     dev = x.device
+    sync = m.stat_sync
+    if sync is not None and sync.counts[sync.rank] != x.shape[0]:
+        raise ValueError(f"ModulatedGCN.stat_sync counts {sync.counts[sync.rank]} items for this rank, the input has {x.shape[0]}")
     hid, nh = m.hid_dim, 2 * m.num_layers
     mods = m._convs()
     with _lib.on_device(dev):
@@ -257,7 +276,7 @@ def forward_train(m, x, save):
             else:                                         # y is kept for the backward only: its gate
                 y = torch.empty(rows, hid, device=dev) if save else None
                 out = torch.zeros(rows_pad, hid, device=dev) if last else torch.empty(rows, hid, device=dev)
-            st = train_conv_forward(h, idx, cws[ci], X, B, bn.eps, bn.momentum, running, res, y, out)
+            st = train_conv_forward(h, idx, cws[ci], X, B, bn.eps, bn.momentum, running, res, y, out, sync)
             bn.running_mean.copy_(running[0])             # (copy_: the buffers' _version moves, which the eval-mode handle's key sees)
             bn.running_var.copy_(running[1])
             bn.num_batches_tracked.add_(1)

@@ -253,6 +253,9 @@ class ModulatedGCN(nn.Module):
     # statistics and num_batches_tracked updated in place, a backward through the mean and the variance (gcn_grad.GCNTrainFunction; csrc/gcn_train.hip).
     # eval() calls do not depend on it
     train_batchnorm = False
+    # A dist.StatSync, set for a call by EgoHMR.training_step behind EgoHMR.data_parallel: the train-mode route's BatchNorm statistics and their backward
+    # sums then run over ALL ranks' rows (one all-gather per BatchNorm each way, also under no_grad).  None: this process's rows, today's calls
+    stat_sync = None
 
     def _check_train(self):
         """What the train-mode route cannot run, refused before any device call."""
@@ -511,6 +514,20 @@ class EgoHMR(nn.Module):
     # .train() on batch statistics as the reference's backbone.train(), egohmr.py:455) and init_optimizers puts backbone.parameters() in front, which
     # is the reference's list (egohmr.py:140-147)
     trunk_grad = False
+    # Consulted on the training route only (behind frozen_trunk_training).  True, with torch.distributed initialised and more than one rank: the ranks
+    # each take their shard of a batch and together make the optimizer step ONE process would make on the whole batch, to rounding - init_optimizers
+    # broadcasts rank 0's parameters and buffers; training_step exchanges the item counts B_r, runs every train-mode BatchNorm on all ranks' rows
+    # (dist.StatSync), backpropagates loss B_r / B and sums the gradients of init_optimizers' list over the ranks in one flat all-reduce before
+    # optimizer.step().  NOT coordinated across the ranks, as with torch's DistributedDataParallel: the cond_mask_prob draw, the caller's timesteps and
+    # the caller's noise - seed them per rank.  Without a process group, or with one rank, it changes nothing, bit for bit
+    data_parallel = False
+
+    def _data_parallel_world(self):
+        """the number of ranks the training route is spread over: 1 unless data_parallel is set and a process group with more ranks exists"""
+        import torch.distributed as td
+        if not (self.data_parallel and td.is_available() and td.is_initialized()):
+            return 1
+        return td.get_world_size()
 
     def forward(self, batch, timesteps, eval_with_uncond=True):
         """One denoising evaluation (egohmr.py:173-303).  Conditioning is cached per batch object.  Under self.training with frozen_trunk_training set: the
@@ -980,18 +997,83 @@ class EgoHMR(nn.Module):
         self.opt_params = ((list(self.backbone.parameters()) if self.trunk_grad else []) + list(self.scene_enc.parameters()) + list(self.transl_enc.parameters()) + list(self.beta_layer.parameters()) +
                            list(self.diffusion_model.parameters()) + list(self.embed_timestep.parameters()) + list(self.input_process.parameters()))
         self.optimizer = torch.optim.AdamW(params=self.opt_params, lr=self.cfg.TRAIN.LR, weight_decay=self.cfg.TRAIN.WEIGHT_DECAY)
+        if self._data_parallel_world() > 1:
+            self._data_parallel_setup()
+
+    def _data_parallel_setup(self):
+        """EgoHMR.data_parallel, once: every rank must hold the same list of (numel, requires_grad) - else the ranks would issue different collectives in a
+        step - and then takes rank 0's parameters and buffers (moved in place, so the handles that key on them rebuild)."""
+        import torch.distributed as td
+        mine = [(p.numel(), bool(p.requires_grad)) for p in self.opt_params]
+        lists = [None] * td.get_world_size()
+        td.all_gather_object(lists, mine)
+        for r, other in enumerate(lists):
+            if other != mine:
+                raise ValueError(f"EgoHMR.data_parallel: rank {r}'s optimizer list differs from rank {td.get_rank()}'s in (numel, requires_grad): "
+                                 f"{len(other)} against {len(mine)} tensors" + "".join(
+                                     f"; entry {i}: {a} against {b}" for i, (a, b) in enumerate(zip(other, mine)) if a != b)[:200])
+        host = td.get_backend() == "gloo"
+        by_dtype = {}
+        for t in list(self.parameters()) + list(self.buffers()):
+            by_dtype.setdefault((t.dtype, t.device), []).append(t)
+        with torch.no_grad():
+            for ts in by_dtype.values():                    # one broadcast per dtype and device (float32; the int64 num_batches_tracked)
+                flat = torch.cat([t.detach().reshape(-1) for t in ts])
+                flat = flat.cpu() if host and flat.is_cuda else flat
+                td.broadcast(flat, src=0)
+                if td.get_rank() != 0:
+                    for t, v in zip(ts, flat.split([t.numel() for t in ts])):
+                        t.copy_(v.view_as(t))
+
+    def _reduce_gradients(self):
+        """The gradients of init_optimizers' list, summed over the ranks in ONE flat all-reduce (flattened and unflattened with torch ops)."""
+        from . import dist as ehm_dist
+        params = [p for p in self.opt_params if p.requires_grad]
+        for p, (name, _) in zip(self.opt_params, self._opt_param_names()):
+            if p.requires_grad and p.grad is None:
+                raise ValueError(f"EgoHMR.data_parallel: {name} requires grad and received none in this step; the ranks sum one gradient per tensor "
+                                 "of init_optimizers' list")
+        flat = torch.cat([p.grad.reshape(-1).float() for p in params])
+        ehm_dist.all_reduce_sum_(flat)
+        torch._foreach_copy_([p.grad for p in params], [c.view_as(p.grad) for p, c in zip(params, flat.split([p.numel() for p in params]))])
+
+    def _opt_param_names(self):
+        """(name, parameter) per entry of opt_params"""
+        names = {id(p): n for n, p in self.named_parameters()}
+        return [(names.get(id(p), f"opt_params[{i}]"), p) for i, p in enumerate(self.opt_params)]
 
     def training_step(self, batch=None, timesteps=None, cur_epoch=0):
         """egohmr.py:453-472 behind frozen_trunk_training (else NotImplementedError): the training modes (_set_train_modes; left as set, validation_setup
-        restores eval), forward, compute_loss, zero_grad, backward, one step of the optimizer of init_optimizers; returns the output dict."""
+        restores eval), forward, compute_loss, zero_grad, backward, one step of the optimizer of init_optimizers; returns the output dict.
+        Behind EgoHMR.data_parallel with more than one rank, `batch` is this rank's shard: the counts B_r are exchanged (one small collective; a rank without
+        items is refused on every rank), the train-mode BatchNorms of the denoiser (diffusion_model.train_batchnorm) and of the backbone (trunk_grad +
+        backbone.train_batchnorm) run on all ranks' rows, loss B_r / B is backpropagated - every term of the loss is a mean over the items, so all
+        cotangents are then in units of the whole batch's mean loss and add over the ranks unweighted, ragged shards included - and the gradients are
+        summed over the ranks before the optimizer step.  output['losses'] stays this rank's."""
         if not getattr(self, "frozen_trunk_training", False):
             raise NotImplementedError("training_step is not built: " + EgoHMR.NOT_BUILT)
         self._check_trainable()
         self._set_train_modes()
-        output = self.forward(batch, timesteps, eval_with_uncond=False)                                    # :465
-        loss = self.compute_loss(batch, output, cur_epoch=cur_epoch)
-        self.optimizer.zero_grad()
-        loss.backward()
+        if self._data_parallel_world() == 1:
+            output = self.forward(batch, timesteps, eval_with_uncond=False)                                # :465
+            loss = self.compute_loss(batch, output, cur_epoch=cur_epoch)
+            self.optimizer.zero_grad()
+            loss.backward()
+            self.optimizer.step()
+            return output
+        from . import dist as ehm_dist
+        dm, bb = self.diffusion_model, self.backbone
+        sync = ehm_dist.StatSync.exchange(int(batch["x_t"].reshape(-1, 144).shape[0]), self.device)
+        try:
+            dm.stat_sync = sync if dm.train_batchnorm else None
+            bb.stat_sync = sync if self.trunk_grad and bb.train_batchnorm else None
+            output = self.forward(batch, timesteps, eval_with_uncond=False)
+            loss = self.compute_loss(batch, output, cur_epoch=cur_epoch)
+            self.optimizer.zero_grad()
+            (loss * sync.loss_weight).backward()
+        finally:
+            dm.stat_sync = bb.stat_sync = None
+        self._reduce_gradients()
         self.optimizer.step()
         return output
 

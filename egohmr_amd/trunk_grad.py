@@ -293,19 +293,31 @@ class TrainRecord:
 
     def __init__(self, keep_z=True):
         self.acts, self.bn, self.keep_z = [], [], keep_z
+        self.sync = None                 # the dist.StatSync the forward ran with (data parallel): the backward gathers through the same one
         self.stem_wt = self.stem_b = None
 
 
 def _bn_ws(pixels, Cn, dev):
-    return _workspace(_lib.api().ehm_bn2d_train_workspace_bytes, pixels, Cn, dtype=torch.float64, device=dev)
+    """(a rank's share of a data-parallel batch may be one row, and float32 rows any multiple of 8 channels: the query's own granules bound both from above)"""
+    return _workspace(_lib.api().ehm_bn2d_train_workspace_bytes, max(pixels, 2), (Cn + 31) // 32 * 32, dtype=torch.float64, device=dev)
 
 
-def bn_stats(z, pixels, Cn, bn=None, x2=True, eps=1e-5, momentum=0.1):
+def _sync_rows(sync, pixels):
+    """(rows per item, all ranks' rows) of a unit whose rank-local z has `pixels` rows"""
+    per_item, rem = divmod(pixels, sync.counts[sync.rank])
+    if rem:
+        raise ValueError(f"the StatSync counts {sync.counts[sync.rank]} items for this rank, which does not divide the unit's {pixels} rows")
+    return per_item, per_item * sync.total
+
+
+def bn_stats(z, pixels, Cn, bn=None, x2=True, eps=1e-5, momentum=0.1, sync=None):
     """ehm_bn2d_train_stats: (mean, biased var, invstd) float32 [C] of the first `pixels` rows of z (an X2 buffer, or x2=False: float32 rows); with bn, its
-    eps and momentum, and its running_mean / running_var / num_batches_tracked are updated IN PLACE on the device (the caller bumps their versions)."""
+    eps and momentum, and its running_mean / running_var / num_batches_tracked are updated IN PLACE on the device (the caller bumps their versions).
+    sync (a dist.StatSync): the statistics of ALL ranks' rows - ehm_bn2d_train_stats_local, one all-gather, ehm_bn2d_train_stats_merge on every rank."""
     dev = z.device
-    if pixels < 2:
-        raise ValueError(f"Expected more than 1 value per channel when training, got {pixels} rows of {Cn} channels")
+    total = pixels if sync is None else _sync_rows(sync, pixels)[1]
+    if total < 2:
+        raise ValueError(f"Expected more than 1 value per channel when training, got {total} rows of {Cn} channels")
     mean, var, invstd = (torch.empty(Cn, device=dev) for _ in range(3))
     ws, nb = _bn_ws(pixels, Cn, dev)
     rm = rv = nbt = None
@@ -314,28 +326,48 @@ def bn_stats(z, pixels, Cn, bn=None, x2=True, eps=1e-5, momentum=0.1):
         if rm.dtype != torch.float32 or rv.dtype != torch.float32 or nbt.dtype != torch.int64:
             raise _lib.EgoHMRHipError("the train-mode BatchNorm2d route updates float32 running statistics and an int64 counter in place")
     z2 = z.view(-1, Cn)
-    _lib.api().ehm_bn2d_train_stats(z2, 1 if x2 else 0, z2.shape[0], pixels, Cn, float(eps), float(momentum), mean, var, invstd, rm, rv, nbt, ws, nb,
-                                    _lib.stream_ptr())
+    A, s = _lib.api(), _lib.stream_ptr()
+    if sync is None:
+        A.ehm_bn2d_train_stats(z2, 1 if x2 else 0, z2.shape[0], pixels, Cn, float(eps), float(momentum), mean, var, invstd, rm, rv, nbt, ws, nb, s)
+    else:
+        local = torch.empty(2, Cn, device=dev, dtype=torch.float64)
+        A.ehm_bn2d_train_stats_local(z2, 1 if x2 else 0, z2.shape[0], pixels, Cn, local, ws, nb, s)
+        A.ehm_bn2d_train_stats_merge(sync.gather(local), sync.rows(_sync_rows(sync, pixels)[0]), sync.world, Cn, float(eps), float(momentum), mean, var,
+                                     invstd, rm, rv, nbt, s)
     return mean, var, invstd
 
 
-def bn_sums(G, z, pixels, Cn, mean, invstd, x2=True):
-    """ehm_bn2d_train_bwd_sums: (betabar, gammabar) float32 [C] from G float32 [pixels, C] and the unit's raw output z."""
-    gbeta, ggamma = torch.empty(Cn, device=G.device), torch.empty(Cn, device=G.device)
-    ws, nb = _bn_ws(pixels, Cn, G.device)
+def bn_sums(G, z, pixels, Cn, mean, invstd, x2=True, sync=None):
+    """ehm_bn2d_train_bwd_sums: (betabar, gammabar) float32 [C] from G float32 [pixels, C] and the unit's raw output z.
+    sync (a dist.StatSync): (betabar, gammabar, this rank's own betabar, gammabar) - the first two over ALL ranks' rows, for bn_zbar(total_rows=...); the
+    own ones are the parameter gradients, which the caller's gradient sum over the ranks completes (ehm_bn2d_train_bwd_local, one all-gather, _bwd_merge)."""
+    A, s, dev = _lib.api(), _lib.stream_ptr(), G.device
+    gbeta, ggamma = torch.empty(Cn, device=dev), torch.empty(Cn, device=dev)
+    ws, nb = _bn_ws(pixels, Cn, dev)
     z2 = z.view(-1, Cn)
-    _lib.api().ehm_bn2d_train_bwd_sums(G, z2, 1 if x2 else 0, z2.shape[0], pixels, Cn, mean, invstd, gbeta, ggamma, ws, nb, _lib.stream_ptr())
-    return gbeta, ggamma
+    if sync is None:
+        A.ehm_bn2d_train_bwd_sums(G, z2, 1 if x2 else 0, z2.shape[0], pixels, Cn, mean, invstd, gbeta, ggamma, ws, nb, s)
+        return gbeta, ggamma
+    local = torch.empty(2, Cn, device=dev, dtype=torch.float64)
+    own_b, own_g = torch.empty(Cn, device=dev), torch.empty(Cn, device=dev)
+    A.ehm_bn2d_train_bwd_local(G, z2, 1 if x2 else 0, z2.shape[0], pixels, Cn, mean, invstd, local, ws, nb, s)
+    A.ehm_bn2d_train_bwd_merge(sync.gather(local), sync.world, sync.rank, Cn, gbeta, ggamma, own_b, own_g, s)
+    return gbeta, ggamma, own_b, own_g
 
 
-def bn_zbar(G, z, shape, Cn, mean, invstd, gamma, gbeta, ggamma, scale=None, out_hw=None, x2=True):
-    """ehm_bn2d_train_bwd_zbar: float32 [N,H,W,C] = scale gamma invstd (G - betabar / R - xhat gammabar / R); dense, or (out_hw) zero-dilated like gate()."""
+def bn_zbar(G, z, shape, Cn, mean, invstd, gamma, gbeta, ggamma, scale=None, out_hw=None, x2=True, total_rows=None):
+    """ehm_bn2d_train_bwd_zbar: float32 [N,H,W,C] = scale gamma invstd (G - betabar / R - xhat gammabar / R); dense, or (out_hw) zero-dilated like gate().
+    total_rows (data parallel): R = all ranks' rows, with all ranks' betabar / gammabar (ehm_bn2d_train_bwd_zbar_rows); None: R = N Ho Wo."""
     N, Ho, Wo = shape
     H, W = (Ho, Wo) if out_hw is None else out_hw
     out = torch.empty(N, H, W, Cn, device=G.device)
     z2 = z.view(-1, Cn)
-    _lib.api().ehm_bn2d_train_bwd_zbar(G, z2, 1 if x2 else 0, z2.shape[0], mean, invstd, gamma, gbeta, ggamma, scale, out, N, Ho, Wo, Cn, H, W,
-                                       _lib.stream_ptr())
+    A, s = _lib.api(), _lib.stream_ptr()
+    if total_rows is None:
+        A.ehm_bn2d_train_bwd_zbar(G, z2, 1 if x2 else 0, z2.shape[0], mean, invstd, gamma, gbeta, ggamma, scale, out, N, Ho, Wo, Cn, H, W, s)
+    else:
+        A.ehm_bn2d_train_bwd_zbar_rows(G, z2, 1 if x2 else 0, z2.shape[0], mean, invstd, gamma, gbeta, ggamma, scale, out, N, Ho, Wo, Cn, H, W,
+                                       int(total_rows), s)
     return out
 
 
@@ -362,6 +394,16 @@ def _train_step(U, img, rec, need, res):
     gradient - (wbar, gammabar, betabar) into res[i] -, zbar brought into the engine's range (dense in place, or made again zero-dilated) for the data
     gradient on the raw weight's pack, built per call."""
     hook = _train_debug_hook
+    sync = rec.sync
+
+    def sums(G, z, zs, Cn, mean, invstd, x2=True):
+        """-> (betabar, gammabar for zbar; betabar, gammabar as parameter gradients; zbar's R or None): one process - the same pair twice; data parallel -
+        all ranks' sums over all ranks' rows, and this rank's own sums, which the gradient sum over the ranks completes"""
+        pixels = zs[0] * zs[1] * zs[2]
+        if sync is None:
+            gb, gg = bn_sums(G, z, pixels, Cn, mean, invstd, x2=x2)
+            return gb, gg, gb, gg, None
+        return (*bn_sums(G, z, pixels, Cn, mean, invstd, x2=x2, sync=sync), _sync_rows(sync, pixels)[1])
 
     def gate_(g, y, shape, Cn, per_image):
         return (gate(g, y, shape, Cn, None, per_image=per_image), g if hook is not None else None), None
@@ -372,24 +414,24 @@ def _train_step(U, img, rec, need, res):
         G, g_in = gated
         z, zs, mean, _, invstd = rec.bn[i]
         Co = conv.out_channels
-        gbeta, ggamma = bn_sums(G, z, zs[0] * zs[1] * zs[2], Co, mean, invstd)
-        Z = bn_zbar(G, z, zs, Co, mean, invstd, _lib.f32(bn.weight), gbeta, ggamma)
+        gbeta, ggamma, pbeta, pgamma, R = sums(G, z, zs, Co, mean, invstd)
+        Z = bn_zbar(G, z, zs, Co, mean, invstd, _lib.f32(bn.weight), gbeta, ggamma, total_rows=R)
         n = need[i] or (False, False, False)
         gw = wgrad(Z, x, x_shape, conv.in_channels, Co, conv.kernel_size[0], conv.stride[0], conv.padding[0], True, False)[0] if n[0] else None
         inv = 1.0 / cum
-        res[i] = (gw * inv if n[0] else None, ggamma * inv if n[1] else None, gbeta * inv if n[2] else None)
+        res[i] = (gw * inv if n[0] else None, pgamma * inv if n[1] else None, pbeta * inv if n[2] else None)
         if hook is not None:
             hook.append((i, g_in, cum, Z.clone()))
-        return Z, gbeta, ggamma
+        return Z, gbeta, ggamma, R
 
     def operand(i, gated, state, out_hw, g):
         """zbar times s = pow2_scale of the dense zbar"""
-        Z, gbeta, ggamma = state
+        Z, gbeta, ggamma, R = state
         s = pow2_scale(Z)
         if out_hw is None:
             return Z.mul_(s), s
         z, zs, mean, _, invstd = rec.bn[i]
-        return bn_zbar(gated[0], z, zs, Z.shape[3], mean, invstd, _lib.f32(U[i][1].weight), gbeta, ggamma, scale=s, out_hw=out_hw), s
+        return bn_zbar(gated[0], z, zs, Z.shape[3], mean, invstd, _lib.f32(U[i][1].weight), gbeta, ggamma, scale=s, out_hw=out_hw, total_rows=R), s
 
     def weight(i):
         return dgrad_weight(U[i][0].weight.detach().float())
@@ -407,18 +449,18 @@ def _train_step(U, img, rec, need, res):
         _, zs, mean, _, invstd = rec.bn[0]
         wt = conv.weight.detach().float().reshape(64, 147).t().contiguous()
         z = stem_preact(img, wt, torch.zeros(64, device=dev))                       # the raw one: the BatchNorm's input
-        gbeta, ggamma = bn_sums(gz, z, zs[0] * zs[1] * zs[2], 64, mean, invstd, x2=False)
+        gbeta, ggamma, pbeta, pgamma, R = sums(gz, z, zs, 64, mean, invstd, x2=False)
         inv = 1.0 / cum
         gw = None
         if n0[0] or hook is not None:
-            Z0 = bn_zbar(gz, z, zs, 64, mean, invstd, _lib.f32(bn.weight), gbeta, ggamma, x2=False)
+            Z0 = bn_zbar(gz, z, zs, 64, mean, invstd, _lib.f32(bn.weight), gbeta, ggamma, x2=False, total_rows=R)
             ws = torch.empty(STEM_WGRAD_WS_FLOATS, device=dev)
             gw = torch.empty(64, 147, device=dev)
             A.ehm_resnet_stem_wgrad(img, Z0, gw, None, N, H, W, ws, ws.numel() * 4, _lib.stream_ptr())
             gw = gw.view(64, 3, 7, 7) * inv
             if hook is not None:
                 hook.append((0, g, cum, Z0, gz))
-        res[0] = (gw if n0[0] else None, ggamma * inv if n0[1] else None, gbeta * inv if n0[2] else None)
+        res[0] = (gw if n0[0] else None, pgamma * inv if n0[1] else None, pbeta * inv if n0[2] else None)
 
     return SimpleNamespace(gate=gate_, head=head, operand=operand, weight=weight, stem=stem)
 

@@ -274,6 +274,26 @@ int ehm_gcn_train_bwd_epilogue(const ehm_gcn* h, int conv, const float* zbar, co
 int ehm_gcn_train_bwd_params_workspace_bytes(const ehm_gcn* h, int conv, int bodies, int64_t* bytes);
 int ehm_gcn_train_bwd_params(const ehm_gcn* h, int conv, const float* zbar, const float* A, const float* pre, int ld_pre, int bodies, float* gM,
                              float* gadj2, void* workspace, int64_t workspace_bytes, void* stream);
+/* Data parallel: the batch's rows are spread over `world` ranks (at most 64), rank r holds R_r = 24 bodies_r of them.  Each rank runs the passes above on
+ * its own rows and stops at local [2][N] float64 ON THE DEVICE; the caller all-gathers them into gathered [world][2][N] (ONE collective per BatchNorm each
+ * way) and every rank merges that buffer in rank order: all ranks get the same bits.  rows [world] int64 ON THE HOST: every R_r (>= 24, a multiple of 24;
+ * together >= 2 rows).  With world == 1 a local + merge pair writes the bits of ehm_gcn_train_stats / ehm_gcn_train_bn_backward.
+ *   stats_local: local = (mu_r, M2_r = sum (z - mu_r)^2), two-pass; have_sums as above; no running-statistic update.
+ *   stats_merge: R = sum R_r,  mu = mu_0 + sum R_r (mu_r - mu_0) / R,  M2 = sum M2_r + sum R_r (mu_r - mu)^2  (Chan et al.; nothing cancels when the
+ *                ranks' means lie many sigma apart),  var = M2 / R -> mean, invstd and the running update with the GLOBAL R (unbiased by R / (R - 1)).
+ *   bwd_local:   local = (sum vbar, sum vbar xhat) with the MERGED mean / invstd.
+ *   bwd_merge:   the ranks' sums added in rank order -> zbar with the global R.  gbn_bias / gbn_weight (either may be NULL) receive rank `rank`'s OWN sums
+ *                (float32 of gathered[rank]): summed over the ranks by the caller's gradient all-reduce they are betabar / gammabar.  rows[rank] must be
+ *                24 bodies. */
+int ehm_gcn_train_stats_local(const ehm_gcn* h, int conv, const float* z, int bodies, int have_sums, double* local, void* workspace,
+                              int64_t workspace_bytes, void* stream);
+int ehm_gcn_train_stats_merge(const ehm_gcn* h, int conv, const double* gathered, const int64_t* rows, int world, double eps, double momentum, float* mean,
+                              float* invstd, float* running_mean, float* running_var, void* stream);
+int ehm_gcn_train_bwd_local(const ehm_gcn* h, int conv, const float* gout, const float* gate, const float* z, const float* mean, const float* invstd,
+                            int bodies, double* local, void* workspace, int64_t workspace_bytes, void* stream);
+int ehm_gcn_train_bwd_merge(const ehm_gcn* h, int conv, const double* gathered, const int64_t* rows, int world, int rank, const float* gout,
+                            const float* gate, const float* z, const float* mean, const float* invstd, int bodies, float* zbar, float* gbn_weight,
+                            float* gbn_bias, void* workspace, int64_t workspace_bytes, void* stream);
 
 /* ------------------------------------------------------------------ scene PointNet (conditioning) ----------- */
 /* Building blocks of ResnetPointnet.forward (models/respointnet.py:33-59, ResnetBlockFC :89-97) on the split-f16
@@ -424,6 +444,26 @@ int ehm_bn2d_train_bwd_sums(const float* G, const void* z, int z_is_x2, int64_t 
 int ehm_bn2d_train_bwd_zbar(const float* G, const void* z, int z_is_x2, int64_t z_rows, const float* mean, const float* invstd, const float* gamma,
                             const float* gbeta, const float* ggamma, const float* scale, float* out, int N, int Ho, int Wo, int C, int H, int W,
                             void* stream);
+/* Data parallel, as the ehm_gcn_train_*_local / _merge entries: local [2][C] float64 on the device, gathered [world][2][C], rows [world] int64 on the host
+ * (each rank's pixel count R_r >= 1; together >= 2), world <= 64.  A rank's `pixels` may be 1 here; float32 rows need C % 8 == 0 only (X2: C % 32 == 0).
+ * The workspace is that of ehm_bn2d_train_workspace_bytes(max(pixels, 2), C rounded up to 32).  With world == 1, local + merge write the bits of
+ * ehm_bn2d_train_stats / ehm_bn2d_train_bwd_sums, and zbar_rows with total_rows = N Ho Wo those of ehm_bn2d_train_bwd_zbar.
+ *   stats_local: local = (mu_r, M2_r), two-pass, no running update.     stats_merge: Chan et al.'s merge in rank order -> mean, var, invstd; the running
+ *   update and *num_batches_tracked += 1 with the GLOBAL R.             bwd_local: local = (sum G, sum G xhat) with the merged mean / invstd.
+ *   bwd_merge: gbeta / ggamma = the ranks' sums added in rank order (for zbar_rows); gbeta_own / ggamma_own (either may be NULL) = float32 of rank `rank`'s
+ *   own sums, the parameter gradients that the caller's gradient all-reduce completes.
+ *   bwd_zbar_rows: ehm_bn2d_train_bwd_zbar with R = total_rows (all ranks' rows; >= 2 and >= N Ho Wo) instead of N Ho Wo. */
+int ehm_bn2d_train_stats_local(const void* z, int z_is_x2, int64_t z_rows, int64_t pixels, int C, double* local, void* workspace, int64_t workspace_bytes,
+                               void* stream);
+int ehm_bn2d_train_stats_merge(const double* gathered, const int64_t* rows, int world, int C, double eps, double momentum, float* mean, float* var,
+                               float* invstd, float* running_mean, float* running_var, int64_t* num_batches_tracked, void* stream);
+int ehm_bn2d_train_bwd_local(const float* G, const void* z, int z_is_x2, int64_t z_rows, int64_t pixels, int C, const float* mean, const float* invstd,
+                             double* local, void* workspace, int64_t workspace_bytes, void* stream);
+int ehm_bn2d_train_bwd_merge(const double* gathered, int world, int rank, int C, float* gbeta, float* ggamma, float* gbeta_own, float* ggamma_own,
+                             void* stream);
+int ehm_bn2d_train_bwd_zbar_rows(const float* G, const void* z, int z_is_x2, int64_t z_rows, const float* mean, const float* invstd, const float* gamma,
+                                 const float* gbeta, const float* ggamma, const float* scale, float* out, int N, int Ho, int Wo, int C, int H, int W,
+                                 int64_t total_rows, void* stream);
 
 /* NHWC convolution + bias (+ identity) + ReLU as an implicit GEMM on the f16 matrix cores with f32-grade accuracy (hi/lo split
  * operands, f32 accumulate): y[n,ho,wo,co] = act(sum x[n, ho*s-p+kh, wo*s-p+kw, ci] w[co,kh,kw,ci] + bias[co] (+ residual)).
