@@ -50,10 +50,25 @@ class ConvWeights:
         return self._bwd
 
 
+def _xt_g(X, G, rows, K, N):
+    """X[:rows, :K]^T G[:, :N] -> a view [K, N] of the engine's result: X^T as the rows, G^T packed at run time as the weight operand (G already carries its
+    power of two).  The contraction runs over the rows: padded to the engine's K granule with zeros."""
+    dev = X.device
+    rp = round_up(rows, 32)
+    alloc = lambda r: torch.empty(r, rp, device=dev) if rp == rows else torch.zeros(r, rp, device=dev)
+    Xt = alloc(X.shape[1])
+    Xt[:, :rows] = X[:rows].t()
+    Gt = alloc(N) if N % 128 == 0 else torch.zeros(round_up(N, 128), rp, device=dev)
+    Gt[:N, :rows] = G[:, :N].t()
+    Gp = torch.empty_like(Gt)
+    _lib.api().ehm_split_pack(Gt, Gp, Gt.shape[0], rp, rp, 1.0, _lib.stream_ptr())
+    return gemm_rows(Xt, Packed(Gp, 1.0, round_up(N, 8), None))[:K, :N]
+
+
 def _gemm_grads(epilogue, cw, X, rows, need_x, need_w, out, res):
     """epilogue(G) writes a conv's G = [h0bar | h1bar] [rows, cw.ldg]; then the two GEMMs behind it: res['x'] = G [W0; W1]^T (need_x),
     res['W'] = X^T G (need_w)."""
-    A, s, N, K, dev = _lib.api(), _lib.stream_ptr(), cw.N, cw.K, X.device
+    N, K, dev = cw.N, cw.K, X.device
     G = torch.empty(rows, cw.ldg, device=dev) if cw.ldg == 2 * N else torch.zeros(rows, cw.ldg, device=dev)
     epilogue(G)
     sc = pow2_scale(G)
@@ -63,15 +78,7 @@ def _gemm_grads(epilogue, cw, X, rows, need_x, need_w, out, res):
         xb = gemm_rows(G, cw.bwd).mul_(inv)        # [rows, K rounded up to the engine's 8-column granule]
         res["x"] = xb if xb.shape[1] == K else xb[:, :K].contiguous()
     if need_w:
-        rp = round_up(rows, 32)                         # the contraction runs over the rows: padded to the engine's K granule with zeros
-        alloc = lambda r: torch.empty(r, rp, device=dev) if rp == rows else torch.zeros(r, rp, device=dev)
-        Xt = alloc(X.shape[1])
-        Xt[:, :rows] = X[:rows].t()
-        Gt = alloc(2 * N) if 2 * N % 128 == 0 else torch.zeros(round_up(2 * N, 128), rp, device=dev)
-        Gt[:2 * N, :rows] = G[:, :2 * N].t()
-        Gp = torch.empty_like(Gt)
-        A.ehm_split_pack(Gt, Gp, Gt.shape[0], rp, rp, 1.0, s)
-        Wg = gemm_rows(Xt, Packed(Gp, 1.0, round_up(2 * N, 8), None))[:K, :2 * N].mul_(inv)          # [K, 2N]
+        Wg = _xt_g(X, G, rows, K, 2 * N).mul_(inv)          # [K, 2N]
         gW = out.get("W")
         if gW is None:
             gW = torch.empty(2, K, N, device=dev)
@@ -178,6 +185,136 @@ def train_conv_backward(h, conv, cw, X, st, gate, gout, bodies, need_x=True, nee
     return res
 
 
+# ---------------------------------------------------------------------------------------------- the non-local block (csrc/nonlocal_bwd.hip)
+# NONLocalBlock2D on the joint axis (modulated_gcn.py:104-110, nets/non_local_embedded_gaussian.py:62-85) on float32 rows X [rows, hid]:
+#     qkv = X [theta | phi | g]^T + b,  y = softmax(theta phi^T) g per body,  u = y W0^T + b0,  out = BatchNorm2d(u) + X
+# behind ModulatedGCN.nonlocal_grad.  The gradients come back under these names, the order in which ModulatedGCN.grad_parameters appends them:
+NONLOCAL_PARAMS = ("theta.weight", "theta.bias", "phi.weight", "phi.bias", "g.weight", "g.bias", "W.0.weight", "W.0.bias", "W.1.weight", "W.1.bias")
+
+
+class NonLocalWeights:
+    """The block's four packed GEMM operands, made on first use from its 1x1 convs (the engine contracts over an operand's columns): `qkv_fwd` =
+    [theta; phi; g] [3 Ci, hid] with its bias and `w0_fwd` = W.0 [hid, Ci] with its bias for the forward, `qkv_bwd`, `w0_bwd` = their transposes for the
+    two data gradients."""
+
+    def __init__(self, nl, dev):
+        f = lambda t: _lib.f32(t, dev)
+        self.Ci, self.hid = nl.g.weight.shape[0], nl.g.weight.shape[1]
+        self.wqkv = torch.cat([f(nl.theta.weight), f(nl.phi.weight), f(nl.g.weight)], 0).flatten(1)       # [3 Ci, hid]
+        self.bqkv = torch.cat([f(nl.theta.bias), f(nl.phi.bias), f(nl.g.bias)], 0)
+        self.w0, self.b0 = f(nl.W[0].weight).flatten(1), f(nl.W[0].bias)                                    # [hid, Ci]
+        if self.hid % 64 or self.w0.shape != (self.hid, self.Ci) or 2 * self.Ci != self.hid:
+            raise _lib.EgoHMRHipError(f"the non-local block's backward is built for hid_dim % 64 == 0 and inter_channels = hid_dim / 2 (got {self.hid}, {self.Ci})")
+        self._packed = {}
+
+    def _get(self, name, make):
+        if name not in self._packed:
+            self._packed[name] = make()
+        return self._packed[name]
+
+    qkv_fwd = property(lambda self: self._get("qkv_fwd", lambda: pack_weight(self.wqkv, self.bqkv)))
+    w0_fwd = property(lambda self: self._get("w0_fwd", lambda: pack_weight(self.w0, self.b0)))
+    qkv_bwd = property(lambda self: self._get("qkv_bwd", lambda: pack_weight(self.wqkv.t().contiguous())))
+    w0_bwd = property(lambda self: self._get("w0_bwd", lambda: pack_weight(self.w0.t().contiguous())))
+
+
+def _column_sums(G, rows, Cn):
+    """sum over the rows of G float32 [rows, Cn] -> [Cn], in the fixed order of ehm_bn2d_train_bwd_sums (its gbeta; its ggamma is not used)."""
+    from . import trunk_grad
+    zero = torch.zeros(Cn, device=G.device)
+    return trunk_grad.bn_sums(G, G, rows, Cn, zero, zero, x2=False)[0]
+
+
+def nonlocal_forward(nw, bn, X, bodies, train, sync=None, out=None, save=True):
+    """The block on X [>= rows, hid] float32 rows (rows = 24 bodies).  bn: its BatchNorm2d (W.1).  train False: frozen running statistics; True: the batch's
+    (ehm_bn2d_train_stats on float32 rows, pixels = rows), with running_mean / running_var / num_batches_tracked updated as nn.BatchNorm2d updates them;
+    sync (a dist.StatSync): the statistics of ALL ranks' rows (ehm_bn2d_train_stats_local, one all-gather, _stats_merge).  out: a float32 buffer of at
+    least rows x hid for the result (None: a new one).  Returns (out, st): st what nonlocal_backward needs besides X, or None without `save`."""
+    from . import trunk_grad
+    A, s, dev = _lib.api(), _lib.stream_ptr(), X.device
+    rows, hid, Ci = bodies * 24, nw.hid, nw.Ci
+    qkv = gemm_rows(X, nw.qkv_fwd, rows)
+    y = torch.empty(rows, Ci, device=dev)
+    A.ehm_nonlocal_attention(qkv, y, bodies, Ci, s)
+    u = gemm_rows(y, nw.w0_fwd, rows)
+    gamma, beta = _lib.f32(bn.weight, dev), _lib.f32(bn.bias, dev)
+    if train:
+        mean, _, invstd = trunk_grad.bn_stats(u, rows, hid, bn, x2=False, sync=sync)
+        for t in (bn.running_mean, bn.running_var, bn.num_batches_tracked):      # the kernel wrote them through their pointers: tell torch (nonlocal_packed's key)
+            torch.autograd.graph.increment_version(t)
+    else:
+        mean = _lib.f32(bn.running_mean, dev)
+        invstd = torch.rsqrt(bn.running_var.detach().to(dev).double() + bn.eps).float()
+    out = torch.empty(rows, hid, device=dev) if out is None else out
+    A.ehm_nonlocal_bn_residual(u, mean, invstd, gamma, beta, X, out, rows, hid, s)
+    return out, (dict(qkv=qkv, y=y, u=u, mean=mean, invstd=invstd, gamma=gamma, train=bool(train), sync=sync if train else None) if save else None)
+
+
+def nonlocal_backward(nw, X, st, gout, bodies, need_x=True, need=(True,) * 10):
+    """VJP of nonlocal_forward.  X: its input; st: its record; gout [rows, hid] float32; need: which of NONLOCAL_PARAMS are wanted.  Returns a dict with 'x'
+    [rows, hid] (need_x; the residual's share included) and the wanted parameter gradients under their NONLOCAL_PARAMS names, shaped like the parameters.
+    The bias gradients are fixed-order column sums (under train-mode statistics that of 'W.0.bias' is zero to rounding: the batch mean removes that bias);
+    under sync the BatchNorm's data gradient runs on all ranks' sums (ehm_bn2d_train_bwd_local / _merge / _zbar_rows) and every parameter gradient is
+    this rank's own, which the caller's sum completes."""
+    from . import trunk_grad
+    A, s, dev = _lib.api(), _lib.stream_ptr(), gout.device
+    rows, hid, Ci = bodies * 24, nw.hid, nw.Ci
+    need = dict(zip(NONLOCAL_PARAMS, need))
+    res = {}
+    sync = st["sync"]
+    # BatchNorm2d
+    if st["train"]:
+        sums = trunk_grad.bn_sums(gout, st["u"], rows, hid, st["mean"], st["invstd"], x2=False, sync=sync)
+        gbeta, ggamma = sums[:2]
+        own_b, own_g = sums[2:] if sync is not None else sums
+        total = None if sync is None else 24 * sync.total
+    else:
+        gbeta = ggamma = torch.zeros(hid, device=dev)                      # frozen statistics: ubar = gamma invstd G
+        total = None
+        if need["W.1.weight"] or need["W.1.bias"]:
+            own_b, own_g = trunk_grad.bn_sums(gout, st["u"], rows, hid, st["mean"], st["invstd"], x2=False)
+    if need["W.1.weight"]:
+        res["W.1.weight"] = own_g
+    if need["W.1.bias"]:
+        res["W.1.bias"] = own_b
+    upstream = need_x or any(need[k] for k in NONLOCAL_PARAMS[:8])
+    if not upstream:
+        return res
+    ubar = trunk_grad.bn_zbar(gout, st["u"], (rows, 1, 1), hid, st["mean"], st["invstd"], st["gamma"], gbeta, ggamma, x2=False,
+                              total_rows=total).view(rows, hid)
+    # W.0: u = y W0^T + b0
+    if need["W.0.bias"]:
+        res["W.0.bias"] = _column_sums(ubar, rows, hid)
+    sc = pow2_scale(ubar)
+    ubar.mul_(sc)
+    inv = 1.0 / sc
+    if need["W.0.weight"]:
+        res["W.0.weight"] = _xt_g(st["y"], ubar, rows, Ci, hid).mul_(inv).t().reshape(hid, Ci, 1, 1).contiguous()
+    if not (need_x or any(need[k] for k in NONLOCAL_PARAMS[:6])):
+        return res
+    ybar = gemm_rows(ubar, nw.w0_bwd).mul_(inv)                            # [rows, Ci]
+    # the attention
+    gqkv = torch.empty(rows, 3 * Ci, device=dev)
+    A.ehm_nonlocal_attention_backward(st["qkv"], ybar, gqkv, bodies, Ci, s)
+    # [theta | phi | g]: qkv = X Wqkv^T + b
+    if any(need[k] for k in ("theta.bias", "phi.bias", "g.bias")):
+        gb = _column_sums(gqkv, rows, 3 * Ci)
+        for i, k in enumerate(("theta.bias", "phi.bias", "g.bias")):
+            if need[k]:
+                res[k] = gb[i * Ci:(i + 1) * Ci].contiguous()
+    sc = pow2_scale(gqkv)
+    gqkv.mul_(sc)
+    inv = 1.0 / sc
+    if any(need[k] for k in ("theta.weight", "phi.weight", "g.weight")):
+        gw = _xt_g(X, gqkv, rows, hid, 3 * Ci).mul_(inv).t()               # [3 Ci, hid]
+        for i, k in enumerate(("theta.weight", "phi.weight", "g.weight")):
+            if need[k]:
+                res[k] = gw[i * Ci:(i + 1) * Ci].reshape(Ci, hid, 1, 1).contiguous()
+    if need_x:
+        res["x"] = gemm_rows(gqkv, nw.qkv_bwd).mul_(inv).add_(gout)       # + the residual's gradient
+    return res
+
+
 # ---------------------------------------------------------------------------------------------- ModulatedGCN.forward with a backward
 # What a forward below keeps for the backward: dict(h, cws, B, x_dtype, convs): the handle and the ConvWeights it ran on, and one record (X, gate, st) per conv
 # in the handle's order (input conv, hidden convs, output conv) - X [>= rows, Kp] the conv's float32 input, gate its activation before the residual add
@@ -195,8 +332,9 @@ def forward_saving(m, x):
     happens on the float32 copies, so that every conv's ReLU output - its gate - exists on its own), then gconv_output.  Returns (out [B, 24, 6], saved)."""
     if m.precision == "f16":
         raise _lib.EgoHMRHipError(m.GRAD_F16)
-    if m.nonlocal_layer:
-        raise NotImplementedError("ModulatedGCN.forward: the non-local block has no backward; the autograd route needs nonlocal_layer=False")
+    if m.nonlocal_layer and not m.nonlocal_grad:
+        raise NotImplementedError("ModulatedGCN.forward: the non-local block has no backward; the autograd route needs nonlocal_layer=False"
+                                  " (or ModulatedGCN.nonlocal_grad = True, which turns the block's backward on)")
     A = _lib.api()
     dev = x.device
     hid, nh = m.hid_dim, 2 * m.num_layers
@@ -235,11 +373,16 @@ def forward_saving(m, x):
             convs += [(cur_f, y1_f, None), (y1_f, y2_f, None)]
             cur_f = y2_f + cur_f                              # modulated_gcn.py:42
             cur = to_mode(cur_f) if l + 2 < nh else cur_f
+        nl = None
+        if m.nonlocal_layer:                                   # modulated_gcn.py:104-110 (the output conv reads whole row tiles: zeros behind the rows)
+            nw = m.nonlocal_weights(dev)
+            feat, st = nonlocal_forward(nw, m.non_local.W[1], cur_f, B, False, out=torch.zeros(rows_pad, hid, device=dev))
+            nl, cur_f = (nw, cur_f, st), feat
         convs.append((cur_f, None, None))
         x0 = torch.empty(B, 144, device=dev)
         A.ehm_gcn_output_layer(h, cur_f, None, x0, B, 1, s)
         A.ehm_gcn_stack_status(h, s)
-    return x0.view(B, 24, 6), dict(h=h, cws=cws, B=B, x_dtype=x.dtype, convs=convs)
+    return x0.view(B, 24, 6), dict(h=h, cws=cws, B=B, x_dtype=x.dtype, convs=convs, nl=nl)
 
 
 @torch.no_grad()
@@ -289,17 +432,22 @@ def forward_train(m, x, save):
         for l in range(0, nh, 2):
             y1 = conv(l, cur, None, False)
             cur = conv(l + 1, y1, cur, l + 2 == nh)
+        nl = None
+        if m.nonlocal_layer:                                   # (behind nonlocal_grad: ModulatedGCN._check_train); its BatchNorm2d joins the ranks' statistics
+            nw = NonLocalWeights(m.non_local, dev)
+            feat, st = nonlocal_forward(nw, m.non_local.W[1], cur, B, True, sync=sync, out=torch.zeros(rows_pad, hid, device=dev), save=save)
+            nl, cur = (nw, cur, st), feat
         convs.append((cur, None, None))
         x0 = torch.empty(B, 144, device=dev)
         A.ehm_gcn_output_layer(h, cur, None, x0, B, 1, s)
         A.ehm_gcn_stack_status(h, s)
-    return x0.view(B, 24, 6), dict(h=h, cws=cws, B=B, x_dtype=x.dtype, convs=convs) if save else None
+    return x0.view(B, 24, 6), dict(h=h, cws=cws, B=B, x_dtype=x.dtype, convs=convs, nl=nl) if save else None
 
 
 class GCNFunction(torch.autograd.Function):
     """ModulatedGCN.forward (modulated_gcn.py:99-116, eval mode) with a backward: forward(module, x, *params) -> [B, 24, 6].  `params` is empty (gradient
     to x only) or ModulatedGCN.grad_parameters(): W, M, adj2, bias, bn.weight, bn.bias of the input conv and every hidden conv, then W, M, adj2, bias
-    of the output conv."""
+    of the output conv, then - a module with the non-local block, behind ModulatedGCN.nonlocal_grad - the block's ten (NONLOCAL_PARAMS)."""
 
     @staticmethod
     def forward(ctx, module, x, *params):
@@ -340,6 +488,15 @@ class GCNFunction(torch.autograd.Function):
 
         with _lib.on_device(gout.device):
             g = conv(last, _lib.f32(gout, gout.device).reshape(B * 24, 6))
+            if sv.get("nl") is not None:                # the non-local block between the last residual add and gconv_output: its ten parameters are appended
+                nw, X, st = sv["nl"]
+                base = 6 * last + 4
+                flags = tuple(bool(f) for f in pneed[base:base + 10]) if pneed else (False,) * 10
+                r = nonlocal_backward(nw, X, st, g, B, True, flags)
+                for k, name in enumerate(NONLOCAL_PARAMS):
+                    if flags[k]:
+                        grads[base + k] = r[name]
+                g = r["x"]
             # the residual blocks, last first: out = y2 + block input, y2 = gconv2(y1), y1 = gconv1(block input)
             for c2 in range(last - 1, 1, -2):
                 g = conv(c2 - 1, conv(c2, g)).add_(g)           # + the residual's gradient

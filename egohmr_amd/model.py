@@ -244,7 +244,24 @@ class ModulatedGCN(nn.Module):
         out = []
         for gc, bn in self._convs():
             out += [gc.W, gc.M, gc.adj2, gc.bias] + ([bn.weight, bn.bias] if bn is not None else [])
+        if self.nonlocal_layer and self.nonlocal_grad:          # appended (gcn_grad.NONLOCAL_PARAMS): the convs keep their 6 ci + k places
+            nl = self.non_local
+            out += [nl.theta.weight, nl.theta.bias, nl.phi.weight, nl.phi.bias, nl.g.weight, nl.g.bias, nl.W[0].weight, nl.W[0].bias, nl.W[1].weight, nl.W[1].bias]
         return out
+
+    # False: every route that needs a backward refuses a module with the non-local block, as ever.  True: the block runs on those routes too, between the last
+    # residual add and gconv_output, with its backward in HIP (gcn_grad.nonlocal_forward / nonlocal_backward; csrc/nonlocal_bwd.hip): grad_parameters() ends with
+    # its ten parameters, under .train() + train_batchnorm its BatchNorm2d (W.1) runs on batch statistics - all ranks' behind stat_sync.  Inference does not
+    # depend on it
+    nonlocal_grad = False
+
+    def nonlocal_weights(self, device):
+        """gcn_grad.NonLocalWeights of the block for the eval-mode autograd route: re-made when one of its conv parameters changes."""
+        nl = self.non_local
+        key = (str(device),) + tuple((p.data_ptr(), p._version) for m in (nl.theta, nl.phi, nl.g, nl.W[0]) for p in m.parameters())
+        if getattr(self, "_nlw_key", None) != key:
+            self._nlw, self._nlw_key = gcn_grad.NonLocalWeights(nl, device), key
+        return self._nlw
 
     def _wants_grad(self, x):
         return torch.is_grad_enabled() and (x.requires_grad or (self.grad_params and any(p.requires_grad for p in self.grad_parameters())))
@@ -261,8 +278,9 @@ class ModulatedGCN(nn.Module):
         """What the train-mode route cannot run, refused before any device call."""
         if self.p_dropout is not None and self.p_dropout != 0:
             raise NotImplementedError(f"ModulatedGCN.forward: the train-mode route has no dropout (p_dropout = {self.p_dropout}); use p_dropout = None or 0")
-        if self.nonlocal_layer:
-            raise NotImplementedError("ModulatedGCN.forward: the non-local block has no backward; the train-mode route needs nonlocal_layer=False")
+        if self.nonlocal_layer and not self.nonlocal_grad:
+            raise NotImplementedError("ModulatedGCN.forward: the non-local block has no backward; the train-mode route needs nonlocal_layer=False"
+                                      " (or ModulatedGCN.nonlocal_grad = True, which turns the block's backward on)")
         if self.precision == "f16":
             raise _lib.EgoHMRHipError(self.GRAD_F16)
         for _, bn in self._convs()[:-1]:
@@ -271,6 +289,14 @@ class ModulatedGCN(nn.Module):
                                           "BatchNorm1d(momentum=None) and track_running_stats=False are not built")
             if bn.training != self.training:
                 raise ValueError("ModulatedGCN.forward: a BatchNorm1d of the denoiser is in eval mode while the module is in training mode; "
+                                 "call .train() / .eval() on the whole ModulatedGCN")
+        if self.nonlocal_layer:
+            bn = self.non_local.W[1]
+            if bn.momentum is None or not bn.track_running_stats:
+                raise NotImplementedError("ModulatedGCN.forward: the train-mode route updates the running statistics with a fixed momentum; "
+                                          "the non-local block's BatchNorm2d(momentum=None) and track_running_stats=False are not built")
+            if bn.training != self.training:
+                raise ValueError("ModulatedGCN.forward: the non-local block's BatchNorm2d is in eval mode while the module is in training mode; "
                                  "call .train() / .eval() on the whole ModulatedGCN")
 
     def _check_input(self, x):
@@ -291,8 +317,8 @@ class ModulatedGCN(nn.Module):
         """modulated_gcn.py:99-116 in eval mode on the HIP kernels: x [B, 24, in_dim] -> [B, 24, out_dim=6].
 
         With grad mode on and x.requires_grad - or `grad_params` set and a parameter that requires grad - the result carries a grad_fn: the same convs one
-        launch each with their backward in HIP (gcn_grad.GCNFunction: eval-mode BatchNorm, first derivatives, precision 'f16x3' or 'f32', no non-local
-        block).  Every other call runs the route below and returns a tensor without grad_fn."""
+        launch each with their backward in HIP (gcn_grad.GCNFunction: eval-mode BatchNorm, first derivatives, precision 'f16x3' or 'f32'; the non-local
+        block only behind `nonlocal_grad`).  Every other call runs the route below and returns a tensor without grad_fn."""
         self._check_input(x)
         if self.training:                                    # train_batchnorm (_check_input)
             if self._wants_grad(x):
@@ -540,8 +566,9 @@ class EgoHMR(nn.Module):
     def _check_trainable(self):
         """What the training route cannot run, refused before any device call."""
         dm = self.diffusion_model
-        if dm.nonlocal_layer:
-            raise NotImplementedError("EgoHMR.frozen_trunk_training: the non-local block has no backward; the training route needs gcn_nonlocal_layer=False")
+        if dm.nonlocal_layer and not dm.nonlocal_grad:
+            raise NotImplementedError("EgoHMR.frozen_trunk_training: the non-local block has no backward; the training route needs gcn_nonlocal_layer=False"
+                                      " (or diffusion_model.nonlocal_grad = True, which turns the block's backward on)")
         if self.gcn_precision == "f16" or dm.precision == "f16":
             raise _lib.EgoHMRHipError(dm.GRAD_F16)
 

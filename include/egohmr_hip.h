@@ -527,6 +527,17 @@ int ehm_x2_group_mean(const void* X, float* Y, int groups, int rows_per_group, i
  *   qkv [bodies*24, 3*Ci] float32 rows = [theta | phi | g] (one 1x1-conv GEMM, e.g. ehm_conv_nhwc_split with H = W = 1);
  *   y [bodies*24, Ci].  The W conv + BatchNorm + residual that follow are another ehm_conv_nhwc_split call. */
 int ehm_nonlocal_attention(const float* qkv, float* y, int64_t bodies, int Ci, void* stream);
+/* Its vector-Jacobian product (csrc/nonlocal_bwd.hip; nets/non_local_embedded_gaussian.py:68-79 - f = matmul(theta_x, phi_x), f_div_C = softmax(f, -1),
+ * y = matmul(f_div_C, g_x) - on the joint axis, modulated_gcn.py:104-110):  qkv as above, gy [bodies*24, Ci] the cotangent of y ->
+ * gqkv [bodies*24, 3*Ci] = [thetabar | phibar | gbar].  Per body P = softmax(theta phi^T) is recomputed with the max-subtraction (no saved probabilities),
+ * Pbar = gy g^T, D_a = sum_b P_ab Pbar_ab, Fbar = P (.) (Pbar - D), thetabar = Fbar phi, phibar = Fbar^T theta, gbar = P^T gy.  One block per body, no
+ * atomics, every sum in index order: two calls on the same inputs give the same bits.  Any Ci > 0; bodies in [1, 2^31). */
+int ehm_nonlocal_attention_backward(const float* qkv, const float* gy, float* gqkv, int64_t bodies, int Ci, void* stream);
+/* The block's tail for the autograd route (non_local_embedded_gaussian.py:81-82: W_y = self.W(y), z = W_y + x), BatchNorm2d unfolded:
+ * out[r,c] = (u[r,c] - mean[c]) invstd[c] gamma[c] + beta[c] + res[r,c] on float32 rows [rows, C]; mean / invstd: the batch's (ehm_bn2d_train_stats) or the
+ * running ones.  out may be res. */
+int ehm_nonlocal_bn_residual(const float* u, const float* mean, const float* invstd, const float* gamma, const float* beta, const float* res,
+                             float* out, int64_t rows, int C, void* stream);
 
 /* ------------------------------------------------------------------ sampler steps ------------- */
 /* diffusion/gaussian_diffusion.py:217-220 + :333-336 (p_sample) and :378-385 (p_sample_with_grad):
