@@ -6,9 +6,11 @@
 //              running_mean / running_var (unbiased) / num_batches_tracked as nn.BatchNorm2d updates them, in the same launch sequence.
 //              Two passes (the mean first, then the centred squares), float64 accumulators: correct to float32 rounding at |mu| / sigma = 1e3.
 //   backward:  with G = g (.) [y > 0] (ehm_conv_bwd_gate) and xhat = (z - mu) invstd:
-//              betabar = sum_p G,  gammabar = sum_p G xhat                                                  bn2d_sum_kernel + bn2d_bwd_finish_kernel
+//              betabar = sum_p G,  gammabar = sum_p G xhat                                                  bn2d_sum_kernel + bn2d_bwd_reduce_kernel
 //              zbar = *scale gamma invstd (G - betabar / R - xhat gammabar / R)                             bn2d_zbar_kernel (dense, or zero-dilated)
 // Data parallel (the *_local / *_merge entries at the end): each rank stops at [2][C] float64, the caller all-gathers, every rank merges in rank order.
+// A pair is the one-call entry's own body cut at the collective: bn2d_moments / bn2d_bwd_partials issue the passes for both, and the one finish kernel
+// and the one reduce kernel write out for both, from the call's own partial sums or from the gathered buffer (BnMoments, common.h).
 // No atomics: a block owns a run of pixels that is a function of the shape alone, a lane adds its rows in row order, the row lanes and then the runs
 // are added in index order - two calls on the same inputs give the same bits.
 #include "common.h"
@@ -103,61 +105,29 @@ __global__ __launch_bounds__(256) void bn2d_sum_kernel(const void* __restrict__ 
   }
 }
 
-__device__ __forceinline__ double runs_sum(const double* __restrict__ p, size_t stride, int n) {
-  double s = 0.0;
-  for (int k = 0; k < n; ++k) s += p[(size_t)k * stride];
-  return s;
-}
-
 __global__ __launch_bounds__(256) void bn2d_mean_finish_kernel(const double* __restrict__ part, double* __restrict__ mean_d, int C, int runs, double R) {
   const int t = blockIdx.x * 256 + threadIdx.x;
   if (t >= C) return;
-  mean_d[t] = runs_sum(part + t, (size_t)C, runs) / R;
+  mean_d[t] = ordered_sum(part + t, (size_t)C, runs) / R;
 }
 
-__global__ __launch_bounds__(256) void bn2d_stats_finish_kernel(const double* __restrict__ part, const double* __restrict__ mean_d, float* __restrict__ mean,
-                                                                float* __restrict__ var, float* __restrict__ invstd, float* __restrict__ running_mean,
-                                                                float* __restrict__ running_var, long long* __restrict__ tracked, int C, int runs,
-                                                                double R, double eps, double momentum) {
-  const int t = blockIdx.x * 256 + threadIdx.x;
-  if (t == 0 && tracked) *tracked += 1;
-  if (t >= C) return;
-  const double mu = mean_d[t], v = runs_sum(part + t, (size_t)C, runs) / R;
-  mean[t] = (float)mu;
-  var[t] = (float)v;
-  invstd[t] = (float)(1.0 / sqrt(v + eps));
-  if (running_mean) running_mean[t] = (float)((1.0 - momentum) * (double)running_mean[t] + momentum * mu);
-  if (running_var) running_var[t] = (float)((1.0 - momentum) * (double)running_var[t] + momentum * (v * R / (R - 1.0)));
-}
-
-__global__ __launch_bounds__(256) void bn2d_bwd_finish_kernel(const double* __restrict__ part, float* __restrict__ gbeta, float* __restrict__ ggamma, int C,
-                                                              int runs) {
-  const int t = blockIdx.x * 256 + threadIdx.x;
-  if (t >= C) return;
-  gbeta[t] = (float)runs_sum(part + t, (size_t)2 * C, runs);
-  ggamma[t] = (float)runs_sum(part + C + t, (size_t)2 * C, runs);
-}
-
-// a rank's own statistics: local[0][c] = its mean, local[1][c] = its sum of squares centred on that mean
-__global__ __launch_bounds__(256) void bn2d_local_stats_kernel(const double* __restrict__ part, const double* __restrict__ mean_d, double* __restrict__ local,
-                                                               int C, int runs) {
-  const int t = blockIdx.x * 256 + threadIdx.x;
-  if (t >= C) return;
-  local[t] = mean_d[t];
-  local[C + t] = runs_sum(part + t, (size_t)C, runs);
-}
-
-// every rank's (mean, M2) [world][2][C] -> what bn2d_stats_finish_kernel writes, for the whole batch's R rows
-__global__ __launch_bounds__(256) void bn2d_merge_stats_kernel(const double* __restrict__ gathered, RankRows rr, int world, float* __restrict__ mean,
-                                                               float* __restrict__ var, float* __restrict__ invstd, float* __restrict__ running_mean,
-                                                               float* __restrict__ running_var, long long* __restrict__ tracked, int C, double eps,
-                                                               double momentum) {
+// (mean, M2 = sum of squares centred on that mean) of this call's own rows or of every rank's (BnMoments, common.h) -> local[0][c] = mean, local[1][c] = M2
+// and nothing else (a rank's share), or what nn.BatchNorm2d keeps of the batch: mean, var, invstd (float32), the running statistics and its call count
+__global__ __launch_bounds__(256) void bn2d_stats_finish_kernel(BnMoments src, double* __restrict__ local, float* __restrict__ mean, float* __restrict__ var,
+                                                                float* __restrict__ invstd, float* __restrict__ running_mean,
+                                                                float* __restrict__ running_var, long long* __restrict__ tracked, int C, double eps,
+                                                                double momentum) {
   const int t = blockIdx.x * 256 + threadIdx.x;
   if (t == 0 && tracked) *tracked += 1;
   if (t >= C) return;
   double mu, M2;
-  merge_moments(gathered + t, (size_t)2 * C, (size_t)C, rr, world, &mu, &M2);
-  const double R = rr.total, v = M2 / R;
+  moments_of(src, t, C, &mu, &M2);
+  if (local) {
+    local[t] = mu;
+    local[C + t] = M2;
+    return;
+  }
+  const double R = src.rr.total, v = M2 / R;
   mean[t] = (float)mu;
   var[t] = (float)v;
   invstd[t] = (float)(1.0 / sqrt(v + eps));
@@ -165,23 +135,24 @@ __global__ __launch_bounds__(256) void bn2d_merge_stats_kernel(const double* __r
   if (running_var) running_var[t] = (float)((1.0 - momentum) * (double)running_var[t] + momentum * (v * R / (R - 1.0)));
 }
 
-__global__ __launch_bounds__(256) void bn2d_local_bwd_kernel(const double* __restrict__ part, double* __restrict__ local, int C, int runs) {
+// A channel's `count` pairs (sum G, sum G xhat) p[k][2][C], added in index order: a call's runs, or every rank's sums.  With `local`: that pair [2][C] in
+// float64 and nothing else (a rank's share).  Without: gbeta / ggamma in float32 (zbar multiplies by 1 / R), and where asked for float32 of pair `own`
+// alone - a rank's OWN parameter gradients, which the caller's gradient all-reduce completes (the batch's sums there would count `world` times).
+__global__ __launch_bounds__(256) void bn2d_bwd_reduce_kernel(const double* __restrict__ p, int count, int own, int C, double* __restrict__ local,
+                                                              float* __restrict__ gbeta, float* __restrict__ ggamma, float* __restrict__ gbeta_own,
+                                                              float* __restrict__ ggamma_own) {
   const int t = blockIdx.x * 256 + threadIdx.x;
   if (t >= C) return;
-  local[t] = runs_sum(part + t, (size_t)2 * C, runs);
-  local[C + t] = runs_sum(part + C + t, (size_t)2 * C, runs);
-}
-
-// the ranks' sums added in rank order -> the whole batch's (gbeta, ggamma) for the zbar launch; the rank's own -> the parameter gradients
-__global__ __launch_bounds__(256) void bn2d_merge_bwd_kernel(const double* __restrict__ gathered, int world, int rank, float* __restrict__ gbeta,
-                                                             float* __restrict__ ggamma, float* __restrict__ gbeta_own, float* __restrict__ ggamma_own,
-                                                             int C) {
-  const int t = blockIdx.x * 256 + threadIdx.x;
-  if (t >= C) return;
-  gbeta[t] = (float)runs_sum(gathered + t, (size_t)2 * C, world);
-  ggamma[t] = (float)runs_sum(gathered + C + t, (size_t)2 * C, world);
-  if (gbeta_own) gbeta_own[t] = (float)gathered[(size_t)rank * 2 * C + t];
-  if (ggamma_own) ggamma_own[t] = (float)gathered[(size_t)rank * 2 * C + C + t];
+  const double sb = ordered_sum(p + t, (size_t)2 * C, count), sg = ordered_sum(p + C + t, (size_t)2 * C, count);
+  if (local) {
+    local[t] = sb;
+    local[C + t] = sg;
+    return;
+  }
+  gbeta[t] = (float)sb;
+  ggamma[t] = (float)sg;
+  if (gbeta_own) gbeta_own[t] = (float)p[(size_t)own * 2 * C + t];
+  if (ggamma_own) ggamma_own[t] = (float)p[(size_t)own * 2 * C + C + t];
 }
 
 struct ZbarArgs {
@@ -255,6 +226,56 @@ void launch_sum(bool x2, const BnPlan& pl, hipStream_t st, const void* z, const 
   else hipLaunchKernelGGL((bn2d_sum_kernel<false, MODE>), grid, dim3(256), 0, st, z, G, mean_d, mean, invstd, part, P, C, pl.run);
 }
 
+bool workspace_ok(const void* workspace, int64_t workspace_bytes, const BnPlan& pl, int C) {
+  return workspace && al16(workspace) && workspace_bytes >= bn_ws_doubles(pl, C) * (int64_t)sizeof(double);
+}
+
+// The launches every statistics entry starts with, and their checks: z -> its mean (float64) and the runs' sums of (z - mean)^2, both in the workspace
+int bn2d_moments(const void* z, int z_is_x2, const BnPlan& pl, int64_t pixels, int C, void* workspace, int64_t workspace_bytes, hipStream_t st,
+                 BnMoments* own) {
+  EHM_CHECK_ARG(z && al16(z) && (z_is_x2 == 0 || z_is_x2 == 1) && workspace_ok(workspace, workspace_bytes, pl, C));
+  double* part = (double*)workspace;
+  double* mean_d = part + (size_t)pl.runs * 2 * C;
+  launch_sum<0>(z_is_x2 != 0, pl, st, z, nullptr, nullptr, nullptr, nullptr, part, pixels, C);
+  hipLaunchKernelGGL(bn2d_mean_finish_kernel, dim3((unsigned)ceil_div(C, 256)), dim3(256), 0, st, (const double*)part, mean_d, C, pl.runs, (double)pixels);
+  launch_sum<1>(z_is_x2 != 0, pl, st, z, nullptr, (const double*)mean_d, nullptr, nullptr, part, pixels, C);
+  *own = own_moments(part, mean_d, pl.runs, (double)pixels);
+  return 0;
+}
+
+// The launch every backward over a rank's own rows starts with, and its checks: the runs' (sum G, sum G xhat) [runs][2][C] in the workspace
+int bn2d_bwd_partials(const float* G, const void* z, int z_is_x2, const BnPlan& pl, int64_t pixels, int C, const float* mean, const float* invstd,
+                      void* workspace, int64_t workspace_bytes, hipStream_t st) {
+  EHM_CHECK_ARG(G && z && mean && invstd && al16(G) && al16(z) && (z_is_x2 == 0 || z_is_x2 == 1) && workspace_ok(workspace, workspace_bytes, pl, C));
+  launch_sum<2>(z_is_x2 != 0, pl, st, z, G, nullptr, mean, invstd, (double*)workspace, pixels, C);
+  return 0;
+}
+
+// zbar's launch and its checks, for `total_rows` rows in the batch statistics: this call's own N Ho Wo (ehm_bn2d_train_bwd_zbar, whole 32-channel granules)
+// or all ranks' (ehm_bn2d_train_bwd_zbar_rows: at least this rank's, which may be one; float32 rows need whole 8-channel lanes only)
+int launch_zbar(const float* G, const void* z, int z_is_x2, int64_t z_rows, const float* mean, const float* invstd, const float* gamma, const float* gbeta,
+                const float* ggamma, const float* scale, float* out, int N, int Ho, int Wo, int C, int H, int W, int cmult, int64_t total_rows,
+                void* stream) {
+  EHM_CHECK_ARG(G && z && mean && invstd && gamma && gbeta && ggamma && out && al16(G) && al16(z) && al16(out) && (z_is_x2 == 0 || z_is_x2 == 1));
+  EHM_CHECK_ARG(N > 0 && Ho > 0 && Wo > 0 && H > 0 && W > 0 && C > 0 && C % cmult == 0);
+  const bool dense = H == Ho && W == Wo;
+  EHM_CHECK_ARG(dense || ((H - 1) / 2 + 1 == Ho && (W - 1) / 2 + 1 == Wo));
+  const long long R = (long long)N * Ho * Wo;
+  EHM_CHECK_ARG(total_rows >= 2 && total_rows >= R && total_rows < (1ll << 40) && z_rows >= R && (long long)N * H * W * C < (1ll << 40) &&
+                (const void*)G != (const void*)out);
+  ZbarArgs a;
+  a.G = G; a.z = z; a.mean = mean; a.invstd = invstd; a.gamma = gamma; a.gbeta = gbeta; a.ggamma = ggamma; a.scale = scale; a.out = out;
+  a.Ho = Ho; a.Wo = Wo; a.C = C; a.H = H; a.W = W; a.dil = dense ? 1 : 2;
+  a.invR = (float)(1.0 / (double)total_rows);
+  a.total8 = (long long)N * H * W * (C / 8);
+  const long long blocks = ceil_div(a.total8, 256);
+  EHM_CHECK_ARG(blocks < (1ll << 31));
+  if (z_is_x2) hipLaunchKernelGGL(bn2d_zbar_kernel<true>, dim3((unsigned)blocks), dim3(256), 0, (hipStream_t)stream, a);
+  else hipLaunchKernelGGL(bn2d_zbar_kernel<false>, dim3((unsigned)blocks), dim3(256), 0, (hipStream_t)stream, a);
+  EHM_LAUNCH_CHECK();
+  return 0;
+}
+
 }  // namespace
 
 extern "C" int ehm_bn2d_train_workspace_bytes(int64_t pixels, int C, int64_t* bytes) {
@@ -270,19 +291,13 @@ extern "C" int ehm_bn2d_train_stats(const void* z, int z_is_x2, int64_t z_rows, 
                                     float* invstd, float* running_mean, float* running_var, int64_t* num_batches_tracked, void* workspace,
                                     int64_t workspace_bytes, void* stream) {
   BnPlan pl;
-  const int rc = bn_plan(pixels, z_rows, C, &pl);
+  BnMoments own;
+  int rc = bn_plan(pixels, z_rows, C, &pl);
   if (rc != 0) return rc;
-  EHM_CHECK_ARG(z && mean && var && invstd && al16(z) && (z_is_x2 == 0 || z_is_x2 == 1) && eps >= 0.0 && momentum >= 0.0 && momentum <= 1.0);
-  EHM_CHECK_ARG(workspace && al16(workspace) && workspace_bytes >= bn_ws_doubles(pl, C) * (int64_t)sizeof(double));
-  hipStream_t st = (hipStream_t)stream;
-  double* part = (double*)workspace;
-  double* mean_d = part + (size_t)pl.runs * 2 * C;
-  const unsigned cb = (unsigned)ceil_div(C, 256);
-  launch_sum<0>(z_is_x2 != 0, pl, st, z, nullptr, nullptr, nullptr, nullptr, part, pixels, C);
-  hipLaunchKernelGGL(bn2d_mean_finish_kernel, dim3(cb), dim3(256), 0, st, (const double*)part, mean_d, C, pl.runs, (double)pixels);
-  launch_sum<1>(z_is_x2 != 0, pl, st, z, nullptr, (const double*)mean_d, nullptr, nullptr, part, pixels, C);
-  hipLaunchKernelGGL(bn2d_stats_finish_kernel, dim3(cb), dim3(256), 0, st, (const double*)part, (const double*)mean_d, mean, var, invstd, running_mean,
-                     running_var, (long long*)num_batches_tracked, C, pl.runs, (double)pixels, eps, momentum);
+  EHM_CHECK_ARG(mean && var && invstd && eps >= 0.0 && momentum >= 0.0 && momentum <= 1.0);
+  if ((rc = bn2d_moments(z, z_is_x2, pl, pixels, C, workspace, workspace_bytes, (hipStream_t)stream, &own)) != 0) return rc;
+  hipLaunchKernelGGL(bn2d_stats_finish_kernel, dim3((unsigned)ceil_div(C, 256)), dim3(256), 0, (hipStream_t)stream, own, (double*)nullptr, mean, var, invstd,
+                     running_mean, running_var, (long long*)num_batches_tracked, C, eps, momentum);
   EHM_LAUNCH_CHECK();
   return 0;
 }
@@ -290,32 +305,12 @@ extern "C" int ehm_bn2d_train_stats(const void* z, int z_is_x2, int64_t z_rows, 
 extern "C" int ehm_bn2d_train_bwd_sums(const float* G, const void* z, int z_is_x2, int64_t z_rows, int64_t pixels, int C, const float* mean,
                                        const float* invstd, float* gbeta, float* ggamma, void* workspace, int64_t workspace_bytes, void* stream) {
   BnPlan pl;
-  const int rc = bn_plan(pixels, z_rows, C, &pl);
+  int rc = bn_plan(pixels, z_rows, C, &pl);
   if (rc != 0) return rc;
-  EHM_CHECK_ARG(G && z && mean && invstd && gbeta && ggamma && al16(G) && al16(z) && (z_is_x2 == 0 || z_is_x2 == 1));
-  EHM_CHECK_ARG(workspace && al16(workspace) && workspace_bytes >= bn_ws_doubles(pl, C) * (int64_t)sizeof(double));
-  hipStream_t st = (hipStream_t)stream;
-  double* part = (double*)workspace;
-  launch_sum<2>(z_is_x2 != 0, pl, st, z, G, nullptr, mean, invstd, part, pixels, C);
-  hipLaunchKernelGGL(bn2d_bwd_finish_kernel, dim3((unsigned)ceil_div(C, 256)), dim3(256), 0, st, (const double*)part, gbeta, ggamma, C, pl.runs);
-  EHM_LAUNCH_CHECK();
-  return 0;
-}
-
-// zbar's launch for R rows in the batch statistics: the N Ho Wo rows of G (ehm_bn2d_train_bwd_zbar) or all ranks' (ehm_bn2d_train_bwd_zbar_rows)
-static int launch_zbar(const float* G, const void* z, int z_is_x2, int64_t z_rows, const float* mean, const float* invstd, const float* gamma,
-                       const float* gbeta, const float* ggamma, const float* scale, float* out, int N, int Ho, int Wo, int C, int H, int W, long long R,
-                       void* stream) {
-  const bool dense = H == Ho && W == Wo;
-  ZbarArgs a;
-  a.G = G; a.z = z; a.mean = mean; a.invstd = invstd; a.gamma = gamma; a.gbeta = gbeta; a.ggamma = ggamma; a.scale = scale; a.out = out;
-  a.Ho = Ho; a.Wo = Wo; a.C = C; a.H = H; a.W = W; a.dil = dense ? 1 : 2;
-  a.invR = (float)(1.0 / (double)R);
-  a.total8 = (long long)N * H * W * (C / 8);
-  const long long blocks = ceil_div(a.total8, 256);
-  EHM_CHECK_ARG(blocks < (1ll << 31));
-  if (z_is_x2) hipLaunchKernelGGL(bn2d_zbar_kernel<true>, dim3((unsigned)blocks), dim3(256), 0, (hipStream_t)stream, a);
-  else hipLaunchKernelGGL(bn2d_zbar_kernel<false>, dim3((unsigned)blocks), dim3(256), 0, (hipStream_t)stream, a);
+  EHM_CHECK_ARG(gbeta && ggamma);
+  if ((rc = bn2d_bwd_partials(G, z, z_is_x2, pl, pixels, C, mean, invstd, workspace, workspace_bytes, (hipStream_t)stream)) != 0) return rc;
+  hipLaunchKernelGGL(bn2d_bwd_reduce_kernel, dim3((unsigned)ceil_div(C, 256)), dim3(256), 0, (hipStream_t)stream, (const double*)workspace, pl.runs, 0, C,
+                     (double*)nullptr, gbeta, ggamma, (float*)nullptr, (float*)nullptr);
   EHM_LAUNCH_CHECK();
   return 0;
 }
@@ -323,46 +318,35 @@ static int launch_zbar(const float* G, const void* z, int z_is_x2, int64_t z_row
 extern "C" int ehm_bn2d_train_bwd_zbar(const float* G, const void* z, int z_is_x2, int64_t z_rows, const float* mean, const float* invstd, const float* gamma,
                                        const float* gbeta, const float* ggamma, const float* scale, float* out, int N, int Ho, int Wo, int C, int H, int W,
                                        void* stream) {
-  EHM_CHECK_ARG(G && z && mean && invstd && gamma && gbeta && ggamma && out && al16(G) && al16(z) && al16(out) && (z_is_x2 == 0 || z_is_x2 == 1));
-  EHM_CHECK_ARG(N > 0 && Ho > 0 && Wo > 0 && H > 0 && W > 0 && C > 0 && C % 32 == 0);
-  const bool dense = H == Ho && W == Wo;
-  EHM_CHECK_ARG(dense || ((H - 1) / 2 + 1 == Ho && (W - 1) / 2 + 1 == Wo));
-  const long long R = (long long)N * Ho * Wo;
-  EHM_CHECK_ARG(R >= 2 && z_rows >= R && (long long)N * H * W * C < (1ll << 40) && (const void*)G != (const void*)out);
-  return launch_zbar(G, z, z_is_x2, z_rows, mean, invstd, gamma, gbeta, ggamma, scale, out, N, Ho, Wo, C, H, W, R, stream);
+  return launch_zbar(G, z, z_is_x2, z_rows, mean, invstd, gamma, gbeta, ggamma, scale, out, N, Ho, Wo, C, H, W, 32, (int64_t)N * Ho * Wo, stream);
 }
 
 // ---- data parallel: a rank's rows -> [2][C] float64, every rank's [world][2][C] (all-gathered by the caller, ONE collective per BatchNorm each way) -> the
 // batch's.  Every rank merges the same buffer in the same order: all ranks hold the same bits.  rows [world] on the host: each rank's pixel count R_r.
-// With world == 1 a local + merge pair gives the bits of ehm_bn2d_train_stats / ehm_bn2d_train_bwd_sums, and zbar_rows with total_rows = N Ho Wo those of
+// Each entry is a one-call entry's own body cut at the collective - the same helpers and kernels, another source or destination -, so with world == 1 a
+// local + merge pair writes the bits of ehm_bn2d_train_stats / ehm_bn2d_train_bwd_sums, and zbar_rows with total_rows = N Ho Wo those of
 // ehm_bn2d_train_bwd_zbar.  A rank may hold ONE row; float32 rows need C % 8 == 0 only (an X2 buffer C % 32 == 0, its format's granule).
 extern "C" int ehm_bn2d_train_stats_local(const void* z, int z_is_x2, int64_t z_rows, int64_t pixels, int C, double* local, void* workspace,
                                           int64_t workspace_bytes, void* stream) {
   BnPlan pl;
-  EHM_CHECK_ARG(z_is_x2 == 0 || z_is_x2 == 1);
-  const int rc = bn_plan(pixels, z_rows, C, &pl, 1, z_is_x2 ? 32 : 8);
+  BnMoments own;
+  int rc = bn_plan(pixels, z_rows, C, &pl, 1, z_is_x2 ? 32 : 8);
   if (rc != 0) return rc;
-  EHM_CHECK_ARG(z && local && al16(z) && (uintptr_t)local % 8 == 0);
-  EHM_CHECK_ARG(workspace && al16(workspace) && workspace_bytes >= bn_ws_doubles(pl, C) * (int64_t)sizeof(double));
-  hipStream_t st = (hipStream_t)stream;
-  double* part = (double*)workspace;
-  double* mean_d = part + (size_t)pl.runs * 2 * C;
-  const unsigned cb = (unsigned)ceil_div(C, 256);
-  launch_sum<0>(z_is_x2 != 0, pl, st, z, nullptr, nullptr, nullptr, nullptr, part, pixels, C);
-  hipLaunchKernelGGL(bn2d_mean_finish_kernel, dim3(cb), dim3(256), 0, st, (const double*)part, mean_d, C, pl.runs, (double)pixels);
-  launch_sum<1>(z_is_x2 != 0, pl, st, z, nullptr, (const double*)mean_d, nullptr, nullptr, part, pixels, C);
-  hipLaunchKernelGGL(bn2d_local_stats_kernel, dim3(cb), dim3(256), 0, st, (const double*)part, (const double*)mean_d, local, C, pl.runs);
+  EHM_CHECK_ARG(local && (uintptr_t)local % 8 == 0);
+  if ((rc = bn2d_moments(z, z_is_x2, pl, pixels, C, workspace, workspace_bytes, (hipStream_t)stream, &own)) != 0) return rc;
+  hipLaunchKernelGGL(bn2d_stats_finish_kernel, dim3((unsigned)ceil_div(C, 256)), dim3(256), 0, (hipStream_t)stream, own, local, (float*)nullptr,
+                     (float*)nullptr, (float*)nullptr, (float*)nullptr, (float*)nullptr, (long long*)nullptr, C, 0.0, 0.0);
   EHM_LAUNCH_CHECK();
   return 0;
 }
 
 extern "C" int ehm_bn2d_train_stats_merge(const double* gathered, const int64_t* rows, int world, int C, double eps, double momentum, float* mean, float* var,
                                           float* invstd, float* running_mean, float* running_var, int64_t* num_batches_tracked, void* stream) {
-  RankRows rr;
-  const int rc = rank_rows_of(rows, world, &rr);
+  BnMoments all = {nullptr, nullptr, 0, gathered, world, {}};
+  const int rc = rank_rows_of(rows, world, &all.rr);
   if (rc != 0) return rc;
   EHM_CHECK_ARG(gathered && (uintptr_t)gathered % 8 == 0 && mean && var && invstd && C > 0 && C % 8 == 0 && eps >= 0.0 && momentum >= 0.0 && momentum <= 1.0);
-  hipLaunchKernelGGL(bn2d_merge_stats_kernel, dim3((unsigned)ceil_div(C, 256)), dim3(256), 0, (hipStream_t)stream, gathered, rr, world, mean, var, invstd,
+  hipLaunchKernelGGL(bn2d_stats_finish_kernel, dim3((unsigned)ceil_div(C, 256)), dim3(256), 0, (hipStream_t)stream, all, (double*)nullptr, mean, var, invstd,
                      running_mean, running_var, (long long*)num_batches_tracked, C, eps, momentum);
   EHM_LAUNCH_CHECK();
   return 0;
@@ -371,41 +355,29 @@ extern "C" int ehm_bn2d_train_stats_merge(const double* gathered, const int64_t*
 extern "C" int ehm_bn2d_train_bwd_local(const float* G, const void* z, int z_is_x2, int64_t z_rows, int64_t pixels, int C, const float* mean,
                                         const float* invstd, double* local, void* workspace, int64_t workspace_bytes, void* stream) {
   BnPlan pl;
-  EHM_CHECK_ARG(z_is_x2 == 0 || z_is_x2 == 1);
-  const int rc = bn_plan(pixels, z_rows, C, &pl, 1, z_is_x2 ? 32 : 8);
+  int rc = bn_plan(pixels, z_rows, C, &pl, 1, z_is_x2 ? 32 : 8);
   if (rc != 0) return rc;
-  EHM_CHECK_ARG(G && z && mean && invstd && local && al16(G) && al16(z) && (uintptr_t)local % 8 == 0);
-  EHM_CHECK_ARG(workspace && al16(workspace) && workspace_bytes >= bn_ws_doubles(pl, C) * (int64_t)sizeof(double));
-  hipStream_t st = (hipStream_t)stream;
-  double* part = (double*)workspace;
-  launch_sum<2>(z_is_x2 != 0, pl, st, z, G, nullptr, mean, invstd, part, pixels, C);
-  hipLaunchKernelGGL(bn2d_local_bwd_kernel, dim3((unsigned)ceil_div(C, 256)), dim3(256), 0, st, (const double*)part, local, C, pl.runs);
+  EHM_CHECK_ARG(local && (uintptr_t)local % 8 == 0);
+  if ((rc = bn2d_bwd_partials(G, z, z_is_x2, pl, pixels, C, mean, invstd, workspace, workspace_bytes, (hipStream_t)stream)) != 0) return rc;
+  hipLaunchKernelGGL(bn2d_bwd_reduce_kernel, dim3((unsigned)ceil_div(C, 256)), dim3(256), 0, (hipStream_t)stream, (const double*)workspace, pl.runs, 0, C,
+                     local, (float*)nullptr, (float*)nullptr, (float*)nullptr, (float*)nullptr);
   EHM_LAUNCH_CHECK();
   return 0;
 }
 
-// gbeta / ggamma: the whole batch's sums, for ehm_bn2d_train_bwd_zbar_rows; gbeta_own / ggamma_own (either may be NULL): float32 of rank `rank`'s own
-// float64 sums - the parameter gradients, which the caller's gradient all-reduce completes (the batch's sums there would count `world` times)
+// gbeta / ggamma: the whole batch's sums, for ehm_bn2d_train_bwd_zbar_rows; gbeta_own / ggamma_own (either may be NULL): rank `rank`'s own
 extern "C" int ehm_bn2d_train_bwd_merge(const double* gathered, int world, int rank, int C, float* gbeta, float* ggamma, float* gbeta_own,
                                         float* ggamma_own, void* stream) {
   EHM_CHECK_ARG(gathered && (uintptr_t)gathered % 8 == 0 && world >= 1 && world <= kMaxRanks && rank >= 0 && rank < world && C > 0 && C % 8 == 0);
   EHM_CHECK_ARG(gbeta && ggamma);
-  hipLaunchKernelGGL(bn2d_merge_bwd_kernel, dim3((unsigned)ceil_div(C, 256)), dim3(256), 0, (hipStream_t)stream, gathered, world, rank, gbeta, ggamma,
-                     gbeta_own, ggamma_own, C);
+  hipLaunchKernelGGL(bn2d_bwd_reduce_kernel, dim3((unsigned)ceil_div(C, 256)), dim3(256), 0, (hipStream_t)stream, gathered, world, rank, C, (double*)nullptr,
+                     gbeta, ggamma, gbeta_own, ggamma_own);
   EHM_LAUNCH_CHECK();
   return 0;
 }
 
-// ehm_bn2d_train_bwd_zbar with the batch statistics' row count given: total_rows = all ranks' rows (>= this rank's N Ho Wo, which may be one)
 extern "C" int ehm_bn2d_train_bwd_zbar_rows(const float* G, const void* z, int z_is_x2, int64_t z_rows, const float* mean, const float* invstd,
                                             const float* gamma, const float* gbeta, const float* ggamma, const float* scale, float* out, int N, int Ho,
                                             int Wo, int C, int H, int W, int64_t total_rows, void* stream) {
-  EHM_CHECK_ARG(G && z && mean && invstd && gamma && gbeta && ggamma && out && al16(G) && al16(z) && al16(out) && (z_is_x2 == 0 || z_is_x2 == 1));
-  EHM_CHECK_ARG(N > 0 && Ho > 0 && Wo > 0 && H > 0 && W > 0 && C > 0 && C % (z_is_x2 ? 32 : 8) == 0);
-  const bool dense = H == Ho && W == Wo;
-  EHM_CHECK_ARG(dense || ((H - 1) / 2 + 1 == Ho && (W - 1) / 2 + 1 == Wo));
-  const long long R = (long long)N * Ho * Wo;
-  EHM_CHECK_ARG(total_rows >= 2 && total_rows >= R && total_rows < (1ll << 40) && z_rows >= R && (long long)N * H * W * C < (1ll << 40) &&
-                (const void*)G != (const void*)out);
-  return launch_zbar(G, z, z_is_x2, z_rows, mean, invstd, gamma, gbeta, ggamma, scale, out, N, Ho, Wo, C, H, W, (long long)total_rows, stream);
+  return launch_zbar(G, z, z_is_x2, z_rows, mean, invstd, gamma, gbeta, ggamma, scale, out, N, Ho, Wo, C, H, W, z_is_x2 ? 32 : 8, total_rows, stream);
 }

@@ -60,6 +60,12 @@ static inline int rank_rows_of(const int64_t* rows, int world, RankRows* rr) {
   rr->total = (double)total;
   return 0;
 }
+// one channel's n float64 partial sums p[k * stride], added in index order: the fixed order every BatchNorm reduction of the two files ends in
+static __device__ __forceinline__ double ordered_sum(const double* __restrict__ p, size_t stride, int n) {
+  double s = 0.0;
+  for (int k = 0; k < n; ++k) s += p[k * stride];
+  return s;
+}
 // Chan et al.'s merge of the ranks' (mean, M2 = sum of squares centred on the rank's own mean) of one channel, in rank order; g: that channel's mean of
 // rank 0, rank k's at g[k * stride], its M2 at g[k * stride + m2].  The mean is taken relative to rank 0's and M2's correction on the merged mean, so
 // ranks whose means lie many sigma apart cancel nothing, and ONE rank gives back its own (mean, M2) bit for bit (mu_0 + 0, M2_0 + R_0 0).
@@ -77,6 +83,28 @@ static __device__ __forceinline__ void merge_moments(const double* __restrict__ 
   }
   *mu = m;
   *M2 = s + c;
+}
+// Where a channel's (mean, M2) over rr.total rows come from, for the one kernel per file that writes a BatchNorm's statistics out.  gathered == NULL: a
+// call's own two passes, mean [N] and `count` partial sums of centred squares part[k * N].  Else every rank's pair [world][2][N], merged.
+struct BnMoments {
+  const double *part, *mean;
+  int count;
+  const double* gathered;
+  int world;
+  RankRows rr;
+};
+static inline BnMoments own_moments(const double* part, const double* mean, int count, double R) {
+  BnMoments m = {part, mean, count, nullptr, 0, {}};
+  m.rr.total = R;
+  return m;
+}
+static __device__ __forceinline__ void moments_of(const BnMoments& s, int n, int N, double* mu, double* M2) {
+  if (s.gathered) {
+    merge_moments(s.gathered + n, (size_t)2 * N, (size_t)N, s.rr, s.world, mu, M2);
+  } else {
+    *mu = s.mean[n];
+    *M2 = ordered_sum(s.part + n, (size_t)N, s.count);
+  }
 }
 
 // ---- float32 chains that must round like the reference's separate torch ops: one correctly rounded operation each, never contracted.

@@ -16,21 +16,22 @@
 //                             float64: partial column sums [groups][N].  HBM bound: 8 N bytes read and 4 N written per row.
 //   train_colsum_kernel       z -> partial sums of z (a z that did not come from train_preact_kernel) or of (z - mean)^2, float64.  4 N bytes read per row.
 //   train_mean_kernel         partial sums, added in index order -> mean (float64, in the workspace).
-//   train_stats_finish        partial sums of squares -> mean, invstd (float32) and the running statistics.
+//   train_stats_finish        (mean, M2 = sum of squares centred on it) of the call's own rows, or of every rank's through merge_moments (BnMoments,
+//                             common.h) -> mean, invstd (float32) and the running statistics; or, for a rank's share, the pair itself [2][N] float64.
 //   train_normalize_kernel    z -> y = relu(gamma xhat + beta) and out = y + res.  4 N (+ 4 N) bytes read and 4 N (+ 4 N) written per row.
 //   train_bnbwd_partial       g, gate, z -> partial sums of vbar and vbar xhat (float64).  12 N bytes read per row.
-//   train_bnbwd_finish        -> betabar, gammabar (float32) and betabar / R, gammabar / R in the workspace.
+//   train_bwd_reduce          partial sums, or every rank's sums, added in index order -> betabar, gammabar (float32; under data parallel the rank's
+//                             OWN) and betabar / R, gammabar / R in the workspace; or, for a rank's share, the two sums themselves [2][N] float64.
 //   train_zbar_kernel         g, gate, z -> zbar.  12 N bytes read and 4 N written per row.
-//   train_local_stats / train_local_bwd     a rank's (mean, M2) / (sum vbar, sum vbar xhat) [2][N] float64, for the data-parallel route below.
-//   train_merge_stats                       every rank's (mean, M2) -> the batch's mean, invstd and the running statistics (merge_moments, common.h).
-//   train_merge_bwd                         every rank's sums, added in rank order -> betabar / R, gammabar / R of the whole batch; the rank's own sums out.
 // The statistics are two-pass sums in float64 in a fixed order: exact to the float32 rounding of their results, whatever |mean| / std is.  No atomics
 // anywhere: two calls on the same inputs give the same bits.  The kernels read the raw parameter arrays the handle was created on, never its
 // BatchNorm-folded tables.
 //
 // Data parallel (ehm_gcn_train_stats_local / _stats_merge / _bwd_local / _bwd_merge): each rank runs the same passes on its own rows and stops at [2][N]
 // float64; the caller all-gathers them ([world][2][N], ONE collective per BatchNorm each way) and every rank merges the same buffer in the same order, so all
-// ranks hold the same bits.  With world == 1 a local + merge pair gives the bits of ehm_gcn_train_stats / ehm_gcn_train_bn_backward.
+// ranks hold the same bits.  The pair is the one-call entry's own body cut at the collective: train_moments / train_bwd_partials issue the passes for
+// both, train_stats_finish / train_bwd_reduce write out for both (merge_moments gives ONE rank's pair back bit for bit), train_backward ends both.  So
+// with world == 1 a local + merge pair gives the bits of ehm_gcn_train_stats / ehm_gcn_train_bn_backward by construction.
 #include "common.h"
 #include "egohmr_hip.h"
 #include "gcn_dev.h"
@@ -118,23 +119,26 @@ __global__ __launch_bounds__(NT) void train_colsum_kernel(const float* __restric
   part[(size_t)grp * N + n] = s;
 }
 
-__device__ __forceinline__ double ordered_sum(const double* __restrict__ p, int N, int groups) {
-  double s = 0.0;
-  for (int g = 0; g < groups; ++g) s += p[(size_t)g * N];
-  return s;
-}
-
 __global__ __launch_bounds__(256) void train_mean_kernel(const double* __restrict__ part, double* __restrict__ meand, int N, int groups, double R) {
   const int n = blockIdx.x * 256 + threadIdx.x;
   if (n < N) meand[n] = ordered_sum(part + n, N, groups) / R;
 }
 
-__global__ __launch_bounds__(256) void train_stats_finish(const double* __restrict__ part, const double* __restrict__ meand, int N, int groups, double R,
-                                                          double eps, double momentum, float* __restrict__ mean, float* __restrict__ invstd,
-                                                          float* __restrict__ running_mean, float* __restrict__ running_var) {
+// (mean, M2 = sum of squares centred on that mean) of this call's own rows or of every rank's (BnMoments, common.h) -> local[0][n] = mean, local[1][n] = M2
+// and nothing else (a rank's share), or the batch's mean, invstd (float32) and the running statistics
+__global__ __launch_bounds__(256) void train_stats_finish(BnMoments src, int N, double eps, double momentum, double* __restrict__ local,
+                                                          float* __restrict__ mean, float* __restrict__ invstd, float* __restrict__ running_mean,
+                                                          float* __restrict__ running_var) {
   const int n = blockIdx.x * 256 + threadIdx.x;
   if (n >= N) return;
-  const double mu = meand[n], var = ordered_sum(part + n, N, groups) / R;
+  double mu, M2;
+  moments_of(src, n, N, &mu, &M2);
+  if (local) {
+    local[n] = mu;
+    local[N + n] = M2;
+    return;
+  }
+  const double R = src.rr.total, var = M2 / R;
   mean[n] = (float)mu;
   invstd[n] = (float)(1.0 / sqrt(var + eps));
   if (running_mean) running_mean[n] = (float)((1.0 - momentum) * (double)running_mean[n] + momentum * mu);
@@ -186,58 +190,23 @@ __global__ __launch_bounds__(NT) void train_bnbwd_partial(const float* __restric
   gpart[(size_t)grp * N + n] = sg;
 }
 
-__global__ __launch_bounds__(256) void train_bnbwd_finish(const double* __restrict__ bpart, const double* __restrict__ gpart, int N, int groups, double R,
-                                                          float* __restrict__ gbn_weight, float* __restrict__ gbn_bias, float* __restrict__ bR,
-                                                          float* __restrict__ gR) {
+// A channel's `count` float64 entries b[k stride] and g[k stride] (sums of vbar and of vbar xhat), added in index order: a call's partial sums (count =
+// groups) or every rank's sums (count = world).  With `local`: that pair [2][N] in float64, a rank's share, and nothing else.  Without: betabar / R and
+// gammabar / R for train_zbar_kernel, and the float32 parameter gradients - of the total, or with own >= 0 of entry `own` alone (the rank's OWN sums: the
+// caller's gradient all-reduce completes them).
+__global__ __launch_bounds__(256) void train_bwd_reduce(const double* __restrict__ b, const double* __restrict__ g, size_t stride, int count, int own,
+                                                        int N, double R, double* __restrict__ local, float* __restrict__ gbn_weight,
+                                                        float* __restrict__ gbn_bias, float* __restrict__ bR, float* __restrict__ gR) {
   const int n = blockIdx.x * 256 + threadIdx.x;
   if (n >= N) return;
-  const double sb = ordered_sum(bpart + n, N, groups), sg = ordered_sum(gpart + n, N, groups);
-  if (gbn_bias) gbn_bias[n] = (float)sb;
-  if (gbn_weight) gbn_weight[n] = (float)sg;
-  bR[n] = (float)(sb / R);
-  gR[n] = (float)(sg / R);
-}
-
-// a rank's own statistics: local[0][n] = its mean, local[1][n] = its sum of squares centred on that mean
-__global__ __launch_bounds__(256) void train_local_stats(const double* __restrict__ part, const double* __restrict__ meand, int N, int groups,
-                                                         double* __restrict__ local) {
-  const int n = blockIdx.x * 256 + threadIdx.x;
-  if (n >= N) return;
-  local[n] = meand[n];
-  local[N + n] = ordered_sum(part + n, N, groups);
-}
-
-__global__ __launch_bounds__(256) void train_merge_stats(const double* __restrict__ gathered, RankRows rr, int world, int N, double eps, double momentum,
-                                                         float* __restrict__ mean, float* __restrict__ invstd, float* __restrict__ running_mean,
-                                                         float* __restrict__ running_var) {
-  const int n = blockIdx.x * 256 + threadIdx.x;
-  if (n >= N) return;
-  double mu, M2;
-  merge_moments(gathered + n, (size_t)2 * N, (size_t)N, rr, world, &mu, &M2);
-  const double R = rr.total, var = M2 / R;
-  mean[n] = (float)mu;
-  invstd[n] = (float)(1.0 / sqrt(var + eps));
-  if (running_mean) running_mean[n] = (float)((1.0 - momentum) * (double)running_mean[n] + momentum * mu);
-  if (running_var) running_var[n] = (float)((1.0 - momentum) * (double)running_var[n] + momentum * var * (R / (R - 1.0)));
-}
-
-__global__ __launch_bounds__(256) void train_local_bwd(const double* __restrict__ bpart, const double* __restrict__ gpart, int N, int groups,
-                                                       double* __restrict__ local) {
-  const int n = blockIdx.x * 256 + threadIdx.x;
-  if (n >= N) return;
-  local[n] = ordered_sum(bpart + n, N, groups);
-  local[N + n] = ordered_sum(gpart + n, N, groups);
-}
-
-// gbn_bias / gbn_weight: the rank's OWN sums (the caller's gradient all-reduce completes them); bR / gR: the whole batch's, over its row count R
-__global__ __launch_bounds__(256) void train_merge_bwd(const double* __restrict__ gathered, int world, int rank, int N, double R,
-                                                       float* __restrict__ gbn_weight, float* __restrict__ gbn_bias, float* __restrict__ bR,
-                                                       float* __restrict__ gR) {
-  const int n = blockIdx.x * 256 + threadIdx.x;
-  if (n >= N) return;
-  const double sb = ordered_sum(gathered + n, 2 * N, world), sg = ordered_sum(gathered + N + n, 2 * N, world);
-  if (gbn_bias) gbn_bias[n] = (float)gathered[(size_t)rank * 2 * N + n];
-  if (gbn_weight) gbn_weight[n] = (float)gathered[(size_t)rank * 2 * N + N + n];
+  const double sb = ordered_sum(b + n, stride, count), sg = ordered_sum(g + n, stride, count);
+  if (local) {
+    local[n] = sb;
+    local[N + n] = sg;
+    return;
+  }
+  if (gbn_bias) gbn_bias[n] = (float)(own < 0 ? sb : b[own * stride + n]);
+  if (gbn_weight) gbn_weight[n] = (float)(own < 0 ? sg : g[own * stride + n]);
   bR[n] = (float)(sb / R);
   gR[n] = (float)(sg / R);
 }
@@ -302,6 +271,57 @@ bool workspace_ok(const void* workspace, int64_t workspace_bytes, int N, int bod
   return workspace && (uintptr_t)workspace % 16 == 0 && workspace_bytes >= train_bytes(N, bodies);
 }
 
+// The launches every statistics entry starts with, and their checks: z -> its mean (float64, w->meand) and the partial sums of (z - mean)^2 (w->part1)
+int train_moments(const TrainConv& c, const float* z, int bodies, int have_sums, void* workspace, int64_t workspace_bytes, hipStream_t st, TrainPlan* w) {
+  EHM_CHECK_ARG(z && bodies > 0 && (have_sums == 0 || have_sums == 1));
+  EHM_CHECK_ARG(workspace_ok(workspace, workspace_bytes, c.N, bodies));
+  *w = plan_of(workspace, c.N, bodies);
+  if (!have_sums)
+    hipLaunchKernelGGL(train_colsum_kernel<false>, w->cgrid, dim3(NT), 0, st, z, (const double*)nullptr, w->part0, c.N, bodies, w->groups, w->chunks);
+  hipLaunchKernelGGL(train_mean_kernel, w->ngrid, dim3(256), 0, st, (const double*)w->part0, w->meand, c.N, w->groups, (double)bodies * kJ);
+  hipLaunchKernelGGL(train_colsum_kernel<true>, w->cgrid, dim3(NT), 0, st, z, (const double*)w->meand, w->part1, c.N, bodies, w->groups, w->chunks);
+  return 0;
+}
+
+// The launch every backward over a rank's own rows starts with, and its checks: partial sums of vbar (w->part0) and of vbar xhat (w->part1)
+int train_bwd_partials(const TrainConv& c, const float* gout, const float* gate, const float* z, const float* mean, const float* invstd, int bodies,
+                       void* workspace, int64_t workspace_bytes, hipStream_t st, TrainPlan* w) {
+  EHM_CHECK_ARG(gout && gate && z && mean && invstd && bodies > 0);
+  EHM_CHECK_ARG(workspace_ok(workspace, workspace_bytes, c.N, bodies));
+  *w = plan_of(workspace, c.N, bodies);
+  hipLaunchKernelGGL(train_bnbwd_partial, w->cgrid, dim3(NT), 0, st, gout, gate, z, mean, invstd, w->part0, w->part1, c.N, bodies, w->groups, w->chunks);
+  return 0;
+}
+
+// The backward from the sums on: betabar / R, gammabar / R, the parameter gradients and zbar, with every check of zbar's launch made before the first
+// launch.  gathered == NULL (ehm_gcn_train_bn_backward): this call's own sums over R = 24 bodies rows, computed here.  Else (ehm_gcn_train_bwd_merge):
+// every rank's [world][2][N] over R rows in all, and the parameter gradients are rank `rank`'s own.
+int train_backward(const TrainConv& c, const double* gathered, int world, int rank, double R, const float* gout, const float* gate, const float* z,
+                   const float* mean, const float* invstd, int bodies, float* zbar, float* gbn_weight, float* gbn_bias, void* workspace,
+                   int64_t workspace_bytes, hipStream_t st) {
+  EHM_CHECK_ARG(gout && gate && z && mean && invstd && zbar && bodies > 0);
+  EHM_CHECK_ARG((const void*)zbar != (const void*)gate && (const void*)zbar != (const void*)z);
+  EHM_CHECK_ARG(((uintptr_t)gout | (uintptr_t)gate | (uintptr_t)z | (uintptr_t)mean | (uintptr_t)invstd | (uintptr_t)zbar |
+                 (uintptr_t)c.raw.bn_weight) % 16 == 0);
+  const long long total4 = (long long)bodies * kJ * (c.N / 4);
+  EHM_CHECK_ARG(ceil_div(total4, 256) < (1ll << 31));
+  TrainPlan w;
+  const bool own = !gathered;
+  if (own) {
+    const int rc = train_bwd_partials(c, gout, gate, z, mean, invstd, bodies, workspace, workspace_bytes, st, &w);
+    if (rc != 0) return rc;
+  } else {
+    EHM_CHECK_ARG(workspace_ok(workspace, workspace_bytes, c.N, bodies));
+    w = plan_of(workspace, c.N, bodies);
+  }
+  hipLaunchKernelGGL(train_bwd_reduce, w.ngrid, dim3(256), 0, st, own ? (const double*)w.part0 : gathered, own ? (const double*)w.part1 : gathered + c.N,
+                     (size_t)(own ? c.N : 2 * c.N), own ? w.groups : world, own ? -1 : rank, c.N, R, (double*)nullptr, gbn_weight, gbn_bias, w.bR, w.gR);
+  hipLaunchKernelGGL(train_zbar_kernel, dim3((unsigned)ceil_div(total4, 256)), dim3(256), 0, st, gout, gate, z, mean, invstd, c.raw.bn_weight,
+                     (const float*)w.bR, (const float*)w.gR, zbar, c.N / 4, total4);
+  EHM_LAUNCH_CHECK();
+  return 0;
+}
+
 }  // namespace
 
 extern "C" int ehm_gcn_train_adjacency(const ehm_gcn* h, int conv, float* A, void* stream) {
@@ -339,20 +359,14 @@ extern "C" int ehm_gcn_train_preact(const ehm_gcn* h, int conv, const float* pre
 extern "C" int ehm_gcn_train_stats(const ehm_gcn* h, int conv, const float* z, int bodies, int have_sums, double eps, double momentum, float* mean,
                                    float* invstd, float* running_mean, float* running_var, void* workspace, int64_t workspace_bytes, void* stream) {
   TrainConv c;
-  const int rc = train_conv_of(h, conv, &c);
+  int rc = train_conv_of(h, conv, &c);
   if (rc != 0) return rc;
-  EHM_CHECK_ARG(z && mean && invstd && bodies > 0 && eps >= 0.0 && momentum >= 0.0 && momentum <= 1.0 && (have_sums == 0 || have_sums == 1));
+  EHM_CHECK_ARG(mean && invstd && eps >= 0.0 && momentum >= 0.0 && momentum <= 1.0);
   EHM_CHECK_ARG((running_mean == nullptr) == (running_var == nullptr));
-  EHM_CHECK_ARG(workspace_ok(workspace, workspace_bytes, c.N, bodies));
-  const TrainPlan w = plan_of(workspace, c.N, bodies);
-  hipStream_t st = (hipStream_t)stream;
-  const double R = (double)bodies * kJ;
-  if (!have_sums)
-    hipLaunchKernelGGL(train_colsum_kernel<false>, w.cgrid, dim3(NT), 0, st, z, (const double*)nullptr, w.part0, c.N, bodies, w.groups, w.chunks);
-  hipLaunchKernelGGL(train_mean_kernel, w.ngrid, dim3(256), 0, st, (const double*)w.part0, w.meand, c.N, w.groups, R);
-  hipLaunchKernelGGL(train_colsum_kernel<true>, w.cgrid, dim3(NT), 0, st, z, (const double*)w.meand, w.part1, c.N, bodies, w.groups, w.chunks);
-  hipLaunchKernelGGL(train_stats_finish, w.ngrid, dim3(256), 0, st, (const double*)w.part1, (const double*)w.meand, c.N, w.groups, R, eps, momentum, mean,
-                     invstd, running_mean, running_var);
+  TrainPlan w;
+  if ((rc = train_moments(c, z, bodies, have_sums, workspace, workspace_bytes, (hipStream_t)stream, &w)) != 0) return rc;
+  hipLaunchKernelGGL(train_stats_finish, w.ngrid, dim3(256), 0, (hipStream_t)stream, own_moments(w.part1, w.meand, w.groups, (double)bodies * kJ), c.N, eps,
+                     momentum, (double*)nullptr, mean, invstd, running_mean, running_var);
   EHM_LAUNCH_CHECK();
   return 0;
 }
@@ -379,41 +393,22 @@ extern "C" int ehm_gcn_train_bn_backward(const ehm_gcn* h, int conv, const float
   TrainConv c;
   const int rc = train_conv_of(h, conv, &c);
   if (rc != 0) return rc;
-  EHM_CHECK_ARG(gout && gate && z && mean && invstd && zbar && bodies > 0);
-  EHM_CHECK_ARG((const void*)zbar != (const void*)gate && (const void*)zbar != (const void*)z);
-  EHM_CHECK_ARG(((uintptr_t)gout | (uintptr_t)gate | (uintptr_t)z | (uintptr_t)mean | (uintptr_t)invstd | (uintptr_t)zbar |
-                 (uintptr_t)c.raw.bn_weight) % 16 == 0);
-  EHM_CHECK_ARG(workspace_ok(workspace, workspace_bytes, c.N, bodies));
-  const TrainPlan w = plan_of(workspace, c.N, bodies);
-  hipStream_t st = (hipStream_t)stream;
-  const long long total4 = (long long)bodies * kJ * (c.N / 4);
-  EHM_CHECK_ARG(ceil_div(total4, 256) < (1ll << 31));
-  const double R = (double)bodies * kJ;
-  hipLaunchKernelGGL(train_bnbwd_partial, w.cgrid, dim3(NT), 0, st, gout, gate, z, mean, invstd, w.part0, w.part1, c.N, bodies, w.groups, w.chunks);
-  hipLaunchKernelGGL(train_bnbwd_finish, w.ngrid, dim3(256), 0, st, (const double*)w.part0, (const double*)w.part1, c.N, w.groups, R, gbn_weight, gbn_bias,
-                     w.bR, w.gR);
-  hipLaunchKernelGGL(train_zbar_kernel, dim3((unsigned)ceil_div(total4, 256)), dim3(256), 0, st, gout, gate, z, mean, invstd, c.raw.bn_weight,
-                     (const float*)w.bR, (const float*)w.gR, zbar, c.N / 4, total4);
-  EHM_LAUNCH_CHECK();
-  return 0;
+  return train_backward(c, nullptr, 1, 0, (double)bodies * kJ, gout, gate, z, mean, invstd, bodies, zbar, gbn_weight, gbn_bias, workspace, workspace_bytes,
+                        (hipStream_t)stream);
 }
 
 // ---- data parallel: a rank's rows -> [2][N] float64, every rank's [world][2][N] -> the batch's.  rows [world] on the host: each rank's R_r = 24 bodies_r.
+// Each entry is the one-call entry's own body cut at the collective: the same helpers, the same kernels, another source or destination.
 extern "C" int ehm_gcn_train_stats_local(const ehm_gcn* h, int conv, const float* z, int bodies, int have_sums, double* local, void* workspace,
                                          int64_t workspace_bytes, void* stream) {
   TrainConv c;
-  const int rc = train_conv_of(h, conv, &c);
+  int rc = train_conv_of(h, conv, &c);
   if (rc != 0) return rc;
-  EHM_CHECK_ARG(z && local && (uintptr_t)local % 8 == 0 && bodies > 0 && (have_sums == 0 || have_sums == 1));
-  EHM_CHECK_ARG(workspace_ok(workspace, workspace_bytes, c.N, bodies));
-  const TrainPlan w = plan_of(workspace, c.N, bodies);
-  hipStream_t st = (hipStream_t)stream;
-  const double R = (double)bodies * kJ;
-  if (!have_sums)
-    hipLaunchKernelGGL(train_colsum_kernel<false>, w.cgrid, dim3(NT), 0, st, z, (const double*)nullptr, w.part0, c.N, bodies, w.groups, w.chunks);
-  hipLaunchKernelGGL(train_mean_kernel, w.ngrid, dim3(256), 0, st, (const double*)w.part0, w.meand, c.N, w.groups, R);
-  hipLaunchKernelGGL(train_colsum_kernel<true>, w.cgrid, dim3(NT), 0, st, z, (const double*)w.meand, w.part1, c.N, bodies, w.groups, w.chunks);
-  hipLaunchKernelGGL(train_local_stats, w.ngrid, dim3(256), 0, st, (const double*)w.part1, (const double*)w.meand, c.N, w.groups, local);
+  EHM_CHECK_ARG(local && (uintptr_t)local % 8 == 0);
+  TrainPlan w;
+  if ((rc = train_moments(c, z, bodies, have_sums, workspace, workspace_bytes, (hipStream_t)stream, &w)) != 0) return rc;
+  hipLaunchKernelGGL(train_stats_finish, w.ngrid, dim3(256), 0, (hipStream_t)stream, own_moments(w.part1, w.meand, w.groups, (double)bodies * kJ), c.N, 0.0,
+                     0.0, local, (float*)nullptr, (float*)nullptr, (float*)nullptr, (float*)nullptr);
   EHM_LAUNCH_CHECK();
   return 0;
 }
@@ -423,13 +418,13 @@ extern "C" int ehm_gcn_train_stats_merge(const ehm_gcn* h, int conv, const doubl
   TrainConv c;
   int rc = train_conv_of(h, conv, &c);
   if (rc != 0) return rc;
-  RankRows rr;
-  if ((rc = rank_rows_of(rows, world, &rr)) != 0) return rc;
+  BnMoments all = {nullptr, nullptr, 0, gathered, world, {}};
+  if ((rc = rank_rows_of(rows, world, &all.rr)) != 0) return rc;
   EHM_CHECK_ARG(gathered && (uintptr_t)gathered % 8 == 0 && mean && invstd && eps >= 0.0 && momentum >= 0.0 && momentum <= 1.0);
   EHM_CHECK_ARG((running_mean == nullptr) == (running_var == nullptr));
   for (int k = 0; k < world; ++k) EHM_CHECK_ARG(rows[k] % kJ == 0);
-  hipLaunchKernelGGL(train_merge_stats, dim3((unsigned)ceil_div(c.N, 256)), dim3(256), 0, (hipStream_t)stream, gathered, rr, world, c.N, eps, momentum, mean,
-                     invstd, running_mean, running_var);
+  hipLaunchKernelGGL(train_stats_finish, dim3((unsigned)ceil_div(c.N, 256)), dim3(256), 0, (hipStream_t)stream, all, c.N, eps, momentum, (double*)nullptr,
+                     mean, invstd, running_mean, running_var);
   EHM_LAUNCH_CHECK();
   return 0;
 }
@@ -437,14 +432,13 @@ extern "C" int ehm_gcn_train_stats_merge(const ehm_gcn* h, int conv, const doubl
 extern "C" int ehm_gcn_train_bwd_local(const ehm_gcn* h, int conv, const float* gout, const float* gate, const float* z, const float* mean,
                                        const float* invstd, int bodies, double* local, void* workspace, int64_t workspace_bytes, void* stream) {
   TrainConv c;
-  const int rc = train_conv_of(h, conv, &c);
+  int rc = train_conv_of(h, conv, &c);
   if (rc != 0) return rc;
-  EHM_CHECK_ARG(gout && gate && z && mean && invstd && local && (uintptr_t)local % 8 == 0 && bodies > 0);
-  EHM_CHECK_ARG(workspace_ok(workspace, workspace_bytes, c.N, bodies));
-  const TrainPlan w = plan_of(workspace, c.N, bodies);
-  hipStream_t st = (hipStream_t)stream;
-  hipLaunchKernelGGL(train_bnbwd_partial, w.cgrid, dim3(NT), 0, st, gout, gate, z, mean, invstd, w.part0, w.part1, c.N, bodies, w.groups, w.chunks);
-  hipLaunchKernelGGL(train_local_bwd, w.ngrid, dim3(256), 0, st, (const double*)w.part0, (const double*)w.part1, c.N, w.groups, local);
+  EHM_CHECK_ARG(local && (uintptr_t)local % 8 == 0);
+  TrainPlan w;
+  if ((rc = train_bwd_partials(c, gout, gate, z, mean, invstd, bodies, workspace, workspace_bytes, (hipStream_t)stream, &w)) != 0) return rc;
+  hipLaunchKernelGGL(train_bwd_reduce, w.ngrid, dim3(256), 0, (hipStream_t)stream, (const double*)w.part0, (const double*)w.part1, (size_t)c.N, w.groups, -1,
+                     c.N, 0.0, local, (float*)nullptr, (float*)nullptr, (float*)nullptr, (float*)nullptr);
   EHM_LAUNCH_CHECK();
   return 0;
 }
@@ -458,18 +452,6 @@ extern "C" int ehm_gcn_train_bwd_merge(const ehm_gcn* h, int conv, const double*
   RankRows rr;
   if ((rc = rank_rows_of(rows, world, &rr)) != 0) return rc;
   EHM_CHECK_ARG(gathered && (uintptr_t)gathered % 8 == 0 && rank >= 0 && rank < world && bodies > 0 && rows[rank] == (int64_t)bodies * kJ);
-  EHM_CHECK_ARG(gout && gate && z && mean && invstd && zbar);
-  EHM_CHECK_ARG((const void*)zbar != (const void*)gate && (const void*)zbar != (const void*)z);
-  EHM_CHECK_ARG(((uintptr_t)gout | (uintptr_t)gate | (uintptr_t)z | (uintptr_t)mean | (uintptr_t)invstd | (uintptr_t)zbar |
-                 (uintptr_t)c.raw.bn_weight) % 16 == 0);
-  EHM_CHECK_ARG(workspace_ok(workspace, workspace_bytes, c.N, bodies));
-  const TrainPlan w = plan_of(workspace, c.N, bodies);
-  hipStream_t st = (hipStream_t)stream;
-  const long long total4 = (long long)bodies * kJ * (c.N / 4);
-  EHM_CHECK_ARG(ceil_div(total4, 256) < (1ll << 31));
-  hipLaunchKernelGGL(train_merge_bwd, w.ngrid, dim3(256), 0, st, gathered, world, rank, c.N, rr.total, gbn_weight, gbn_bias, w.bR, w.gR);
-  hipLaunchKernelGGL(train_zbar_kernel, dim3((unsigned)ceil_div(total4, 256)), dim3(256), 0, st, gout, gate, z, mean, invstd, c.raw.bn_weight,
-                     (const float*)w.bR, (const float*)w.gR, zbar, c.N / 4, total4);
-  EHM_LAUNCH_CHECK();
-  return 0;
+  return train_backward(c, gathered, world, rank, rr.total, gout, gate, z, mean, invstd, bodies, zbar, gbn_weight, gbn_bias, workspace, workspace_bytes,
+                        (hipStream_t)stream);
 }

@@ -277,7 +277,8 @@ int ehm_gcn_train_bwd_params(const ehm_gcn* h, int conv, const float* zbar, cons
 /* Data parallel: the batch's rows are spread over `world` ranks (at most 64), rank r holds R_r = 24 bodies_r of them.  Each rank runs the passes above on
  * its own rows and stops at local [2][N] float64 ON THE DEVICE; the caller all-gathers them into gathered [world][2][N] (ONE collective per BatchNorm each
  * way) and every rank merges that buffer in rank order: all ranks get the same bits.  rows [world] int64 ON THE HOST: every R_r (>= 24, a multiple of 24;
- * together >= 2 rows).  With world == 1 a local + merge pair writes the bits of ehm_gcn_train_stats / ehm_gcn_train_bn_backward.
+ * together >= 2 rows).  A local + merge pair and the one-call entry share one body (the same passes, one write-out kernel, one reduce kernel), cut at the
+ * collective: with world == 1 the pair writes the bits of ehm_gcn_train_stats / ehm_gcn_train_bn_backward by construction.
  *   stats_local: local = (mu_r, M2_r = sum (z - mu_r)^2), two-pass; have_sums as above; no running-statistic update.
  *   stats_merge: R = sum R_r,  mu = mu_0 + sum R_r (mu_r - mu_0) / R,  M2 = sum M2_r + sum R_r (mu_r - mu)^2  (Chan et al.; nothing cancels when the
  *                ranks' means lie many sigma apart),  var = M2 / R -> mean, invstd and the running update with the GLOBAL R (unbiased by R / (R - 1)).
@@ -446,8 +447,9 @@ int ehm_bn2d_train_bwd_zbar(const float* G, const void* z, int z_is_x2, int64_t 
                             void* stream);
 /* Data parallel, as the ehm_gcn_train_*_local / _merge entries: local [2][C] float64 on the device, gathered [world][2][C], rows [world] int64 on the host
  * (each rank's pixel count R_r >= 1; together >= 2), world <= 64.  A rank's `pixels` may be 1 here; float32 rows need C % 8 == 0 only (X2: C % 32 == 0).
- * The workspace is that of ehm_bn2d_train_workspace_bytes(max(pixels, 2), C rounded up to 32).  With world == 1, local + merge write the bits of
- * ehm_bn2d_train_stats / ehm_bn2d_train_bwd_sums, and zbar_rows with total_rows = N Ho Wo those of ehm_bn2d_train_bwd_zbar.
+ * The workspace is that of ehm_bn2d_train_workspace_bytes(max(pixels, 2), C rounded up to 32).  A local + merge pair and the one-call entry share one body, cut at
+ * the collective, and both zbar entries one checked launch: with world == 1, local + merge write the bits of ehm_bn2d_train_stats /
+ * ehm_bn2d_train_bwd_sums, and zbar_rows with total_rows = N Ho Wo those of ehm_bn2d_train_bwd_zbar, by construction.
  *   stats_local: local = (mu_r, M2_r), two-pass, no running update.     stats_merge: Chan et al.'s merge in rank order -> mean, var, invstd; the running
  *   update and *num_batches_tracked += 1 with the GLOBAL R.             bwd_local: local = (sum G, sum G xhat) with the merged mean / invstd.
  *   bwd_merge: gbeta / ggamma = the ranks' sums added in rank order (for zbar_rows); gbeta_own / ggamma_own (either may be NULL) = float32 of rank `rank`'s
