@@ -11,6 +11,7 @@ _LAZY = {
     "create_gaussian_diffusion": ("diffusion", "create_gaussian_diffusion"),
     "SpacedDiffusion": ("diffusion", "SpacedDiffusion"),
     "GaussianDiffusion": ("diffusion", "GaussianDiffusion"),
+    "ClassifierFreeSampleModel": ("diffusion", "ClassifierFreeSampleModel"),
     "EgoHMR": ("model", "EgoHMR"),
     "EgoHMRVolsmpl": ("model", "EgoHMRVolsmpl"),
     "rot6d_to_rotmat": ("geometry", "rot6d_to_rotmat"),

@@ -150,7 +150,7 @@ class ItemPrepDesc(C.Structure):
                 ("tW1", C.c_void_p), ("tb1", C.c_void_p), ("tW2", C.c_void_p), ("tb2", C.c_void_p), ("t_hidden", C.c_int), ("t_out", C.c_int),
                 ("img_rowsum", C.c_void_p), ("scene_rowsum", C.c_void_p), ("other", C.c_void_p), ("other_ld", C.c_int), ("other_col0", C.c_int),
                 ("vis", C.c_void_p), ("mask_slot", C.c_void_p), ("mask_items", C.c_void_p), ("count", C.c_void_p), ("finite", C.c_void_p),
-                ("need_scratch", C.c_void_p), ("pass_group", C.c_int), ("B", C.c_int)]
+                ("need_scratch", C.c_void_p), ("pass_group", C.c_int), ("B", C.c_int), ("need_all", C.c_int)]
 
 
 class PackDesc(C.Structure):
@@ -265,6 +265,8 @@ PROTOTYPES = {
     "ehm_gcn_stack_status": (_I, [_P, _P]),
     "ehm_gcn_stack_status_async": (_I, [_P, _P, _P]),
     "ehm_gcn_output_layer": (_I, [_P, _P, _P, _P, _I, _I, _P]),
+    "ehm_gcn_output_layer_cfg": (_I, [_P, _P, _P, _P, _I, _I, _F, _F, _P]),
+    "ehm_gcn_set_fuse_scales": (_I, [_P, _I, _F, _F]),
     "ehm_gcn_bwd_epilogue": (_I, [_P, _I, _P, _P, _P, _I, _I, _P]),
     "ehm_gcn_bwd_params_workspace_bytes": (_I, [_P, _I, _I, C.POINTER(C.c_int64)]),
     "ehm_gcn_bwd_params": (_I, [_P, _I, _P, _P, _P, _I, _I, _P, _P, _P, _P, _P, _P, _L, _P]),

@@ -18,6 +18,7 @@
 //   * BatchNorm is folded into per-channel scale/shift, the adjacency is symmetrised once.
 #include <stdlib.h>
 
+#include <cmath>
 #include "common.h"
 #include "egohmr_hip.h"
 #include "gcn_dev.h"
@@ -274,7 +275,8 @@ __global__ __launch_bounds__(256) void gcn_input_rows_kernel(GcnInputArgs a) {
 // ------------------------------------------------------------------------------------------------
 // output conv (hid -> 6, both branches) + visibility fuse, two kernels:
 //   gcn_out_dot_kernel   HBM-bound: every activation row is read once (float4); [rows,K] x [K,12] on the exact-f32 MFMA.
-//   gcn_out_mix_kernel   per body: modulated adjacency mix of the [24 x 12] responses, bias, pass selection by visibility.
+//   gcn_out_mix_kernel   per body: modulated adjacency mix of the [24 x 12] responses, bias, pass selection by visibility (CFG: the two passes
+//                        combined with guidance scales, x0 = u + s (c - u), s = vis ? s_vis : s_inv; s == 1 / s == 0 select c / u unchanged).
 // ------------------------------------------------------------------------------------------------
 
 // [rows, K] x [K, 12] on the exact-f32 MFMA (v_mfma_f32_16x16x4_f32: 16 rows x 16 columns, 12 used).  Block = 16 rows, its 4 waves
@@ -288,8 +290,10 @@ __global__ __launch_bounds__(256) void gcn_out_dot_kernel(const float* __restric
   gcn_out_dot_rows16<HALF_IN, 0>(X, O, hs, (int64_t)blockIdx.x * OUT_ROWS_PER_BLOCK, rows, part, (int)threadIdx.x);
 }
 
+template <bool CFG>
 __global__ __launch_bounds__(192) void gcn_out_mix_kernel(const float* __restrict__ hs, OutDev O, const uint8_t* __restrict__ vis,
-                                                          float* __restrict__ x0, int B, int passes, const int32_t* __restrict__ mask_slot) {
+                                                          float* __restrict__ x0, int B, int passes, const int32_t* __restrict__ mask_slot,
+                                                          float s_vis, float s_inv) {
   __shared__ float sh[2][kJ][12];
   __shared__ float outs[2][kJ][6];
   const int b = blockIdx.x, tid = threadIdx.x;
@@ -312,7 +316,15 @@ __global__ __launch_bounds__(192) void gcn_out_mix_kernel(const float* __restric
   if (tid < kPoseDim) {
     const int j = tid / 6, c = tid % 6;
     float v = outs[0][j][c];
-    if (passes == 2 && !vis[(size_t)b * kJ + j]) v = outs[1][j][c];   // egohmr.py:249-254
+    if constexpr (CFG) {
+      // (a pruned item, slot < 0, has scale-1 joints only by the pass map's rule: its zero second-pass rows never reach a result)
+      const float gs = (passes == 2 && slot >= 0) ? (vis[(size_t)b * kJ + j] ? s_vis : s_inv) : 1.f;
+      const float u = outs[passes - 1][j][c];
+      if (gs == 0.f) v = u;
+      else if (gs != 1.f) v = __fadd_rn(u, __fmul_rn(gs, __fsub_rn(v, u)));   // egohmr.py:249, one rounding per torch op
+    } else {
+      if (passes == 2 && !vis[(size_t)b * kJ + j]) v = outs[1][j][c];   // egohmr.py:249-254
+    }
     x0[(size_t)b * kPoseDim + tid] = v;
   }
 }
@@ -655,15 +667,38 @@ int ehm_gcn_output_dot_impl(ehm_gcn* h, const GcnRun& r, const float* X, int B, 
   return 0;
 }
 
+namespace {
+template <bool CFG>
+int gcn_output_layer(ehm_gcn* h, const float* X, const uint8_t* vis, float* x0, int B, int passes, float s_vis, float s_inv, hipStream_t st) {
+  const float* hs;
+  const int rc = ehm_gcn_output_dot_impl(h, h->run, X, B, passes, &hs, st);
+  if (rc != 0) return rc;
+  hipLaunchKernelGGL(gcn_out_mix_kernel<CFG>, dim3(B), dim3(192), 0, st, hs, h->out, vis, x0, B, passes, h->run.slots(passes), s_vis, s_inv);
+  EHM_LAUNCH_CHECK();
+  return 0;
+}
+}  // namespace
+
 extern "C" int ehm_gcn_output_layer(ehm_gcn* h, const float* X, const uint8_t* vis, float* x0, int B, int passes,
                                     void* stream) {
   EHM_CHECK_ARG(h && X && x0);
   EHM_CHECK_ARG(B > 0 && (passes == 1 || (passes == 2 && vis)));
-  const float* hs;
-  const int rc = ehm_gcn_output_dot_impl(h, h->run, X, B, passes, &hs, (hipStream_t)stream);
-  if (rc != 0) return rc;
-  hipLaunchKernelGGL(gcn_out_mix_kernel, dim3(B), dim3(192), 0, (hipStream_t)stream, hs, h->out, vis, x0, B, passes, h->run.slots(passes));
-  EHM_LAUNCH_CHECK();
+  return gcn_output_layer<false>(h, X, vis, x0, B, passes, 1.f, 0.f, (hipStream_t)stream);
+}
+
+extern "C" int ehm_gcn_output_layer_cfg(ehm_gcn* h, const float* X, const uint8_t* vis, float* x0, int B, int passes, float scale_visible,
+                                        float scale_invisible, void* stream) {
+  EHM_CHECK_ARG(h && X && x0);
+  EHM_CHECK_ARG(B > 0 && (passes == 1 || (passes == 2 && vis)));
+  EHM_CHECK_ARG(std::isfinite(scale_visible) && std::isfinite(scale_invisible));
+  return gcn_output_layer<true>(h, X, vis, x0, B, passes, scale_visible, scale_invisible, (hipStream_t)stream);
+}
+
+extern "C" int ehm_gcn_set_fuse_scales(ehm_gcn* h, int cfg, float scale_visible, float scale_invisible) {
+  EHM_CHECK_ARG(h && (cfg == 0 || (cfg == 1 && std::isfinite(scale_visible) && std::isfinite(scale_invisible))));
+  h->run.cfg = cfg;
+  h->run.s_vis = cfg ? scale_visible : 1.f;
+  h->run.s_inv = cfg ? scale_invisible : 0.f;
   return 0;
 }
 

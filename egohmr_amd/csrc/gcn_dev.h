@@ -48,6 +48,8 @@ struct GcnRun {
   const int32_t* mask_items = nullptr;   // exact pass pruning (ehm_gcn_set_pass_map): items that need the second pass, [num_masked] ...
   const int32_t* mask_slot = nullptr;    // ... and for every item its slot in that list or -1, [B]; nullptr = every item has a second pass
   int num_masked = -1;
+  int cfg = 0;                           // visibility fuse of the sampling loop's steps (ehm_gcn_set_fuse_scales): 0 = select, 1 = u + s (c - u) with ...
+  float s_vis = 1.f, s_inv = 0.f;        // ... s on visible / invisible joints
   int uncond_masks_all = 0;              // second ("unconditional") pass of diffuse_fuse: 0 = image features masked, 1 = whole condition masked
   int64_t valid_rows = 0;                // rows the input conv / checked pack produced (0: unknown = all): what the epilogues' range guard looks at - the
                                          // tile padding behind them holds don't-care values (float32 rows of a last conv re-read as X2 halves, uninitialised scratch)

@@ -3,6 +3,11 @@
 #include "common.h"
 #include "egohmr_hip.h"
 
+// the visibility fuse of a step: cfg = 0 selects (x0 = vis ? c : u), cfg = 1 combines with guidance scales (ehm_gcn_set_fuse_scales, step_dev.h)
+struct EhmFuseScales {
+  int cfg = 0;
+  float s_vis = 1.f, s_inv = 0.f;
+};
 // smpl.hip
 int ehm_smpl_forward_impl(ehm_smpl* h, const float* betas, const float* rot_or_x, bool from_rot6d, const float* mean,
                           const float* std_, float* verts, float* joints, float* Rws, float* Aws, float* pose6d_out, int B,
@@ -18,13 +23,13 @@ int ehm_step_body_impl(ehm_smpl* h, const float* hs, const void* out_dev, const 
                        const float* grad, float* x_next, float* x0, const ehm_step_coefs* c, int ddim, int passes, const int32_t* mask_slot, int do_pose,
                        const float* betas, const float* mean, const float* std_, float* verts, float* joints, float* Rws, float* Aws,
                        float* pose6d, int B, hipStream_t st, const struct GcnInputArgs* next_input = nullptr, int next_prec = 0,
-                       int* fused = nullptr, void* defer_pf = nullptr);   // defer_pf: write the blend fragments there and launch NO skinning (ehm_skin_steps_impl later)
+                       int* fused = nullptr, void* defer_pf = nullptr, const EhmFuseScales& fs = EhmFuseScales());   // defer_pf: write the blend fragments there and launch NO skinning (ehm_skin_steps_impl later)
 int ehm_skin_steps_impl(ehm_smpl* h, const float* A_steps, const void* pf_steps, int nsteps, int final_step, int B, float* verts, float* joints,
                         float* scratch_verts, float* scratch_joints, hipStream_t st);
 // step.hip: a step's tail (output responses, x0, x_{t-1}) + the next step's input conv in one launch; the poses of pending steps in one launch
 int ehm_step_fused_impl(const void* out_dev, const float* X, int prec, const uint8_t* vis, const float* x, const float* noise, const float* grad,
                         float* x_next, float* x0, const ehm_step_coefs* c, int ddim, int passes, const int32_t* mask_slot, int B,
-                        const struct GcnInputArgs* next_input, int next_prec, hipStream_t st);
+                        const struct GcnInputArgs* next_input, int next_prec, hipStream_t st, const EhmFuseScales& fs = EhmFuseScales());
 int ehm_pose_steps_impl(ehm_smpl* smpl, const float* x0_steps, int nsteps, int final_step, int B, const float* betas, const float* mean,
                         const float* std_, float* A_steps, void* pf_steps, float* R, float* joints, float* pose6d, float* x0_final,
                         float* scratch_joints, hipStream_t st);

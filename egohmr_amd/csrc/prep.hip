@@ -66,7 +66,7 @@ __global__ __launch_bounds__(kPrepThreads) void item_prep_kernel(ehm_item_prep_d
     if (d.img_rowsum) ok = ok && isfinite(d.img_rowsum[b]);
     if (d.scene_rowsum) ok = ok && isfinite(d.scene_rowsum[b]);
     d.finite[b] = ok ? 1 : 0;
-    need[b] = all_vis ? 0 : 1;
+    need[b] = (d.need_all || !all_vis) ? 1 : 0;
   }
 }
 

@@ -236,6 +236,9 @@ extern "C" int ehm_sample_loop(ehm_gcn* gcn, ehm_smpl* smpl, const ehm_sample_de
   EHM_CHECK_ARG(d->B > 0 && d->num_steps > 0 && (d->passes == 1 || d->passes == 2));
   GcnRun base = gcn->run;      // the handle's settings at entry: every step runs on a copy of them, the handle is left as it is
   EHM_CHECK_ARG(d->passes == 1 || base.virtual_bodies(d->B, 2) == d->B + (d->num_masked >= 0 ? d->num_masked : d->B));   // desc and ehm_gcn_set_pass_map agree
+  // the visibility fuse of every step (both launch routes; ehm_gcn_set_fuse_scales): cfg = 0 selects and does not look at the scales
+  EhmFuseScales fuse;
+  fuse.cfg = base.cfg; fuse.s_vis = base.s_vis; fuse.s_inv = base.s_inv;
   const int hid = gcn->hid, nh = gcn->num_hidden, V = ehm_smpl_num_verts(smpl);
   EHM_CHECK_ARG(nh % 2 == 0);
   bool any_guided = false;
@@ -342,7 +345,7 @@ extern "C" int ehm_sample_loop(ehm_gcn* gcn, ehm_smpl* smpl, const ehm_sample_de
       if (rc == 0 && !last) rc = ehm_gcn_input_args(gcn, run, h_img, h_oth, vis, dst, Wx, tvecs + (int64_t)(k + 1) * 2 * hid, w.X[0], B, d->passes, &nin);
       if (rc == 0)
         rc = ehm_step_fused_impl(out_dev, feat, run.precision, vis, w.x_cur, eps, grad, dst, defer_skin ? w.loop_x0 + (int64_t)pending * n : x0_final,
-                                 &c, d->ddim, d->passes, run.slots(d->passes), B, last ? nullptr : &nin, gcn_input_format(gcn, prec_of(k + 1)), st);
+                                 &c, d->ddim, d->passes, run.slots(d->passes), B, last ? nullptr : &nin, gcn_input_format(gcn, prec_of(k + 1)), st, fuse);
       input_done = !last;
       if (rc == 0 && defer_skin) {
         pending_poses = true;
@@ -373,13 +376,13 @@ extern "C" int ehm_sample_loop(ehm_gcn* gcn, ehm_smpl* smpl, const ehm_sample_de
         // the step leaves its transforms and fragments in slot `pending`; no skinning (and no fused input conv) launch now
         rc = ehm_step_body_impl(smpl, hs, out_dev, vis, w.x_cur, eps, grad, dst, x0_final, &c, d->ddim, d->passes, run.slots(d->passes), 1,
                                 betas, mean, std_, verts, joints, R, w.loop_A + (int64_t)pending * B * kJ * 12, pose6d, B, st, nullptr, 0, nullptr,
-                                (char*)w.loop_pf + (int64_t)pending * pf_bytes_step);
+                                (char*)w.loop_pf + (int64_t)pending * pf_bytes_step, fuse);
         ++pending;
         if (rc == 0 && (pending == w.skin_seg || last)) rc = flush_skin(last);
       } else if (rc == 0) {
         rc = ehm_step_body_impl(smpl, hs, out_dev, vis, w.x_cur, eps, grad, dst, x0_final, &c, d->ddim, d->passes, run.slots(d->passes),
                                 (d->lbs_every_step || last) ? 1 : 0,
-                                betas, mean, std_, verts, joints, R, w.A, pose6d, B, st, pnin, gcn_input_format(gcn, prec_of(k + 1)), &fused);
+                                betas, mean, std_, verts, joints, R, w.A, pose6d, B, st, pnin, gcn_input_format(gcn, prec_of(k + 1)), &fused, nullptr, fuse);
       }
       input_done = fused != 0;
     }

@@ -616,12 +616,17 @@ __global__ __launch_bounds__(64) void step_body_kernel(StepBodyArgs a, SmplDev S
   __shared__ StepBodyLds L;
   step_body_one(blockIdx.x, threadIdx.x, a, S, L, [] { __syncthreads(); });
 }
+// ... with guidance scales on the two passes (ehm_gcn_set_fuse_scales: cfg = 1)
+__global__ __launch_bounds__(64) void step_body_cfg_kernel(StepBodyArgs a, SmplDev S) {
+  __shared__ StepBodyLds L;
+  step_body_one<false, true, false, true>(blockIdx.x, threadIdx.x, a, S, L, [] { __syncthreads(); });
+}
 
 // sampler.hip's per-step call: output-conv mix + sampler update + pose chain + fragment pack in one launch, then the skinning launch.
 int ehm_step_body_impl(ehm_smpl* h, const float* hs, const void* out_dev, const uint8_t* vis, const float* x, const float* noise,
                        const float* grad, float* x_next, float* x0, const ehm_step_coefs* c, int ddim, int passes, const int32_t* mask_slot, int do_pose,
                        const float* betas, const float* mean, const float* std_, float* verts, float* joints, float* Rws, float* Aws,
-                       float* pose6d, int B, hipStream_t st, const GcnInputArgs* next_input, int next_prec, int* fused, void* defer_pf) {
+                       float* pose6d, int B, hipStream_t st, const GcnInputArgs* next_input, int next_prec, int* fused, void* defer_pf, const EhmFuseScales& fs) {
   const SmplDev& d = h->d;
   if (fused) *fused = 0;
   constexpr int mfma_min = kSkinMfmaMinBodies;
@@ -648,7 +653,9 @@ int ehm_step_body_impl(ehm_smpl* h, const float* hs, const void* out_dev, const 
   {
     EhmProfScope ps(EHM_PROF_STEP_BODY, st);
     a.trace = nullptr;
-    hipLaunchKernelGGL(step_body_kernel, dim3(B), dim3(64), 0, st, a, d);
+    a.s_vis = fs.s_vis; a.s_inv = fs.s_inv;
+    if (fs.cfg) hipLaunchKernelGGL(step_body_cfg_kernel, dim3(B), dim3(64), 0, st, a, d);
+    else hipLaunchKernelGGL(step_body_kernel, dim3(B), dim3(64), 0, st, a, d);
   }
   if (do_pose && !defer_pf) {
     EhmProfScope ps(EHM_PROF_SKIN_INPUT, st);

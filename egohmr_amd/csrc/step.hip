@@ -37,7 +37,9 @@ constexpr int kFusedT = kJ * 256;              // floats of one 256-channel grou
 //  and a race: the chain's result and the next input rows share one buffer, which is only safe while ONE block reads a body's rows before it
 //  overwrites them.)  The update runs on three waves (48 elements each) instead of one.
 // Per output the arithmetic is that of the per-step kernels (same device functions, same order): bit-equal.
-template <bool HALF_IN, int OUT, int NT>
+// CFG: the update combines the two passes with guidance scales (step_dev.h: step_body_one<.., CFG>) - instantiations of their own, so that the
+// visibility select keeps its code.
+template <bool HALF_IN, int OUT, int NT, bool CFG = false>
 __global__ __launch_bounds__(NT, 4) void step_fused_kernel(StepFusedArgs a) {
   constexpr int G = NT / 256, NWV = NT / 64;                        // 256-thread groups, waves
   __shared__ __attribute__((aligned(16))) float T[G * kFusedT];     // G transpose tiles (24 KiB each); the response partials alias the first 12 KiB
@@ -70,7 +72,7 @@ __global__ __launch_bounds__(NT, 4) void step_fused_kernel(StepFusedArgs a) {
   // ---- x0 and x_{t-1} of the body (three waves, 48 elements each; the step's pose is left to pose_steps_kernel)
   if (wave < 3) {
     SmplDev unused;                                                        // (WITH_POSE = false: never read)
-    step_body_one<true, false, true>(b, lane, a.sb, unused, L, [] {}, wave, 3);
+    step_body_one<true, false, true, CFG>(b, lane, a.sb, unused, L, [] {}, wave, 3);
   }
   if (!a.do_input) return;
   __syncthreads();                                                         // L.xn is complete
@@ -117,15 +119,20 @@ __global__ __launch_bounds__(64) void pose_steps_kernel(PoseStepsArgs p, SmplDev
   step_pose_part(b, lane, a, S, L, [] { __syncthreads(); }, L.x0s);
 }
 
-template <bool HALF_IN, int NT>
+template <bool HALF_IN, int NT, bool CFG = false>
 void launch_fused2(int next_prec, int B, hipStream_t st, const StepFusedArgs& a) {
   const dim3 grid((unsigned)B), blk(NT);
-  if (next_prec == EHM_PREC_F32) hipLaunchKernelGGL((step_fused_kernel<HALF_IN, 0, NT>), grid, blk, 0, st, a);
-  else if (next_prec == EHM_PREC_F16X3) hipLaunchKernelGGL((step_fused_kernel<HALF_IN, 1, NT>), grid, blk, 0, st, a);
-  else hipLaunchKernelGGL((step_fused_kernel<HALF_IN, 2, NT>), grid, blk, 0, st, a);
+  if (next_prec == EHM_PREC_F32) hipLaunchKernelGGL((step_fused_kernel<HALF_IN, 0, NT, CFG>), grid, blk, 0, st, a);
+  else if (next_prec == EHM_PREC_F16X3) hipLaunchKernelGGL((step_fused_kernel<HALF_IN, 1, NT, CFG>), grid, blk, 0, st, a);
+  else hipLaunchKernelGGL((step_fused_kernel<HALF_IN, 2, NT, CFG>), grid, blk, 0, st, a);
 }
 template <bool HALF_IN>
-void launch_fused(int next_prec, int B, hipStream_t st, const StepFusedArgs& a) {
+void launch_fused(int next_prec, int B, hipStream_t st, const StepFusedArgs& a, bool cfg) {
+  if (cfg) {      // guidance scales: the wide block up to one body per CU, the 256-thread one beyond (the 512-thread form spills at its register cap)
+    if (B <= ehm_num_cus()) launch_fused2<HALF_IN, 1024, true>(next_prec, B, st, a);
+    else launch_fused2<HALF_IN, 256, true>(next_prec, B, st, a);
+    return;
+  }
   if (B <= ehm_num_cus()) launch_fused2<HALF_IN, 1024>(next_prec, B, st, a);     // one body per CU: the wide block
   else if (B > 2 * ehm_num_cus()) launch_fused2<HALF_IN, 256>(next_prec, B, st, a);   // four blocks per CU (round 6: 1280 bodies 246 -> 222 us, same box)
   else launch_fused2<HALF_IN, 512>(next_prec, B, st, a);                          // two blocks per CU
@@ -137,12 +144,13 @@ void launch_fused(int next_prec, int B, hipStream_t st, const StepFusedArgs& a) 
 // precision `prec` (f16 rows for EHM_PREC_F16, float32 rows otherwise); the next step's rows are written in the format `next_prec` (gcn_input_format).
 int ehm_step_fused_impl(const void* out_dev, const float* X, int prec, const uint8_t* vis, const float* x, const float* noise, const float* grad,
                         float* x_next, float* x0, const ehm_step_coefs* c, int ddim, int passes, const int32_t* mask_slot, int B,
-                        const GcnInputArgs* next_input, int next_prec, hipStream_t st) {
+                        const GcnInputArgs* next_input, int next_prec, hipStream_t st, const EhmFuseScales& fs) {
   StepFusedArgs a{};
   a.X = X;
   a.sb.hs = nullptr; a.sb.O = *(const OutDev*)out_dev; a.sb.vis = vis; a.sb.x = x; a.sb.noise = noise; a.sb.grad = grad; a.sb.x_next = x_next;
   a.sb.x0 = x0; a.sb.c = *c; a.sb.ddim = ddim; a.sb.passes = passes; a.sb.B = B; a.sb.do_pose = 0; a.sb.mask_slot = mask_slot;
   a.sb.trace = nullptr; a.sb.pf = nullptr;
+  a.sb.s_vis = fs.s_vis; a.sb.s_inv = fs.s_inv;
   if (a.sb.O.K % 64 != 0) {
     ehm_set_error("ehm_step_fused_impl: hidden width %d is not a multiple of 64", a.sb.O.K);
     return EHM_EINVAL;
@@ -150,8 +158,8 @@ int ehm_step_fused_impl(const void* out_dev, const float* X, int prec, const uin
   a.do_input = next_input ? 1 : 0;
   if (next_input) a.in = *next_input;
   EhmProfScope ps(EHM_PROF_STEP_FUSED, st);
-  if (prec == EHM_PREC_F16) launch_fused<true>(next_prec, B, st, a);
-  else launch_fused<false>(next_prec, B, st, a);
+  if (prec == EHM_PREC_F16) launch_fused<true>(next_prec, B, st, a, fs.cfg != 0);
+  else launch_fused<false>(next_prec, B, st, a, fs.cfg != 0);
   EHM_LAUNCH_CHECK();
   return 0;
 }

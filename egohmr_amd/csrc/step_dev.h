@@ -102,10 +102,15 @@ struct StepBodyArgs {
   float* x0;                // [B,144]
   ehm_step_coefs c;
   int ddim, passes, B, do_pose;
+  float s_vis;              // guidance scales of the CFG instantiations of step_body_one: x0 = u + s (c - u), s = vis ? s_vis : s_inv.  The select
+                            // (CFG = false, ehm_gcn_set_fuse_scales: cfg = 0) never reads them; which of the two runs is the host's choice of kernel, so there
+                            // is no `cfg` word here.  Both sit in what was alignment padding: the struct - and with it the kernel-argument layout of
+                            // every kernel that takes it - keeps its size, and the select kernels their scalar-register allocation.
   const int32_t* mask_slot; // pass pruning (ehm_gcn_set_pass_map) or nullptr
   const float *betas, *mean, *std_;
   float *Rws, *Aws, *joints, *pose6d;
   int jstride;
+  float s_inv;
   sk_half8* pf;             // nullptr: VALU skinning path (B < 24), no fragments
   float* trace;             // [B,144] or nullptr: receives x_t as this step read it
 };
@@ -180,7 +185,10 @@ __device__ __forceinline__ void step_stage_tables(int b, int lane, const StepBod
 // step_stage_tables itself (and ordered it).
 // (wi, nw): the body's 144 elements are dealt out to `nw` cooperating waves, this one being number `wi` (the arithmetic per element does not
 // depend on who computes it; a caller with nw > 1 orders the waves' LDS results itself and must not ask for the pose).
-template <bool HS_LDS = false, bool WITH_POSE = true, bool STAGED = false, class Sync>
+// CFG: the two passes' outputs c (conditional) and u (masked) are combined per joint as u + s (c - u), s = vis ? a.s_vis : a.s_inv, one rounding per
+// torch op of egohmr.py:249; s == 1 takes c and s == 0 takes u unchanged (selects: (1, 0) is the CFG = false fuse, bit for bit).  An item without
+// a second pass (passes == 1, or pruned: slot < 0, every joint of it has s == 1 by the pass map's rule) takes c: its sh[1] rows are never read.
+template <bool HS_LDS = false, bool WITH_POSE = true, bool STAGED = false, bool CFG = false, class Sync>
 __device__ __forceinline__ void step_body_one(int b, int lane, const StepBodyArgs& a, const SmplDev& S, StepBodyLds& L, Sync sync, int wi = 0, int nw = 1) {
   float (&sh)[2][kJ][12] = L.sh;
   float (&x0s)[kPoseDim] = L.x0s;
@@ -188,14 +196,31 @@ __device__ __forceinline__ void step_body_one(int b, int lane, const StepBodyArg
   float (&sMo)[kJ * 6] = L.sMo;
   if constexpr (!STAGED) step_stage_tables<HS_LDS>(b, lane, a, L);
   sync();
+  bool two = false;                                                               // CFG: this body has a second pass to combine with
+  if constexpr (CFG) two = a.passes == 2 && (!a.mask_slot || a.mask_slot[b] >= 0);
   for (int e = lane + 64 * wi; e < kPoseDim; e += 64 * nw) {
     const int j = e / 6, c = e % 6;
-    const int p = (a.passes == 2 && !a.vis[(size_t)b * kJ + j]) ? 1 : 0;          // egohmr.py:249-254
-    const float s = sAo[j * kJ + j] * (sMo[j * 6 + c] * sh[p][j][c]);
-    float t = 0.f;
-    for (int jp = 0; jp < kJ; ++jp)
-      if (jp != j) t = fmaf(sAo[j * kJ + jp], sMo[jp * 6 + c] * sh[p][jp][6 + c], t);
-    const float x0 = s + t + a.O.bias[c];
+    float x0;                   // (the output mix is spelled out in both branches: shared as a lambda it cost the select's 512-thread kernels 20 bytes of scratch)
+    if constexpr (CFG) {
+      const float gs = two ? (a.vis[(size_t)b * kJ + j] ? a.s_vis : a.s_inv) : 1.f;
+      float o[2] = {0.f, 0.f};                                                    // output conv of the passes that are asked for: c, u
+      for (int p = 0; p < 2; ++p) {
+        if (p == 0 ? gs == 0.f : gs == 1.f) continue;
+        const float s = sAo[j * kJ + j] * (sMo[j * 6 + c] * sh[p][j][c]);
+        float t = 0.f;
+        for (int jp = 0; jp < kJ; ++jp)
+          if (jp != j) t = fmaf(sAo[j * kJ + jp], sMo[jp * 6 + c] * sh[p][jp][6 + c], t);
+        o[p] = s + t + a.O.bias[c];
+      }
+      x0 = gs == 1.f ? o[0] : gs == 0.f ? o[1] : __fadd_rn(o[1], __fmul_rn(gs, __fsub_rn(o[0], o[1])));   // egohmr.py:249, one rounding per torch op
+    } else {
+      const int p = (a.passes == 2 && !a.vis[(size_t)b * kJ + j]) ? 1 : 0;          // egohmr.py:249-254
+      const float s = sAo[j * kJ + j] * (sMo[j * 6 + c] * sh[p][j][c]);
+      float t = 0.f;
+      for (int jp = 0; jp < kJ; ++jp)
+        if (jp != j) t = fmaf(sAo[j * kJ + jp], sMo[jp * 6 + c] * sh[p][jp][6 + c], t);
+      x0 = s + t + a.O.bias[c];
+    }
     const size_t i = (size_t)b * kPoseDim + e;
     a.x0[i] = x0;
     x0s[e] = x0;

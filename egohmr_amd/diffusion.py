@@ -21,6 +21,7 @@ reference's order (randn(*shape) once, then randn_like once per step, t == 0 inc
 """
 from __future__ import annotations
 
+import contextlib
 import math
 
 import numpy as np
@@ -28,7 +29,70 @@ import torch as th
 
 from . import _lib
 
-__all__ = ["create_gaussian_diffusion", "GaussianDiffusion", "SpacedDiffusion", "space_timesteps", "get_named_beta_schedule"]
+__all__ = ["create_gaussian_diffusion", "GaussianDiffusion", "SpacedDiffusion", "space_timesteps", "get_named_beta_schedule",
+           "ClassifierFreeSampleModel"]
+
+
+class ClassifierFreeSampleModel(th.nn.Module):
+    """diffusion/cfg_sampler.py::ClassifierFreeSampleModel(model, guidance_param=2.5), runnable: the reference's wrapper calls
+    `model(batch, t, force_mask=True)` on a forward without that argument and does arithmetic on the two returned dicts.  What it intends,
+
+        out = U + w (F - U),    F = model(batch, t), U = model(batch, t, force_mask=True), w = guidance_param,
+
+    is applied here to `pred_x_start`, and every other entry of the output dict is decoded from that x0 as EgoHMR.forward decodes its own.  With
+    c / u the denoiser's conditional / masked outputs, the model's own fuse is F = u + g (c - u) per joint (g = guidance_param_visible on visible
+    joints, the model's guidance_param on invisible ones; g = guidance_param_visible on all joints without diffuse_fuse) and U = u, so
+
+        U + w (F - U) = u + w g (c - u):
+
+    the wrapped model with its scales multiplied by w - s_vis = w * guidance_param_visible, s_inv = w * model.guidance_param for a fuse model, w * g
+    on all joints otherwise (EgoHMR.fuse_scales(outer=w)).  One denoiser evaluation of two passes computes it (three forwards would compute u twice),
+    inside the same kernels: `forward`, p_sample_loop, ddim_sample_loop and val_losses run the native routes of the wrapped model with the outer scale.
+
+    Holds `.model` and `.guidance_param`; every other attribute (parameters, validation_setup, guide_coll, compute_loss, eval_coll, fused_sampler, ...)
+    is the wrapped model's."""
+
+    def __init__(self, model, guidance_param=2.5):
+        super().__init__()
+        self.model = model
+        self.guidance_param = guidance_param
+
+    def __getattr__(self, name):
+        try:
+            return super().__getattr__(name)
+        except AttributeError:
+            inner = self.__dict__.get("_modules", {}).get("model", self.__dict__.get("model"))   # (a wrapped callable that is no nn.Module is a plain attribute)
+            if inner is None or name == "model":
+                raise
+            return getattr(inner, name)
+
+    @contextlib.contextmanager
+    def guidance_scope(self):
+        """The wrapped model samples with this wrapper's scale as its outer scale inside the block (EgoHMR.outer_guidance).  Entering it again
+        inside (a sampler's step around this wrapper's forward) changes nothing; a wrapper around a wrapper multiplies the scales, as the formula does."""
+        inner, w = self, 1.0
+        while isinstance(inner, ClassifierFreeSampleModel):
+            inner, w = inner.model, w * float(inner.guidance_param)
+        if self.__dict__.get("_in_scope"):
+            yield inner
+            return
+        keep = inner.outer_guidance
+        inner.outer_guidance = keep * w
+        self.__dict__["_in_scope"] = True
+        try:
+            yield inner
+        finally:
+            self.__dict__["_in_scope"] = False
+            inner.outer_guidance = keep
+
+    def forward(self, batch, timesteps):
+        with self.guidance_scope() as inner:
+            return inner(batch, timesteps)
+
+
+def _guidance_scope(model):
+    """The block in which `model` samples: a ClassifierFreeSampleModel sets its outer scale on the wrapped model, anything else changes nothing."""
+    return model.guidance_scope() if isinstance(model, ClassifierFreeSampleModel) else contextlib.nullcontext(model)
 
 
 def get_named_beta_schedule(schedule_name, num_diffusion_timesteps, scale_betas=1.0):
@@ -181,6 +245,10 @@ class GaussianDiffusion:
         return int(t[0])
 
     def _step(self, model, batch, x, t, ddim, guided, cond_grad_weight, eta, noise, index=None):
+        with _guidance_scope(model):     # (a ClassifierFreeSampleModel: its forward and its guide_coll see one set of scales, one cached conditioning)
+            return self._step_scoped(model, batch, x, t, ddim, guided, cond_grad_weight, eta, noise, index)
+
+    def _step_scoped(self, model, batch, x, t, ddim, guided, cond_grad_weight, eta, noise, index):
         i = self._uniform_index(t) if index is None else index      # the loops pass their python index: no device read-back
         batch["x_t"] = x
         mo = model(batch, self._model_timesteps(t))
@@ -297,7 +365,8 @@ class GaussianDiffusion:
         if self._fused_ok(model, skip_timesteps, init_data, dump_steps, progress, 0.0, guided=cond_fn_with_grad):
             device = self._device_of(model, device)
             stack = noise_stack if noise_stack is not None else self._draw_stack(shape, device, noise)
-            return model.fused_sampler.run(self, batch, stack, ddim=False, guided=cond_fn_with_grad, cond_grad_weight=cond_grad_weight)
+            with _guidance_scope(model):
+                return model.fused_sampler.run(self, batch, stack, ddim=False, guided=cond_fn_with_grad, cond_grad_weight=cond_grad_weight)
         final, dump = None, []
         for i, sample in enumerate(self.p_sample_loop_progressive(
                 model, batch, shape, noise=noise, clip_denoised=clip_denoised, denoised_fn=denoised_fn, device=device,
@@ -315,7 +384,8 @@ class GaussianDiffusion:
             # (cond_fn_with_grad: ddim_sample_with_grad inside the one-call loop - the collision gradient enters eps on the last four respaced steps)
             device = self._device_of(model, device)
             stack = noise_stack if noise_stack is not None else self._draw_stack(shape, device, noise)
-            return model.fused_sampler.run(self, batch, stack, ddim=True, guided=bool(cond_fn_with_grad), cond_grad_weight=1.0 if cond_fn_with_grad else 0.0)
+            with _guidance_scope(model):
+                return model.fused_sampler.run(self, batch, stack, ddim=True, guided=bool(cond_fn_with_grad), cond_grad_weight=1.0 if cond_fn_with_grad else 0.0)
         final = None
         for sample in self.ddim_sample_loop_progressive(
                 model, batch, shape, noise=noise, clip_denoised=clip_denoised, denoised_fn=denoised_fn, device=device,

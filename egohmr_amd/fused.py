@@ -30,6 +30,20 @@ def pass_map(need):
     return mask_items, mask_slot, int(mask_items.numel())
 
 
+def need_all_items(scales) -> bool:
+    """THE need rule, part 1 (per call): with guidance scales (s_vis, s_inv) on the fuse x0 = u + s (c - u), item b needs the masked second pass iff
+    some joint of it has s != 1.  s_vis != 1: every joint does, so every item needs it and the pass map is the identity."""
+    return float(scales[0]) != 1.0
+
+
+def item_need(vis_bool, need_all):
+    """THE need rule, part 2 (per item), for calls that run two passes at all (EgoHMR.fuse_passes: s_inv != 1 or s_vis != 1): [B] bool, every item
+    under need_all, else the items with an invisible joint - what item_prep_kernel (csrc/prep.hip, ehm_item_prep_desc.need_all) computes."""
+    if need_all:
+        return torch.ones(vis_bool.shape[0], dtype=torch.bool, device=vis_bool.device)
+    return ~vis_bool.all(dim=1)
+
+
 @dataclasses.dataclass
 class _Prepared:
     """The step-invariant conditioning of a batch (FusedSampler.prepare)."""
@@ -52,6 +66,10 @@ class _Prepared:
     num_masked: int
     inputs: list = None                 # strong references to the batch tensors behind the cache key (prepare)
 
+    # the pass map was made for scales with s_vis != 1 (need_all_items): every item has a second pass.  A plain attribute that the operations below
+    # hand on, not a field: it describes the map, like num_masked, and is set by whoever makes one
+    need_all = False
+
     PER_ITEM = ("h_img", "h_oth", "vis", "vis_bool", "betas", "scene", "transl", "fx", "cam_cx", "cam_cy", "img_feats", "scene_feats", "finite")
 
     def take(self, index):
@@ -62,20 +80,34 @@ class _Prepared:
             index = torch.arange(index, device=self.vis.device)
         index = index.to(self.vis.device, torch.long)
         picked = {k: getattr(self, k).index_select(0, index).contiguous() for k in self.PER_ITEM}
-        mask_items, mask_slot, num_masked = pass_map(~picked["vis_bool"].all(dim=1))
-        return dataclasses.replace(self, B=int(index.numel()), mask_items=mask_items, mask_slot=mask_slot, num_masked=num_masked, **picked)
+        mask_items, mask_slot, num_masked = pass_map(item_need(picked["vis_bool"], self.need_all))
+        out = dataclasses.replace(self, B=int(index.numel()), mask_items=mask_items, mask_slot=mask_slot, num_masked=num_masked, **picked)
+        out.need_all = self.need_all
+        return out
+
+    def with_need(self, need_all):
+        """The same batch with the pass map of the other need rule (one host read-back; nothing is encoded again)."""
+        if bool(need_all) == bool(self.need_all):
+            return self
+        mask_items, mask_slot, num_masked = pass_map(item_need(self.vis_bool, need_all))
+        out = dataclasses.replace(self, mask_items=mask_items, mask_slot=mask_slot, num_masked=num_masked)
+        out.need_all = bool(need_all)
+        return out
 
     def tile(self, S):
         """The batch S times, sample-major (body s * B + b); its pass map by offset arithmetic on the device (= pass_map(need.repeat(S)),
-        tests/test_prepared_cpu.py, without the host read-back).  num_masked = -1 (no map) stays -1."""
+        tests/test_prepared_cpu.py, without the host read-back; the arithmetic holds for any per-item need, so for either rule of item_need).
+        num_masked = -1 (no map) stays -1."""
         B, nm = self.B, max(self.num_masked, 0)
         off = torch.arange(S, device=self.mask_slot.device, dtype=torch.int32).view(-1, 1)
         slot = self.mask_slot.view(1, -1)
         tiled = {k: getattr(self, k).repeat(S, *([1] * (getattr(self, k).dim() - 1))).contiguous() for k in self.PER_ITEM}
-        return dataclasses.replace(
+        out = dataclasses.replace(
             self, B=S * B, mask_items=(self.mask_items.view(1, -1) + off * B).reshape(-1).contiguous(),
             mask_slot=torch.where(slot >= 0, slot + off * nm, torch.full_like(slot, -1)).reshape(-1).contiguous(),
             num_masked=S * self.num_masked if self.num_masked >= 0 else self.num_masked, **tiled)
+        out.need_all = self.need_all
+        return out
 
 
 @dataclasses.dataclass
@@ -103,6 +135,7 @@ class FusedSampler:
         self.schedule_info = None       # the calibration the most recent 'auto' run used (None: ran all-f16x3 / explicit k)
         self.last_lowprec = 0
         self.last_twoterm = 0           # two-term steps (behind the plain-f16 ones) of the last call
+        self.last_fuse = (0, 1.0, 0.0)  # (cfg, s_vis, s_inv) the handle was given for the last loop (ehm_gcn_set_fuse_scales)
         self.last_trace = None
 
     @property
@@ -159,17 +192,20 @@ class FusedSampler:
 
     # ------------------------------------------------------------------ step-invariant conditioning
     @torch.no_grad()
-    def prepare(self, batch, _constants_only=False, _no_trunk=False) -> _Prepared:
+    def prepare(self, batch, _constants_only=False, _no_trunk=False, scales=None) -> _Prepared:
         """Everything in EgoHMR.forward that does not depend on x_t / t (egohmr.py:182-223, :263-265).
+        scales: the call's guidance scales (EgoHMR.fuse_scales; None = the model's for a default call) - they decide which items the pass map keeps
+        (need_all_items).
         _constants_only (the training route of EgoHMR.forward): only what stays constant with the trunk frozen - trunk, visibility, camera columns, scene,
         translation; the PointNet, the projections, the beta head and the native handle are left out (h_img, h_oth, betas, scene_feats = None, no pass map,
         no host read-back; `other` holds ehm_item_prep's operand).  Such an entry is cached under a key of its own: no other caller ever sees it.
         _no_trunk (with _constants_only, behind EgoHMR.trunk_grad): the trunk is left out too - img_feats = None, the caller runs it with a graph -
         again under a key of its own."""
         with _lib.on_device(self.model.device):          # every native call below launches on the CURRENT device's stream
-            return self._prepare_on_device(batch, _constants_only, _constants_only and _no_trunk)
+            need_all = False if _constants_only else need_all_items(self.model.sampling_scales() if scales is None else scales)
+            return self._prepare_on_device(batch, _constants_only, _constants_only and _no_trunk, need_all)
 
-    def _prepare_on_device(self, batch, constants_only=False, no_trunk=False) -> _Prepared:
+    def _prepare_on_device(self, batch, constants_only=False, no_trunk=False, need_all=False) -> _Prepared:
         m = self.model
         # Cache key = identity AND version of every tensor the conditioning is computed from, and of every weight it passes
         # through.  The cached entry keeps strong references to those input tensors, so neither their id() nor their storage can be
@@ -189,7 +225,12 @@ class FusedSampler:
             key += ("constants_only",)
         if no_trunk:
             key += ("no_trunk",)
+        base_key, key = key, key + (("need_all", bool(need_all)),)
         if self._prep is not None and self._prep_key == key:
+            return self._prep
+        if self._prep is not None and not constants_only and self._prep_key[:-1] == base_key and isinstance(self._prep_key[-1], tuple):
+            # the same batch under the other need rule: only the pass map differs, the conditioning is not encoded again
+            self._prep, self._prep_key = self._prep.with_need(need_all), key
             return self._prep
         if not constants_only:
             self.gcn()
@@ -236,7 +277,7 @@ class FusedSampler:
                               tW2=P(tw[2]), tb2=P(tw[3]), t_hidden=te[0].out_features, t_out=n_tr, img_rowsum=P(sums[0]),
                               scene_rowsum=P(sums[1]), other=P(oth), other_ld=k_oth, other_col0=n_scene, vis=P(vis),
                               mask_slot=P(maps), mask_items=P(maps[B:]), count=P(maps[2 * B:]), finite=P(flags),
-                              need_scratch=P(flags[1]), pass_group=1, B=B)
+                              need_scratch=P(flags[1]), pass_group=1, B=B, need_all=int(bool(need_all)))
         _lib.api().ehm_item_prep(C.byref(d), st)
         if self._count_host is None:
             self._count_host = torch.zeros(1, dtype=torch.int32).pin_memory()
@@ -267,6 +308,7 @@ class FusedSampler:
                                betas=betas, scene=scene, transl=transl, fx=fx, cam_cx=cx, cam_cy=cy, img_feats=img_feats,
                                scene_feats=scene_feats, finite=flags[0].view(torch.bool), mask_items=maps[B:B + num_masked],
                                mask_slot=maps[:B], num_masked=num_masked, inputs=ins)      # (inputs: strong references, see the key above)
+        self._prep.need_all = bool(need_all)
         self._prep_key = key
         return self._prep
 
@@ -378,12 +420,24 @@ class FusedSampler:
         return self._ws
 
     @torch.no_grad()
-    def denoise_once(self, st, x_t, tvec, passes):
+    def denoise_once(self, st, x_t, tvec, passes=None, scales=None):
+        """x0 [B,144] of one denoiser evaluation with guidance scales `scales` on the two passes (None: the model's for a default call; passes follows
+        from them, EgoHMR.fuse_passes).  Scales (1, 0) - the reference's fuse - and one-pass calls take the select of ehm_gcn_output_layer."""
         m, A = self.model, _lib.api()
+        scales = m.sampling_scales() if scales is None else tuple(float(v) for v in scales)
+        passes = m.fuse_passes(scales) if passes is None else passes
+        if passes == 2:
+            st = st.with_need(need_all_items(scales))
         rows = self._apply_pass_map(st, passes)[0] * 24
         h = self.gcn()
         fill = lambda X0: A.ehm_gcn_input_layer(h, st.h_img, st.h_oth, st.vis, x_t, self._folded.Wx, tvec, X0, st.B, passes, _lib.stream_ptr())
-        return m.diffusion_model.denoiser_tail(h, fill, rows=rows, B=st.B, passes=passes, vis=st.vis, precision=m.gcn_precision, device=m.device)
+        return m.diffusion_model.denoiser_tail(h, fill, rows=rows, B=st.B, passes=passes, vis=st.vis, precision=m.gcn_precision, device=m.device,
+                                               scales=scales if self._cfg_kernels(passes, scales) else None)
+
+    def _cfg_kernels(self, passes, scales) -> bool:
+        """Whether a call combines its passes with the guidance kernels (ehm_gcn_set_fuse_scales: cfg = 1, ehm_gcn_output_layer_cfg) or takes the select:
+        the select computes exactly the scales (1, 0), and a one-pass call has nothing to combine."""
+        return passes == 2 and (tuple(scales) != (1.0, 0.0) or bool(self.model.force_cfg_kernels))
 
     # ------------------------------------------------------------------ guidance pieces
     @torch.no_grad()
@@ -427,13 +481,14 @@ class FusedSampler:
     # ------------------------------------------------------------------ precision schedule: calibrated per checkpoint
     def schedule_key(self, diffusion, ddim: bool, n_guided: int, cond_grad_weight: float = 0.0, guide_denom: float = 1.0):
         """What a calibrated k is valid for: these denoiser / embedder weights (identity + version of every tensor), this sampler
-        (original timesteps visited, ancestral or DDIM), this guidance window, weight and reduction, this tolerance.  The batch size behind a
+        (original timesteps visited, ancestral or DDIM), this guidance window, weight and reduction, these classifier-free guidance scales
+        (EgoHMR.sampling_scales), this tolerance.  The batch size behind a
         `-loss.mean()` (guide_denom) is NOT part of the key: a ragged last batch, or ranks with different shard sizes, must find the job's one
         calibration (the f16 steps end >= 8 steps before the guided window whatever its strength)."""
         m = self.model
         return (self._param_key(), self._cond_param_key(), tuple(diffusion.timestep_map), int(getattr(diffusion, "original_num_steps", diffusion.num_timesteps)),
                 bool(ddim), int(n_guided), (float(cond_grad_weight), str(m.guide_reduction)) if n_guided else None, bool(m.guide_all_points) if n_guided else False,
-                bool(m.diffuse_fuse),
+                bool(m.diffuse_fuse), tuple(float(v) for v in m.sampling_scales()),   # (s multiplies the two passes' rounding errors: k is per scale pair)
                 float(m.schedule_tol), str(getattr(m, "f16x2_steps", 0)))
 
     def lowprec_steps(self, T: int, guided=False, ddim: bool = True, key=None) -> int:
@@ -610,12 +665,11 @@ class FusedSampler:
         x = torch.randn(st.B, 144, device=m.device, generator=g)
         d = torch.randn(st.B, 144, device=m.device, generator=g)
         d = d / d.norm(dim=1, keepdim=True) * delta
-        passes = 2 if m.diffuse_fuse else 1
         out = {}
         for t in timesteps:
             tv = self.timestep_vectors(torch.tensor([int(t)], device=m.device))[0]
-            a = self.denoise_once(st, x, tv, passes).clone()
-            b = self.denoise_once(st, (x + d).contiguous(), tv, passes)
+            a = self.denoise_once(st, x, tv).clone()
+            b = self.denoise_once(st, (x + d).contiguous(), tv)
             out[int(t)] = float(((b - a).norm(dim=1) / delta).mean())
         return out
 
@@ -700,7 +754,10 @@ class FusedSampler:
             raise _lib.EgoHMRHipError(m.diffusion_model.NONLOCAL_F16)
         if self._status_event is not None and self._status_event.query():   # a deferred status word of an earlier call has arrived: look at it now
             self.check_status()
-        st = prepared if prepared is not None else self.prepare(batch)
+        scales = m.sampling_scales()                      # (raises on a non-finite scale before any device call)
+        st = prepared if prepared is not None else self.prepare(batch, scales=scales)
+        if m.fuse_passes(scales) == 2:
+            st = st.with_need(need_all_items(scales))     # (a `prepared` batch made under the other need rule: its pass map again, nothing else)
         B, T = st.B, diffusion.num_timesteps
         noise = _lib.f32(noise_stack, m.device)
         assert noise.shape[0] >= T + 1 and noise.shape[1] == B and noise.shape[2] == 144, noise.shape
@@ -716,7 +773,7 @@ class FusedSampler:
         self.last_lowprec = int(lowprec)                  # leading steps of THIS call on plain f16 operands
         self.last_twoterm = twoterm                       # ... and behind them on two-term split-f16 products
         desc, nbytes = self._describe(st=st, T=T, ddim=ddim, any_guided=any_guided, denom_items=denom_items or B, lowprec=lowprec, nonlocal_ci=nonlocal_ci,
-                                      twoterm=twoterm)
+                                      twoterm=twoterm, scales=scales)
         gcn, smpl_h = self.gcn(), m.smpl.handle()
         launch = partial(self._launch, gcn=gcn, smpl_h=smpl_h, desc=desc, steps=steps, nbytes=nbytes, any_guided=any_guided)
         ins = dict(h_img=st.h_img, h_oth=st.h_oth, vis=st.vis, tvecs=tvecs, noise=noise[: T + 1].contiguous(), betas=st.betas, scene=st.scene)
@@ -743,11 +800,17 @@ class FusedSampler:
         lowprec = self.lowprec_steps(diffusion.num_timesteps, n_guided, ddim, key=skey)
         return lowprec, self.twoterm_steps(diffusion.num_timesteps, lowprec, key=skey)
 
-    def _describe(self, *, st, T, ddim, any_guided, denom_items, lowprec, nonlocal_ci, twoterm=0):
-        """(the loop's descriptor, its workspace size) after giving the handle this batch's pass map."""
+    def _describe(self, *, st, T, ddim, any_guided, denom_items, lowprec, nonlocal_ci, twoterm=0, scales=None):
+        """(the loop's descriptor, its workspace size) after giving the handle this batch's pass map.  scales: the call's guidance scales (None: the
+        model's); passes = 2 unless both are 1 - also for a diffuse_fuse=False model under a wrapper's outer scale."""
         m = self.model
-        passes = 2 if m.diffuse_fuse else 1
+        scales = m.sampling_scales() if scales is None else scales
+        passes = m.fuse_passes(scales)
+        cfg = self._cfg_kernels(passes, scales)
         _, num_masked = self._apply_pass_map(st, passes)
+        # ... and how the loop's steps combine the two passes (a setting of the handle, read by ehm_sample_loop at entry like the map)
+        self.last_fuse = (int(cfg), float(scales[0]) if cfg else 1.0, float(scales[1]) if cfg else 0.0)
+        _lib.api().ehm_gcn_set_fuse_scales(self.gcn(), *self.last_fuse)
         desc = _lib.SampleDesc(B=st.B, passes=passes, num_steps=T, ddim=int(ddim), per_step_launches=int(bool(m.per_step_launches)),
                                lbs_every_step=int(m.lbs_every_step), num_scene_points=st.scene.shape[1] if any_guided else 0,
                                guide_denom=self.guide_denom(denom_items), tau=m.collision_tau, num_masked=num_masked,
@@ -773,7 +836,7 @@ class FusedSampler:
         mean, std = m._std_mean()
         # (every pointer the captured launches bake in that is not inside `bufs`: the two native handles - by serial, a recreated handle
         # can reuse a destroyed one's address - and the mean / std buffers)
-        key = (st.B, desc.num_steps, desc.ddim, desc.passes, desc.lbs_every_step, desc.lowprec_steps, desc.twoterm_steps, m.gcn_precision, gcn.serial,
+        key = (st.B, desc.num_steps, desc.ddim, desc.passes, desc.lbs_every_step, desc.lowprec_steps, desc.twoterm_steps, self.last_fuse, m.gcn_precision, gcn.serial,
                bytes(steps), st.scene.shape[1], desc.num_masked, smpl_h.serial,
                mean.data_ptr(), std.data_ptr(), self._folded.Wx.data_ptr(), self._nl_set)
         ent = self._graphs.get(key)

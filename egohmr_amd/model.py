@@ -16,6 +16,7 @@ denoiser, rot6d->rotmat, SMPL LBS and the sampler update are hand-written HIP ke
 from __future__ import annotations
 
 import ctypes as C
+import math
 from types import SimpleNamespace
 
 import numpy as np
@@ -180,9 +181,10 @@ class ModulatedGCN(nn.Module):
     NONLOCAL_F16 = "the optional non-local GCN block runs on float32 features; use precision 'f16x3' or 'f32' (EgoHMR.gcn_precision, ModulatedGCN.precision) with it"
 
     @torch.no_grad()
-    def denoiser_tail(self, h, fill, *, rows, B, passes, vis, precision, device):
+    def denoiser_tail(self, h, fill, *, rows, B, passes, vis, precision, device, scales=None):
         """x0 [B, 144] from the native handle `h`: fill(X0) writes the input conv's `rows` rows into a zeroed [rows_pad, hid] buffer, then the residual blocks as
-        ONE chained launch, the optional non-local block and gconv_output (vis / passes: the image-masked second pass).  precision: its name, as set on `h`."""
+        ONE chained launch, the optional non-local block and gconv_output (vis / passes: the image-masked second pass).  precision: its name, as set on `h`.
+        scales = (s_vis, s_inv): the two passes are combined per joint as u + s (c - u) (ehm_gcn_output_layer_cfg); None = the visibility select."""
         A = _lib.api()
         tile = A.ehm_gcn_row_tile()
         rows_pad = (rows + tile - 1) // tile * tile
@@ -198,7 +200,10 @@ class ModulatedGCN(nn.Module):
                 raise _lib.EgoHMRHipError(self.NONLOCAL_F16)
             feat = self.non_local_native(feat, rows, rows_pad)
         x0 = torch.empty(B, 144, device=device)
-        A.ehm_gcn_output_layer(h, feat, vis, x0, B, passes, s)
+        if scales is None:
+            A.ehm_gcn_output_layer(h, feat, vis, x0, B, passes, s)
+        else:
+            A.ehm_gcn_output_layer_cfg(h, feat, vis, x0, B, passes, float(scales[0]), float(scales[1]), s)
         return x0
 
     # ------------------------------------------------------------------ ModulatedGCN.forward on its own (modulated_gcn.py:99-116)
@@ -489,6 +494,13 @@ class EgoHMR(nn.Module):
         self.loop_bodies = 256
         self.per_step_launches = False     # True: the separate per-step launches of rounds 2-3 instead of step_fused_kernel (same bits; A/B runs and tests)
         self.prune_passes = True           # exact: items whose 24 joints are all visible skip the image-masked pass (egohmr.py:239-254)
+        # classifier-free guidance on the visibility fuse (egohmr.py:248-249, `diffuse_output_uncond + guidance_param * (diffuse_output -
+        # diffuse_output_uncond)`): x0 = u + s (c - u) per joint, s = guidance_param_visible on visible joints, guidance_param (the reference's local
+        # of :248, a literal 0 there) on invisible ones.  (1, 0) is the reference's fuse; see fuse_scales
+        self.guidance_param = 0.0
+        self.guidance_param_visible = 1.0
+        self.outer_guidance = 1.0          # the scale of a ClassifierFreeSampleModel around this model while it samples (diffusion.py); 1 = none
+        self.force_cfg_kernels = False     # True: scales (1, 0) run the guidance kernels too instead of the select (same bits; tests)
         # arithmetic of the hidden GCN convs: 'f32' (f32-input MFMA), 'f16x3' (split-f16 MFMA, f32-grade), 'f16' (plain f16, not parity-grade)
         self.gcn_precision = "f16x3"
         # arithmetic of the two conditioning encoders: 'f16x3' (split-f16, f32 grade - the parity path) | 'f16' (plain f16 operands and activations: the
@@ -555,13 +567,41 @@ class EgoHMR(nn.Module):
             return 1
         return td.get_world_size()
 
-    def forward(self, batch, timesteps, eval_with_uncond=True):
-        """One denoising evaluation (egohmr.py:173-303).  Conditioning is cached per batch object.  Under self.training with frozen_trunk_training set: the
-        training route (_forward_train), one pass whatever eval_with_uncond says."""
+    def fuse_scales(self, eval_with_uncond=True, force_mask=False, outer=1.0):
+        """(s_vis, s_inv): the guidance scales of visible / invisible joints in x0 = u + s (c - u), c the conditional output and u the masked one
+        (mask_cond(force_mask=True): image only or the whole condition, as only_mask_img_cond says).  force_mask: (0, 0), the masked output alone;
+        a diffuse_fuse model evaluated with its masked pass: outer * (guidance_param_visible, guidance_param); else outer * guidance_param_visible on
+        every joint.  `outer` is the scale of a wrapper (diffusion.ClassifierFreeSampleModel).  Python floats, handed to the device as float32: a scale
+        that is not finite there raises ValueError."""
+        gv, gi, w = float(self.guidance_param_visible), float(self.guidance_param), float(outer)
+        if force_mask:
+            s = (0.0, 0.0)
+        elif self.diffuse_fuse and eval_with_uncond:
+            s = (w * gv, w * gi)
+        else:
+            s = (w * gv, w * gv)
+        with np.errstate(over="ignore"):
+            if not all(math.isfinite(v) and math.isfinite(float(np.float32(v))) for v in s):
+                raise ValueError(f"guidance scales must be finite in float32: guidance_param_visible={gv}, guidance_param={gi}, outer scale={w}")
+        return s
+
+    @staticmethod
+    def fuse_passes(scales) -> int:
+        """Denoiser passes of a call with these scales: 1 exactly when both are 1.0 (x0 = c, no masked pass), else 2."""
+        return 1 if (scales[0] == 1.0 and scales[1] == 1.0) else 2
+
+    def sampling_scales(self, eval_with_uncond=True, force_mask=False):
+        """fuse_scales with the outer scale a wrapper has set for the call in progress (outer_guidance)."""
+        return self.fuse_scales(eval_with_uncond, force_mask, outer=self.outer_guidance)
+
+    def forward(self, batch, timesteps, eval_with_uncond=True, force_mask=False):
+        """One denoising evaluation (egohmr.py:173-303).  Conditioning is cached per batch object.  force_mask: the masked output alone
+        (mask_cond(force_mask=True), scales (0, 0)).  Under self.training with frozen_trunk_training set: the training route (_forward_train), one pass
+        whatever eval_with_uncond / force_mask say."""
         with _lib.on_device(self.device):                 # native calls launch on the CURRENT device's stream
             if self.training and self.frozen_trunk_training:
                 return self._forward_train(batch, timesteps)
-            return self._forward_on_device(batch, timesteps, eval_with_uncond)
+            return self._forward_on_device(batch, timesteps, eval_with_uncond, force_mask)
 
     def _check_trainable(self):
         """What the training route cannot run, refused before any device call."""
@@ -646,12 +686,13 @@ class EgoHMR(nn.Module):
         finally:
             self.smpl.ordered_backward = keep_ordered
 
-    def _forward_on_device(self, batch, timesteps, eval_with_uncond):
+    def _forward_on_device(self, batch, timesteps, eval_with_uncond, force_mask=False):
         fs = self.fused_sampler
-        st = fs.prepare(batch)
+        scales = self.sampling_scales(eval_with_uncond, force_mask)          # (raises on a non-finite scale before any device call)
+        passes = self.fuse_passes(scales)
+        st = fs.prepare(batch, scales=scales)
         x_t = _lib.f32(batch["x_t"], self.device).reshape(-1, 144)
         B = x_t.shape[0]
-        passes = 2 if (self.diffuse_fuse and eval_with_uncond) else 1
         # egohmr.py:178 embeds `timesteps` [bs] row by row.  The samplers always pass one value for the whole batch (gaussian_diffusion.py:495):
         # that is the one-launch route; a direct call with different values per item runs one denoiser evaluation per distinct value.
         ts = torch.as_tensor(timesteps, device=self.device).reshape(-1).long()
@@ -659,13 +700,13 @@ class EgoHMR(nn.Module):
             raise ValueError(f"timesteps must hold one value per item: got {ts.numel()} for a batch of {B}")
         uniq = torch.unique(ts) if ts.numel() > 1 else ts[:1]
         if uniq.numel() == 1:
-            x0 = fs.denoise_once(st, x_t, fs.timestep_vectors(uniq)[0], passes)
+            x0 = fs.denoise_once(st, x_t, fs.timestep_vectors(uniq)[0], passes, scales)
         else:
             x0 = torch.empty(B, 144, device=self.device)
             tv = fs.timestep_vectors(uniq)
             for i, t in enumerate(uniq.tolist()):
                 sel = torch.nonzero(ts == t).reshape(-1)
-                x0[sel] = fs.denoise_once(st.take(sel), x_t[sel].contiguous(), tv[i], passes)
+                x0[sel] = fs.denoise_once(st.take(sel), x_t[sel].contiguous(), tv[i], passes, scales)
         mean, std = self._std_mean()
         verts = torch.empty(B, self.smpl.num_verts, 3, device=self.device)
         joints = torch.empty(B, self.smpl.num_joints_out, 3, device=self.device)

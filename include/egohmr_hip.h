@@ -205,6 +205,19 @@ int ehm_gcn_stack_status_async(ehm_gcn* h, uint32_t* host_flag, void* stream);
  * X [rows_pad,hid] -> x0 [B,144]. */
 int ehm_gcn_output_layer(ehm_gcn* h, const float* X, const uint8_t* vis, float* x0, int B, int passes,
                          void* stream);
+/* The same with classifier-free guidance scales on the two passes (egohmr.py:248-249 with its `guidance_param` a knob, per joint class):
+ *   x0[b, j*6+c] = u + s (c - u),  c = out_cond[b,j,c], u = out_uncond[b,j,c],  s = vis[b,j] ? scale_visible : scale_invisible      (passes == 2)
+ *   x0 = out_cond                                                                                                                   (passes == 1)
+ * as float32 sub, mul, add with one rounding each; s == 1 takes c and s == 0 takes u unchanged, so (1, 0) gives ehm_gcn_output_layer's bits.
+ * An item the pass map prunes (ehm_gcn_set_pass_map: slot < 0) takes c on every joint: the caller's map must keep every item that has a joint
+ * with s != 1 (ehm_item_prep_desc.need_all when scale_visible != 1).  Non-finite scales are refused. */
+int ehm_gcn_output_layer_cfg(ehm_gcn* h, const float* X, const uint8_t* vis, float* x0, int B, int passes, float scale_visible,
+                             float scale_invisible, void* stream);
+/* The visibility fuse of ehm_sample_loop's steps (both launch routes), a setting of the handle like the pass map it goes with: the loop reads it at
+ * entry with the rest of the handle's settings.  cfg = 0 (the handle's default) = the select x0 = vis ? c : u, the scales are not read; cfg = 1 =
+ * x0 = u + s (c - u) as ehm_gcn_output_layer_cfg computes it ((1, 0) gives cfg = 0's bits; a loop of passes == 1 takes c).  ehm_sample_desc
+ * carries no such fields: its layout is pinned.  ehm_gcn_output_layer / _cfg do not look at this setting. */
+int ehm_gcn_set_fuse_scales(ehm_gcn* h, int cfg, float scale_visible, float scale_invisible);
 
 /* ------------------------------------------------------------------ Modulated-GCN denoiser: backward ---- */
 /* First derivatives of one graph conv in eval mode (frozen BatchNorm statistics) - modulated_gcn_conv.py:39-50, modulated_gcn.py:21-28, :38-42 -
@@ -732,6 +745,8 @@ int ehm_scene_select(const ehm_scene_desc* d, void* stream);
  *   mask_slot [B], mask_items [count], count [1] (int32)   which items need the image-masked second pass (:249-254: any invisible
  *                       joint), as ehm_gcn_set_pass_map wants them: slot of the item among those that do (ascending) or -1, and the
  *                       items in slot order.  pass_group > 1 rounds the need up to groups of pass_group consecutive items.
+ *                       need_all = 1: EVERY item needs the second pass (guidance scales with scale_visible != 1: every joint combines the
+ *                       two passes); 0 = the rule above.
  *   other[:, other_col0 ...] = TranslEnc(transl) (:217, Linear(3,t_hidden) -> ReLU -> Linear(t_hidden,t_out), torch [out,in] weights)
  *                       | camera features (:195-205: [cx, cy] / (fx*fx_norm), [box_center, box_size] / (fx*fx_norm), fx), zero-filled
  *                       up to other_ld (row stride of `other`; columns [0, other_col0) are the caller's: the scene features)
@@ -757,6 +772,7 @@ typedef struct ehm_item_prep_desc {
   uint8_t* need_scratch;
   int pass_group;
   int B;
+  int need_all;
 } ehm_item_prep_desc;
 int ehm_item_prep(const ehm_item_prep_desc* d, void* stream);
 
