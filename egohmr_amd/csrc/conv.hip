@@ -842,6 +842,8 @@ extern "C" int ehm_conv_nhwc_split(const ehm_conv_desc* d, void* stream) {
   EHM_CHECK_ARG(d->N > 0 && d->H > 0 && d->Wd > 0 && d->Ci > 0 && d->Co > 0 && d->Ci % CBK == 0 && d->Co % 8 == 0);
   EHM_CHECK_ARG(d->KH > 0 && d->KW > 0 && d->KH * d->KW <= 32 && (d->stride == 1 || d->stride == 2) && d->pad >= 0);
   EHM_CHECK_ARG(d->w_scale > 0.f);
+  // (a kernel larger than the padded image: with stride 2 the C division below would round -1 / 2 to 0 and hand out one output row)
+  EHM_CHECK_ARG(d->H + 2 * d->pad >= d->KH && d->Wd + 2 * d->pad >= d->KW);
   const int Ho = (d->H + 2 * d->pad - d->KH) / d->stride + 1, Wo = (d->Wd + 2 * d->pad - d->KW) / d->stride + 1;
   EHM_CHECK_ARG(Ho > 0 && Wo > 0);
   ConvArgs a;

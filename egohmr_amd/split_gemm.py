@@ -20,26 +20,35 @@ def round_up(n, m):
 
 
 def weight_scale(amax):
-    """The power of two a weight matrix of largest magnitude `amax` is packed with; 1 for an all-zero or non-finite one."""
-    return 2.0 ** math.floor(math.log2(2048.0 / amax)) if 0.0 < amax < float("inf") else 1.0
+    """The power of two a weight matrix of largest magnitude `amax` is packed with; 1 for an all-zero or non-finite one.  It brings amax into
+    (1024, 2048] and stops at 2^126: the engine takes it and its reciprocal as float32, and past 2^127 the one is inf and the other flushes (a
+    matrix whose largest entry is below 2^-115 is packed below 2048 instead)."""
+    if not 0.0 < amax < float("inf"):
+        return 1.0
+    r = 2048.0 / amax
+    return 2.0 ** min(math.floor(math.log2(r)), 126) if r < float("inf") else 2.0 ** 126
 
 
 class Packed(NamedTuple):
     buf: torch.Tensor               # X2 [Co padded to 128, K padded to 32]
     scale: float
     cols: int                       # Co rounded up to 8: the column count ehm_conv_nhwc_split writes
-    bias: Optional[torch.Tensor]    # float32 [Co] or None
+    bias: Optional[torch.Tensor]    # float32 [cols] (zeros behind Co) or None
 
 
 def pack_weight(w2, bias=None):
-    """float32 [Co, K] on a HIP device -> Packed (ehm_split_pack, scaled by weight_scale)."""
+    """float32 [Co, K] on a HIP device -> Packed (ehm_split_pack, scaled by weight_scale).  The engine reads bias[0 .. cols): a bias [Co] with
+    Co % 8 != 0 is zero-padded to cols here (the padding columns then come out as the residual alone, or zero)."""
     Co, K = w2.shape
     wp = torch.zeros(round_up(Co, 128), round_up(K, 32), device=w2.device)
     wp[:Co, :K] = w2
     scale = weight_scale(float(wp.abs().max()))
     buf = torch.empty_like(wp)
     _lib.api().ehm_split_pack(wp, buf, wp.shape[0], wp.shape[1], wp.shape[1], scale, _lib.stream_ptr())
-    return Packed(buf, scale, round_up(Co, 8), bias)
+    cols = round_up(Co, 8)
+    if bias is not None and bias.shape[0] != cols:
+        bias = torch.cat([bias, bias.new_zeros(cols - bias.shape[0])])
+    return Packed(buf, scale, cols, bias)
 
 
 def gemm_rows(x, packed, rows=None, res=None, out=None):

@@ -486,7 +486,19 @@ int ehm_bn2d_train_bwd_zbar_rows(const float* G, const void* z, int z_is_x2, int
  * ResNet-50 backbone (models/egohmr/egohmr.py:183).
  *   x [N,H,W,Ci] float32, Ci % 32 == 0;   y [N,Ho,Wo,Co] float32, Co % 8 == 0;   residual NULL or like y;   bias NULL or [Co]
  *   W: the weights as [Co_pad][KH*KW*Ci] (tap-major: k = (kh*KW + kw)*Ci + ci), Co_pad = Co rounded up to 128 with zero rows,
- *      multiplied by w_scale (a power of two) and packed with ehm_split_pack(..., K, K, w_scale, ...);  KH*KW <= 32 */
+ *      multiplied by w_scale (a power of two) and packed with ehm_split_pack(..., K, K, w_scale, ...);  KH*KW <= 32
+ * Lengths: the kernel stages 128 weight rows per column tile whatever Co is, so W must hold all Co_pad rows; bias is read at [0, Co) - a caller
+ *   whose true column count is no multiple of 8 passes Co rounded up to 8, zero weight rows behind the true ones and a bias of THAT length
+ *   (split_gemm.pack_weight pads it): a padding column comes out as act(residual), or 0.  stride is 1 or 2, pad >= 0, and the kernel must fit the
+ *   padded image (H + 2 pad >= KH, W + 2 pad >= KW); anything else is EHM_EINVAL before any device call.
+ * Range: an activation is split in the kernel into hi = f16(clamp(x, +-65504)) and lo = f16(x - hi): |x| <= 65504 is represented to 2^-22 |x| + 2^-25
+ *   (tests/conv_split_ref.py has the error bound the tests hold every output to).  A larger magnitude is outside the contract: lo carries the excess
+ *   over 65504 at f16 precision only, and past the format's 131008 it is inf - such an activation acts like an inf one (below); there is no range
+ *   flag.  Magnitudes below about 2^-14 lose their lo half to the f16 subnormal range: callers scale small operands up by a power of two first
+ *   (split_gemm.pow2_scale).
+ * Non-finite: a NaN or +-inf activation lands in its lo half and makes every output whose receptive field holds that pixel non-finite, in every
+ *   channel (0 . inf of a zero weight included), and no other output; with relu = 1 the epilogue's max(v, 0) then returns 0 for a NaN or -inf, so
+ *   a caller that must see the poison carries a flag beside the data.  An all-zero W on finite activations gives exactly act(bias + residual). */
 typedef struct ehm_conv_desc {
   const float* x; const void* W; const float* bias; const float* residual; float* y;
   int N, H, Wd, Ci, Co;
