@@ -29,7 +29,7 @@ _HERE = os.path.dirname(os.path.abspath(__file__))
 LIB_PATH = os.environ.get("EHM_LIB_PATH") or os.path.join(_HERE, "libegohmr_hip.so")   # EHM_LIB_PATH: A/B a second build (experiments)
 CSRC = os.path.join(_HERE, "csrc")
 INCLUDE = os.path.join(os.path.dirname(_HERE), "include")
-SOURCES = ["gcn.hip", "gcn_tile.hip", "linear.hip", "conv.hip", "stem.hip", "metrics.hip", "smpl.hip", "sampler.hip", "guidance.hip", "prep.hip", "step.hip", "eval.hip", "stage1.hip", "scene.hip", "loss.hip", "gcn_bwd.hip", "gcn_train.hip", "pointnet_bwd.hip", "train.hip", "conv_bwd.hip", "bn2d_train.hip", "nonlocal_bwd.hip"]
+SOURCES = ["gcn.hip", "gcn_tile.hip", "linear.hip", "conv.hip", "stem.hip", "metrics.hip", "smpl.hip", "sampler.hip", "guidance.hip", "prep.hip", "step.hip", "eval.hip", "stage1.hip", "scene.hip", "loss.hip", "gcn_bwd.hip", "gcn_train.hip", "pointnet_bwd.hip", "train.hip", "conv_bwd.hip", "bn2d_train.hip", "nonlocal_bwd.hip", "batch.hip"]
 
 
 class EgoHMRHipError(RuntimeError):
@@ -230,6 +230,12 @@ class SceneDesc(C.Structure):
                 ("status", C.c_void_p), ("workspace", C.c_void_p), ("workspace_bytes", C.c_int64)]
 
 
+class ImagePatchDesc(C.Structure):
+    """ehm_image_patch_desc"""
+    _fields_ = [("frames", C.c_void_p), ("F", C.c_int), ("H", C.c_int), ("W", C.c_int), ("frame_index", C.c_void_p), ("params", C.c_void_p),
+                ("B", C.c_int), ("P", C.c_int), ("quantize", C.c_int), ("mean", C.c_double * 3), ("std", C.c_double * 3), ("img", C.c_void_p)]
+
+
 _P, _I, _L, _F = C.c_void_p, C.c_int, C.c_int64, C.c_float
 
 # name -> (restype, argtypes); every symbol include/egohmr_hip.h declares
@@ -341,6 +347,8 @@ PROTOTYPES = {
     "ehm_stage1_head": (_I, [C.POINTER(Stage1Desc), _P]),
     "ehm_scene_workspace_bytes": (_I, [C.POINTER(SceneDesc), C.POINTER(C.c_int64)]),
     "ehm_scene_select": (_I, [C.POINTER(SceneDesc), _P]),
+    "ehm_image_patch": (_I, [C.POINTER(ImagePatchDesc), _P]),
+    "ehm_scene_augment": (_I, [_P, _I, _P, _P, _I, _I, _I, _P]),
     "ehm_sample_workspace_bytes": (_L, [C.POINTER(SampleDesc), _I, _I]),
     "ehm_sample_loop": (_I, [_P, _P, C.POINTER(SampleDesc), C.POINTER(StepCoefs)] + [_P] * 18 + [_L, _P]),
     "ehm_item_prep": (_I, [C.POINTER(ItemPrepDesc), _P]),

@@ -751,6 +751,51 @@ typedef struct ehm_scene_desc {
 int ehm_scene_workspace_bytes(const ehm_scene_desc* d, int64_t* bytes);
 int ehm_scene_select(const ehm_scene_desc* d, void* stream);
 
+/* ------------------------------------------------------------------ batch building ------------ */
+/* The two per-pixel / per-point stages of the reference loader's item (dataloaders/augmentation.py:get_example), per batch, on the device
+ * (csrc/batch.hip).  Everything else of the item is 25 rows of arithmetic and stays on the host (egohmr_amd/batch.py).
+ *
+ * Image patch: generate_image_patch's warp + BGR -> RGB + convert_cvimg_to_tensor + the colour / normalise loop (augmentation.py:121-150,
+ * :373-383) in one launch.  frames uint8 [F,H,W,3], BGR as decoded; item b reads frame frame_index[b] (any order, frames may be shared).
+ * params [B, EHM_PATCH_PARAMS] float64 per item: Minv (2x3, patch pixel -> source pixel: the closed-form inverse of the loader's `trans`), the
+ * flip flag (!= 0: the source is the mirrored frame, column W-1-x) and the three colour scales (RGB).  Output pixel (x, y), channel c (RGB;
+ * BGR channel 2-c), every float64 operation rounded on its own:
+ *   sx = (Minv00 x + Minv01 y) + Minv02, sy alike; x0 = floor(sx), fx = sx - x0; y0, fy alike
+ *   a, b, c, d = source (x0, y0), (x0+1, y0), (x0, y0+1), (x0+1, y0+1); a neighbour outside the frame is 0 and is never loaded
+ *   v = (a (1-fx) + b fx) (1-fy) + (c (1-fx) + d fx) fy;  quantize != 0: v = floor(v + 0.5) (the uint8 patch of the loader)
+ *   p = float32(v); p = clip(p * float32(color[c]), 0, 255); img = (p - float32(mean[c])) / float32(std[c])     (float32 operations)
+ * This is the real-valued bilinear rule, not cv2.warpAffine's 1/32-pixel grid with 15-bit weights.  An item whose frame index is outside
+ * [0, F) gets NaN pixels.  P % 4 == 0 (one thread writes four consecutive x of each plane), img 16-byte aligned, B <= 65535.  No atomics:
+ * two calls give the same bits. */
+#define EHM_PATCH_PARAMS 16
+#define EHM_PATCH_P_MINV 0    /* 6: the rows of Minv */
+#define EHM_PATCH_P_FLIP 6
+#define EHM_PATCH_P_COLOR 7   /* 3: RGB */
+typedef struct ehm_image_patch_desc {
+  const uint8_t* frames;        /* [F, H, W, 3] BGR */
+  int F, H, W;
+  const int32_t* frame_index;   /* [B] */
+  const double* params;         /* [B, EHM_PATCH_PARAMS] */
+  int B, P, quantize;
+  double mean[3], std[3];       /* RGB, 0..255 units */
+  float* img;                   /* [B, 3, P, P] */
+} ehm_image_patch_desc;
+int ehm_image_patch(const ehm_image_patch_desc* d, void* stream);
+
+/* Scene-cloud augmentation: augmentation.py:429-438 + scene_verts_3d_processing + egobody_dataset.py:272-273 in one pass.  scene [B,N,3]
+ * float32 (scene_is_f64 == 0) or float64; params [B, EHM_AUG_PARAMS] float64 per item: cam_t_full, cam_t_crop, the flip flag, cos and sin of
+ * -rot.  Rows 0, stride, 2 stride, ... only; out float32 [B, ceil(N/stride), 3].  Per point p, every float64 operation rounded on its own:
+ *   q = (p - t_full) + t_crop;  flip: q.x = -q.x;  r = ((cos q.x + (-sin) q.y) + 0 q.z, (sin q.x + cos q.y) + 0 q.z, (0 q.x + 0 q.y) + q.z)
+ *   r = float32(r) (augmentation.py:287);  out = float32((r - t_crop') + t_full'), t' = t with x negated under flip (:434-436)
+ * B <= 65535. */
+#define EHM_AUG_PARAMS 16
+#define EHM_AUG_P_TFULL 0     /* 3 */
+#define EHM_AUG_P_TCROP 3     /* 3 */
+#define EHM_AUG_P_FLIP 6
+#define EHM_AUG_P_COS 7
+#define EHM_AUG_P_SIN 8
+int ehm_scene_augment(const void* scene, int scene_is_f64, const double* params, float* out, int B, int N, int stride, void* stream);
+
 /* ------------------------------------------------------------------ per-item scalars ---------- */
 /* The per-item scalar work of EgoHMR.forward in front of the encoders, in two launches:
  *   vis [B,24] u8       models/egohmr/egohmr.py:186-188: confidence > 0, OpenPose joint `force_visible` (8) always on, gathered by joint_map
