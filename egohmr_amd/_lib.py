@@ -29,7 +29,7 @@ _HERE = os.path.dirname(os.path.abspath(__file__))
 LIB_PATH = os.environ.get("EHM_LIB_PATH") or os.path.join(_HERE, "libegohmr_hip.so")   # EHM_LIB_PATH: A/B a second build (experiments)
 CSRC = os.path.join(_HERE, "csrc")
 INCLUDE = os.path.join(os.path.dirname(_HERE), "include")
-SOURCES = ["gcn.hip", "gcn_tile.hip", "linear.hip", "conv.hip", "stem.hip", "metrics.hip", "smpl.hip", "sampler.hip", "guidance.hip", "prep.hip", "step.hip", "eval.hip", "stage1.hip", "scene.hip", "loss.hip", "gcn_bwd.hip", "gcn_train.hip", "pointnet_bwd.hip", "train.hip", "conv_bwd.hip", "bn2d_train.hip", "nonlocal_bwd.hip", "batch.hip"]
+SOURCES = ["gcn.hip", "gcn_tile.hip", "linear.hip", "conv.hip", "stem.hip", "metrics.hip", "smpl.hip", "sampler.hip", "guidance.hip", "prep.hip", "step.hip", "eval.hip", "stage1.hip", "scene.hip", "loss.hip", "gcn_bwd.hip", "gcn_train.hip", "pointnet_bwd.hip", "train.hip", "conv_bwd.hip", "bn2d_train.hip", "nonlocal_bwd.hip", "batch.hip", "render.hip"]
 
 
 class EgoHMRHipError(RuntimeError):
@@ -236,6 +236,15 @@ class ImagePatchDesc(C.Structure):
                 ("B", C.c_int), ("P", C.c_int), ("quantize", C.c_int), ("mean", C.c_double * 3), ("std", C.c_double * 3), ("img", C.c_void_p)]
 
 
+class RenderDesc(C.Structure):
+    """ehm_render_desc"""
+    _fields_ = ([(n, C.c_void_p) for n in ("vertices", "faces", "vf_offsets", "vf_faces", "vertex_colors", "fx", "fy", "cx", "cy", "frames", "frame_index")] +
+                [(n, C.c_int) for n in ("B", "V", "F", "Fr", "H", "W", "smooth", "two_sided", "cull_backface")] +
+                [("z_near", C.c_float), ("base_color", C.c_float * 3), ("light_dir", C.c_float * 3), ("ambient", C.c_float), ("diffuse", C.c_float),
+                 ("bg_color", C.c_uint8 * 4), ("bin_capacity", C.c_int)] +
+                [(n, C.c_void_p) for n in ("needed_capacity", "color", "depth", "face_index", "workspace")] + [("workspace_bytes", C.c_int64)])
+
+
 _P, _I, _L, _F = C.c_void_p, C.c_int, C.c_int64, C.c_float
 
 # name -> (restype, argtypes); every symbol include/egohmr_hip.h declares
@@ -349,6 +358,8 @@ PROTOTYPES = {
     "ehm_scene_select": (_I, [C.POINTER(SceneDesc), _P]),
     "ehm_image_patch": (_I, [C.POINTER(ImagePatchDesc), _P]),
     "ehm_scene_augment": (_I, [_P, _I, _P, _P, _I, _I, _I, _P]),
+    "ehm_render_workspace_bytes": (_I, [C.POINTER(RenderDesc), C.POINTER(C.c_int64)]),
+    "ehm_render": (_I, [C.POINTER(RenderDesc), _P]),
     "ehm_sample_workspace_bytes": (_L, [C.POINTER(SampleDesc), _I, _I]),
     "ehm_sample_loop": (_I, [_P, _P, C.POINTER(SampleDesc), C.POINTER(StepCoefs)] + [_P] * 18 + [_L, _P]),
     "ehm_item_prep": (_I, [C.POINTER(ItemPrepDesc), _P]),

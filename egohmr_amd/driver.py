@@ -157,6 +157,31 @@ class Stage2Driver:
         self._lists["gt_cam_full"].append(gt_cam_full)
         return dict(pred=pred, decoded=p, gt=g, joint_vis_mask=jvis, vertex_vis_mask=vvis, **res)
 
+    # ------------------------------------------------------------------ :555-589
+    @torch.no_grad()
+    def render(self, step_result, batch, frames, frame_index, items=(0,), samples=None, renderer=None):
+        """The overlay of test_egohmr.py:576-589 for the batch items ``items`` and the samples ``samples`` (None: all S) of one ``step`` result:
+        ``decoded['vertices_full']`` over frame ``frame_index[item]`` of ``frames`` uint8 [Fr,H,W,3] (BGR as decoded, on the device), with
+        fx = fy = ``batch['fx'] * fx_norm_coeff`` and the principal point ``int(cam_cx), int(cam_cy)`` as there.  -> uint8 [len(items), S', H, W, 3].
+        The bbox rectangle and the image grid of the script are not drawn.  ``renderer``: a ``MeshRenderer`` over ``smpl_neutral.faces`` to reuse
+        (one is built and kept otherwise).  The pixels are egohmr_amd.render's rule, not pyrender's."""
+        from .render import MeshRenderer
+        verts = step_result["decoded"]["vertices_full"]
+        dev = verts.device
+        if renderer is None:
+            if getattr(self, "_renderer", None) is None or self._renderer.device != dev:
+                self._renderer = MeshRenderer(self.smpl_neutral.faces, dev, num_vertices=verts.shape[2])
+            renderer = self._renderer
+        it = torch.as_tensor(list(items), dtype=torch.long, device=dev)
+        sm = torch.arange(verts.shape[1], device=dev) if samples is None else torch.as_tensor(list(samples), dtype=torch.long, device=dev)
+        n_i, n_s = it.numel(), sm.numel()
+        v = verts[it][:, sm].reshape(n_i * n_s, verts.shape[2], 3)
+        per = lambda x: x.to(dev).float()[it].repeat_interleave(n_s)
+        focal = per(batch["fx"]) * self.fx_norm_coeff
+        fidx = torch.as_tensor(frame_index).to(dev)[it].repeat_interleave(n_s).to(torch.int32)
+        img = renderer.render(v, focal, focal, per(batch["cam_cx"]).trunc(), per(batch["cam_cy"]).trunc(), frames=frames, frame_index=fidx, bgr=True)["color"]
+        return img.reshape(n_i, n_s, *img.shape[1:])
+
     # ------------------------------------------------------------------ :507-560, :660-670
     def summary(self) -> dict:
         a = {k: torch.cat(v, 0).double().cpu().numpy() for k, v in self._acc.items()}

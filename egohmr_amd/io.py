@@ -6,6 +6,7 @@
   consumed by `--two_stage` runs; `save_stage1_results` writes that file from egohmr_amd.stage1's translations.
 * `load_stage1_checkpoint`: a ProHMR-scene checkpoint into egohmr_amd.stage1.ProHMRSceneTransl (test_prohmr_scene.py:81-85).
 * `read_obj_vertices`: the vertex array of a scene mesh OBJ (scene_mesh/{scene}/{scene}.obj), for egohmr_amd.scene.SceneClouds.
+* `read_obj_mesh`: the same file with its faces and vertex colours, for egohmr_amd.render (test_egohmr.py:595-597 loads it with trimesh).
 * `load_preprocess_stats`, `load_smpl_mean_params`, `load_checkpoint`: test_egohmr.py:109-111, models/egohmr/egohmr.py:669-671,
   test_egohmr.py:125-127.
 
@@ -154,3 +155,37 @@ def read_obj_vertices(path: str) -> np.ndarray:
                     raise ValueError(f"{path}: vertex line with fewer than 3 coordinates: {line.strip()!r}")
                 rows.append((float(tok[1]), float(tok[2]), float(tok[3])))
     return np.asarray(rows, np.float64).reshape(-1, 3).astype(np.float32).astype(np.float64)
+
+
+def read_obj_mesh(path: str):
+    """An OBJ file as a triangle mesh -> (vertices float32 [V,3], faces int32 [F,3], colors float32 [V,3] or None), what egohmr_amd.render draws.
+
+    ``v x y z [r g b]`` lines (the colours are kept when EVERY vertex has them; a lone fourth value is a weight and is ignored); ``f`` lines with
+    tokens ``a``, ``a/b``, ``a/b/c`` or ``a//c``, of which the vertex index ``a`` is read: 1-based, or negative and then relative to the vertices
+    read so far; polygons are fan-triangulated around their first corner.  Normals, texture coordinates, groups and materials are not read."""
+    verts, cols, faces = [], [], []
+    with open(path, "r") as f:
+        for ln, line in enumerate(f, 1):
+            tok = line.split()
+            if not tok:
+                continue
+            if tok[0] == "v":
+                if len(tok) < 4:
+                    raise ValueError(f"{path}:{ln}: vertex line with fewer than 3 coordinates: {line.strip()!r}")
+                verts.append((float(tok[1]), float(tok[2]), float(tok[3])))
+                if len(tok) >= 7:
+                    cols.append((float(tok[4]), float(tok[5]), float(tok[6])))
+            elif tok[0] == "f":
+                if len(tok) < 4:
+                    raise ValueError(f"{path}:{ln}: face with fewer than 3 corners: {line.strip()!r}")
+                idx = []
+                for t in tok[1:]:
+                    a = int(t.split("/")[0])
+                    a = a - 1 if a > 0 else len(verts) + a
+                    if a < 0 or a >= len(verts):
+                        raise ValueError(f"{path}:{ln}: face corner {t!r} is outside the {len(verts)} vertices read so far")
+                    idx.append(a)
+                faces.extend((idx[0], idx[k], idx[k + 1]) for k in range(1, len(idx) - 1))
+    v = np.asarray(verts, np.float64).reshape(-1, 3).astype(np.float32)
+    c = np.asarray(cols, np.float64).reshape(-1, 3).astype(np.float32) if verts and len(cols) == len(verts) else None
+    return v, np.asarray(faces, np.int64).reshape(-1, 3).astype(np.int32), c

@@ -796,6 +796,69 @@ int ehm_image_patch(const ehm_image_patch_desc* d, void* stream);
 #define EHM_AUG_P_SIN 8
 int ehm_scene_augment(const void* scene, int scene_is_f64, const double* params, float* out, int B, int N, int stride, void* stream);
 
+/* ------------------------------------------------------------------ mesh rendering ------------ */
+/* A software rasteriser for the overlays of test_egohmr.py --render True (utils/renderer.py:15-47 render_on_img / render_in_scene, called at
+ * test_egohmr.py:576-619), which the reference draws with pyrender (csrc/render.hip).  The pixels are THIS RULE'S, not pyrender's: its PBR
+ * shader, gamma and anti-aliasing are not reproduced.
+ *
+ * Inputs.  vertices float32 [B,V,3] in the camera frame, x right, y down, z forward (the reference's camera_pose = diag(1,-1,-1,1) is this
+ * conversion); faces int32 [F,3], shared by the items; fx, fy, cx, cy float32 [B]; the output size H, W.
+ * Projection and sampling.  u = fx x / z + cx, v = fy y / z + cy; pixel (row i, column j) is sampled at (u, v) = (j + 0.5, i + 0.5).
+ * Coverage.  With p_k = (u_k, v_k) the projected vertices and s the sample, the edge functions are formed from differences to the triangle's own
+ * vertices, never from products of absolute pixel coordinates:
+ *   e0 = (u1-u0)(s.v-v0) - (v1-v0)(s.u-u0)    e1 = (u2-u1)(s.v-v1) - (v2-v1)(s.u-u1)    e2 = (u0-u2)(s.v-v2) - (v0-v2)(s.u-u2)
+ *   area = (u1-u0)(v2-v0) - (v1-v0)(u2-u0)
+ * The sample is covered when e0, e1, e2 all have the sign of area or are zero (edges inclusive, no top-left rule) and e0 + e1 + e2 != 0.
+ * Dropped faces: area == 0; a vertex index outside [0, V); a non-finite vertex or projection; a vertex at z <= z_near (there is no near-plane
+ * clipping: a mesh that reaches behind the near plane loses those faces whole); cull_backface != 0 and area > 0 (v points down, so a face
+ * that is counter-clockwise for an OpenGL viewer, i.e. front-facing, has area < 0).
+ * Depth.  Perspective-correct: b = (e1, e2, e0) / (e0 + e1 + e2) are the weights of vertices 0, 1, 2; 1/z = b0/z0 + b1/z1 + b2/z2, evaluated as
+ * z = (e0 + e1 + e2) / (e1/z0 + e2/z1 + e0/z2) with 1/z_k rounded to float32 once per face.  A pixel's
+ * winner is the lexicographic minimum of (z, face index) over the covering faces, so the result does not depend on the order of the faces.
+ * Normals.  Flat (smooth == 0): n = (p1 - p0) x (p2 - p0) of the camera-frame vertices.  smooth != 0: a vertex normal is the sum of that
+ * un-normalised cross product over the incident faces in face-index order, gathered through the vertex -> face CSR (vf_offsets [V+1],
+ * vf_faces [3F]; no atomics); a face whose cross product is not finite adds nothing.  The pixel's normal is sum_k (b_k / z_k) n_k.  It is
+ * normalised per pixel; a zero or non-finite one gives n.l = 0.
+ * Colour.  c = base * (ambient + diffuse * max(0, n.l)), two_sided != 0: |n.l|; base is base_color, or the per-vertex colours [V,3]
+ * interpolated perspective-correctly (sum_k (b_k / z_k) c_k * z); clamped to [0, 1]; level = floor(255 c + 0.5).  light_dir is used as given
+ * (the direction towards the light, unit length).
+ * Composite (alphaMode OPAQUE).  A covered pixel takes the three levels, in the order of base_color's / vertex_colors' channels; every other
+ * pixel keeps the background: frame frame_index[b] of frames uint8 [Fr,H,W,3] (items may share frames; an index outside [0, Fr) gives
+ * bg_color), or bg_color when frames is NULL.
+ * Outputs, each nullable and then not computed: color uint8 [B,H,W,3], depth float32 [B,H,W] (0 on background), face_index int32 [B,H,W] (-1).
+ *
+ * Faces are binned into 64 x 16 pixel tiles by their bounding boxes; an item's lists hold bin_capacity entries.  needed_capacity [B] receives
+ * every item's need; an item that needs more is rendered as pure background (nothing is written past its lists) and the caller runs again with
+ * max(needed_capacity).  ehm_render_workspace_bytes gives the workspace for a descriptor (its outputs' and workspace fields' VALUES are not
+ * used, but at least one output must be requested).  No allocation, no host synchronisation, no float atomics: two calls give the same bits.
+ * 16-byte stores of the colour tile need W % 16 == 0 and 16-byte aligned color / frames; any other case is written byte by byte.
+ * B <= 65535, H, W <= 32768, V, F <= 2^24. */
+typedef struct ehm_render_desc {
+  const float* vertices;        /* [B, V, 3] */
+  const int32_t* faces;         /* [F, 3] */
+  const int32_t* vf_offsets;    /* [V + 1], smooth != 0 only */
+  const int32_t* vf_faces;      /* [3 F],   smooth != 0 only */
+  const float* vertex_colors;   /* [V, 3] or NULL */
+  const float *fx, *fy, *cx, *cy; /* [B] each */
+  const uint8_t* frames;        /* [Fr, H, W, 3] or NULL */
+  const int32_t* frame_index;   /* [B], with frames */
+  int B, V, F, Fr, H, W;
+  int smooth, two_sided, cull_backface;
+  float z_near;
+  float base_color[3], light_dir[3];
+  float ambient, diffuse;
+  uint8_t bg_color[4];          /* three used */
+  int bin_capacity;             /* list entries per item */
+  int32_t* needed_capacity;     /* [B] out */
+  uint8_t* color;               /* [B, H, W, 3] or NULL */
+  float* depth;                 /* [B, H, W] or NULL */
+  int32_t* face_index;          /* [B, H, W] or NULL */
+  void* workspace;
+  int64_t workspace_bytes;
+} ehm_render_desc;
+int ehm_render_workspace_bytes(const ehm_render_desc* d, int64_t* bytes);
+int ehm_render(const ehm_render_desc* d, void* stream);
+
 /* ------------------------------------------------------------------ per-item scalars ---------- */
 /* The per-item scalar work of EgoHMR.forward in front of the encoders, in two launches:
  *   vis [B,24] u8       models/egohmr/egohmr.py:186-188: confidence > 0, OpenPose joint `force_visible` (8) always on, gathered by joint_map
