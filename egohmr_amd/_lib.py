@@ -29,7 +29,7 @@ _HERE = os.path.dirname(os.path.abspath(__file__))
 LIB_PATH = os.environ.get("EHM_LIB_PATH") or os.path.join(_HERE, "libegohmr_hip.so")   # EHM_LIB_PATH: A/B a second build (experiments)
 CSRC = os.path.join(_HERE, "csrc")
 INCLUDE = os.path.join(os.path.dirname(_HERE), "include")
-SOURCES = ["gcn.hip", "gcn_tile.hip", "linear.hip", "conv.hip", "stem.hip", "metrics.hip", "smpl.hip", "sampler.hip", "guidance.hip", "prep.hip", "step.hip", "eval.hip", "stage1.hip", "scene.hip", "loss.hip", "gcn_bwd.hip", "gcn_train.hip", "pointnet_bwd.hip", "train.hip", "conv_bwd.hip", "bn2d_train.hip", "nonlocal_bwd.hip", "batch.hip", "render.hip"]
+SOURCES = ["gcn.hip", "gcn_tile.hip", "linear.hip", "conv.hip", "stem.hip", "metrics.hip", "smpl.hip", "sampler.hip", "guidance.hip", "prep.hip", "step.hip", "eval.hip", "stage1.hip", "scene.hip", "loss.hip", "gcn_bwd.hip", "gcn_train.hip", "pointnet_bwd.hip", "train.hip", "conv_bwd.hip", "bn2d_train.hip", "nonlocal_bwd.hip", "batch.hip", "render.hip", "mesh_collision.hip"]
 
 
 class EgoHMRHipError(RuntimeError):
@@ -342,6 +342,8 @@ PROTOTYPES = {
     "ehm_ddim_step": (_I, [_P, _P, _P, _P, _F, _F, _F, _F, _F, _F, _L, _P]),
     "ehm_collision_proxy": (_I, [_P, _P, _P, _P, _I, _I, _I, _F, _P]),
     "ehm_collision_query": (_I, [_P, _P, _P, _P, _P, _I, _I, _I, _F, _I, _P]),
+    "ehm_mesh_collision_query": (_I, [_P, _P, _P, _P, _P, _P, _I, _I, _I, _I, _I, _P]),
+    "ehm_smpl_set_collision_mesh": (_I, [_P, _P, _I]),
     "ehm_smpl_backward_rot6d": (_I, [_P, _P, _P, _P, _P, _P, _P, _I, _P]),
     "ehm_guidance_grad_finish": (_I, [_P, _P, _P, _I, _F, _P]),
     "ehm_smpl_backward": (_I, [_P, _P, _P, _P, _P, _P, _P, _I, _P, _L, _P]),
@@ -374,6 +376,7 @@ PROTOTYPES = {
     "ehm_profile_begin": (_I, []),
     "ehm_profile_end": (_I, [C.POINTER(C.c_double), C.POINTER(C.c_int64), _I]),
 }
+MESH_COLLISION_FACE_CHUNK, MESH_COLLISION_POINT_BLOCK = 512, 256     # EHM_MESH_COLLISION_* of the header (tests size their edge cases by them)
 PROF_CLASSES = ("input", "chain_f16x3", "chain_f16", "hidden_f32", "out_dot", "step_body", "skin_input", "guidance", "reserved_8", "reserved_9",
                 "guid_nearest", "guid_skin_bwd", "guid_posefeat_bwd", "step_fused", "guid_nearest_evals",   # EHM_PROF_* of the header ("guid_nearest_evals" is a COUNT in `launches`)
                 "chain_f16x2")

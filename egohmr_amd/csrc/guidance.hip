@@ -8,6 +8,8 @@
 //   select_kernel        ordered compaction of the scene points inside the box              (egohmr.py:552)
 //   nearest_kernel       build-defined proxy: nearest body vertex of every selected point from an LDS-resident copy of
 //                        the body (SoA, broadcast reads), hinge relu(tau - d)^2, scatter of d loss / d vertex
+//   (mesh_collision.hip) opt-in instead of nearest_kernel: winding-number occupancy and penetration depth of the posed mesh, when the
+//                        handle holds a collision mesh (ehm_smpl_set_collision_mesh)
 //   skin_bwd_kernel      VJP of the skinning + pose-corrective blend w.r.t. posed rest vertices and the 24 transforms
 //   posefeat_bwd_mfma_kernel  VJP of the 207-basis pose blend (a [B,20670] x [20670,207] contraction, exact-f32 MFMA)
 //   chain_bwd_kernel     one wave per body, lane = joint: reverse kinematic chain through LDS (children -> parent in
@@ -1111,6 +1113,19 @@ int collision_impl(const float* verts, const float* scene, float* loss, float* g
   return 0;
 }
 
+// The mesh collision term (mesh_collision.hip) behind the same selection: the bounding box with both ends inclusive and no margin, or every point.
+// Any V, any F >= 1 (nothing of the body has to fit the LDS).  The blocks' sums land in the index list's own slots: no scratch beyond `s`.
+int mesh_collision_impl(const float* verts, const int32_t* faces, const float* scene, float* loss, float* gverts, int* hits, int B, int V, int F, int N,
+                        bool all_points, const Scratch& s, hipStream_t st) {
+  if (!all_points) {
+    hipLaunchKernelGGL(bbox_kernel, dim3(B), dim3(256), 0, st, verts, s.bbox, V);
+    hipLaunchKernelGGL(select_kernel, dim3(B), dim3(1024), 0, st, scene, s.bbox, s.idx, s.count, N, 0.f);
+    EHM_LAUNCH_CHECK();
+  }
+  return ehm_mesh_collision_launch(verts, faces, scene, all_points ? nullptr : s.idx, all_points ? nullptr : s.count, s.idx, loss, gverts, hits, B, V,
+                                   F, N, st);
+}
+
 // the part of the VJP that both chain kernels share: gverts -> d loss / d blended rest vertex (in place), gA, and (want_gpf) the pose-feature gradient
 int skin_posefeat_bwd(ehm_smpl* h, const float* betas, const float* Rws, const float* Aws, float* gverts, int B, const Scratch& s, hipStream_t st,
                       const float* vposed, bool want_gpf) {
@@ -1156,7 +1171,11 @@ int ehm_guidance_impl(ehm_smpl* smpl, const float* betas, const float* x, const 
   int rc = ehm_smpl_forward_impl(smpl, betas, x, true, mean, std_, verts_ws, joints_ws, R_ws, A_ws, nullptr, B, st, vposed_ws);   // egohmr.py:528-537
   if (rc == 0) {
     EhmProfScope ps(EHM_PROF_G_NEAREST, st);      // memsets + bbox + select + nearest_grid_kernel (the search dominates)
-    rc = collision_impl(verts_ws, scene, loss, gverts, nullptr, B, V, N, tau, margin, s, st);
+    // a collision mesh on the handle (ehm_smpl_set_collision_mesh): the mesh term, tau unused; margin != 0 is the loop's "all points" (sampler.hip)
+    if (smpl->coll_F > 0)
+      rc = mesh_collision_impl(verts_ws, smpl->coll_faces, scene, loss, gverts, nullptr, B, V, smpl->coll_F, N, margin != 0.f, s, st);
+    else
+      rc = collision_impl(verts_ws, scene, loss, gverts, nullptr, B, V, N, tau, margin, s, st);
   }
   if (rc == 0) rc = backward_impl(smpl, betas, x, mean, std_, R_ws, A_ws, gverts, gpose, B, s, st, vposed_ws);
   if (rc == 0) {
@@ -1184,6 +1203,15 @@ extern "C" int ehm_collision_query(const float* verts, const float* scene, float
   int rc = own_scratch(ehm_guidance_scratch_bytes(B, N), &sc);
   if (rc) return rc;
   return collision_impl(verts, scene, loss, gverts, hits, B, V, N, tau, all_points ? tau : 0.f, carve_scratch(sc, B, N), (hipStream_t)stream);
+}
+
+extern "C" int ehm_mesh_collision_query(const float* verts, const int32_t* faces, const float* scene, float* loss, float* gverts, int32_t* hits, int B,
+                                        int V, int F, int N, int all_points, void* stream) {
+  EHM_CHECK_ARG(verts && faces && scene && loss && B > 0 && B <= 65535 && V > 0 && F >= 1 && N > 0);
+  void* sc = nullptr;
+  int rc = own_scratch(ehm_guidance_scratch_bytes(B, N), &sc);
+  if (rc) return rc;
+  return mesh_collision_impl(verts, faces, scene, loss, gverts, hits, B, V, F, N, all_points != 0, carve_scratch(sc, B, N), (hipStream_t)stream);
 }
 
 extern "C" int ehm_smpl_backward_rot6d(ehm_smpl* h, const float* betas, const float* x, const float* mean, const float* std_,

@@ -65,6 +65,10 @@ int ehm_guidance_impl(ehm_smpl* smpl, const float* betas, const float* x, const 
                       const float* scene, int B, int N, float tau, float denom, float margin, float* verts_ws, float* joints_ws, float* R_ws,
                       float* A_ws, float* gverts, float* loss, float* gpose, float* grad, void* scratch, hipStream_t st,
                       float* vposed_ws = nullptr);   // [B,V,3] scratch or nullptr: the forward's blended rest vertices for the skinning VJP (else recomputed there)
+// mesh_collision.hip: the mesh collision term over an already selected point list (idx / count of select_kernel, or nullptr / nullptr = every point);
+// partial: [B][N] 4-byte words of scratch, which MAY be idx's own memory.  Clears gverts / hits, writes every loss[b].
+int ehm_mesh_collision_launch(const float* verts, const int32_t* faces, const float* scene, const int* idx, const int* count, void* partial,
+                              float* loss, float* gverts, int* hits, int B, int V, int F, int N, hipStream_t st);
 // sampler.hip: launch-class timing for bench.py (ehm_profile_begin / ehm_profile_end); a no-op unless a profile is open
 unsigned long long* ehm_prof_evals_ptr();   // device counter of the collision search's distance evaluations, or nullptr when no profile is open
 struct EhmProfScope {

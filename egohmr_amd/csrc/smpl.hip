@@ -558,7 +558,31 @@ extern "C" void ehm_smpl_destroy(ehm_smpl* h) {
   if (h->ws) (void)hipFree(h->ws);
   if (h->pdf) (void)hipFree(h->pdf);
   if (h->pf) (void)hipFree(h->pf);
+  if (h->coll_faces) (void)hipFree(h->coll_faces);
   delete h;
+}
+
+extern "C" int ehm_smpl_set_collision_mesh(ehm_smpl* h, const int32_t* faces_host, int F) {
+  EHM_CHECK_ARG(h && F >= 0 && (F == 0 || faces_host));
+  for (int64_t i = 0; i < (int64_t)F * 3; ++i) {
+    if (faces_host[i] < 0 || faces_host[i] >= h->d.V) {
+      ehm_set_error("ehm_smpl_set_collision_mesh: faces[%lld] = %d is not a vertex of this body (V = %d)", (long long)i, faces_host[i], h->d.V);
+      return EHM_EINVAL;
+    }
+  }
+  if (h->coll_faces) EHM_HIP(hipFree(h->coll_faces));     // (hipFree waits for the device: no guided step in flight reads the old copy)
+  h->coll_faces = nullptr;
+  h->coll_F = 0;
+  if (F == 0) return 0;
+  EHM_HIP(hipMalloc((void**)&h->coll_faces, (size_t)F * 3 * sizeof(int32_t)));
+  if (hipMemcpy(h->coll_faces, faces_host, (size_t)F * 3 * sizeof(int32_t), hipMemcpyHostToDevice) != hipSuccess) {
+    (void)hipFree(h->coll_faces);
+    h->coll_faces = nullptr;
+    ehm_set_error("ehm_smpl_set_collision_mesh: the upload of %d faces failed", F);
+    return EHM_EIO;
+  }
+  h->coll_F = F;
+  return 0;
 }
 
 // internal entry shared with sampler.hip: caller provides R/A scratch (no allocation -> graph safe)

@@ -66,6 +66,8 @@ struct ehm_smpl {
   void* pdf = nullptr;         // SmplDev::PDf storage
   void* pf = nullptr;          // blend coefficients of the current batch as MFMA A fragments [ceil(B/32)][14][hi/lo][64][8 halves]
   int pf_cap = 0;              // bodies
+  int32_t* coll_faces = nullptr;   // ehm_smpl_set_collision_mesh: the handle's own device copy of the faces [coll_F,3], or nullptr (vertex proxy)
+  int coll_F = 0;
 };
 // tests/test_smpl_autograd_cpu.py hands the argument checks of ehm_smpl_backward a host stand-in for a handle that holds V and n_extra only:
 // the two ints lead the handle.  Moving them fails the build here, not the test in host code that reads garbage.

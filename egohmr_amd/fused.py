@@ -442,16 +442,25 @@ class FusedSampler:
     # ------------------------------------------------------------------ guidance pieces
     @torch.no_grad()
     def collision(self, verts, scene, want_grad=True, want_hits=False, all_points=None):
-        """The collision proxy for a batch of bodies: (loss [B], d loss / d verts [B,V,3] or None, hits [B] int32 or None)."""
+        """The collision proxy for a batch of bodies: (loss [B], d loss / d verts [B,V,3] or None, hits [B] int32 or None).  EgoHMR.collision_proxy:
+        'vertex' = the nearest-vertex hinge (ehm_collision_query), 'mesh' = winding-number occupancy and penetration depth of the posed mesh
+        `smpl.faces_tensor` (ehm_mesh_collision_query)."""
         m = self.model
         verts, scene = _lib.f32(verts, m.device), _lib.f32(scene, m.device)
         B, V, N = verts.shape[0], verts.shape[1], scene.shape[1]
+        mesh = m.mesh_collision()
+        if mesh and V != m.smpl.num_verts:
+            raise ValueError(f"collision_proxy = 'mesh': {V} vertices per body, the model's mesh has {m.smpl.num_verts}")
+        faces = m.smpl.collision_faces() if mesh else None      # (validated when uploaded: ValueError before any launch)
         loss = torch.empty(B, device=m.device)
         gverts = torch.empty_like(verts) if want_grad else None
         hits = torch.empty(B, device=m.device, dtype=torch.int32) if want_hits else None
         allp = m.guide_all_points if all_points is None else all_points
         with torch.cuda.device(m.device):
-            _lib.api().ehm_collision_query(verts, scene, loss, gverts, hits, B, V, N, m.collision_tau, int(bool(allp)), _lib.stream_ptr())
+            if mesh:
+                _lib.api().ehm_mesh_collision_query(verts, faces, scene, loss, gverts, hits, B, V, faces.shape[0], N, int(bool(allp)), _lib.stream_ptr())
+            else:
+                _lib.api().ehm_collision_query(verts, scene, loss, gverts, hits, B, V, N, m.collision_tau, int(bool(allp)), _lib.stream_ptr())
         return loss, gverts, hits
 
     @torch.no_grad()
@@ -487,7 +496,8 @@ class FusedSampler:
         calibration (the f16 steps end >= 8 steps before the guided window whatever its strength)."""
         m = self.model
         return (self._param_key(), self._cond_param_key(), tuple(diffusion.timestep_map), int(getattr(diffusion, "original_num_steps", diffusion.num_timesteps)),
-                bool(ddim), int(n_guided), (float(cond_grad_weight), str(m.guide_reduction)) if n_guided else None, bool(m.guide_all_points) if n_guided else False,
+                bool(ddim), int(n_guided), (float(cond_grad_weight), str(m.guide_reduction), "mesh" if m.mesh_collision() else "vertex") if n_guided else None,
+                bool(m.guide_all_points) if n_guided else False,
                 bool(m.diffuse_fuse), tuple(float(v) for v in m.sampling_scales()),   # (s multiplies the two passes' rounding errors: k is per scale pair)
                 float(m.schedule_tol), str(getattr(m, "f16x2_steps", 0)))
 
@@ -811,6 +821,9 @@ class FusedSampler:
         # ... and how the loop's steps combine the two passes (a setting of the handle, read by ehm_sample_loop at entry like the map)
         self.last_fuse = (int(cfg), float(scales[0]) if cfg else 1.0, float(scales[1]) if cfg else 0.0)
         _lib.api().ehm_gcn_set_fuse_scales(self.gcn(), *self.last_fuse)
+        # ... and which collision term its guided steps run: the SMPL handle's mesh, set under collision_proxy = 'mesh' and cleared otherwise (an
+        # upload only when that changes), so that a model switched back to 'vertex' runs the vertex proxy's bits again
+        m.smpl.set_collision_mesh(m.mesh_collision())
         desc = _lib.SampleDesc(B=st.B, passes=passes, num_steps=T, ddim=int(ddim), per_step_launches=int(bool(m.per_step_launches)),
                                lbs_every_step=int(m.lbs_every_step), num_scene_points=st.scene.shape[1] if any_guided else 0,
                                guide_denom=self.guide_denom(denom_items), tau=m.collision_tau, num_masked=num_masked,

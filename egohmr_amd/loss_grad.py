@@ -2,7 +2,8 @@
 compute_loss runs behind when a gradient is asked for (model.py).
 
     ValLossesFunction      ehm_val_losses forward, ehm_val_losses_backward as its VJP w.r.t. the eight prediction arrays and the penetration term
-    ProxyPenetration       the build's collision proxy as the penetration term [B] of the bodies' vertices (ehm_scene_cap_points + ehm_collision_query);
+    ProxyPenetration       the build's collision proxy as the penetration term [B] of the bodies' vertices (ehm_scene_cap_points + ehm_collision_query, or
+                           ehm_mesh_collision_query under EgoHMR.collision_proxy = 'mesh');
                            the bounding box and the point cap carry no gradient, as the reference detaches them (egohmr.py:406-407)
 
 First derivatives only (``once_differentiable``).  No host synchronisation.

@@ -479,7 +479,13 @@ class EgoHMR(nn.Module):
         # query(points, smpl_output); guide_coll / eval_coll / _penetration_term then run the reference's autograd route through the differentiable
         # SMPL.forward, and guided loops take the per-step route (the native loop cannot call Python between steps); unguided loops stay fused
         self.collision_model = None
-        self.guide_reduction = "mean"          # COAP variant: -loss.mean() (egohmr.py:562); 'sum' = VolSMPL variant (egohmr_volsmpl.py:618)
+        # What stands in for the collision model while none is attached.  'vertex' (the default): the nearest-vertex proxy, relu(tau - distance to the
+        # nearest body vertex)^2.  'mesh': the mesh collision term (include/egohmr_hip.h): occupancy of the posed mesh `smpl.faces_tensor` by its
+        # generalised winding number, penetration depth to the nearest face - in the guided loops, guide_coll, eval_coll / eval_coll_volsmpl, the
+        # penetration term of compute_loss and its gradient.  The mesh's OWN occupancy, not a COAP / VolumetricSMPL output; meaningful on a closed
+        # mesh (the real SMPL asset), defined but fractional on the synthetic asset's random faces.  collision_tau is not used by it.
+        self.collision_proxy = "vertex"
+        self.guide_reduction = "mean"         # COAP variant: -loss.mean() (egohmr.py:562); 'sum' = VolSMPL variant (egohmr_volsmpl.py:618)
         self.guide_denom_override = None       # sharded / sub-batch runs: the GLOBAL batch size of `-loss.mean()`, else None
         self.guide_all_points = False          # COAP variant: bbox-selected scene points (egohmr.py:550-552); True = all points (egohmr_volsmpl.py:609-612)
         self.lbs_every_step = True             # EgoHMR.forward decodes the body in every step (egohmr.py:276)
@@ -747,8 +753,24 @@ class EgoHMR(nn.Module):
             "pred_keypoints_2d_full": kp2d.view(B, J, 2),                              # :295-301
         }
 
+    COLLISION_PROXIES = ("vertex", "mesh")
+
+    @property
+    def collision_proxy(self):
+        return self._collision_proxy
+
+    @collision_proxy.setter
+    def collision_proxy(self, value):
+        if value not in self.COLLISION_PROXIES:                      # (at the assignment: before any device call)
+            raise ValueError(f"collision_proxy must be one of {self.COLLISION_PROXIES} (got {value!r})")
+        self._collision_proxy = value
+
+    def mesh_collision(self) -> bool:
+        """Whether the collision term is the mesh one: collision_proxy = 'mesh' and no `collision_model` attached (that takes precedence)."""
+        return self.collision_model is None and self.collision_proxy == "mesh"
+
     def guide_coll(self, batch, output, t, compute_grad="x_t"):
-        """egohmr.py:517-570 with the build's collision proxy in place of COAP; returns [B,144].  With `collision_model` attached: the reference's
+        """egohmr.py:517-570 with the build's collision proxy (vertex or mesh, `collision_proxy`) in place of COAP; returns [B,144].  With `collision_model` attached: the reference's
         own autograd route through that model (_guide_coll_model), for compute_grad 'x_t' and 'x_0' alike."""
         fs = self.fused_sampler
         st = fs.prepare(batch)
@@ -840,7 +862,9 @@ class EgoHMR(nn.Module):
     def eval_coll(self, output):
         """egohmr.py:487-514 with the build's proxy in place of `coap.query(...) > 0.5`: per item, the share of the scene points that
         lie inside the body's bounding box AND closer than tau to its surface.  One kernel sequence for the batch, one host sync
-        (`.tolist()`, the reference syncs per item); returns the reference's python list [B] of floats.  NOT a COAP number - unless
+        (`.tolist()`, the reference syncs per item); returns the reference's python list [B] of floats.  With collision_proxy = 'mesh': the share
+        of the scene points inside the bounding box AND inside the posed mesh (winding number > 0.5) - the quantity the reference's metric estimates,
+        computed on the mesh itself.  NOT a COAP number - unless
         `collision_model` is attached: then `collision_model.query(points, smpl_output) > 0.5` per item, as the reference runs it."""
         if self.collision_model is not None:
             return self._hit_share_model(output, self.collision_model.query, lambda occ: occ > 0.5)
@@ -1154,7 +1178,7 @@ class EgoHMRVolsmpl(EgoHMR):
       eval_coll_volsmpl   :548-579  per item, bbox-selected points with `volume.query_fast(...) < 0` over N
       eval_coll           :519-546  the COAP metric, kept (the reference keeps COAP attached for training)
     VolumetricSMPL is a learned SDF that cannot be obtained offline: the collision term is the build's proxy (docs/EXPERIMENTS.md 3.5),
-    with `sdf < 0` read as `distance to the surface < tau`.  Numbers from it are NOT VolumetricSMPL numbers - unless the user's model is attached as
+    with `sdf < 0` read as `distance to the surface < tau` (collision_proxy = 'mesh': as "inside the posed mesh").  Numbers from it are NOT VolumetricSMPL numbers - unless the user's model is attached as
     `collision_model`: guide_coll then makes the reference's one batched `collision_loss(scene, smpl_output)` call and differentiates `-loss.sum()` through
     the differentiable SMPL.forward, eval_coll_volsmpl reads its `query_fast` (or `query`) as a signed distance, and guided loops run step by step."""
 

@@ -136,6 +136,45 @@ class SMPL(nn.Module):
             self._handle, self._handle_key = _lib.Handle(h, _lib.api().ehm_smpl_destroy), key
         return self._handle
 
+    # ------------------------------------------------------------------ collision mesh (EgoHMR.collision_proxy = 'mesh')
+    def _faces_key(self):
+        return (self.faces_tensor.data_ptr(), self.faces_tensor._version, tuple(self.faces_tensor.shape), self.num_verts)
+
+    def collision_faces_host(self):
+        """faces_tensor as int32 [F,3] on the host, validated ONCE per faces_tensor: F >= 1, every index a vertex of this body (ValueError)."""
+        key = self._faces_key()
+        if getattr(self, "_coll_host", None) is None or self._coll_host[0] != key:
+            f = self.faces_tensor.detach().cpu()
+            if f.dim() != 2 or f.shape[1] != 3 or f.shape[0] < 1 or f.dtype.is_floating_point:
+                raise ValueError(f"collision mesh: faces_tensor must be an integer [F,3] with F >= 1 (got {tuple(f.shape)}, {f.dtype})")
+            if int(f.min()) < 0 or int(f.max()) >= self.num_verts:
+                raise ValueError(f"collision mesh: faces_tensor indexes outside the body's {self.num_verts} vertices")
+            self._coll_host = (key, np.ascontiguousarray(f.numpy().astype(np.int32)))
+            self._coll_dev = None
+        return self._coll_host[1]
+
+    def collision_faces(self):
+        """The validated faces as an int32 device tensor [F,3] beside the body's buffers (for ehm_mesh_collision_query)."""
+        host = self.collision_faces_host()
+        dev = self.v_template.device
+        if getattr(self, "_coll_dev", None) is None or self._coll_dev.device != dev:
+            self._coll_dev = torch.from_numpy(host).to(dev)
+        return self._coll_dev
+
+    def set_collision_mesh(self, on: bool):
+        """Give the native handle this body's faces as its collision mesh (the guided steps of ehm_sample_loop then run the mesh collision term), or
+        clear it.  Uploads only when the handle's state differs from what is asked."""
+        h = self.handle()
+        have = getattr(self, "_coll_set", None)            # (handle serial, faces key) of the mesh last set, or None
+        if have is not None and have[0] != h.serial:
+            have = None                                    # (a re-created handle starts without a mesh)
+        want = (h.serial, self._faces_key()) if on else None
+        if have != want:
+            host = self.collision_faces_host() if on else None
+            with torch.cuda.device(self.v_template.device):
+                _lib.api().ehm_smpl_set_collision_mesh(h, host.ctypes.data if on else None, host.shape[0] if on else 0)
+        self._coll_set = want
+
     # ------------------------------------------------------------------ forward
     def forward(self, betas=None, body_pose=None, global_orient=None, transl=None, return_verts=True,
                 return_full_pose=False, pose2rot=True, **kwargs):

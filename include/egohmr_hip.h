@@ -600,6 +600,37 @@ int ehm_collision_proxy(const float* verts, const float* scene, float* loss, flo
 int ehm_collision_query(const float* verts, const float* scene, float* loss, float* gverts, int32_t* hits, int B, int V, int N,
                         float tau, int all_points, void* stream);
 
+/* ---- mesh collision term (opt-in; EgoHMR.collision_proxy = 'mesh') ----
+ * What COAP approximates is the occupancy of the posed SMPL mesh; a closed mesh gives it exactly.  Numbers from this term are the mesh's own
+ * occupancy and depth, NOT outputs of COAP / VolumetricSMPL.  Per body b: verts[b] [V,3] float32, ONE faces [F,3] int32 for all bodies, wound so
+ * that (v1 - v0) x (v2 - v0) points outwards (as SMPL's are), scene[b] [N,3].
+ *   selection   all_points == 0: the points inside the vertex bounding box, both ends inclusive (egohmr.py:550-552); else every point
+ *               (egohmr_volsmpl.py:609-612).  No tau, no margin.
+ *   occupancy   with a = v0 - p, b = v1 - p, c = v2 - p:
+ *                 Omega_f = 2 atan2(a . (b x c), |a||b||c| + (a.b)|c| + (b.c)|a| + (c.a)|b|),   w(p) = sum_f Omega_f / (4 pi),
+ *               inside <=> w(p) > 0.5.  On a closed mesh w is 0 or 1 up to rounding; on a mesh that is not closed (the synthetic asset's
+ *               random faces) w is fractional: the term is then defined, but not meaningful.
+ *   depth       d(p) = min_f dist(p, triangle f), at the closest point c = sum_k beta_k v_{f,k} (closest point on a triangle: vertex, edge
+ *               and face regions); among equally near faces the lowest index.
+ *   degenerate  a face that repeats a vertex index has no area and no side: it adds 0 to w (never a NaN) and is left out of the minimum.
+ *   outputs     loss[b] = sum over selected, inside points of d(p)^2;  hits[b] (may be NULL) = their number;
+ *               gverts[b, f_k] (may be NULL; [B,V,3], overwritten) += 2 beta_k (c - p): the derivative of d^2 at fixed beta, exact in the face,
+ *               edge and vertex regions alike (envelope argument); the indicator carries no gradient.  A body without a selected inside point has
+ *               exact zeros in all three.
+ * Any V, any F >= 1 (B <= 65535).  loss and hits are the same bits from call to call; gverts is accumulated with float atomics (last-bit spread).
+ * faces is on the DEVICE; an index outside [0, V) is the caller's to avoid (nothing checks it here).
+ * The kernel walks the faces through LDS in chunks of EHM_MESH_COLLISION_FACE_CHUNK, for blocks of EHM_MESH_COLLISION_POINT_BLOCK points. */
+#define EHM_MESH_COLLISION_FACE_CHUNK 512
+#define EHM_MESH_COLLISION_POINT_BLOCK 256
+int ehm_mesh_collision_query(const float* verts, const int32_t* faces, const float* scene, float* loss, float* gverts, int32_t* hits, int B,
+                             int V, int F, int N, int all_points, void* stream);
+
+/* The collision term of the guided steps of ehm_sample_loop, as a setting of the SMPL handle (read at the loop's entry, like the GCN handle's
+ * pass map and fuse scales): faces_host [F,3] int32 on the HOST, every index in [0, V) (else EINVAL, nothing changed); the handle takes its own
+ * device copy.  F = 0 clears it.  With a mesh set the guided steps use the mesh collision term above (ehm_sample_desc.tau is ignored;
+ * guide_all_points selects every point); with none they use the vertex proxy of ehm_collision_proxy, as before.  Waits for the device. */
+int ehm_smpl_set_collision_mesh(ehm_smpl* h, const int32_t* faces_host, int F);
+
 /* VJP of ehm_smpl_forward_rot6d w.r.t. the DE-NORMALISED 6-D pose (the quirk of egohmr.py:523-528:
  * autograd.grad is taken w.r.t. x_t*std+mean): gverts [B,V,3] -> gpose6d [B,144].
  * Needs the forward's x/mean/std/betas again (recomputes the chain). */
