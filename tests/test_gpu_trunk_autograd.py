@@ -9,6 +9,7 @@ tests/test_trunk_autograd_cpu.py (E2E_SEED: a float32 run of the reference stays
 Bar: the project's VJP bar (tests/test_gpu_gcn_autograd.py, tests/test_gpu_pointnet_autograd.py): atol = 2e-4 max|ref|, rtol = 2e-3; the free-running
 test per tensor in the max norm, max|g - ref| <= 2e-4 max|ref| (the form of tests/test_gpu_train_step.py).  Every case prints what it measured."""
 import ctypes as C
+import functools
 import os
 import sys
 
@@ -20,6 +21,7 @@ sys.path.insert(0, os.path.dirname(os.path.abspath(__file__)))
 import train_step_ref as TR  # noqa: E402
 import val_losses_ref as VR  # noqa: E402
 from egohmr_amd import synthetic as syn  # noqa: E402
+from tests import stem_ref as SR  # noqa: E402
 from tests import trunk_grad_ref as R  # noqa: E402
 from tests.test_trunk_autograd_cpu import ATOL, E2E_F32_ERROR, E2E_SEED, E2E_SHAPE, RTOL  # noqa: E402
 
@@ -28,6 +30,7 @@ pytestmark = pytest.mark.gpu
 CANARY = 12345.0
 GUARD = 64                                 # floats in front of and behind every output (16-byte alignment kept)
 NAN = float("nan")
+STEM_WGRAD_BLOCKS = 256                    # the fixed grid of stem_bwd_wgrad_kernel (csrc/conv_bwd.hip: SB_BLOCKS)
 
 
 @pytest.fixture(scope="module")
@@ -196,9 +199,9 @@ def test_data_gradient_through_the_conv_engine(dev, N, H, W, Ci, Co, K, stride, 
 
 
 # ---------------------------------------------------------------------------------------------- 4. the stem
-@pytest.mark.parametrize("N,H,W", [(1, 32, 32), (2, 64, 32)])
-def test_stem_backward(dev, N, H, W):
-    from egohmr_amd import trunk_grad
+@functools.lru_cache(maxsize=1)
+def stem_inputs(N, H, W):
+    """(img, w, b, wt, z64, gated) of a stem backward case; the float64 activation is computed once for the tests that share a case"""
     g = _rng(N + H)
     img = _f32(g, N, 3, H, W)
     img[0, :, 4:28, 6:30] = 0.75                                           # a constant patch: the windows inside it hold ties
@@ -211,6 +214,17 @@ def test_stem_backward(dev, N, H, W):
     cot = _f32(g, N, H // 4, W // 4, 64)
     gated = torch.where(pooled.permute(0, 2, 3, 1) > 0, cot.double(), torch.zeros(1, dtype=torch.float64)).float().contiguous()
     assert not bool(gated[..., 5].any())
+    return img, w, b, wt, z64, gated
+
+
+# (11, 224, 224): image chunks of 10 + 1 (stem_plan: 8 Mi floats of pre-pool activations at a time), 1232 weight-gradient rows on the 256 blocks of
+# stem_bwd_wgrad_kernel; (129, 64, 64): chunks of 128 + 1, 4128 rows.  From the second chunk on the kernel accumulates onto the partial sums before it
+@pytest.mark.parametrize("N,H,W", [(1, 32, 32), (2, 64, 32), (11, 224, 224), (129, 64, 64)])
+def test_stem_backward(dev, N, H, W):
+    from egohmr_amd import trunk_grad
+    img, w, b, wt, z64, gated = stem_inputs(N, H, W)
+    if N > 2:                                                              # the cases that are here for their second turns: prove they take them
+        assert N > SR.backward_chunk(H, W) and N * (H // 2) > STEM_WGRAD_BLOCKS
     runs = [trunk_grad.stem_backward(img.to(dev), wt.to(dev), b.to(dev), gated.to(dev), debug=True) for _ in range(2)]
     torch.cuda.synchronize()
     gw, gb, z, gz = runs[0]
@@ -238,6 +252,35 @@ def test_stem_backward(dev, N, H, W):
     only_w = trunk_grad.stem_backward(img.to(dev), wt.to(dev), b.to(dev), gated.to(dev), True, False)
     only_b = trunk_grad.stem_backward(img.to(dev), wt.to(dev), b.to(dev), gated.to(dev), False, True)
     assert only_w[1] is None and only_b[0] is None and torch.equal(only_w[0], gw) and torch.equal(only_b[1], gb)
+
+
+def test_stem_backward_chunks_agree_with_whole_batch_steps(dev):
+    """ehm_resnet_stem_backward (image chunks, partial sums accumulated from the second chunk on) against the three steps the train-mode BatchNorm route
+    runs over the whole batch (ehm_resnet_stem_preact / _route / _wgrad): z and gz are per-pixel results and bit-equal; the weight and bias gradients
+    are summed in different orders, so each is held to float64 at the VJP bar instead."""
+    from egohmr_amd import _lib, trunk_grad
+    A = _lib.api()
+    N, H, W = 129, 64, 64
+    assert N > SR.backward_chunk(H, W) and N * H // 2 > STEM_WGRAD_BLOCKS                                # a second chunk, a second row per block
+    img, w, b, wt, z64, gated = stem_inputs(N, H, W)
+    imgd, wtd, bd, gd = img.to(dev), wt.to(dev), b.to(dev), gated.to(dev)
+    gw, gb, z, gz = trunk_grad.stem_backward(imgd, wtd, bd, gd, debug=True)
+    fz, z2 = guarded(dev, N, H // 2, W // 2, 64)
+    fgz, gz2 = guarded(dev, N, H // 2, W // 2, 64)
+    fw, gw2 = guarded(dev, 64, 147)
+    fb, gb2 = guarded(dev, 64)
+    z2.fill_(NAN), gz2.fill_(NAN)
+    ws = torch.full((trunk_grad.STEM_WGRAD_WS_FLOATS,), NAN, device=dev)
+    A.ehm_resnet_stem_preact(imgd, wtd, bd, z2, N, H, W, _lib.stream_ptr())
+    A.ehm_resnet_stem_route(z2, gd, gz2, N, H, W, _lib.stream_ptr())
+    A.ehm_resnet_stem_wgrad(imgd, gz2, gw2, gb2, N, H, W, ws, ws.numel() * 4, _lib.stream_ptr())
+    torch.cuda.synchronize()
+    assert all(guards_intact(f) for f in (fz, fgz, fw, fb))
+    assert torch.equal(z.view(torch.int32), z2.view(torch.int32)) and torch.equal(gz.view(torch.int32), gz2.view(torch.int32))
+    rw, rb, _ = R.stem_vjp(img.double(), gated.double().permute(0, 3, 1, 2), z.double().cpu().permute(0, 3, 1, 2))
+    for tag, a, c in (("chunked", gw, gb), ("whole batch", gw2.view(64, 3, 7, 7), gb2)):
+        check(f"stem N={N} {H}x{W} {tag} w", a, rw)
+        check(f"stem N={N} {H}x{W} {tag} b", c, rb)
 
 
 # ---------------------------------------------------------------------------------------------- 5. the whole trunk on the device's gates
