@@ -20,6 +20,7 @@ _LAZY = {
     "ProHMRSceneTransl": ("stage1", "ProHMRSceneTransl"),
     "BatchBuilder": ("batch", "BatchBuilder"),
     "AugmentConfig": ("batch", "AugmentConfig"),
+    "JpegDecoder": ("jpeg", "JpegDecoder"),
     "MeshRenderer": ("render", "MeshRenderer"),
     "render_on_img": ("render", "render_on_img"),
     "render_in_scene": ("render", "render_in_scene"),
@@ -31,7 +32,7 @@ def __getattr__(name):
         import importlib
         mod, attr = _LAZY[name]
         return getattr(importlib.import_module(f"{__name__}.{mod}"), attr)
-    if name in ("smpl", "synthetic", "diffusion", "model", "geometry", "dist", "_lib", "encoders", "stage1", "render"):
+    if name in ("smpl", "synthetic", "diffusion", "model", "geometry", "dist", "_lib", "encoders", "stage1", "render", "jpeg"):
         import importlib
         return importlib.import_module(f"{__name__}.{name}")
     raise AttributeError(name)

@@ -29,7 +29,7 @@ _HERE = os.path.dirname(os.path.abspath(__file__))
 LIB_PATH = os.environ.get("EHM_LIB_PATH") or os.path.join(_HERE, "libegohmr_hip.so")   # EHM_LIB_PATH: A/B a second build (experiments)
 CSRC = os.path.join(_HERE, "csrc")
 INCLUDE = os.path.join(os.path.dirname(_HERE), "include")
-SOURCES = ["gcn.hip", "gcn_tile.hip", "linear.hip", "conv.hip", "stem.hip", "metrics.hip", "smpl.hip", "sampler.hip", "guidance.hip", "prep.hip", "step.hip", "eval.hip", "stage1.hip", "scene.hip", "loss.hip", "gcn_bwd.hip", "gcn_train.hip", "pointnet_bwd.hip", "train.hip", "conv_bwd.hip", "bn2d_train.hip", "nonlocal_bwd.hip", "batch.hip", "render.hip", "mesh_collision.hip"]
+SOURCES = ["gcn.hip", "gcn_tile.hip", "linear.hip", "conv.hip", "stem.hip", "metrics.hip", "smpl.hip", "sampler.hip", "guidance.hip", "prep.hip", "step.hip", "eval.hip", "stage1.hip", "scene.hip", "loss.hip", "gcn_bwd.hip", "gcn_train.hip", "pointnet_bwd.hip", "train.hip", "conv_bwd.hip", "bn2d_train.hip", "nonlocal_bwd.hip", "batch.hip", "render.hip", "mesh_collision.hip", "jpeg.hip"]
 
 
 class EgoHMRHipError(RuntimeError):
@@ -245,6 +245,19 @@ class RenderDesc(C.Structure):
                 [(n, C.c_void_p) for n in ("needed_capacity", "color", "depth", "face_index", "workspace")] + [("workspace_bytes", C.c_int64)])
 
 
+class JpegHeader(C.Structure):
+    """ehm_jpeg_header"""
+    _fields_ = ([(n, C.c_int32) for n in ("H", "W", "components", "hmax", "vmax", "mcus_x", "mcus_y", "restart_interval")] +
+                [(n, C.c_int32 * 3) for n in ("h", "v", "blocks_x", "blocks_y", "quant_id")] +
+                [("quant", (C.c_uint16 * 64) * 4), ("coef_count", C.c_int64)])
+
+
+class JpegDecodeDesc(C.Structure):
+    """ehm_jpeg_decode_desc"""
+    _fields_ = [("coef", C.c_void_p), ("quant", C.c_void_p), ("H", C.c_int), ("W", C.c_int), ("components", C.c_int), ("hmax", C.c_int),
+                ("vmax", C.c_int), ("F", C.c_int), ("frames", C.c_void_p), ("workspace", C.c_void_p), ("workspace_bytes", C.c_int64)]
+
+
 _P, _I, _L, _F = C.c_void_p, C.c_int, C.c_int64, C.c_float
 
 # name -> (restype, argtypes); every symbol include/egohmr_hip.h declares
@@ -360,6 +373,10 @@ PROTOTYPES = {
     "ehm_scene_select": (_I, [C.POINTER(SceneDesc), _P]),
     "ehm_image_patch": (_I, [C.POINTER(ImagePatchDesc), _P]),
     "ehm_scene_augment": (_I, [_P, _I, _P, _P, _I, _I, _I, _P]),
+    "ehm_jpeg_read_header": (_I, [_P, _L, C.POINTER(JpegHeader)]),
+    "ehm_jpeg_entropy_decode": (_I, [_P, _L, C.POINTER(JpegHeader), _P, _L]),
+    "ehm_jpeg_workspace_bytes": (_I, [C.POINTER(JpegDecodeDesc), C.POINTER(C.c_int64)]),
+    "ehm_jpeg_decode": (_I, [C.POINTER(JpegDecodeDesc), _P]),
     "ehm_render_workspace_bytes": (_I, [C.POINTER(RenderDesc), C.POINTER(C.c_int64)]),
     "ehm_render": (_I, [C.POINTER(RenderDesc), _P]),
     "ehm_sample_workspace_bytes": (_L, [C.POINTER(SampleDesc), _I, _I]),

@@ -13,12 +13,17 @@ dtypes follow the reference's operands: centre and box are float32 (egobody_data
 drawn parameters float64; a float32 value meeting a float64 one is promoted to float64, which is how numpy 1.22 (the reference's) evaluates
 these scalar expressions.
 
-Not built: JPEG decoding, the dataset index, a prefetching loader, `orig_img` / `imgname`, the commented-out extreme
+The frames themselves may arrive decoded (uint8 [F,H,W,3] BGR) or still encoded: a sequence of baseline-JPEG ``bytes`` or paths is decoded
+onto the device by egohmr_amd.jpeg.JpegDecoder (host Huffman stage, HIP IDCT / upsampling / colour: libjpeg's pixels, which are cv2.imread's
+with IMREAD_COLOR | IMREAD_IGNORE_ORIENTATION, augmentation.py:346; checked against PIL, not against cv2).
+
+Not built: the dataset index, a prefetching loader, `orig_img` / `imgname`, the commented-out extreme
 crop, and cv2's fixed-point interpolation grid - the patch is the real-valued bilinear rule of include/egohmr_hip.h.
 """
 from __future__ import annotations
 
 import ctypes as C
+import os
 import random as _random
 from dataclasses import dataclass
 
@@ -369,7 +374,7 @@ class BatchBuilder:
     scene_downsample_rate."""
 
     def __init__(self, device, img_size=224, mean=IMAGE_MEAN, std=IMAGE_STD, fx_norm_coeff=1500.0, smpl_male=None, smpl_female=None,
-                 scene_stride=1, fy_norm_coeff=None, flip_cam_width=FLIP_CAM_WIDTH, augment_config=None):
+                 scene_stride=1, fy_norm_coeff=None, flip_cam_width=FLIP_CAM_WIDTH, augment_config=None, jpeg_threads=8):
         device = torch.device(device)
         if device.type != "cuda":
             raise _lib.EgoHMRHipError("BatchBuilder runs on the HIP kernels only (got a CPU device); there is no CPU path")
@@ -385,6 +390,16 @@ class BatchBuilder:
         self.flip_cam_width = flip_cam_width
         self.augment_config = augment_config if augment_config is not None else AugmentConfig()
         self.quantize = True
+        self.jpeg_threads, self._jpeg = jpeg_threads, None          # the decoder of encoded frames, made at their first use
+
+    def _decoded(self, frames):
+        """Encoded frames (a sequence of JPEG bytes / paths) -> uint8 [F,H,W,3] on the device; anything else passes through."""
+        if isinstance(frames, (list, tuple)) and len(frames) and all(isinstance(f, (bytes, bytearray, memoryview, str, os.PathLike)) for f in frames):
+            if self._jpeg is None:
+                from .jpeg import JpegDecoder
+                self._jpeg = JpegDecoder(self.device, threads=self.jpeg_threads)
+            return self._jpeg.decode(frames)
+        return frames
 
     def _device_tensor(self, x, dtypes, name):
         t = x if isinstance(x, torch.Tensor) else torch.from_numpy(np.ascontiguousarray(x))
@@ -393,7 +408,7 @@ class BatchBuilder:
         return t.to(self.device).contiguous()
 
     def build(self, frames, frame_index, center, bbox_size, keypoints_2d, keypoints_3d, smpl_params, gender, fx, fy, cx, cy, scene, augment=None):
-        """``frames`` uint8 [F,H,W,3] BGR as decoded and ``scene`` [B,N,3] float32 / float64 in the PV camera (numpy, or tensors already on the
+        """``frames`` uint8 [F,H,W,3] BGR as decoded - or a sequence of F encoded baseline-JPEG frames, ``bytes`` or paths, decoded here - and ``scene`` [B,N,3] float32 / float64 in the PV camera (numpy, or tensors already on the
         device: SceneClouds output); ``frame_index`` [B]; ``center`` [B,2], ``bbox_size`` [B] (scale * 200); ``keypoints_2d`` [B,25,3];
         ``keypoints_3d`` [B,24,3]; ``smpl_params`` with global_orient [B,3], body_pose [B,69], betas [B,10], transl [B,3]; ``gender`` [B]
         (0 male, 1 female); ``fx, fy, cx, cy`` [B].  ``augment``: None (the test loader), 'draw' (draw_augmentation on the global generators) or
@@ -402,7 +417,7 @@ class BatchBuilder:
         B = len(fidx)
         if B == 0:
             raise ValueError("empty batch")
-        frames_d = self._device_tensor(frames, (torch.uint8,), "frames")
+        frames_d = self._device_tensor(self._decoded(frames), (torch.uint8,), "frames")
         if frames_d.dim() != 4 or frames_d.shape[3] != 3:
             raise ValueError(f"frames has shape {tuple(frames_d.shape)}, expected [F,H,W,3]")
         F, H, W = (int(v) for v in frames_d.shape[:3])

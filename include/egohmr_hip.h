@@ -827,6 +827,71 @@ int ehm_image_patch(const ehm_image_patch_desc* d, void* stream);
 #define EHM_AUG_P_SIN 8
 int ehm_scene_augment(const void* scene, int scene_is_f64, const double* params, float* out, int B, int N, int stride, void* stream);
 
+/* ------------------------------------------------------------------ JPEG decoding ------------- */
+/* Baseline JPEG -> uint8 [F,H,W,3] BGR frames on the device, split where the format is serial: the bit-serial Huffman stage runs on the
+ * host (csrc/jpeg_entropy.h, plain C++, one frame per caller thread), every arithmetic stage in two kernels (csrc/jpeg.hip).  The pixels
+ * are libjpeg's defaults - the ISLOW integer IDCT, "fancy" upsampling, its fixed-point colour tables - which is what the reference's
+ * cv2.imread(path, IMREAD_COLOR | IMREAD_IGNORE_ORIENTATION) (dataloaders/augmentation.py:346) and PIL both produce.  The rule was checked
+ * bit for bit against PIL's decode (tests/golden/jpeg), NOT against cv2.  EXIF orientation is ignored, as the reference's flag asks.
+ *
+ * Entropy stage (host).  Markers SOI, DQT (8-bit tables), DHT, SOF0 / SOF1 with 8-bit precision, DRI, SOS, RSTn, EOI; APPn and COM are
+ * skipped.  One interleaved scan of 1 or 3 components; luma sampling (1,1), (2,1) or (2,2) with chroma (1,1); a one-component frame counts
+ * as (1,1).  Per block: the DC difference on a per-component predictor that resets at each restart interval, the AC run/size pairs (EOB,
+ * ZRL), un-zigzag.  The output is the QUANTISED int16 coefficients (a dequantised value does not fit in int16): component planes one after
+ * the other, each plane blocks in row-major order over the MCU-padded grid [blocks_y][blocks_x], each block 64 values in natural order.
+ * Status -22 with a text for: progressive, arithmetic, lossless, 12-bit, 16-bit tables, 4 components, any other sampling, several scans, data
+ * that ends early (a missing EOI included), a Huffman code with no entry, a coefficient index above 63, restart markers out of order, an
+ * undefined table, a capacity too small.  Both host entries run without a GPU and make no device call.
+ *
+ * IDCT (jidctint; all int32, arithmetic right shifts).  x = coef * q, natural order.  One 1-D pass over x0..x7 with rounding r and shift s:
+ *   z1 = (x2 + x6) 4433; t2 = z1 - x6 15137; t3 = z1 + x2 6270; t0 = ((x0 + x4) << 13) + r; t1 = ((x0 - x4) << 13) + r
+ *   t10 = t0 + t3, t13 = t0 - t3, t11 = t1 + t2, t12 = t1 - t2
+ *   a0 = x7, a1 = x5, a2 = x3, a3 = x1; z1 = a0 + a3, z2 = a1 + a2, z3 = a0 + a2, z4 = a1 + a3; z5 = (z3 + z4) 9633
+ *   a0 *= 2446, a1 *= 16819, a2 *= 25172, a3 *= 12299; z1 *= -7373, z2 *= -20995; z3 = z3 (-16069) + z5, z4 = z4 (-3196) + z5
+ *   a0 += z1 + z3, a1 += z2 + z4, a2 += z2 + z3, a3 += z1 + z4
+ *   outputs 0..7 = (t10 + a3, t11 + a2, t12 + a1, t13 + a0, t13 - a0, t12 - a1, t11 - a2, t10 - a3) >> s
+ * Columns first (s = 11, r = 1 << 10), then rows on their results (s = 18, r = 1 << 17); sample = clamp(result + 128, 0, 255).
+ * Upsampling, on each chroma plane cropped to its real size ceil(H v / vmax) x ceil(W h / hmax); edges replicate the last real row or
+ * column, the samples of the MCU padding are never read:
+ *   h2v1: out[2i] = (3 s[i] + s[i-1] + 1) >> 2, out[2i+1] = (3 s[i] + s[i+1] + 2) >> 2
+ *   h2v2: u = 3 cur + above for the upper output row, 3 cur + below for the lower one (at the plane's top and bottom the neighbour is cur);
+ *         out[2i] = (3 u[i] + u[i-1] + 8) >> 4, out[2i+1] = (3 u[i] + u[i+1] + 7) >> 4
+ *   a chroma plane of one or two columns is replicated instead (out[y][x] = s[y / v][x / h]): libjpeg takes the filter only above two.
+ * Colour.  cb, cr = sample - 128; FIX(x) = int(x 65536 + 0.5); R = Y + ((FIX(1.40200) cr + 32768) >> 16);
+ * B = Y + ((FIX(1.77200) cb + 32768) >> 16); G = Y + ((-FIX(0.34414) cb + (-FIX(0.71414) cr + 32768)) >> 16); clamped to 0..255, stored
+ * B, G, R.  A one-component frame replicates Y.
+ *
+ * Device stage.  One call decodes F frames of ONE geometry (H, W, components, hmax, vmax - the block grids follow from them); quant holds a
+ * row of 64 per frame and component (natural order), so qualities may differ within a call.  Two launches, no atomics, every byte written
+ * once by one thread: two calls give the same bits.  The workspace holds the uint8 component planes on the MCU grid (coef_count bytes per
+ * frame).  F <= 65535; coef 16-byte aligned. */
+#define EHM_JPEG_MAX_COMPONENTS 3
+typedef struct ehm_jpeg_header {
+  int32_t H, W, components, hmax, vmax;
+  int32_t mcus_x, mcus_y;                 /* the MCU grid */
+  int32_t restart_interval;               /* MCUs, 0: none */
+  int32_t h[EHM_JPEG_MAX_COMPONENTS], v[EHM_JPEG_MAX_COMPONENTS];                 /* sampling factors */
+  int32_t blocks_x[EHM_JPEG_MAX_COMPONENTS], blocks_y[EHM_JPEG_MAX_COMPONENTS];   /* per-component block grid (MCU padded) */
+  int32_t quant_id[EHM_JPEG_MAX_COMPONENTS];
+  uint16_t quant[4][64];                  /* natural order; an undefined table is zero */
+  int64_t coef_count;                     /* int16 values of one frame's coefficients */
+} ehm_jpeg_header;
+int ehm_jpeg_read_header(const uint8_t* data, int64_t n, ehm_jpeg_header* hdr);
+/* hdr (may be NULL) is written as by the call above; nothing is written at or past coef + capacity (capacity in int16 values) */
+int ehm_jpeg_entropy_decode(const uint8_t* data, int64_t n, ehm_jpeg_header* hdr, int16_t* coef, int64_t capacity);
+
+typedef struct ehm_jpeg_decode_desc {
+  const int16_t* coef;          /* device [F, coef_count] */
+  const uint16_t* quant;        /* device [F, 3, 64]: frame f, component c (a one-component frame uses row 0) */
+  int H, W, components, hmax, vmax;
+  int F;
+  uint8_t* frames;              /* device [F, H, W, 3] BGR */
+  void* workspace;
+  int64_t workspace_bytes;
+} ehm_jpeg_decode_desc;
+int ehm_jpeg_workspace_bytes(const ehm_jpeg_decode_desc* d, int64_t* bytes);
+int ehm_jpeg_decode(const ehm_jpeg_decode_desc* d, void* stream);
+
 /* ------------------------------------------------------------------ mesh rendering ------------ */
 /* A software rasteriser for the overlays of test_egohmr.py --render True (utils/renderer.py:15-47 render_on_img / render_in_scene, called at
  * test_egohmr.py:576-619), which the reference draws with pyrender (csrc/render.hip).  The pixels are THIS RULE'S, not pyrender's: its PBR
