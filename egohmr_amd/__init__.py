@@ -21,6 +21,7 @@ _LAZY = {
     "BatchBuilder": ("batch", "BatchBuilder"),
     "AugmentConfig": ("batch", "AugmentConfig"),
     "JpegDecoder": ("jpeg", "JpegDecoder"),
+    "JpegEncoder": ("jpeg", "JpegEncoder"),
     "MeshRenderer": ("render", "MeshRenderer"),
     "render_on_img": ("render", "render_on_img"),
     "render_in_scene": ("render", "render_in_scene"),

@@ -29,7 +29,7 @@ _HERE = os.path.dirname(os.path.abspath(__file__))
 LIB_PATH = os.environ.get("EHM_LIB_PATH") or os.path.join(_HERE, "libegohmr_hip.so")   # EHM_LIB_PATH: A/B a second build (experiments)
 CSRC = os.path.join(_HERE, "csrc")
 INCLUDE = os.path.join(os.path.dirname(_HERE), "include")
-SOURCES = ["gcn.hip", "gcn_tile.hip", "linear.hip", "conv.hip", "stem.hip", "metrics.hip", "smpl.hip", "sampler.hip", "guidance.hip", "prep.hip", "step.hip", "eval.hip", "stage1.hip", "scene.hip", "loss.hip", "gcn_bwd.hip", "gcn_train.hip", "pointnet_bwd.hip", "train.hip", "conv_bwd.hip", "bn2d_train.hip", "nonlocal_bwd.hip", "batch.hip", "render.hip", "mesh_collision.hip", "jpeg.hip"]
+SOURCES = ["gcn.hip", "gcn_tile.hip", "linear.hip", "conv.hip", "stem.hip", "metrics.hip", "smpl.hip", "sampler.hip", "guidance.hip", "prep.hip", "step.hip", "eval.hip", "stage1.hip", "scene.hip", "loss.hip", "gcn_bwd.hip", "gcn_train.hip", "pointnet_bwd.hip", "train.hip", "conv_bwd.hip", "bn2d_train.hip", "nonlocal_bwd.hip", "batch.hip", "render.hip", "mesh_collision.hip", "jpeg.hip", "jpeg_enc.hip"]
 
 
 class EgoHMRHipError(RuntimeError):
@@ -258,6 +258,19 @@ class JpegDecodeDesc(C.Structure):
                 ("vmax", C.c_int), ("F", C.c_int), ("frames", C.c_void_p), ("workspace", C.c_void_p), ("workspace_bytes", C.c_int64)]
 
 
+class JpegForwardDesc(C.Structure):
+    """ehm_jpeg_forward_desc"""
+    _fields_ = [("frames", C.c_void_p), ("quant", C.c_void_p), ("H", C.c_int), ("W", C.c_int), ("hmax", C.c_int), ("vmax", C.c_int),
+                ("F", C.c_int), ("rgb", C.c_int), ("coef", C.c_void_p)]
+
+
+class JpegEntropyEncodeDesc(C.Structure):
+    """ehm_jpeg_entropy_encode_desc"""
+    _fields_ = [("coef", C.c_void_p), ("H", C.c_int), ("W", C.c_int), ("hmax", C.c_int), ("vmax", C.c_int), ("F", C.c_int),
+                ("streams", C.c_void_p), ("capacity", C.c_int64), ("lengths", C.c_void_p), ("needed", C.c_void_p),
+                ("workspace", C.c_void_p), ("workspace_bytes", C.c_int64)]
+
+
 _P, _I, _L, _F = C.c_void_p, C.c_int, C.c_int64, C.c_float
 
 # name -> (restype, argtypes); every symbol include/egohmr_hip.h declares
@@ -377,6 +390,11 @@ PROTOTYPES = {
     "ehm_jpeg_entropy_decode": (_I, [_P, _L, C.POINTER(JpegHeader), _P, _L]),
     "ehm_jpeg_workspace_bytes": (_I, [C.POINTER(JpegDecodeDesc), C.POINTER(C.c_int64)]),
     "ehm_jpeg_decode": (_I, [C.POINTER(JpegDecodeDesc), _P]),
+    "ehm_jpeg_quality_tables": (_I, [_I, _P]),
+    "ehm_jpeg_write_header": (_I, [_I, _I, _I, _I, _P, _P, _L, C.POINTER(C.c_int64)]),
+    "ehm_jpeg_forward": (_I, [C.POINTER(JpegForwardDesc), _P]),
+    "ehm_jpeg_entropy_encode_workspace_bytes": (_I, [C.POINTER(JpegEntropyEncodeDesc), C.POINTER(C.c_int64)]),
+    "ehm_jpeg_entropy_encode": (_I, [C.POINTER(JpegEntropyEncodeDesc), _P]),
     "ehm_render_workspace_bytes": (_I, [C.POINTER(RenderDesc), C.POINTER(C.c_int64)]),
     "ehm_render": (_I, [C.POINTER(RenderDesc), _P]),
     "ehm_sample_workspace_bytes": (_L, [C.POINTER(SampleDesc), _I, _I]),
@@ -394,6 +412,7 @@ PROTOTYPES = {
     "ehm_profile_end": (_I, [C.POINTER(C.c_double), C.POINTER(C.c_int64), _I]),
 }
 MESH_COLLISION_FACE_CHUNK, MESH_COLLISION_POINT_BLOCK = 512, 256     # EHM_MESH_COLLISION_* of the header (tests size their edge cases by them)
+JPEG_ENC_HEADER_BYTES, JPEG_ENC_SCAN_CHUNK, JPEG_ENC_STUFF_CHUNK, JPEG_ENC_MAX_BLOCK_BYTES = 623, 256, 4096, 208   # EHM_JPEG_ENC_* of the header
 PROF_CLASSES = ("input", "chain_f16x3", "chain_f16", "hidden_f32", "out_dot", "step_body", "skin_input", "guidance", "reserved_8", "reserved_9",
                 "guid_nearest", "guid_skin_bwd", "guid_posefeat_bwd", "step_fused", "guid_nearest_evals",   # EHM_PROF_* of the header ("guid_nearest_evals" is a COUNT in `launches`)
                 "chain_f16x2")

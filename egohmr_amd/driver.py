@@ -16,6 +16,8 @@ the Procrustes alignment as a CPU loop of numpy SVDs (utils/pose_utils.py).  The
 """
 from __future__ import annotations
 
+import os
+
 import numpy as np
 import torch
 
@@ -181,6 +183,32 @@ class Stage2Driver:
         fidx = torch.as_tensor(frame_index).to(dev)[it].repeat_interleave(n_s).to(torch.int32)
         img = renderer.render(v, focal, focal, per(batch["cam_cx"]).trunc(), per(batch["cam_cy"]).trunc(), frames=frames, frame_index=fidx, bgr=True)["color"]
         return img.reshape(n_i, n_s, *img.shape[1:])
+
+    # ------------------------------------------------------------------ :619-626
+    @torch.no_grad()
+    def save_overlays(self, images, names, folder, in_scene=None, frames=None, frame_index=None, quality=95, encoder=None):
+        """The files of test_egohmr.py:619-626: one contact sheet per item of ``images`` (what ``render`` returns, uint8 [items, S, H, W, 3] BGR)
+        written as ``<folder>/<names[i]>`` - the naming '{recording}_{frame}' stays the caller's.  Each sheet row is [input | overlay | in-scene]:
+        the input is frame ``frame_index[i]`` of ``frames`` uint8 [Fr,H,W,3] (left out when ``frames`` is None), ``in_scene`` uint8
+        [items, S, H, W, 3] is optional.  The sheet is halved (egohmr_amd.render.contact_sheet) and encoded on the device by a ``JpegEncoder``
+        (``encoder``: one to reuse; one is built and kept otherwise) at ``quality`` and 4:2:0, cv2.imwrite's documented defaults.  -> the paths."""
+        from .jpeg import JpegEncoder
+        from .render import contact_sheet
+        names = list(names)
+        if images.dim() != 5 or len(names) != images.shape[0]:
+            raise ValueError(f"save_overlays: {len(names)} names for images of shape {tuple(images.shape)}")
+        dev = images.device
+        if encoder is None:
+            if getattr(self, "_encoder", None) is None or self._encoder.device != dev:
+                self._encoder = JpegEncoder(dev)
+            encoder = self._encoder
+        inputs = None
+        if frames is not None:
+            fidx = torch.arange(len(names)) if frame_index is None else torch.as_tensor(frame_index)
+            inputs = frames.to(dev)[fidx.to(dev).long()]
+        sheets = [contact_sheet(None if inputs is None else inputs[i], images[i], None if in_scene is None else in_scene[i]) for i in range(len(names))]
+        os.makedirs(folder, exist_ok=True)
+        return encoder.write(torch.stack(sheets), [os.path.join(folder, n) for n in names], bgr=True, quality=quality)
 
     # ------------------------------------------------------------------ :507-560, :660-670
     def summary(self) -> dict:

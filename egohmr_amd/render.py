@@ -205,3 +205,24 @@ def render_in_scene(fx, fy, cx, cy, body_vertices, scene_vertices, scene_faces=N
     both = torch.cat([v, s.unsqueeze(0).expand(v.shape[0], -1, -1)], 1).contiguous()
     img = renderer.render(both, fx, fy, cx, cy, size=size, bg_color=bg_color, bgr=bgr)["color"]
     return img[0] if one else img
+
+
+def contact_sheet(input_frames, on_img, in_scene=None, halve=True):
+    """test_egohmr.py:619-625: per sample the row [input | overlay | in-scene] (a column given as None is left out), the S rows stacked, the sheet
+    halved.  ``input_frames`` uint8 [S,H,W,3] (or one [H,W,3] frame for every sample), ``on_img`` and ``in_scene`` uint8 [S,H,W,3], all on one
+    device -> uint8 [S H // 2, n W // 2, 3] (``halve=False``: [S H, n W, 3]).  The halving is the 2 x 2 mean (a + b + c + d + 2) >> 2 on integer
+    torch ops; an odd height or width drops its last row or column first, as ``dsize = shape // 2`` does.  It stands for the script's
+    cv2.resize(.., INTER_AREA); cv2's rounding was NOT compared, because cv2 is not installed."""
+    if input_frames is not None and input_frames.dim() == 3:
+        input_frames = input_frames.unsqueeze(0).expand(on_img.shape[0], -1, -1, -1)
+    parts = [p for p in (input_frames, on_img, in_scene) if p is not None]
+    for p in parts:
+        if p.dtype != torch.uint8 or p.dim() != 4 or p.shape[-1] != 3 or p.shape[:3] != on_img.shape[:3]:
+            raise ValueError(f"contact_sheet takes uint8 [S,H,W,3] tensors of one size, got {p.dtype} {tuple(p.shape)}")
+    sheet = torch.cat([p.to(on_img.device) for p in parts], 2)
+    sheet = sheet.reshape(-1, sheet.shape[2], 3)
+    if not halve:
+        return sheet.contiguous()
+    h, w = sheet.shape[0] // 2, sheet.shape[1] // 2
+    q = sheet[:2 * h, :2 * w].to(torch.int32).reshape(h, 2, w, 2, 3)
+    return ((q.sum((1, 3)) + 2) >> 2).to(torch.uint8)

@@ -892,6 +892,92 @@ typedef struct ehm_jpeg_decode_desc {
 int ehm_jpeg_workspace_bytes(const ehm_jpeg_decode_desc* d, int64_t* bytes);
 int ehm_jpeg_decode(const ehm_jpeg_decode_desc* d, void* stream);
 
+/* ------------------------------------------------------------------ JPEG encoding ------------- */
+/* uint8 [F,H,W,3] frames on the device -> baseline JPEG, every stage on the device (csrc/jpeg_enc.hip); only the compressed stream crosses
+ * to the host, which writes 623 bytes of markers around it (csrc/jpeg_enc.h).  The rule is libjpeg's default encoder, the one behind
+ * cv2.imwrite and PIL; it was checked bit for bit against PIL (libjpeg-turbo), NOT against cv2.  Fixed Huffman tables (no `optimize`), no
+ * restart markers, no progressive mode.  Grey and 4-component files are out of scope.
+ *
+ * Input.  uint8 [F,H,W,3], B G R order (what the renderer and the decoder produce) or R G B with `rgb` set.
+ * Colour (jccolor.c).  FIX(x) = int(x 65536 + 0.5), all integer:
+ *   Y  = (FIX(.29900) R + FIX(.58700) G + FIX(.11400) B + 32768) >> 16
+ *   Cb = (-FIX(.16874) R - FIX(.33126) G + FIX(.50000) B + (128 << 16) + 32767) >> 16
+ *   Cr = (FIX(.50000) R - FIX(.41869) G - FIX(.08131) B + (128 << 16) + 32767) >> 16
+ * Sampling.  Luma (hmax, vmax) is (1,1), (2,1) or (2,2), chroma (1,1): the decoder's three cases.
+ * Padding and downsampling (jcsample.c, jcprepct.c).  The REAL block grid of a component is rw = ceil(W h / (8 hmax)) by
+ * rh = ceil(H v / (8 vmax)).  Horizontally the full-resolution plane is extended to rw 8 (hmax / h) columns by repeating the last column,
+ * then downsampled.  Vertically it is extended only to a multiple of vmax / v rows by repeating the last row, then downsampled; AFTER that
+ * the plane is extended to rh 8 rows by repeating its last row (repeating full-resolution rows up to the block grid gives other numbers).
+ *   h2v1: (a + b + bias) >> 1 with bias 0, 1, 0, 1, ... along the output row;  h2v2: (a + b + c + d + bias) >> 2 with bias 1, 2, 1, 2, ...
+ * FDCT (jfdctint; int32; on the sample minus 128).  Rows first, then columns.  D(x, n) = (x + (1 << (n - 1))) >> n.  One pass over d0..d7:
+ *   t0..t3 = d0 + d7, d1 + d6, d2 + d5, d3 + d4;  t7..t4 = d0 - d7, d1 - d6, d2 - d5, d3 - d4
+ *   t10 = t0 + t3, t13 = t0 - t3, t11 = t1 + t2, t12 = t1 - t2
+ *   out0, out4 = (t10 +- t11) << 2 in pass 1, D(t10 +- t11, 2) in pass 2
+ *   z1 = (t12 + t13) 4433; out2 = D(z1 + t13 6270, n); out6 = D(z1 - t12 15137, n)
+ *   z1 = t4 + t7, z2 = t5 + t6, z3 = t4 + t6, z4 = t5 + t7; z5 = (z3 + z4) 9633
+ *   t4 *= 2446, t5 *= 16819, t6 *= 25172, t7 *= 12299; z1 *= -7373, z2 *= -20995; z3 = -16069 z3 + z5, z4 = -3196 z4 + z5
+ *   out7 = D(t4 + z1 + z3, n), out5 = D(t5 + z2 + z4, n), out3 = D(t6 + z2 + z3, n), out1 = D(t7 + z1 + z4, n)
+ * with n = 11 in pass 1 and n = 15 in pass 2; the result is 8 x the DCT.
+ * Quantisation (jcdctmgr.c).  d = 8 q; a = |x| + (d >> 1); r = a / d if a >= d, else 0; the sign is restored.
+ * Dummy blocks (jccoefct.c).  The coefficients use the decoder's layout: each plane [blocks_y = mcus_y v][blocks_x = mcus_x h][64] in natural
+ * order, planes one after the other, int16 [F, coef_count].  Blocks beyond rw or rh are not transforms of padding: all their AC are zero; in a
+ * real row a dummy block takes the DC of the block to its left; in a dummy row every block of an MCU takes the DC of the last block of the
+ * previous block row of the same MCU (which may itself be a dummy column block).
+ * Tables.  libjpeg's quality scaling of the Annex K.1 / K.2 tables: s = 5000 / q if q < 50, else 200 - 2 q; entry = clamp((base s + 50) / 100,
+ * 1, 255).  Explicit uint16 [2][64] tables are accepted as well; luma uses table 0, both chroma planes table 1.  The four Annex K.3 - K.6
+ * Huffman tables are fixed.
+ * Entropy coding.  One interleaved scan, no restart markers.  MCUs in row-major order; within an MCU the luma blocks (rows, then columns),
+ * then Cb, then Cr.  DC: the difference d to the previous block of the same component in scan order (predictor 0 at the start), size
+ * s = bitlength(|d|): the Huffman code of s, then the low s bits of d if d >= 0, else of d - 1.  AC in zigzag order: a run of more than 15
+ * zeros is one or more ZRL codes (0xF0), then the (run << 4) | size code and the value bits as for DC; a block that ends in zeros ends in
+ * EOB (0x00).  The last byte is padded with 1 bits; then every byte FF is followed by 00.
+ * File.  SOI, APP0 JFIF 1.01 (units 0, density 1 x 1, no thumbnail), DQT table 0, DQT table 1, SOF0, DHT DC0, AC0, DC1, AC1, SOS, the
+ * stream, EOI (FF D9, the caller's two bytes): the order PIL writes.
+ *
+ * ehm_jpeg_forward: one launch; every value written once by one thread.  quant is [F,3,64] (natural order, the decoder's convention: rows 1
+ * and 2 are the chroma table twice), so a call may mix qualities; an entry of 0 is the caller's error (the device table is not inspected).
+ * Its output is directly what ehm_jpeg_decode reads.  coef 16-byte aligned.
+ * ehm_jpeg_entropy_encode: coefficients -> the stuffed streams uint8 [F, capacity] (SOS's end to EOI's start), lengths int64 [F] and needed
+ * int64 [F].  needed[f] is the exact stream size whatever the capacity; lengths[f] = needed[f], or -1 when needed[f] > capacity (that
+ * frame's stream is then not written; the others are), or -2 (needed 0) when a DC difference beyond +-2047 or an AC value beyond +-1023 has
+ * no code.  Nothing is written at or past capacity.  Eight launches; the scans are one workgroup per frame walking
+ * EHM_JPEG_ENC_SCAN_CHUNK elements at a time, the stuffing works on chunks of EHM_JPEG_ENC_STUFF_CHUNK bytes; no workgroup waits on
+ * another.  The packing ORs atomically into the words two blocks share: OR commutes, so two calls give the same bits.  The workspace
+ * (ehm_jpeg_entropy_encode_workspace_bytes; 16-byte aligned) holds EHM_JPEG_ENC_MAX_BLOCK_BYTES per block for the packed stream.
+ * Both host entries run without a GPU.  Status -22 with a text, before any device call, for: a sampling other than the three, F > 65535,
+ * misaligned buffers, a NULL pointer, a quantisation entry outside 1..255, a quality outside 1..100, a capacity below the header's size. */
+#define EHM_JPEG_ENC_HEADER_BYTES 623
+#define EHM_JPEG_ENC_SCAN_CHUNK 256
+#define EHM_JPEG_ENC_STUFF_CHUNK 4096
+#define EHM_JPEG_ENC_MAX_BLOCK_BYTES 208
+int ehm_jpeg_quality_tables(int quality, uint16_t* quant /* [2][64] */);
+/* SOI ... SOS into out[0 .. capacity): *n = EHM_JPEG_ENC_HEADER_BYTES, or 0 on a refusal (nothing is written then) */
+int ehm_jpeg_write_header(int H, int W, int hmax, int vmax, const uint16_t* quant /* [2][64] */, uint8_t* out, int64_t capacity, int64_t* n);
+
+typedef struct ehm_jpeg_forward_desc {
+  const uint8_t* frames;        /* device [F, H, W, 3] */
+  const uint16_t* quant;        /* device [F, 3, 64] */
+  int H, W, hmax, vmax;
+  int F;
+  int rgb;                      /* 0: B G R, else R G B */
+  int16_t* coef;                /* device [F, coef_count] */
+} ehm_jpeg_forward_desc;
+int ehm_jpeg_forward(const ehm_jpeg_forward_desc* d, void* stream);
+
+typedef struct ehm_jpeg_entropy_encode_desc {
+  const int16_t* coef;          /* device [F, coef_count] */
+  int H, W, hmax, vmax;
+  int F;
+  uint8_t* streams;             /* device [F, capacity] */
+  int64_t capacity;
+  int64_t* lengths;             /* device [F] */
+  int64_t* needed;              /* device [F] */
+  void* workspace;
+  int64_t workspace_bytes;
+} ehm_jpeg_entropy_encode_desc;
+int ehm_jpeg_entropy_encode_workspace_bytes(const ehm_jpeg_entropy_encode_desc* d, int64_t* bytes);
+int ehm_jpeg_entropy_encode(const ehm_jpeg_entropy_encode_desc* d, void* stream);
+
 /* ------------------------------------------------------------------ mesh rendering ------------ */
 /* A software rasteriser for the overlays of test_egohmr.py --render True (utils/renderer.py:15-47 render_on_img / render_in_scene, called at
  * test_egohmr.py:576-619), which the reference draws with pyrender (csrc/render.hip).  The pixels are THIS RULE'S, not pyrender's: its PBR
