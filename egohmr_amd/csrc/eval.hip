@@ -14,6 +14,7 @@
 // reference does with them is dozens of eager ops + a per-sample numpy SVD loop on the CPU with a device -> host copy in front.
 #include "common.h"
 #include "egohmr_hip.h"
+#include "procrustes_solve.h"
 
 namespace {
 
@@ -176,57 +177,7 @@ __global__ __launch_bounds__(256) void point_errors_kernel(const float* __restri
 }
 
 // ------------------------------------------------------------------------------------------------ Procrustes
-constexpr int PJ_MAX = 32;
-
-// One-sided Jacobi on the columns of a 3 x 3 matrix: K V = B with orthogonal columns (B = U diag(s)).  float64: converges in 4 - 6 sweeps.
-__device__ void svd3(const double K[3][3], double U[3][3], double s[3], double V[3][3]) {
-  double Bm[3][3];
-  for (int r = 0; r < 3; ++r)
-    for (int c = 0; c < 3; ++c) { Bm[r][c] = K[r][c]; V[r][c] = r == c ? 1.0 : 0.0; }
-  for (int sweep = 0; sweep < 30; ++sweep) {
-    double off = 0.0;
-    for (int p = 0; p < 2; ++p)
-      for (int q = p + 1; q < 3; ++q) {
-        double al = 0.0, be = 0.0, ga = 0.0;
-        for (int r = 0; r < 3; ++r) { al += Bm[r][p] * Bm[r][p]; be += Bm[r][q] * Bm[r][q]; ga += Bm[r][p] * Bm[r][q]; }
-        if (ga == 0.0 || fabs(ga) <= 1e-300) continue;
-        off = fmax(off, fabs(ga) / sqrt(fmax(al * be, 1e-300)));
-        const double zeta = (be - al) / (2.0 * ga);
-        const double t = (zeta >= 0.0 ? 1.0 : -1.0) / (fabs(zeta) + sqrt(1.0 + zeta * zeta));
-        const double c = 1.0 / sqrt(1.0 + t * t), sn = c * t;
-        for (int r = 0; r < 3; ++r) {
-          const double bp = Bm[r][p], bq = Bm[r][q];
-          Bm[r][p] = c * bp - sn * bq; Bm[r][q] = sn * bp + c * bq;
-          const double vp = V[r][p], vq = V[r][q];
-          V[r][p] = c * vp - sn * vq; V[r][q] = sn * vp + c * vq;
-        }
-      }
-    if (off < 1e-15) break;
-  }
-  double smax = 0.0;
-  for (int c = 0; c < 3; ++c) {
-    s[c] = sqrt(Bm[0][c] * Bm[0][c] + Bm[1][c] * Bm[1][c] + Bm[2][c] * Bm[2][c]);
-    smax = fmax(smax, s[c]);
-  }
-  int good[3], ng = 0;
-  for (int c = 0; c < 3; ++c) {
-    if (s[c] > 1e-13 * smax && s[c] > 0.0) { for (int r = 0; r < 3; ++r) U[r][c] = Bm[r][c] / s[c]; good[ng++] = c; }
-  }
-  if (ng == 2) {               // rank 2: the missing left vector completes the frame (its sign is absorbed by Z = diag(1, 1, det))
-    const int m = 3 - good[0] - good[1], a = good[0], bq = good[1];
-    U[0][m] = U[1][a] * U[2][bq] - U[2][a] * U[1][bq];
-    U[1][m] = U[2][a] * U[0][bq] - U[0][a] * U[2][bq];
-    U[2][m] = U[0][a] * U[1][bq] - U[1][a] * U[0][bq];
-  } else if (ng < 2) {         // rank <= 1: the rotation is not determined by the data; any orthonormal completion (the reference's is LAPACK's)
-    for (int r = 0; r < 3; ++r)
-      for (int c = 0; c < 3; ++c) U[r][c] = V[r][c];
-  }
-}
-
-__device__ __forceinline__ double det3(const double A[3][3]) {
-  return A[0][0] * (A[1][1] * A[2][2] - A[1][2] * A[2][1]) - A[0][1] * (A[1][0] * A[2][2] - A[1][2] * A[2][0]) + A[0][2] * (A[1][0] * A[2][1] - A[1][1] * A[2][0]);
-}
-
+// The solve (3 x 3 Jacobi SVD, R = V Z U^T, scale, translation) is csrc/procrustes_solve.h, shared with tools/procrustes_check.cpp.
 __global__ __launch_bounds__(64) void procrustes_kernel(const float* __restrict__ pred, const float* __restrict__ gt, const uint8_t* __restrict__ mask,
                                                         float* __restrict__ aligned, float* __restrict__ per_joint, float* __restrict__ mean,
                                                         float* __restrict__ vis_sum, float* __restrict__ invis_sum, int n, int S, int J) {
@@ -246,24 +197,8 @@ __global__ __launch_bounds__(64) void procrustes_kernel(const float* __restrict_
     for (int r = 0; r < 3; ++r)
       for (int c = 0; c < 3; ++c) K[r][c] += x1[r] * x2[c];                  // K = X1 X2^T in the reference's 3 x N layout (pose_utils.py:36)
   }
-  double U[3][3], s[3], V[3][3];
-  svd3(K, U, s, V);
-  // Z = diag(1, 1, sign(det(U V^T))) acts on the SMALLEST singular value (numpy sorts them in descending order: pose_utils.py:42-46)
-  int mn = 0;
-  if (s[1] < s[mn]) mn = 1;
-  if (s[2] < s[mn]) mn = 2;
-  const double dsign = det3(U) * det3(V) >= 0.0 ? 1.0 : -1.0;               // det(U V^T) = det U det V
-  double Rm[3][3], tr = 0.0;
-  for (int r = 0; r < 3; ++r)
-    for (int c = 0; c < 3; ++c) {
-      double acc = 0.0;
-      for (int k = 0; k < 3; ++k) acc += (k == mn ? dsign : 1.0) * V[r][k] * U[c][k];   // R = V Z U^T
-      Rm[r][c] = acc;
-    }
-  for (int k = 0; k < 3; ++k) tr += (k == mn ? dsign : 1.0) * s[k];          // trace(R K) = sum_k z_k s_k
-  const double scale = tr / var1;
-  double t[3];
-  for (int r = 0; r < 3; ++r) t[r] = mu2[r] - scale * (Rm[r][0] * mu1[0] + Rm[r][1] * mu1[1] + Rm[r][2] * mu1[2]);
+  double Rm[3][3], scale, t[3];
+  procrustes_solve::similarity(K, var1, mu1, mu2, Rm, &scale, t);
   double s_all = 0.0, s_vis = 0.0;
   for (int j = 0; j < J; ++j) {
     double e2 = 0.0;
@@ -309,23 +244,8 @@ __global__ __launch_bounds__(64) void procrustes_vis_kernel(const float* __restr
     for (int r = 0; r < 3; ++r)
       for (int c = 0; c < 3; ++c) K[r][c] += x1[r] * x2[c];
   }
-  double U[3][3], s[3], V[3][3];
-  svd3(K, U, s, V);
-  int mn = 0;                                                                // Z acts on the smallest singular value (see procrustes_kernel)
-  if (s[1] < s[mn]) mn = 1;
-  if (s[2] < s[mn]) mn = 2;
-  const double dsign = det3(U) * det3(V) >= 0.0 ? 1.0 : -1.0;
-  double Rm[3][3], tr = 0.0;
-  for (int r = 0; r < 3; ++r)
-    for (int c = 0; c < 3; ++c) {
-      double acc = 0.0;
-      for (int k = 0; k < 3; ++k) acc += (k == mn ? dsign : 1.0) * V[r][k] * U[c][k];
-      Rm[r][c] = acc;
-    }
-  for (int k = 0; k < 3; ++k) tr += (k == mn ? dsign : 1.0) * s[k];
-  const double scale = tr / var1;                                            // no visible joint: 0 / 0 = NaN, as the reference
-  double t[3];
-  for (int r = 0; r < 3; ++r) t[r] = mu2[r] - scale * (Rm[r][0] * mu1[0] + Rm[r][1] * mu1[1] + Rm[r][2] * mu1[2]);
+  double Rm[3][3], scale, t[3];
+  procrustes_solve::similarity(K, var1, mu1, mu2, Rm, &scale, t);   // no visible joint: var1 = 0, scale = 0 / 0 = NaN, as the reference
   double s_all = 0.0, s_vis = 0.0, s_inv = 0.0;
   for (int j = 0; j < J; ++j) {
     double e2 = 0.0;
@@ -412,7 +332,8 @@ extern "C" int ehm_eval_point_errors(const ehm_eval_points_desc* d, void* stream
 
 extern "C" int ehm_eval_procrustes(const float* pred, const float* gt, const uint8_t* mask, float* aligned, float* per_joint, float* mean, float* vis_sum,
                                    float* invis_sum, int B, int S, int J, void* stream) {
-  EHM_CHECK_ARG(pred && gt && B > 0 && S > 0 && J >= 3 && J <= PJ_MAX && (aligned || per_joint || mean));
+  EHM_CHECK_ARG(pred && gt && B > 0 && S > 0 && J >= 3 && (aligned || per_joint || mean));   // any J: the kernel has no J-sized array
+  EHM_CHECK_ARG((int64_t)B * S <= INT32_MAX);
   const int n = B * S;
   hipLaunchKernelGGL(procrustes_kernel, dim3((unsigned)ceil_div(n, 64)), dim3(64), 0, (hipStream_t)stream, pred, gt, mask, aligned, per_joint, mean, vis_sum,
                      invis_sum, n, S, J);

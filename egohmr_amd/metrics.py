@@ -126,10 +126,12 @@ def v2v(pred_vertices: torch.Tensor, pred_pelvis, gt_vertices: torch.Tensor, gt_
 
 
 def procrustes(pred: torch.Tensor, gt: torch.Tensor, mask=None, aligned: bool = False, per_joint: bool = False, align_mask=None) -> dict:
-    """ehm_eval_procrustes (csrc/eval.hip): utils/pose_utils.py:10-66 batched - pred [B,S,J,3] against gt [B,J,3], float64 inside the kernel.
+    """ehm_eval_procrustes (csrc/eval.hip): utils/pose_utils.py:10-66 batched - pred [B,S,J,3] against gt [B,J,3], float64 inside the kernel, any
+    J >= 3 (joints or vertices).  A collinear or planar cloud keeps every singular vector the data determine (csrc/procrustes_solve.h).
     align_mask [B,J]: the visible-joint alignment of --eval_with_vis_mask_pa instead (ehm_eval_procrustes_vis, pose_utils.py:75-107): invisible
     joints of both clouds enter the solve as points at the origin, the error is taken over all J, and the same mask splits vis_sum / invis_sum
-    (test_egohmr.py:427-437) - `mask` must then be None or that same tensor.  An item without a visible joint gives NaN, as the reference."""
+    (test_egohmr.py:427-437) - `mask` must then be None or that same tensor.  An item without a visible joint gives NaN, as the reference; with ONE
+    visible joint that joint is aligned exactly (the other joints' errors depend on a rotation the data do not determine)."""
     pred, gt = _f32c(pred), _f32c(gt)
     B, S, J = pred.shape[0], pred.shape[1], pred.shape[2]
     assert gt.shape == (B, J, 3), (tuple(pred.shape), tuple(gt.shape))
@@ -148,12 +150,12 @@ def procrustes(pred: torch.Tensor, gt: torch.Tensor, mask=None, aligned: bool = 
 
 
 def similarity_align(S1: torch.Tensor, S2: torch.Tensor) -> torch.Tensor:
-    """utils/pose_utils.py:10-66 batched on the device: the similarity transform of S1 [n,J,3] closest to S2 [n,J,3] (float32 out, float64 inside)."""
+    """utils/pose_utils.py:10-66 batched on the device: the similarity transform of S1 [n,J,3] closest to S2 [n,J,3] (float32 out, float64 inside); any J >= 3."""
     return procrustes(S1.reshape(-1, 1, *S1.shape[-2:]), S2.reshape(-1, *S2.shape[-2:]), aligned=True)["aligned"].reshape(S1.shape)
 
 
 def pa_mpjpe(pred_joints: torch.Tensor, gt_joints: torch.Tensor) -> torch.Tensor:
-    """utils/pose_utils.py:109-126 (reconstruction_error): Procrustes-aligned mean joint error -> [n]."""
+    """utils/pose_utils.py:109-126 (reconstruction_error): Procrustes-aligned mean joint error -> [n]; any J >= 3."""
     p = pred_joints.reshape(-1, 1, pred_joints.shape[-2], 3)
     g = gt_joints.reshape(-1, gt_joints.shape[-2], 3)
     return procrustes(p, g)["mean"].reshape(-1)

@@ -688,7 +688,8 @@ int ehm_eval_point_errors(const ehm_eval_points_desc* d, void* stream);
 /* utils/pose_utils.py:10-66 (compute_similarity_transform) + :109-126 (reconstruction_error) as called at test_egohmr.py:419-437: the similarity transform
  * (scale, rotation, translation) of each pred[b,s] [J,3] closest to gt[b] [J,3] - float64 in registers like the reference's per-sample numpy loop, the
  * 3 x 3 SVD by one-sided Jacobi - then the per-joint error.  aligned [B,S,J,3], per_joint [B,S,J], mean [B,S], vis_sum / invis_sum [B,S] with mask [B,J]:
- * each may be NULL (one of aligned / per_joint / mean must not be).  3 <= J <= 32. */
+ * each may be NULL (one of aligned / per_joint / mean must not be).  Any J >= 3 (no per-joint arrays).  A rank-deficient correlation matrix (a collinear or
+ * planar cloud) gets an orthonormal completion that keeps every known singular vector (csrc/procrustes_solve.h); a one-point pred is NaN, as the reference. */
 int ehm_eval_procrustes(const float* pred, const float* gt, const uint8_t* mask, float* aligned, float* per_joint, float* mean, float* vis_sum,
                         float* invis_sum, int B, int S, int J, void* stream);
 /* utils/pose_utils.py:75-107 (compute_similarity_transform_with_vis_mask) + :119-126 as test_egohmr.py:427-437 runs it with --eval_with_vis_mask_pa:
