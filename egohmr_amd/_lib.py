@@ -242,7 +242,8 @@ class RenderDesc(C.Structure):
                 [(n, C.c_int) for n in ("B", "V", "F", "Fr", "H", "W", "smooth", "two_sided", "cull_backface")] +
                 [("z_near", C.c_float), ("base_color", C.c_float * 3), ("light_dir", C.c_float * 3), ("ambient", C.c_float), ("diffuse", C.c_float),
                  ("bg_color", C.c_uint8 * 4), ("bin_capacity", C.c_int)] +
-                [(n, C.c_void_p) for n in ("needed_capacity", "color", "depth", "face_index", "workspace")] + [("workspace_bytes", C.c_int64)])
+                [(n, C.c_void_p) for n in ("needed_capacity", "color", "depth", "face_index", "workspace")] + [("workspace_bytes", C.c_int64),
+                                                                                                              ("clip_near", C.c_int)])
 
 
 class JpegHeader(C.Structure):

@@ -3,8 +3,10 @@
 What it stands in for: ``utils/renderer.py:15-47`` (``render_on_img``, ``render_in_scene``) as ``test_egohmr.py:153-166, :555-619`` calls them with
 ``--render True``, where pyrender, EGL and trimesh draw the SMPL mesh.  Here ``csrc/render.hip`` (``ehm_render``) rasterises it: the rule is
 written out in ``include/egohmr_hip.h``, restated in float64 by ``tests/render_ref.py``, and its pixels are that rule's, not pyrender's - a Lambert
-term under one directional light, no PBR shader, no gamma, no anti-aliasing, and no near-plane clipping (a face with a vertex at ``z <= z_near``
-is dropped whole, which shows in ``render_in_scene`` when the scene mesh reaches behind the camera).
+term under one directional light, no PBR shader, no gamma, no anti-aliasing.  By default there is no near-plane clipping either: a face with a vertex
+at ``z <= z_near`` is dropped whole, which shows in ``render_in_scene`` as holes where the scene mesh reaches behind the camera.  ``clip_near=True``
+(``MeshRenderer``, and through ``**kw`` ``scene_renderer`` and ``render_in_scene``) draws such a face where it lies in front of the plane, by the
+header's homogeneous rule on the face's own vertices; faces wholly in front keep their bits.
 
 The camera frame is the package's: x right, y down, z forward - what ``Stage2Driver.step`` returns in ``decoded['vertices_full']`` and what the
 reference's ``camera_pose = diag(1, -1, -1, 1)`` converts to OpenGL's.  The defaults are the reference's scene: ambient light 0.3, a directional light
@@ -52,10 +54,11 @@ def _per_item(x, B, dev, what):
 class MeshRenderer:
     """One mesh topology (``faces`` int [F,3], shared by every item of a call) with its material and light.  ``faces`` is validated on the host, once
     (``0 <= index < V``), and the vertex -> face lists of the smooth normals are built there.  ``vertex_colors`` float [V,3] in [0,1] replaces
-    ``base_color``; both are RGB.  ``light_dir`` points from the surface towards the light."""
+    ``base_color``; both are RGB.  ``light_dir`` points from the surface towards the light.  ``clip_near``: a face that straddles ``z = z_near`` is
+    drawn where it lies in front of the plane, not dropped (off by default; a mesh without such a face renders to the same bits either way)."""
 
     def __init__(self, faces, device, vertex_colors=None, base_color=BASE_COLOR, ambient=AMBIENT, light_dir=(0.0, 0.0, -1.0), diffuse=DIFFUSE,
-                 smooth=True, two_sided=False, cull_backface=False, z_near=Z_NEAR, num_vertices=None, bin_capacity=None):
+                 smooth=True, two_sided=False, cull_backface=False, z_near=Z_NEAR, num_vertices=None, bin_capacity=None, clip_near=False):
         f = faces.detach().cpu().numpy() if isinstance(faces, torch.Tensor) else np.asarray(faces)
         if f.ndim != 2 or f.shape[1] != 3 or f.shape[0] == 0 or not np.issubdtype(f.dtype, np.integer):
             raise ValueError(f"faces must be an integer array [F,3] with F > 0, not {f.dtype} {f.shape}")
@@ -84,6 +87,7 @@ class MeshRenderer:
         self.light_dir = tuple(float(c) for c in l / np.linalg.norm(l))
         self.ambient, self.diffuse, self.z_near = float(ambient), float(diffuse), float(z_near)
         self.smooth, self.two_sided, self.cull_backface = bool(smooth), bool(two_sided), bool(cull_backface)
+        self.clip_near = bool(clip_near)
         self.bin_capacity = int(bin_capacity) if bin_capacity is not None else 4 * self.F + 64
         self.reruns = 0                                 # calls whose lists did not fit the capacity and ran twice
 
@@ -96,7 +100,8 @@ class MeshRenderer:
                             smooth=int(self.smooth), two_sided=int(self.two_sided), cull_backface=int(self.cull_backface), z_near=self.z_near,
                             base_color=(C.c_float * 3)(*base), light_dir=(C.c_float * 3)(*self.light_dir), ambient=self.ambient, diffuse=self.diffuse,
                             bg_color=(C.c_uint8 * 4)(*[int(c) for c in bg_color], 0), bin_capacity=int(capacity), needed_capacity=P(needed),
-                            color=P(outs.get("color")), depth=P(outs.get("depth")), face_index=P(outs.get("face_index")))
+                            color=P(outs.get("color")), depth=P(outs.get("depth")), face_index=P(outs.get("face_index")),
+                            clip_near=int(self.clip_near))
         return d
 
     @torch.no_grad()

@@ -992,8 +992,8 @@ int ehm_jpeg_entropy_encode(const ehm_jpeg_entropy_encode_desc* d, void* stream)
  *   e0 = (u1-u0)(s.v-v0) - (v1-v0)(s.u-u0)    e1 = (u2-u1)(s.v-v1) - (v2-v1)(s.u-u1)    e2 = (u0-u2)(s.v-v2) - (v0-v2)(s.u-u2)
  *   area = (u1-u0)(v2-v0) - (v1-v0)(u2-u0)
  * The sample is covered when e0, e1, e2 all have the sign of area or are zero (edges inclusive, no top-left rule) and e0 + e1 + e2 != 0.
- * Dropped faces: area == 0; a vertex index outside [0, V); a non-finite vertex or projection; a vertex at z <= z_near (there is no near-plane
- * clipping: a mesh that reaches behind the near plane loses those faces whole); cull_backface != 0 and area > 0 (v points down, so a face
+ * Dropped faces: area == 0; a vertex index outside [0, V); a non-finite vertex or projection; a vertex at z <= z_near (without clip_near, below,
+ * a mesh that reaches behind the near plane loses those faces whole); cull_backface != 0 and area > 0 (v points down, so a face
  * that is counter-clockwise for an OpenGL viewer, i.e. front-facing, has area < 0).
  * Depth.  Perspective-correct: b = (e1, e2, e0) / (e0 + e1 + e2) are the weights of vertices 0, 1, 2; 1/z = b0/z0 + b1/z1 + b2/z2, evaluated as
  * z = (e0 + e1 + e2) / (e1/z0 + e2/z1 + e0/z2) with 1/z_k rounded to float32 once per face.  A pixel's
@@ -1015,7 +1015,26 @@ int ehm_jpeg_entropy_encode(const ehm_jpeg_entropy_encode_desc* d, void* stream)
  * max(needed_capacity).  ehm_render_workspace_bytes gives the workspace for a descriptor (its outputs' and workspace fields' VALUES are not
  * used, but at least one output must be requested).  No allocation, no host synchronisation, no float atomics: two calls give the same bits.
  * 16-byte stores of the colour tile need W % 16 == 0 and 16-byte aligned color / frames; any other case is written byte by byte.
- * B <= 65535, H, W <= 32768, V, F <= 2^24. */
+ * B <= 65535, H, W <= 32768, V, F <= 2^24.
+ *
+ * Near-plane clipping (clip_near != 0; 0 is the rule above, bit for bit).  No geometry is cut: a face that straddles z = z_near is rasterised by a
+ * homogeneous rule on its own three vertices, so its face index, normals and colours are the parent face's.
+ * Which faces.  A face is CROSSING when its three vertex indices are valid, its three vertices are finite, at least one has z > z_near and at
+ * least one has z <= z_near (a vertex exactly on the plane counts as behind).  A face wholly in front takes the rule above unchanged, with the same
+ * bits; a face wholly behind, or with a non-finite vertex, is dropped as above.
+ * The rule of a crossing face, in coordinates relative to the principal point (no product of absolute pixel coordinates appears):
+ *   g_k = (fx x_k, fy y_k, z_k)        c_k = g_{k+1} x g_{k+2} (indices mod 3), a x b = (a_y b_z - a_z b_y, a_z b_x - a_x b_z, a_x b_y - a_y b_x)
+ *   D = (g_0x c_0x + g_0y c_0y) + g_0z c_0z                                    (= g_0 . (g_1 x g_2) = z_0 z_1 z_2 area)
+ *   E_k = (c_kx (s.u - cx) + c_ky (s.v - cy)) + c_kz        S = (E_0 + E_1) + E_2
+ * g_k, c_k and D are rounded once per face, not per pixel.  The face is dropped when D is 0 or not finite, or when cull_backface != 0 and D > 0
+ * (the orientation test above).  The sample is covered when E_0, E_1, E_2 each have the sign of D or are zero, S != 0 and z = D / S > z_near:
+ * the last condition is the clip.  Depth is that z.  The weights of vertices 0, 1, 2 are beta_k = E_k / S - the perspective-correct ones, what the
+ * rule above calls (b_k / z_k) z - so the smooth normal is sum_k beta_k n_k (the flat one is unchanged) and the interpolated colour sum_k beta_k c_k.
+ * The winner of a pixel is still the lexicographic minimum of (z, face index), over both kinds of face.
+ * Binning box of a crossing face: the projections of its front vertices and of the two points where its edges meet the plane - on the edge a -> b
+ * with exactly one end in front, t = (z_near - z_a) / (z_b - z_a), p = a + t (b - a), projected with z = z_near - padded and clamped like any
+ * other box; the whole image when one of those coordinates is not finite.  A crossing face counts in needed_capacity like any other, its record
+ * fits the same 64 bytes, and the workspace does not depend on clip_near.  clip_near must be 0 or 1. */
 typedef struct ehm_render_desc {
   const float* vertices;        /* [B, V, 3] */
   const int32_t* faces;         /* [F, 3] */
@@ -1038,6 +1057,7 @@ typedef struct ehm_render_desc {
   int32_t* face_index;          /* [B, H, W] or NULL */
   void* workspace;
   int64_t workspace_bytes;
+  int clip_near;                /* 0: a face with a vertex at z <= z_near is dropped whole; 1: it is drawn where z > z_near */
 } ehm_render_desc;
 int ehm_render_workspace_bytes(const ehm_render_desc* d, int64_t* bytes);
 int ehm_render(const ehm_render_desc* d, void* stream);
