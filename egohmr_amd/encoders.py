@@ -10,13 +10,15 @@ parameter names follow the reference so its checkpoints load (``backbone.*`` mod
 """
 from __future__ import annotations
 
+import ctypes as C
+from typing import NamedTuple
+
 import numpy as np
 import torch
 import torch.nn as nn
-import torch.nn.functional as F
 
 from . import _lib, trunk_grad
-from .split_gemm import weight_scale
+from .split_gemm import pack_weight
 
 
 # measurement hook (tools/exp_encoder_precision.py): called with every X2 activation buffer an encoder kernel has just written, (buffer, channels).
@@ -147,230 +149,264 @@ class ResNet50Features(nn.Module):
                 _lib.api().ehm_conv_x2_workspace_status(ws, None, _lib.stream_ptr())
 
     # ------------------------------------------------------------------ inference form: BatchNorm folded into the convolutions
-    @torch.no_grad()
     def folded(self, x2_activations: bool = True, fuse_shortcut: bool = True, train: bool = False):
-        """Eval-mode ResNet-50 on the matrix cores with every BatchNorm2d folded into its convolution (trunk_grad.fold: w' = w * g/sqrt(v+eps),
-        b' = beta - mean * g/sqrt(v+eps); exact up to float re-association).  x2_activations=True (the product path): the activations
-        stay in the X2 split format from the stem to the average pool (ehm_conv_x2); False: float32 NHWC activations between the
-        convolutions (ehm_conv_nhwc_split - the kernel the non-local GCN block also uses; kept as a second implementation the tests
-        compare).  HIP tensors only: there is no eager / library-convolution route.
-        The X2 route is ONE walk over trunk_grad.units (run_x2); where a unit's (w', b', stride, padding) come from is its operand provider.  Eval
-        (folded_units): folded here, once, and their packed form cached by unit index.  train=True (ResNet50Features.train_batchnorm; batch_units):
-        nothing is folded here; run(x, rec=None) folds each BatchNorm2d on the statistics of the batch it is given, updates the running ones, and packs
-        per call."""
-        import ctypes as C
+        """Eval-mode ResNet-50 on the matrix cores with every BatchNorm2d folded into its convolution: a FoldedTrunk (below) for the weights as they are."""
+        return FoldedTrunk(self, x2_activations, fuse_shortcut, train)
 
+
+class ConvPack(NamedTuple):
+    """A conv's packed launch operand (pack_conv).  Ci2 / stride2: the input channels and the stride of the projection shortcut where the pack holds a
+    bottleneck's last conv AND its projection as one matrix; zero otherwise."""
+    buf: torch.Tensor               # X2 [Co padded to 128, KH*KW*Ci (+ Ci2)], tap-major, times `scale`
+    scale: float
+    bias: torch.Tensor              # float32 [Co]
+    Co: int
+    Ci: int
+    KH: int
+    KW: int
+    stride: int
+    pad: int
+    Ci2: int = 0
+    stride2: int = 0
+
+    def out_hw(self, H, W):
+        return (H + 2 * self.pad - self.KH) // self.stride + 1, (W + 2 * self.pad - self.KW) // self.stride + 1
+
+
+def pack_conv(p, ds=None):
+    """A unit's operands (w' [Co,Ci,KH,KW], b', stride, padding) -> ConvPack: the weight tap-major [Co, KH*KW*Ci] through split_gemm.pack_weight.
+    ds: the operands of the block's projection shortcut - then p is the bottleneck's last conv and both (1 x 1) go into ONE matrix [Co, Ci + Ci_in]
+    with a common scale and the summed bias."""
+    w, b, stride, pad = p
+    Co, Ci, KH, KW = w.shape
+    w2 = w.permute(0, 2, 3, 1).reshape(Co, KH * KW * Ci)
+    if ds is None:
+        packed = pack_weight(w2)
+        return ConvPack(packed.buf, packed.scale, b.contiguous(), Co, Ci, KH, KW, stride[0], pad[0])
+    wd = ds[0]
+    assert (KH, KW) == (1, 1) and wd.shape[2:] == (1, 1) and wd.shape[0] == Co and Co % 128 == 0
+    packed = pack_weight(torch.cat([w2, wd.reshape(Co, -1)], dim=1))
+    return ConvPack(packed.buf, packed.scale, (b.double() + ds[1].double()).float().contiguous(), Co, Ci, 1, 1, stride[0], pad[0], wd.shape[1], ds[2][0])
+
+
+def x2_buffer(pixels, ch, dev, clear_last=False):
+    """X2 activation matrix for ehm_conv_x2: pixels rounded up to the row tile + one all-zero row (out-of-image taps read it; ehm_conv_x2 clears it
+    in its output, the stem's buffer is cleared here)"""
+    rows = int(_lib.api().ehm_conv_x2_rows(pixels))
+    buf = torch.empty(rows, ch, device=dev)                                         # X2 rows have the byte size of float rows
+    if clear_last:
+        buf[rows - 1].zero_()
+    return buf
+
+
+def _operands(conv, bn, stats=None):
+    """a unit's launch operands: trunk_grad.fold's (w', b') in float32, the conv's stride and padding"""
+    w, b = trunk_grad.fold(conv, bn, stats)
+    return w.float(), b.float(), conv.stride, conv.padding
+
+
+class _FoldedUnits:
+    """The eval provider of FoldedTrunk's walk: the operands folded once by the trunk, their packed form kept under the unit's index."""
+
+    def __init__(self, trunk, x, rec):
+        self.trunk = trunk
+
+    def stem(self, x):
+        return self.trunk.stem_wt, self.trunk.stem_b
+
+    def unit(self, i, x, shp):
+        return self.trunk.ops[i], i
+
+    def finish(self):
+        pass
+
+
+class _BatchUnits:
+    """The train provider of FoldedTrunk's walk; nothing is kept between calls.  Per (conv, BatchNorm2d) unit: the RAW conv output z on the same launch
+    (unfolded weight through the same pack, zero bias, no ReLU, no residual; a projection block's conv3 and downsample apart - each BatchNorm has its
+    own statistics), its mean / biased variance / invstd and the running-statistics update (ehm_bn2d_train_stats), then the operands folded on the
+    float32 batch statistics: the output has the bits of an eval-mode call whose running statistics are that batch's.
+    rec: a trunk_grad.TrainRecord that receives what the backward needs (bn: per unit of trunk_grad.units (z or None, z's shape, mean, var, invstd),
+    None for an identity block's absent downsample; the stem's operands), or None."""
+
+    def __init__(self, trunk, x, rec):
+        self.trunk, self.rec, self.sync, self.bumped = trunk, rec, trunk.module.stat_sync, []
+        self.zero = torch.zeros(2048, device=x.device)
+        sync = self.sync
+        if sync is not None and sync.counts[sync.rank] != x.shape[0]:
+            raise ValueError(f"ResNet50Features.stat_sync counts {sync.counts[sync.rank]} items for this rank, the input has {x.shape[0]}")
+        if rec is not None:
+            rec.bn = [None] * len(trunk.units)
+            rec.sync = sync
+
+    def note(self, i, *e):
+        self.bumped.append(self.trunk.units[i][1])
+        if self.rec is not None:
+            self.rec.bn[i] = e
+
+    def stem(self, x):
+        N, _, H, W = x.shape
+        conv, bn = self.trunk.units[0]
+        raw_wt, _ = trunk_grad.stem_operands(conv.weight.detach().float(), self.zero[:64])
+        z = trunk_grad.stem_preact(x, raw_wt, self.zero[:64])
+        mean, var, invstd = trunk_grad.bn_stats(z, N * (H // 2) * (W // 2), 64, bn, x2=False, sync=self.sync)
+        del z                                                                       # (recomputed by the backward, like the eval route's)
+        self.note(0, None, (N, H // 2, W // 2), mean, var, invstd)
+        wt, b = trunk_grad.stem_operands(*_operands(conv, bn, (mean, var))[:2])
+        if self.rec is not None:
+            self.rec.stem_wt, self.rec.stem_b = wt, b
+        return wt, b
+
+    def unit(self, i, x, shp):
+        conv, bn = self.trunk.units[i]
+        Co, rec = conv.out_channels, self.rec
+        z, zs = self.trunk.conv_x2(x, shp, (conv.weight.detach().float(), self.zero[:Co], conv.stride, conv.padding), None, relu=False)
+        mean, var, invstd = trunk_grad.bn_stats(z, zs[0] * zs[1] * zs[2], Co, bn, sync=self.sync)
+        self.note(i, z if rec is not None and rec.keep_z else None, zs, mean, var, invstd)
+        return _operands(conv, bn, (mean, var)), None
+
+    def finish(self):
+        """the kernels wrote the buffers through their pointers: tell torch (current() refolds on the next eval call)"""
+        for bn in self.bumped:
+            for t in (bn.running_mean, bn.running_var, bn.num_batches_tracked):
+                torch.autograd.graph.increment_version(t)
+
+
+class FoldedTrunk:
+    """What ResNet50Features.folded() returns: the trunk on HIP tensors (there is no eager / library-convolution route), every BatchNorm2d folded into
+    its convolution (trunk_grad.fold: w' = w * g/sqrt(v+eps), b' = beta - mean * g/sqrt(v+eps); exact up to float re-association).
+    x2_activations=True (the product path): the activations stay in the X2 split format from the stem to the average pool (ehm_conv_x2), ONE walk over
+    trunk_grad.units (_walk_x2) whose operand provider says where a unit's (w', b', stride, padding) come from: _FoldedUnits (eval: folded here, once,
+    packed on first use) or _BatchUnits (train=True, ResNet50Features.train_batchnorm: folded per call on the batch's statistics, nothing kept).
+    x2_activations=False: float32 NHWC activations between the convolutions (ehm_conv_nhwc_split - the kernel the non-local GCN block also uses; kept
+    as a second implementation the tests compare)."""
+
+    def __init__(self, module, x2_activations=True, fuse_shortcut=True, train=False):
+        self.module, self.x2_activations, self.fuse_shortcut, self.train = module, x2_activations, fuse_shortcut, train
+        self.units = trunk_grad.units(module)
+        with torch.no_grad():
+            self.ops = [] if train else [None if u is None else _operands(*u) for u in self.units]
+            # the folded parameters as trunk_grad reads them: (w', b', stride, padding) of the stem; of conv1, conv2, conv3, downsample (or None) per block
+            self.stem, self.blocks = (self.ops[0], [tuple(self.ops[i:i + 4]) for i in range(1, len(self.ops), 4)]) if self.ops else (None, [])
+            self.stem_wt, self.stem_b = trunk_grad.stem_operands(*self.stem[:2]) if self.ops else (None, None)
+        self.packs = {}                                    # the eval operands' packed form: unit index -> ConvPack, ("dual", conv3's index) -> conv3 + projection
+        self.dgrad = {}                                    # unit index -> the data gradient's pack (trunk_grad's eval-mode backward fills it)
+        self.sk_ws = {}                                    # device -> scratch of the stream-K convs (one conv at a time on a stream), zeroed ONCE
+
+    def __call__(self, x, saved=None, *, rec=None):
+        """x [N,3,H,W] -> [N,2048].  saved: a list that receives (X2 buffer, (N, H, W)) of the stem's and of every conv's output in launch order
+        instead of letting them go.  rec (train route): a trunk_grad.TrainRecord; its `acts` is that list."""
+        if not (saved is None or isinstance(saved, list)) or (rec is not None and not self.train):
+            raise TypeError("FoldedTrunk(x, saved, rec=): `saved` is a list, and a trunk_grad.TrainRecord goes in as `rec` on the train route")
+        if not x.is_cuda:
+            raise _lib.EgoHMRHipError("the ResNet-50 backbone needs its input on a HIP device; egohmr_amd has no CPU path")
+        x = _lib.f32(x)
+        if x.shape[1] != 3 or x.shape[2] % 32 or x.shape[3] % 32:
+            raise _lib.EgoHMRHipError(f"the fused stem needs [N,3,H,W] images with H, W multiples of 32 (the reference feeds 224 x 224 crops); got {tuple(x.shape)}")
+        with _lib.on_device(x.device):                                              # the library launches on the CURRENT device's stream
+            if self.train:
+                with torch.no_grad():
+                    return self._walk_x2(x, saved, rec)
+            return self._walk_x2(x, saved, rec) if self.x2_activations else self._walk_nhwc(x)
+
+    def _packed(self, key, p, ds=None):
+        """pack_conv(p, ds), kept under `key` (with ds: ("dual", key)); key None (the train route's per-call operands): not kept"""
+        if key is None:
+            return pack_conv(p, ds)
+        key = key if ds is None else ("dual", key)
+        if key not in self.packs:
+            self.packs[key] = pack_conv(p, ds)
+        return self.packs[key]
+
+    def stem_launch(self, x, wt, b, x2=False):
+        """conv1 + bn1 + relu + maxpool in one pass, NCHW in -> NHWC out (csrc/stem.hip); x2: output in the X2 split format"""
+        A = _lib.api()
+        N, _, H, W = x.shape
+        if wt.device != x.device:
+            raise _lib.EgoHMRHipError("ResNet50Features.folded(): weights and input live on different devices")
+        scratch = torch.empty(A.ehm_resnet_stem_scratch_bytes(N, H, W) // 4, device=x.device)
+        y = x2_buffer(N * (H // 4) * (W // 4), 64, x.device, clear_last=True) if x2 else torch.empty(N, H // 4, W // 4, 64, device=x.device)
+        A.ehm_resnet_stem(x, wt, b, scratch, y, N, H, W, 1 if x2 else 0, _lib.stream_ptr())
+        if x2 and _x2_debug_hook is not None:
+            _x2_debug_hook(y, 64)
+        return y
+
+    def conv_nhwc(self, x, i, res=None, relu=True):
+        """unit i on float32 NHWC activations (ehm_conv_nhwc_split)"""
+        k, P = self._packed(i, self.ops[i]), _lib.ptr
+        N, H, W, _ = x.shape
+        y = torch.empty(N, *k.out_hw(H, W), k.Co, device=x.device)
+        d = _lib.ConvDesc(P(x), P(k.buf), P(k.bias), P(res), P(y), N, H, W, k.Ci, k.Co, k.KH, k.KW, k.stride, k.pad, 1 if relu else 0, k.scale)
+        _lib.api().ehm_conv_nhwc_split(C.byref(d), _lib.stream_ptr())
+        return y
+
+    def conv_x2(self, x, shape, p, key, res=None, relu=True, shortcut=None):
+        """one bottleneck conv on X2 activations (csrc/conv.hip conv_x2_tile_kernel); shape = (N, H, W) of x; p: the unit's operands, key: what
+        their packed form is cached under (_packed).
+        shortcut = (block input, its shape, folded downsample): the projection shortcut accumulates inside this conv (second K segment)."""
         A, P = _lib.api(), _lib.ptr
-        U = trunk_grad.units(self)
+        N, H, W = shape
+        k = self._packed(key, p, None if shortcut is None else shortcut[2])
+        Ho, Wo = k.out_hw(H, W)
+        y = x2_buffer(N * Ho * Wo, k.Co, x.device)
+        d = _lib.ConvX2Desc(P(x), x.shape[0], P(k.buf), P(k.bias), P(res), P(y), N, H, W, k.Ci, k.Co, k.KH, k.KW, k.stride, k.pad, 1 if relu else 0,
+                            k.scale, None, 0)
+        d.hi_only = int(bool(self.module.hi_only))                                  # the plain-f16 tier (EgoHMR.encoder_precision = 'f16'): NOT parity grade
+        if shortcut is not None:
+            x_in, (_, H2, W2) = shortcut[0], shortcut[1]
+            d.x2, d.x2_rows, d.H2, d.W2, d.Ci2, d.stride2 = P(x_in), x_in.shape[0], H2, W2, k.Ci2, k.stride2
+        need = int(A.ehm_conv_x2_workspace_bytes(C.byref(d)))                       # stream-K scratch (layers 3 / 4: tile counts that straddle the block slots)
+        if need:
+            ws = self.sk_ws.get(str(x.device))
+            if ws is None or ws.numel() < need:
+                ws = self.sk_ws[str(x.device)] = torch.zeros(need, dtype=torch.uint8, device=x.device)
+            d.workspace, d.workspace_bytes, d.workspace_clean = P(ws), ws.numel(), 1
+        A.ehm_conv_x2(C.byref(d), _lib.stream_ptr())
+        if _x2_debug_hook is not None:
+            _x2_debug_hook(y, k.Co)
+        return y, (N, Ho, Wo)
 
-        def operands(conv, bn, stats=None):
-            """a unit's launch operands: trunk_grad.fold's (w', b') in float32, the conv's stride and padding"""
-            w, b = trunk_grad.fold(conv, bn, stats)
-            return w.float(), b.float(), conv.stride, conv.padding
-
-        ops = [] if train else [None if u is None else operands(*u) for u in U]
-        stem, blocks = (ops[0], [tuple(ops[i:i + 4]) for i in range(1, len(U), 4)]) if ops else (None, [])
-        packs = {}                                         # the eval operands' packed form: unit index -> pack(), ("dual", conv3's index) -> pack_dual()
-        sk_ws = {}                                         # device -> scratch of the stream-K convs (one conv at a time on a stream)
-
-        def cached(key, build, *args):
-            """build(*args), kept under `key`; key None (the train route's per-call operands): not kept"""
-            if key is None:
-                return build(*args)
-            if key not in packs:
-                packs[key] = build(*args)
-            return packs[key]
-
-        def pack(p):
-            """weights [Co,Ci,KH,KW] -> tap-major [Co_pad, KH*KW*Ci] X2 split format, scaled by a power of two"""
-            w = p[0]
-            Co, Ci, KH, KW = w.shape
-            K = KH * KW * Ci
-            Co_pad = (Co + 127) // 128 * 128
-            w2 = torch.zeros(Co_pad, K, device=w.device)
-            w2[:Co] = w.permute(0, 2, 3, 1).reshape(Co, K)
-            scale = weight_scale(float(w2.abs().max()))
-            buf = torch.empty(Co_pad, K, device=w.device)              # X2 rows have the byte size of float rows
-            A.ehm_split_pack(w2, buf, Co_pad, K, K, scale, _lib.stream_ptr())
-            return buf, scale, p[1].contiguous(), (Co, Ci, KH, KW), p[2][0], p[3][0]
-
-        def conv_mc(x, i, res=None, relu=True):
-            buf, scale, bias, (Co, Ci, KH, KW), stride, pad = cached(i, pack, ops[i])
-            N, H, W, _ = x.shape
-            Ho, Wo = (H + 2 * pad - KH) // stride + 1, (W + 2 * pad - KW) // stride + 1
-            y = torch.empty(N, Ho, Wo, Co, device=x.device)
-            d = _lib.ConvDesc(P(x), P(buf), P(bias), P(res), P(y), N, H, W, Ci, Co, KH, KW, stride, pad, 1 if relu else 0, scale)
-            A.ehm_conv_nhwc_split(C.byref(d), _lib.stream_ptr())
-            return y
-
-        def stem_operands(w, b):
-            return w.reshape(64, 147).t().contiguous(), b.contiguous()             # [147][64], k = (ci*7 + kh)*7 + kw
-
-        stem_wt, stem_b = (None, None) if train else stem_operands(*stem[:2])
-
-        def x2_buffer(pixels, ch, dev, clear_last=False):
-            """X2 activation matrix for ehm_conv_x2: pixels rounded up to the row tile + one all-zero row (out-of-image taps read it;
-            ehm_conv_x2 clears it in its output, the stem's buffer is cleared here)"""
-            rows = int(A.ehm_conv_x2_rows(pixels))
-            buf = torch.empty(rows, ch, device=dev)                                 # X2 rows have the byte size of float rows
-            if clear_last:
-                buf[rows - 1].zero_()
-            return buf
-
-        def stem_mc(x, wt, b, x2=False):
-            """conv1 + bn1 + relu + maxpool in one pass, NCHW in -> NHWC out (csrc/stem.hip); x2: output in the X2 split format"""
-            N, _, H, W = x.shape
-            if wt.device != x.device:
-                raise _lib.EgoHMRHipError("ResNet50Features.folded(): weights and input live on different devices")
-            scratch = torch.empty(A.ehm_resnet_stem_scratch_bytes(N, H, W) // 4, device=x.device)
-            y = x2_buffer(N * (H // 4) * (W // 4), 64, x.device, clear_last=True) if x2 else torch.empty(N, H // 4, W // 4, 64, device=x.device)
-            A.ehm_resnet_stem(x, wt, b, scratch, y, N, H, W, 1 if x2 else 0, _lib.stream_ptr())
-            if x2 and _x2_debug_hook is not None:
-                _x2_debug_hook(y, 64)
-            return y
-
-        def pack_dual(p, ds):
-            """a bottleneck's last conv and its projection shortcut as ONE weight matrix [Co_pad, Ci + Ci_in] (both 1 x 1), common scale, summed bias"""
-            w, wd = p[0], ds[0]
-            Co, Ci = w.shape[:2]
-            assert w.shape[2:] == (1, 1) and wd.shape[2:] == (1, 1) and wd.shape[0] == Co and Co % 128 == 0
-            K = Ci + wd.shape[1]
-            w2 = torch.cat([w.reshape(Co, Ci), wd.reshape(Co, -1)], dim=1).contiguous()
-            scale = weight_scale(float(w2.abs().max()))
-            buf = torch.empty(Co, K, device=w.device)
-            A.ehm_split_pack(w2, buf, Co, K, K, scale, _lib.stream_ptr())
-            return buf, scale, (p[1].double() + ds[1].double()).float().contiguous(), (Co, Ci, 1, 1), p[2][0], p[3][0], wd.shape[1], ds[2][0]
-
-        def conv_x2(x, shape, p, key, res=None, relu=True, shortcut=None):
-            """one bottleneck conv on X2 activations (csrc/conv.hip conv_x2_tile_kernel); shape = (N, H, W) of x; p: the unit's operands, key: what
-            their packed form is cached under (`cached`).
-            shortcut = (block input, its shape, folded downsample): the projection shortcut accumulates inside this conv (second K segment)."""
-            N, H, W = shape
-            if shortcut is not None:
-                buf, scale, bias, (Co, Ci, KH, KW), stride, pad, Ci2, stride2 = cached(None if key is None else ("dual", key), pack_dual, p, shortcut[2])
+    def _walk_x2(self, x, saved, rec):
+        """the whole trunk with the activations in the X2 split format between the layers (taps gathered by the LDS DMA)"""
+        U, conv, m = self.units, self.conv_x2, self.module
+        N = x.shape[0]
+        shp = (N, x.shape[2] // 4, x.shape[3] // 4)
+        acts = saved if rec is None else rec.acts
+        keep = (lambda *e: None) if acts is None else (lambda *e: acts.append(e))
+        units = (_BatchUnits if self.train else _FoldedUnits)(self, x, rec)
+        wt, b = units.stem(x)
+        x = self.stem_launch(x, wt, b, x2=True)
+        keep(x, shp)
+        for i1 in range(1, len(U), 4):
+            i2, i3, id_ = i1 + 1, i1 + 2, i1 + 3
+            y, s1 = conv(x, shp, *units.unit(i1, x, shp))
+            keep(y, s1)
+            y, s2 = conv(y, s1, *units.unit(i2, y, s1))
+            keep(y, s2)
+            p3, k3 = units.unit(i3, y, s2)
+            if U[id_] is None:
+                x, shp = conv(y, s2, p3, k3, res=x)
             else:
-                buf, scale, bias, (Co, Ci, KH, KW), stride, pad = cached(key, pack, p)
-            Ho, Wo = (H + 2 * pad - KH) // stride + 1, (W + 2 * pad - KW) // stride + 1
-            y = x2_buffer(N * Ho * Wo, Co, x.device)
-            d = _lib.ConvX2Desc(P(x), x.shape[0], P(buf), P(bias), P(res), P(y), N, H, W, Ci, Co, KH, KW, stride, pad, 1 if relu else 0, scale, None, 0)
-            d.hi_only = int(bool(self.hi_only))                                  # the plain-f16 tier (EgoHMR.encoder_precision = 'f16'): NOT parity grade
-            if shortcut is not None:
-                x_in, (_, H2, W2) = shortcut[0], shortcut[1]
-                d.x2, d.x2_rows, d.H2, d.W2, d.Ci2, d.stride2 = P(x_in), x_in.shape[0], H2, W2, Ci2, stride2
-            need = int(A.ehm_conv_x2_workspace_bytes(C.byref(d)))      # stream-K scratch (layers 3 / 4: tile counts that straddle the block slots)
-            if need:
-                ws = sk_ws.get(str(x.device))
-                if ws is None or ws.numel() < need:
-                    ws = sk_ws[str(x.device)] = torch.zeros(need, dtype=torch.uint8, device=x.device)   # zeroed ONCE: the convs leave their counters zeroed
-                d.workspace, d.workspace_bytes, d.workspace_clean = P(ws), ws.numel(), 1
-            A.ehm_conv_x2(C.byref(d), _lib.stream_ptr())
-            if _x2_debug_hook is not None:
-                _x2_debug_hook(y, Co)
-            return y, (N, Ho, Wo)
-
-        def folded_units(x, rec):
-            """the eval provider: the operands folded above, packed once per closure"""
-            return (stem_wt, stem_b), (lambda i, x, shp: (ops[i], i)), (lambda: None)
-
-        def batch_units(x, rec):
-            """the train provider.  Per (conv, BatchNorm2d) unit: the RAW conv output z on the same launch (unfolded weight through the same pack, zero
-            bias, no ReLU, no residual; a projection block's conv3 and downsample apart - each BatchNorm has its own statistics), its mean / biased
-            variance / invstd and the running-statistics update (ehm_bn2d_train_stats), then the operands folded on the float32 batch statistics: the
-            output has the bits of an eval-mode call whose running statistics are that batch's.
-            rec: a trunk_grad.TrainRecord that receives what the backward needs (bn: per unit of trunk_grad.units (z or None, z's shape, mean, var,
-            invstd), None for an identity block's absent downsample; the stem's operands)."""
-            N, _, H, W = x.shape
-            zero = torch.zeros(2048, device=x.device)
-            bumped = []
-            sync = self.stat_sync
-            if sync is not None and sync.counts[sync.rank] != N:
-                raise ValueError(f"ResNet50Features.stat_sync counts {sync.counts[sync.rank]} items for this rank, the input has {N}")
-            if rec is not None:
-                rec.bn = [None] * len(U)
-                rec.sync = sync
-
-            def note(i, *e):
-                bumped.append(U[i][1])
-                if rec is not None:
-                    rec.bn[i] = e
-
-            def unit(i, x, shp):
-                conv, bn = U[i]
-                Co = conv.out_channels
-                z, zs = conv_x2(x, shp, (conv.weight.detach().float(), zero[:Co], conv.stride, conv.padding), None, relu=False)
-                mean, var, invstd = trunk_grad.bn_stats(z, zs[0] * zs[1] * zs[2], Co, bn, sync=sync)
-                note(i, z if rec is not None and rec.keep_z else None, zs, mean, var, invstd)
-                return operands(conv, bn, (mean, var)), None
-
-            def finish():               # the kernels wrote the buffers through their pointers: tell torch (current() refolds on the next eval call)
-                for bn in bumped:
-                    for t in (bn.running_mean, bn.running_var, bn.num_batches_tracked):
-                        torch.autograd.graph.increment_version(t)
-
-            raw_wt, _ = stem_operands(self.conv1.weight.detach().float(), zero[:64])
-            z = trunk_grad.stem_preact(x, raw_wt, zero[:64])
-            mean, var, invstd = trunk_grad.bn_stats(z, N * (H // 2) * (W // 2), 64, self.bn1, x2=False, sync=sync)
-            del z                                                                   # (recomputed by the backward, like the eval route's)
-            note(0, None, (N, H // 2, W // 2), mean, var, invstd)
-            wt, b = stem_operands(*operands(self.conv1, self.bn1, (mean, var))[:2])
-            if rec is not None:
-                rec.stem_wt, rec.stem_b = wt, b
-            return (wt, b), unit, finish
-
-        def run_x2(x, saved=None, rec=None):
-            """the whole trunk with the activations in the X2 split format between the layers (taps gathered by the LDS DMA).
-            saved (train: rec.acts): a list that receives (X2 buffer, (N, H, W)) of the stem's and of every conv's output in launch order instead of
-            letting them go"""
-            N = x.shape[0]
-            shp = (N, x.shape[2] // 4, x.shape[3] // 4)
-            if rec is not None:
-                saved = rec.acts
-            keep = (lambda *e: None) if saved is None else (lambda *e: saved.append(e))
-            (wt, b), unit, finish = (batch_units if train else folded_units)(x, rec)
-            x = stem_mc(x, wt, b, x2=True)
-            keep(x, shp)
-            for i1 in range(1, len(U), 4):
-                i2, i3, id_ = i1 + 1, i1 + 2, i1 + 3
-                y, s1 = conv_x2(x, shp, *unit(i1, x, shp))
-                keep(y, s1)
-                y, s2 = conv_x2(y, s1, *unit(i2, y, s1))
-                keep(y, s2)
-                p3, k3 = unit(i3, y, s2)
-                if U[id_] is None:
-                    x, shp = conv_x2(y, s2, p3, k3, res=x)
+                pd, kd = units.unit(id_, x, shp)
+                if self.fuse_shortcut:
+                    x, shp = conv(y, s2, p3, k3, shortcut=(x, shp, pd))             # out = conv3(.) + downsample(x) in one launch: no shortcut tensor
                 else:
-                    pd, kd = unit(id_, x, shp)
-                    if fuse_shortcut:
-                        x, shp = conv_x2(y, s2, p3, k3, shortcut=(x, shp, pd))      # out = conv3(.) + downsample(x) in one launch: no shortcut tensor
-                    else:
-                        x, shp = conv_x2(y, s2, p3, k3, res=conv_x2(x, shp, pd, kd, relu=False)[0])
-                keep(x, shp)
-            out = torch.empty(N, x.shape[1], device=x.device)
-            A.ehm_x2_group_mean(x, out, N, shp[1] * shp[2], x.shape[1], int(bool(self.hi_only)), _lib.stream_ptr())
-            self._sk_status_async(sk_ws.get(str(x.device)))
-            finish()
-            return out
+                    x, shp = conv(y, s2, p3, k3, res=conv(x, shp, pd, kd, relu=False)[0])
+            keep(x, shp)
+        out = torch.empty(N, x.shape[1], device=x.device)
+        _lib.api().ehm_x2_group_mean(x, out, N, shp[1] * shp[2], x.shape[1], int(bool(m.hi_only)), _lib.stream_ptr())
+        m._sk_status_async(self.sk_ws.get(str(x.device)))
+        units.finish()
+        return out
 
-        def run(x, saved=None):
-            if not x.is_cuda:
-                raise _lib.EgoHMRHipError("the ResNet-50 backbone needs its input on a HIP device; egohmr_amd has no CPU path")
-            x = _lib.f32(x)
-            if x.shape[1] != 3 or x.shape[2] % 32 or x.shape[3] % 32:
-                raise _lib.EgoHMRHipError(f"the fused stem needs [N,3,H,W] images with H, W multiples of 32 (the reference feeds 224 x 224 crops); got {tuple(x.shape)}")
-            with _lib.on_device(x.device):                                          # the library launches on the CURRENT device's stream
-                if train:
-                    with torch.no_grad():
-                        return run_x2(x, rec=saved)
-                if x2_activations:
-                    return run_x2(x, saved)
-                x = stem_mc(x, stem_wt, stem_b)                                     # NHWC float32 from here on
-                for i1 in range(1, len(U), 4):
-                    y = conv_mc(conv_mc(x, i1), i1 + 1)
-                    x = conv_mc(y, i1 + 2, res=x if U[i1 + 3] is None else conv_mc(x, i1 + 3, relu=False))
-                return x.mean(dim=(1, 2))
-
-        run.stem, run.blocks, run.stem_wt, run.stem_b = stem, blocks, stem_wt, stem_b         # the folded parameters (trunk_grad reads them)
-        return run
+    def _walk_nhwc(self, x):
+        """the second implementation: float32 NHWC activations from the stem on"""
+        U, conv = self.units, self.conv_nhwc
+        x = self.stem_launch(x, self.stem_wt, self.stem_b)
+        for i1 in range(1, len(U), 4):
+            y = conv(conv(x, i1), i1 + 1)
+            x = conv(y, i1 + 2, res=x if U[i1 + 3] is None else conv(x, i1 + 3, relu=False))
+        return x.mean(dim=(1, 2))
 
 
 class _ResBlockFC(nn.Module):

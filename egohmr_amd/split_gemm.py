@@ -38,10 +38,13 @@ class Packed(NamedTuple):
 
 def pack_weight(w2, bias=None):
     """float32 [Co, K] on a HIP device -> Packed (ehm_split_pack, scaled by weight_scale).  The engine reads bias[0 .. cols): a bias [Co] with
-    Co % 8 != 0 is zero-padded to cols here (the padding columns then come out as the residual alone, or zero)."""
+    Co % 8 != 0 is zero-padded to cols here (the padding columns then come out as the residual alone, or zero).  A contiguous float32 matrix that has the
+    padded shape already (Co % 128 == 0, K % 32 == 0) is packed as it is: no zero-filled copy."""
     Co, K = w2.shape
-    wp = torch.zeros(round_up(Co, 128), round_up(K, 32), device=w2.device)
-    wp[:Co, :K] = w2
+    wp = w2
+    if Co % 128 or K % 32 or not w2.is_contiguous() or w2.dtype != torch.float32:
+        wp = torch.zeros(round_up(Co, 128), round_up(K, 32), device=w2.device)
+        wp[:Co, :K] = w2
     scale = weight_scale(float(wp.abs().max()))
     buf = torch.empty_like(wp)
     _lib.api().ehm_split_pack(wp, buf, wp.shape[0], wp.shape[1], wp.shape[1], scale, _lib.stream_ptr())

@@ -1,7 +1,7 @@
 """Backward of the ResNet-50 trunk in eval mode on libegohmr_hip (csrc/conv_bwd.hip + the split-f16 conv engine), and the ``torch.autograd.Function``
 that ResNet50Features.__call__ runs behind with ``grad_params`` set (encoders.py).
 
-The forward is ResNet50Features.folded()'s X2 route with every conv's output kept: a conv's saved output is its ReLU gate (sign only) and the next conv's
+The forward is the X2 route of encoders.FoldedTrunk with every conv's output kept: a conv's saved output is its ReLU gate (sign only) and the next conv's
 input.  Per conv with folded weight w', folded bias b', input x, output y = relu(conv(x, w') + b' (+ res)) and g = dL/dy:
 
     G = s g (.) [y > 0]                         ehm_conv_bwd_gate      (s: a power of two on the device that brings max|g| to about 2^10 - pow2_scale;
@@ -19,7 +19,7 @@ parameters again (unfold), so one changed between forward and backward (TensorKe
 One function walks the blocks from the top for both routes (`_walk`): it owns the pruning, the three data gradients per block, the shortcut riding in as
 conv1's `residual`, the tensor lifetimes and the powers of two.  What a route does per unit is its step: `_eval_step` is the list above; `_train_step`
 (ResNet50Features.train_batchnorm: BatchNorm2d on batch statistics, csrc/bn2d_train.hip) runs a BatchNorm backward per unit on the raw weight, no fold to undo.
-`fold` and `units` are also what ResNet50Features.folded() builds its forward from.
+`fold`, `units` and `stem_operands` are also what encoders.FoldedTrunk builds its forward from.
 """
 from __future__ import annotations
 
@@ -65,6 +65,11 @@ def units(m):
             out += [(blk.conv1, blk.bn1), (blk.conv2, blk.bn2), (blk.conv3, blk.bn3),
                     (blk.downsample[0], blk.downsample[1]) if blk.downsample is not None else None]
     return out
+
+
+def stem_operands(w, b):
+    """The stem kernels' operand layout: weight [64,3,7,7] -> [147][64], k = (ci*7 + kh)*7 + kw; the bias contiguous."""
+    return w.reshape(64, 147).t().contiguous(), b.contiguous()
 
 
 def _workspace(query, *dims, dtype=torch.float32, device=None):
@@ -217,11 +222,9 @@ def _walk(U, acts, gout, need, res, step):
 
 def _eval_step(U, fn, img, acts, need, res):
     """The eval-mode unit step of _walk: the gate scaled into the conv engine's range (dense for the weight gradient, gated again zero-dilated for a
-    stride-2 data gradient), (w'bar, b'bar) of the FOLDED weight into res[i], the data gradient on the folded weight's pack - kept on the folded()
-    closure `fn` (fn.dgrad), so rebuilt with it when a weight changes."""
+    stride-2 data gradient), (w'bar, b'bar) of the FOLDED weight into res[i], the data gradient on the folded weight's pack - kept on the
+    FoldedTrunk `fn` the forward ran (fn.dgrad), so rebuilt with it when a weight changes."""
     ops = [fn.stem] + [p for blk in fn.blocks for p in blk]
-    if getattr(fn, "dgrad", None) is None:
-        fn.dgrad = {}
 
     def scaled(t, cum):
         return None if t is None else t * (1.0 / cum)
@@ -263,7 +266,7 @@ def _eval_step(U, fn, img, acts, need, res):
 
 
 def trunk_backward(m, fn, img, acts, gout, need):
-    """VJP of the folded trunk.  fn: the folded() closure the forward ran; img [N,3,H,W] float32; acts: what its `saved` list received; gout [N,2048];
+    """VJP of the folded trunk.  fn: the FoldedTrunk the forward ran; img [N,3,H,W] float32; acts: what its `saved` list received; gout [N,2048];
     need: per unit of units(m) a pair (w' wanted, b' wanted) or None.  Returns per unit (w'bar [Co,Ci,KH,KW] float32 or None, b'bar or None): what is
     not asked for is neither computed nor written, and no data gradient runs below the lowest unit that wants something."""
     U = units(m)
@@ -273,7 +276,7 @@ def trunk_backward(m, fn, img, acts, gout, need):
 
 # ------------------------------------------------------------------------------------------------------------------ train-mode BatchNorm2d (csrc/bn2d_train.hip)
 # With ResNet50Features.train_batchnorm under .train() every BatchNorm2d normalises with the statistics of the batch.  Once (mu, var) are known that IS the
-# eval-mode fold with running_mean := mu, running_var := var, so the forward (folded(train=True)'s unit provider) is: raw conv z -> ehm_bn2d_train_stats -> the folded
+# eval-mode fold with running_mean := mu, running_var := var, so the forward (encoders._BatchUnits) is: raw conv z -> ehm_bn2d_train_stats -> the folded
 # launch.  The backward differs per unit: with G = g (.) [y > 0], R = N H W rows, xhat = (z - mu) invstd:
 #     betabar = sum_p G,  gammabar = sum_p G xhat                   ehm_bn2d_train_bwd_sums  (float64 partial sums, fixed order)
 #     zbar = s gamma invstd (G - betabar / R - xhat gammabar / R)   ehm_bn2d_train_bwd_zbar  (dense for the weight gradient; s: pow2_scale of the dense result,
@@ -382,7 +385,7 @@ def stem_preact(img, wt, b):
 def train_forward(m, img, keep_z=True):
     """The train-mode forward with its record kept: (out [N,2048], TrainRecord).  Updates m's running statistics."""
     rec = TrainRecord(keep_z)
-    return m.folded(train=True)(img, rec), rec
+    return m.folded(train=True)(img, rec=rec), rec
 
 
 # ehm_resnet_stem_wgrad's scratch in floats (include/egohmr_hip.h: "workspace: 256 * 148 * 64 floats"; it has no size query)
@@ -447,8 +450,8 @@ def _train_step(U, img, rec, need, res):
         del zf, G0
         conv, bn = U[0]
         _, zs, mean, _, invstd = rec.bn[0]
-        wt = conv.weight.detach().float().reshape(64, 147).t().contiguous()
-        z = stem_preact(img, wt, torch.zeros(64, device=dev))                       # the raw one: the BatchNorm's input
+        wt, zero = stem_operands(conv.weight.detach().float(), torch.zeros(64, device=dev))
+        z = stem_preact(img, wt, zero)                                              # the raw one: the BatchNorm's input
         gbeta, ggamma, pbeta, pgamma, R = sums(gz, z, zs, 64, mean, invstd, x2=False)
         inv = 1.0 / cum
         gw = None
