@@ -852,6 +852,9 @@ int ehm_scene_augment(const void* scene, int scene_is_f64, const double* params,
  *   a0 += z1 + z3, a1 += z2 + z4, a2 += z2 + z3, a3 += z1 + z4
  *   outputs 0..7 = (t10 + a3, t11 + a2, t12 + a1, t13 + a0, t13 - a0, t12 - a1, t11 - a2, t10 - a3) >> s
  * Columns first (s = 11, r = 1 << 10), then rows on their results (s = 18, r = 1 << 17); sample = clamp(result + 128, 0, 255).
+ * The rule is exact where every intermediate of both passes - each value named above and the eight sums before the shift - fits in int32,
+ * which holds for any block a DCT of 8-bit samples can produce (all 64 dequantised values at 1024 stay inside, all at 2048 leave it, and a
+ * baseline stream may carry up to 1023 x 255).  Beyond that domain the pixels are unspecified, but every write stays inside frames and the workspace.
  * Upsampling, on each chroma plane cropped to its real size ceil(H v / vmax) x ceil(W h / hmax); edges replicate the last real row or
  * column, the samples of the MCU padding are never read:
  *   h2v1: out[2i] = (3 s[i] + s[i-1] + 1) >> 2, out[2i+1] = (3 s[i] + s[i+1] + 2) >> 2
@@ -863,7 +866,8 @@ int ehm_scene_augment(const void* scene, int scene_is_f64, const double* params,
  * B, G, R.  A one-component frame replicates Y.
  *
  * Device stage.  One call decodes F frames of ONE geometry (H, W, components, hmax, vmax - the block grids follow from them); quant holds a
- * row of 64 per frame and component (natural order), so qualities may differ within a call.  Two launches, no atomics, every byte written
+ * row of 64 per frame and component (natural order), so qualities may differ within a call; rows 1 and 2 are independent: Cb is dequantised
+ * with row 1 and Cr with row 2, whether or not the file gave them one table.  Two launches, no atomics, every byte written
  * once by one thread: two calls give the same bits.  The workspace holds the uint8 component planes on the MCU grid (coef_count bytes per
  * frame).  F <= 65535; coef 16-byte aligned. */
 #define EHM_JPEG_MAX_COMPONENTS 3
@@ -935,8 +939,9 @@ int ehm_jpeg_decode(const ehm_jpeg_decode_desc* d, void* stream);
  * File.  SOI, APP0 JFIF 1.01 (units 0, density 1 x 1, no thumbnail), DQT table 0, DQT table 1, SOF0, DHT DC0, AC0, DC1, AC1, SOS, the
  * stream, EOI (FF D9, the caller's two bytes): the order PIL writes.
  *
- * ehm_jpeg_forward: one launch; every value written once by one thread.  quant is [F,3,64] (natural order, the decoder's convention: rows 1
- * and 2 are the chroma table twice), so a call may mix qualities; an entry of 0 is the caller's error (the device table is not inspected).
+ * ehm_jpeg_forward: one launch; every value written once by one thread.  quant is [F,3,64] (natural order, the decoder's convention), so a call may mix
+ * qualities; rows 1 and 2 are independent - Cb is quantised with row 1, Cr with row 2 - and a caller that writes a file with two tables
+ * passes the chroma table twice; an entry of 0 is the caller's error (the device table is not inspected).
  * Its output is directly what ehm_jpeg_decode reads.  coef 16-byte aligned.
  * ehm_jpeg_entropy_encode: coefficients -> the stuffed streams uint8 [F, capacity] (SOS's end to EOI's start), lengths int64 [F] and needed
  * int64 [F].  needed[f] is the exact stream size whatever the capacity; lengths[f] = needed[f], or -1 when needed[f] > capacity (that

@@ -1,7 +1,8 @@
 """A numpy restatement of the baseline-JPEG ENCODING rule of include/egohmr_hip.h (section "JPEG encoding"): libjpeg's default encoder -
 its fixed-point colour conversion, chroma downsampling with its padding order, the ISLOW integer forward DCT, its quantiser, the dummy
 blocks of the MCU padding, the fixed Annex K Huffman tables, byte stuffing and the marker segments in the order PIL writes them.  It is the
-reference of tests/test_jpeg_enc_cpu.py (where it is compared with PIL's bytes) and tests/test_gpu_jpeg_enc.py.  Slow and plain on purpose.
+reference of tests/test_jpeg_enc_cpu.py (where it is compared with PIL's bytes), tests/test_gpu_jpeg_enc.py and, with one table row per
+component and its planted mistakes (``wrong=``), of tests/test_gpu_jpeg_kernels.py.  Slow and plain on purpose.
 """
 from __future__ import annotations
 
@@ -60,14 +61,17 @@ def _extend(p, rows, cols):
     return np.concatenate([p, np.repeat(p[:, -1:], cols - p.shape[1], 1)], 1) if cols > p.shape[1] else p
 
 
-def component_planes(rgb, hmax, vmax):
+def component_planes(rgb, hmax, vmax, wrong=None):
     """-> [(samples int32 [rh * 8, rw * 8], rw, rh)] per component: the REAL block grid's samples (jcprepct.c / jcsample.c)."""
     H, W = rgb.shape[:2]
     out = []
+    if wrong == "odd_height_reads_padding" and vmax == 2 and H % 2:    # the row under the frame read as it is (black here), not as row H - 1
+        rgb = np.concatenate([rgb, np.zeros_like(rgb[:1])], 0)
     for c, full in enumerate(ycc(rgb)):
         h, v = (hmax, vmax) if c == 0 else (1, 1)
         fh, fv = hmax // h, vmax // v
         rw, rh = -(-W * h // (8 * hmax)), -(-H * v // (8 * vmax))
+        full = full[:-(-H // fv) * fv]
         p = _extend(full, -(-H // fv) * fv, rw * 8 * fh)           # columns to the block grid, rows only to a multiple of the factor
         if (fh, fv) == (2, 1):
             bias = np.arange(p.shape[1] // 2) & 1
@@ -117,29 +121,44 @@ def fdct_quant(samples, quant):
     return np.where(x < 0, -r, r)
 
 
-def coefficient_planes(rgb, quant, hmax, vmax):
-    """rgb uint8 [H, W, 3], quant [2, 64] -> three int16 planes [blocks_y, blocks_x, 64] over the MCU grid, dummy blocks included."""
+FORWARD_WRONG = ("cr_uses_cb_table", "quant_of_frame0", "bgr_as_rgb", "dummy_keeps_ac", "dummy_row_from_left", "odd_height_reads_padding")
+
+
+def coefficient_planes(rgb, quant, hmax, vmax, wrong=None, quant0=None):
+    """rgb uint8 [H, W, 3], quant [2, 64] (luma, both chroma planes) or [3, 64] (one row per component, ehm_jpeg_forward's) -> three int16
+    planes [blocks_y, blocks_x, 64] over the MCU grid, dummy blocks included.
+    wrong: one of FORWARD_WRONG, a planted mistake (quant_of_frame0 takes the rows from ``quant0``, frame 0's)."""
+    assert wrong is None or wrong in FORWARD_WRONG
+    quant = np.asarray(quant0 if wrong == "quant_of_frame0" else quant)
+    assert quant.shape in ((2, 64), (3, 64))
+    rows = [0, 1, 1] if len(quant) == 2 or wrong == "cr_uses_cb_table" else [0, 1, 2]
+    if wrong == "bgr_as_rgb":
+        rgb = rgb[..., ::-1]
     H, W = rgb.shape[:2]
     mx, my = -(-W // (8 * hmax)), -(-H // (8 * vmax))
     planes = []
-    for c, (samples, rw, rh) in enumerate(component_planes(rgb, hmax, vmax)):
+    for c, (samples, rw, rh) in enumerate(component_planes(rgb, hmax, vmax, wrong)):
         h, v = (hmax, vmax) if c == 0 else (1, 1)
-        real = fdct_quant(samples, quant[min(c, 1)])
+        real = fdct_quant(samples, quant[rows[c]])
         out = np.zeros((my * v, mx * h, 64), np.int32)
         out[:rh, :rw] = real
+        keep = 64 if wrong == "dummy_keeps_ac" else 1               # all AC of a dummy block are zero
         for by in range(rh):                                        # dummy columns of real rows: the DC of the block to the left
             for bx in range(rw, mx * h):
-                out[by, bx, 0] = out[by, bx - 1, 0]
+                out[by, bx, :keep] = out[by, bx - 1, :keep]
         for by in range(rh, my * v):                                # dummy rows: the DC of the MCU's last block of the row above
             for m in range(mx):
-                out[by, m * h:(m + 1) * h, 0] = out[by - 1, m * h + h - 1, 0]
+                out[by, m * h:(m + 1) * h, :keep] = out[by - 1, m * h + h - 1, :keep]
+            if wrong == "dummy_row_from_left":
+                for bx in range(1, mx * h):
+                    out[by, bx, 0] = out[by, bx - 1, 0]
         planes.append(out.astype(np.int16))
     return planes
 
 
-def coefficients(rgb, quant, hmax, vmax):
+def coefficients(rgb, quant, hmax, vmax, wrong=None, quant0=None):
     """The decoder's layout: the planes one after the other, int16 [coef_count]."""
-    return np.concatenate([p.reshape(-1) for p in coefficient_planes(rgb, quant, hmax, vmax)])
+    return np.concatenate([p.reshape(-1) for p in coefficient_planes(rgb, quant, hmax, vmax, wrong, quant0)])
 
 
 def split_planes(coef, H, W, hmax, vmax):

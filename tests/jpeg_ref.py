@@ -2,6 +2,9 @@
 bit by bit, then libjpeg's defaults - the ISLOW integer IDCT, "fancy" chroma upsampling, its fixed-point colour tables.  It is the
 reference of tests/test_jpeg_cpu.py (header fields, quantisation tables, quantised coefficients) and, through the committed pixels it
 reproduces with difference 0, of tests/test_gpu_jpeg.py.  Slow and plain on purpose: test fixtures are a few thousand pixels.
+planes_and_pixels is the device stage alone, on coefficients and one table row per component - the reference of
+tests/test_gpu_jpeg_kernels.py on the synthetic cases of tests/jpeg_cases.py - with the IDCT in int64 under a range check and a set of
+planted mistakes (``wrong=``) that tests/test_jpeg_cases_cpu.py shows the cases to catch.
 """
 from __future__ import annotations
 
@@ -230,10 +233,43 @@ def parse(data: bytes, decode: bool = True) -> SimpleNamespace:
     return out
 
 
-def _idct_pass(x, shift, round_):
-    """One 1-D pass of jidctint over the LAST axis of int32 x[..., 8]."""
-    x = x.astype(np.int32)
-    x0, x1, x2, x3, x4, x5, x6, x7 = (x[..., i] for i in range(8))
+DECODE_WRONG = ("cr_uses_cb_table", "quant_of_frame0", "replicate_le1", "replicate_le3", "below_from_padding", "right_from_padding",
+                "h2v2_bias_swapped", "h2v1_bias_swapped", "idct_wraps", "colour_wraps", "rows_before_columns", "luma_stride_unpadded")
+_I32 = (-(1 << 31), (1 << 31) - 1)
+
+
+class _Tracked:
+    """An integer array whose +, -, *, << return a _Tracked again and widen the shared ``span`` [lowest, highest] by every result: whatever the
+    pass below computes is range-checked, named or not, without the pass having to list it."""
+
+    def __init__(self, v, span):
+        self.v, self.span = v, span
+        if span is not None and v.size:
+            span[0], span[1] = min(span[0], int(v.min())), max(span[1], int(v.max()))
+
+    def _op(self, other, f):
+        return _Tracked(f(self.v, other.v if isinstance(other, _Tracked) else other), self.span)
+
+    def __add__(self, o):
+        return self._op(o, lambda a, b: a + b)
+
+    def __sub__(self, o):
+        return self._op(o, lambda a, b: a - b)
+
+    def __mul__(self, o):
+        return self._op(o, lambda a, b: a * b)
+
+    def __lshift__(self, o):
+        return self._op(o, lambda a, b: a << b)
+
+
+def _idct_pass(x, shift, round_, dtype=np.int64):
+    """One 1-D pass of jidctint over the LAST axis of x[..., 8], every operation in the kernel's order.  dtype int64 (the default): exact, and
+    JpegError if the input or the result of ANY operation of the pass before the final shift - every named value, every operand, the eight
+    sums - leaves int32: the domain on which the header's "all int32" rule says anything.  dtype int32: what an int32 machine computes
+    (numpy wraps silently); inside the domain the two agree."""
+    span = [0, 0] if dtype == np.int64 else None                       # (nothing to track where wrapping is the point)
+    x0, x1, x2, x3, x4, x5, x6, x7 = (_Tracked(x[..., i].astype(dtype), span) for i in range(8))
     z1 = (x2 + x6) * 4433
     t2 = z1 - x6 * 15137
     t3 = z1 + x2 * 6270
@@ -246,69 +282,105 @@ def _idct_pass(x, shift, round_):
     a0, a1, a2, a3 = a0 * 2446, a1 * 16819, a2 * 25172, a3 * 12299
     z1, z2 = z1 * -7373, z2 * -20995
     z3, z4 = z3 * -16069 + z5, z4 * -3196 + z5
-    a0, a1, a2, a3 = a0 + z1 + z3, a1 + z2 + z4, a2 + z2 + z3, a3 + z1 + z4
-    return np.stack([t10 + a3, t11 + a2, t12 + a1, t13 + a0, t13 - a0, t12 - a1, t11 - a2, t10 - a3], -1) >> shift
+    a0, a1, a2, a3 = a0 + (z1 + z3), a1 + (z2 + z4), a2 + (z2 + z3), a3 + (z1 + z4)
+    sums = (t10 + a3, t11 + a2, t12 + a1, t13 + a0, t13 - a0, t12 - a1, t11 - a2, t10 - a3)
+    if span is not None and (span[0] < _I32[0] or span[1] > _I32[1]):
+        raise JpegError(f"IDCT intermediate outside int32 ({span[0]} ... {span[1]}): beyond the domain of the integer rule")
+    return np.stack([s.v for s in sums], -1) >> shift
 
 
-def idct_plane(coef, quant):
-    """coef int16 [by, bx, 64], quant uint16 [64] -> uint8 samples [by * 8, bx * 8]."""
+def idct_samples(coef, quant, dtype=np.int64, wrong=None):
+    """coef int16 [by, bx, 64], quant uint16 [64] -> the IDCT's results + 128 BEFORE the clamp, [by * 8, bx * 8] (dtype)."""
     by, bx, _ = coef.shape
-    x = (coef.astype(np.int32) * quant.astype(np.int32)).reshape(by, bx, 8, 8)
-    ws = _idct_pass(x.swapaxes(-1, -2), 11, 1 << 10).swapaxes(-1, -2)          # columns first
-    out = _idct_pass(ws, 18, 1 << 17)                                           # then rows
-    return np.clip(out + 128, 0, 255).astype(np.uint8).transpose(0, 2, 1, 3).reshape(by * 8, bx * 8)
+    x = (coef.astype(dtype) * quant.astype(dtype)).reshape(by, bx, 8, 8)
+    if wrong == "rows_before_columns":
+        out = _idct_pass(_idct_pass(x, 11, 1 << 10, dtype).swapaxes(-1, -2), 18, 1 << 17, dtype).swapaxes(-1, -2)
+    else:
+        ws = _idct_pass(x.swapaxes(-1, -2), 11, 1 << 10, dtype).swapaxes(-1, -2)    # columns first
+        out = _idct_pass(ws, 18, 1 << 17, dtype)                                    # then rows
+    return (out + 128).transpose(0, 2, 1, 3).reshape(by * 8, bx * 8)
 
 
-def _upsample_h(u, bias_even, bias_odd, shift):
-    """out[2i] = (3 u[i] + u[i-1] + bias_even) >> shift, out[2i+1] = (3 u[i] + u[i+1] + bias_odd) >> shift, edges replicated."""
-    left = np.concatenate([u[:, :1], u[:, :-1]], 1)
-    right = np.concatenate([u[:, 1:], u[:, -1:]], 1)
-    out = np.empty((u.shape[0], 2 * u.shape[1]), np.int32)
-    out[:, 0::2] = (3 * u + left + bias_even) >> shift
-    out[:, 1::2] = (3 * u + right + bias_odd) >> shift
-    return out
+def _to_u8(v, wraps):
+    return (v & 255).astype(np.uint8) if wraps else np.clip(v, 0, 255).astype(np.uint8)
 
 
-def upsample(s, hf, vf, H, W):
-    """A chroma plane cropped to its real size -> [H, W] int32.  libjpeg takes the triangle filter only for planes more than two samples
-    wide (jdsample.c); a narrower one is replicated."""
-    s = s.astype(np.int32)
+def idct_plane(coef, quant, dtype=np.int64, wrong=None):
+    """coef int16 [by, bx, 64], quant uint16 [64] -> uint8 samples [by * 8, bx * 8]."""
+    return _to_u8(idct_samples(coef, quant, dtype, wrong), wrong == "idct_wraps")
+
+
+def upsample(plane, ch, cw, hf, vf, H, W, wrong=None):
+    """A chroma plane on the MCU grid, its real size ch x cw -> [H, W] int32.  Edges replicate the last REAL row and column; libjpeg takes the
+    triangle filter only for planes more than two samples wide (jdsample.c), a narrower one is replicated."""
+    plane = plane.astype(np.int32)
     if hf == 1 and vf == 1:
-        return s[:H, :W]
-    if s.shape[1] <= 2:
-        return np.repeat(np.repeat(s, vf, 0), hf, 1)[:H, :W]
+        return plane[:H, :W]
+    limit = {"replicate_le1": 1, "replicate_le3": 3}.get(wrong, 2)
+    if cw <= limit:
+        return np.repeat(np.repeat(plane[:ch, :cw], vf, 0), hf, 1)[:H, :W]
+    below = ch if wrong == "below_from_padding" and ch < plane.shape[0] else ch - 1
+    right = cw if wrong == "right_from_padding" and cw < plane.shape[1] else cw - 1
+    e = plane[np.ix_([0] + list(range(ch)) + [below], [0] + list(range(cw)) + [right])]     # the real samples with one neighbour on each side
     if vf == 1:
-        return _upsample_h(s, 1, 2, 2)[:H, :W]
-    above = np.concatenate([s[:1], s[:-1]], 0)
-    below = np.concatenate([s[1:], s[-1:]], 0)
-    u = np.empty((2 * s.shape[0], s.shape[1]), np.int32)
-    u[0::2] = 3 * s + above
-    u[1::2] = 3 * s + below
-    return _upsample_h(u, 8, 7, 4)[:H, :W]
+        rows, (even, odd), shift = [e[1:-1]], ((2, 1) if wrong == "h2v1_bias_swapped" else (1, 2)), 2
+    else:
+        rows, (even, odd), shift = [3 * e[1:-1] + e[:-2], 3 * e[1:-1] + e[2:]], ((7, 8) if wrong == "h2v2_bias_swapped" else (8, 7)), 4
+    out = np.empty((vf * ch, 2 * cw), np.int32)
+    for k, u in enumerate(rows):
+        out[k::vf, 0::2] = (3 * u[:, 1:-1] + u[:, :-2] + even) >> shift
+        out[k::vf, 1::2] = (3 * u[:, 1:-1] + u[:, 2:] + odd) >> shift
+    return out[:H, :W]
 
 
 def _fix(x):
     return int(x * 65536 + 0.5)
 
 
-def pixels(p) -> np.ndarray:
+def block_grids(H, W, components, hmax, vmax):
+    """-> [(blocks_y, blocks_x)] per component over the MCU grid"""
+    mx, my = -(-W // (8 * hmax)), -(-H // (8 * vmax))
+    return [(my * vmax, mx * hmax)] + [(my, mx)] * (components - 1)
+
+
+def planes_and_pixels(coef, quant, H, W, components, hmax, vmax, wrong=None, quant0=None, dtype=np.int64, detail=None):
+    """One frame through the device stage's rule.  coef int16 [coef_count] in the decoder's layout, quant uint16 [3, 64]: one row per component
+    (a one-component frame uses row 0) -> (planes, pixels): the uint8 component planes on the MCU grid, padding blocks included - one after the
+    other they are what ehm_jpeg_decode leaves in its workspace for the frame - and the uint8 [H, W, 3] BGR pixels.
+    wrong: one of DECODE_WRONG, a planted mistake (quant_of_frame0 takes the rows from ``quant0``, frame 0's).  dtype: see _idct_pass.
+    detail: a dict that receives "samples" (per plane, before the clamp) and "bgr" (int32 [H, W, 3] before the clamp)."""
+    assert wrong is None or wrong in DECODE_WRONG
+    coef, quant = np.asarray(coef), np.asarray(quant if wrong != "quant_of_frame0" else quant0)
+    rows = [0, 1, 1] if wrong == "cr_uses_cb_table" else [0, 1, 2]
+    samples, o = [], 0
+    for c, (by, bx) in enumerate(block_grids(H, W, components, hmax, vmax)):
+        samples.append(idct_samples(coef[o:o + by * bx * 64].reshape(by, bx, 64), quant[rows[c]], dtype, wrong))
+        o += by * bx * 64
+    assert o == coef.size
+    planes = [_to_u8(s, wrong == "idct_wraps") for s in samples]
+    if wrong == "luma_stride_unpadded":
+        y = planes[0].reshape(-1)[:H * W].reshape(H, W).astype(np.int32)
+    else:
+        y = planes[0][:H, :W].astype(np.int32)
+    if components == 1:
+        bgr = np.repeat(y[:, :, None], 3, 2)
+    else:
+        ch, cw = -(-H // vmax), -(-W // hmax)
+        cb = upsample(planes[1], ch, cw, hmax, vmax, H, W, wrong) - 128
+        cr = upsample(planes[2], ch, cw, hmax, vmax, H, W, wrong) - 128
+        r = y + ((_fix(1.40200) * cr + 32768) >> 16)
+        b = y + ((_fix(1.77200) * cb + 32768) >> 16)
+        g = y + ((-_fix(0.34414) * cb + (-_fix(0.71414) * cr + 32768)) >> 16)
+        bgr = np.stack([b, g, r], -1)
+    if detail is not None:
+        detail["samples"], detail["bgr"] = samples, bgr
+    return planes, _to_u8(bgr, wrong == "colour_wraps")
+
+
+def pixels(p, wrong=None) -> np.ndarray:
     """parse()'s result -> uint8 [H, W, 3] BGR."""
-    H, W = p.H, p.W
-    planes, o = [], 0
-    for c in range(p.components):
-        n = p.blocks_y[c] * p.blocks_x[c] * 64
-        planes.append(idct_plane(p.coef[o:o + n].reshape(p.blocks_y[c], p.blocks_x[c], 64), p.quant[p.quant_id[c]]))
-        o += n
-    y = planes[0][:H, :W].astype(np.int32)
-    if p.components == 1:
-        return np.repeat(y[:, :, None], 3, 2).astype(np.uint8)
-    ch, cw = -(-H // p.vmax), -(-W // p.hmax)
-    cb = upsample(planes[1][:ch, :cw], p.hmax, p.vmax, H, W) - 128
-    cr = upsample(planes[2][:ch, :cw], p.hmax, p.vmax, H, W) - 128
-    r = y + ((_fix(1.40200) * cr + 32768) >> 16)
-    b = y + ((_fix(1.77200) * cb + 32768) >> 16)
-    g = y + ((-_fix(0.34414) * cb + (-_fix(0.71414) * cr + 32768)) >> 16)
-    return np.clip(np.stack([b, g, r], -1), 0, 255).astype(np.uint8)
+    quant = p.quant[[p.quant_id[min(c, p.components - 1)] for c in range(3)]]
+    return planes_and_pixels(p.coef, quant, p.H, p.W, p.components, p.hmax, p.vmax, wrong=wrong)[1]
 
 
 def decode(data: bytes) -> np.ndarray:
