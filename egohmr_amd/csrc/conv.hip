@@ -265,7 +265,7 @@ template <int NU, bool SK, bool DS = false, bool HO = false>
 __global__ __launch_bounds__(256, 2) void conv_x2_tile_kernel(ConvX2Args p) {
   constexpr int XBN = 64 * NU, XSTG = x_stage_floats(NU);
   __shared__ __attribute__((aligned(16))) float lds[2 * XSTG];   // 80 / 64 KiB; the ONLY LDS object
-  x2_fp16_ovfl_on();
+  // (MODE.FP16_OVFL is set around each epilogue only: the K loop's MFMAs run with it clear, so that a NaN / inf activation reaches its outputs)
 
   constexpr int KS = 2, NM = 9 * NU, NR = 6 + 2 * NU, NBD = 2 * NU;
   // split-f16 products on the 16 x 16 x 32 MFMA (x2_tile_dev.h; see tile16 in gcn_tile.hip); the hi-only tier keeps the 32 x 32 x 16 form
@@ -667,6 +667,7 @@ __global__ __launch_bounds__(256, 2) void conv_x2_tile_kernel(ConvX2Args p) {
     // 2 gi + u), 4 passes; NU = 1: 6 groups x 32 columns (piece gi), 2 passes.  Read items = (row, 8 columns), three per lane.
     if constexpr (M16) {
      if (cols_live && finish) {
+      x2_fp16_ovfl_on();                                           // the conversions below saturate a finite overflow; NaN and inf pass
       // accumulator layout: lane (i = l & 15, rg = l >> 4) owns columns 32 NU wn + 16 ct + i; register r of c16[rt][ct] is row 16 rt + 4 rg + r.  One pass per
       // row tile (16 rows x 32 NU columns through 2 NU of the wave's six 1 KiB pieces): piece NU (row >> 3) + (col >> 5) holds [8 rows][32 columns]; inside a piece
       // row (row & 7) sits at (row & 7) ^ (row >> 3) and its two 16-column halves swap places for odd rg (four lane groups of a write -> four 16-bank groups).
@@ -737,9 +738,11 @@ __global__ __launch_bounds__(256, 2) void conv_x2_tile_kernel(ConvX2Args p) {
           }
         }
       }
+      x2_fp16_ovfl_off();
      }
     } else
     if (cols_live && finish) {
+      x2_fp16_ovfl_on();
       constexpr int GP = NU == 2 ? 3 : 6, NPASS = 12 / GP;       // row groups per pass
       const unsigned int yrow = (unsigned int)p.Co * 4u;
       const __amdgpu_buffer_rsrc_t yB = ehm_buffer_rsrc(p.y + (row0 + 96 * wm) * (size_t)yrow);
@@ -815,6 +818,7 @@ __global__ __launch_bounds__(256, 2) void conv_x2_tile_kernel(ConvX2Args p) {
           }
         }
       }
+      x2_fp16_ovfl_off();
     }
     if (!have_next) break;
 #pragma unroll

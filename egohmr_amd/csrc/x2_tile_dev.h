@@ -32,6 +32,10 @@ constexpr int SG_MFMA = 0x008, SG_DS_READ = 0x100, SG_VMEM = 0x010;
 // + its canonicalising v_max, twice; in the GCN tile engine 144 v_med3_f32 + their canonicalising v_max_f32 per wave and tile, in an epilogue
 // during which the block's matrix pipes idle).
 static __device__ __forceinline__ void x2_fp16_ovfl_on() { __builtin_amdgcn_s_setreg(1 | (23 << 6), 1); }
+// ... and back to 0.  A kernel whose activations may hold a NaN or an infinity keeps the bit CLEAR while its matrix cores run and sets it around the
+// epilogue's conversions alone: with the bit set an MFMA does not propagate a non-finite f16 operand (measured on an MI355X: a NaN half left finite,
+// wrong sums - docs/EXPERIMENTS.md, round 32), while the conversions keep a NaN and an infinity of their f32 input as they are.
+static __device__ __forceinline__ void x2_fp16_ovfl_off() { __builtin_amdgcn_s_setreg(1 | (23 << 6), 0); }
 
 // The hi / lo split of a value (MODE.FP16_OVFL: the conversions saturate at +-65504, never inf); hi and lo may be elements of a half8, hence a macro.
 #define X2_SPLIT(v, hi, lo) ((hi) = (half_t)(v), (lo) = (half_t)((v) - (float)(hi)))

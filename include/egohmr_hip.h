@@ -511,7 +511,21 @@ int ehm_conv_nhwc_split(const ehm_conv_desc* d, void* stream);
  * models/resnet.py:139-150 / models/egohmr/egohmr.py:183 end to end): x, residual, y are X2 [rows, C] matrices (ehm_split_pack layout,
  * pixel-major NHWC) whose row count is ehm_conv_x2_rows(N*H*W) = pixels rounded up to the 192-row tile + ONE extra row; the LAST
  * row of x must be all zero (out-of-image taps read it).  Ci % 32 == 0, Co % 32 == 0, KH*KW*Ci >= 64; W, bias, relu, w_scale as
- * in ehm_conv_desc.  y's padding rows receive don't-care values; its last row is cleared by the call. */
+ * in ehm_conv_desc.  y's padding rows receive don't-care values; its last row is cleared by the call.
+ * Pinned by tests/test_gpu_conv_x2.py (every valid output against float64 of the decoded operands, under the per-output bound derived in
+ * tests/conv_x2_ref.py):
+ *   rows: x may have MORE than ehm_conv_x2_rows(N*H*W) rows - the zero row is always row x_rows - 1.  The rows between the last pixel and the zero
+ *   row (of x, x2 and residual) never reach a valid output: a row past the last output pixel gathers the zero row, and only y's own padding rows
+ *   see the residual's.  No byte of y past column Co of a row, and none behind its last row, is written; hi_only leaves every lo half of y alone.
+ *   range: activations and outputs up to +-65504 stay within the bound.  A FINITE output v past 65504 saturates (the epilogue converts with
+ *   MODE.FP16_OVFL = 1): hi = +-65504, lo = f16(v -+ 65504) clamped to +-65504 - v itself to about 2^-11 of the part past 65504 up to +-131008,
+ *   +-131008 beyond, never inf (hi_only: +-65504) - the halves ehm_split_pack writes for such a value.  An activation stored in that saturated form
+ *   IS 131008 to the engine: there is no range flag in the data.
+ *   non-finite: a NaN or +-inf half of an activation (hi, or lo in the split tier) makes every output whose receptive field holds that pixel
+ *   non-finite, in every channel, and no other output: all others keep the bits of the clean launch.  With relu = 1 the epilogue's max(v, 0)
+ *   returns 0 for a NaN or -inf, as in the float32-activation engine above.  The hi_only tier does not read lo halves at all.  (The K loop runs
+ *   with MODE.FP16_OVFL clear: with the bit set the matrix cores do not propagate a non-finite half.)
+ *   An all-zero W gives exactly the X2 split of act(bias + residual). */
 typedef struct ehm_conv_x2_desc {
   const void* x; int64_t x_rows; const void* W; const float* bias; const void* residual; void* y;
   int N, H, Wd, Ci, Co;
