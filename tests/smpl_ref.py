@@ -295,7 +295,7 @@ def blend_operands(asset, betas, rotmats):
     return c, D
 
 
-def _bound(asset, betas, rotmats, valu, ref=None):
+def _bound(asset, betas, rotmats, valu, ref=None, E_R=None):
     ref = forward64(asset, betas, rotmats) if ref is None else ref
     f64 = lambda k: np.asarray(asset[k], np.float64)
     vt, sd, Jr, W = f64("v_template"), f64("shapedirs"), f64("J_regressor"), f64("lbs_weights")
@@ -319,11 +319,13 @@ def _bound(asset, betas, rotmats, valu, ref=None):
     # chain
     E_Grot, E_Gt = np.zeros((B, KJ, 3, 3)), np.zeros((B, KJ, 3))
     E_Gt[:, 0] = E_t[:, 0]
+    E_R = np.zeros((B, KJ, 3, 3)) if E_R is None else np.asarray(E_R, np.float64)      # (rotations that the device formed itself: bound_valu's E_R)
+    E_Grot[:, 0] = E_R[:, 0]
     mv = lambda M, v: np.einsum("brc,bc->br", M, v)
     for j in range(1, KJ):
         p = par[j]
         aP, aR, at = np.abs(Grot[:, p]), np.abs(R[:, j]), np.abs(t[:, j])
-        E_Grot[:, j] = E_Grot[:, p] @ aR + 3 * U * (aP @ aR)
+        E_Grot[:, j] = E_Grot[:, p] @ aR + aP @ E_R[:, j] + 3 * U * (aP @ aR)
         E_Gt[:, j] = mv(E_Grot[:, p], at) + mv(aP, E_t[:, j]) + E_Gt[:, p] + 4 * U * (mv(aP, at) + np.abs(Gt[:, p]))
     E_A = np.zeros((B, KJ, 3, 4))
     E_A[..., :3] = E_Grot
@@ -335,8 +337,9 @@ def _bound(asset, betas, rotmats, valu, ref=None):
     S = (np.abs(c) @ np.abs(D)).reshape(B, V, 3)
     p = vt[None] + (c @ D).reshape(B, V, 3)
     if valu:
-        E_p = K_VALU * U * (np.abs(vt)[None] + S) + U * S
+        E_p = K_VALU * U * (np.abs(vt)[None] + S) + U * S + (E_R[:, 1:].reshape(B, POSE_BASIS) @ np.abs(D[:POSE_BASIS])).reshape(B, V, 3)
     else:
+        assert not E_R.any(), "a rotation error is carried through the VALU blend only"
         s = pd_scale(asset)
         E_p = (K_BLEND * U * S + F16_FLOOR * np.abs(D).sum(0).reshape(1, V, 3) + (F16_FLOOR / s) * np.abs(c).sum(1)[:, None, None] + U * np.abs(p))
     # weighted transform and apply
@@ -348,7 +351,8 @@ def _bound(asset, betas, rotmats, valu, ref=None):
     E_v = (np.einsum("bvrc,bvc->bvr", E_T[..., :3], ap) + np.einsum("bvrc,bvc->bvr", np.abs(T[..., :3]), E_p) + E_T[..., 3]
            + 4 * U * (np.einsum("bvrc,bvc->bvr", np.abs(T[..., :3]), ap) + np.abs(T[..., 3])))
     extra = E_v[:, np.asarray(asset["extra_joints_idxs"], np.int64)]
-    return SimpleNamespace(A=E_A, joints=E_Gt, vertices=E_v, extra=extra, all_joints=np.concatenate([E_Gt, extra], 1), ref=ref)
+    return SimpleNamespace(A=E_A, joints=E_Gt, vertices=E_v, extra=extra, all_joints=np.concatenate([E_Gt, extra], 1), ref=ref,
+                           p=E_p, J=E_J, t=E_t, J_shape=E_Js, rest=SimpleNamespace(p=p, J=J, t=t, J_shape=Js))
 
 
 def bound(asset, betas, rotmats, ref=None):
@@ -357,9 +361,12 @@ def bound(asset, betas, rotmats, ref=None):
     return _bound(asset, betas, rotmats, False, ref)
 
 
-def bound_valu(asset, betas, rotmats, ref=None):
-    """The same for the VALU skinning kernel (B < 24, or an asset with more than four weights in a row)"""
-    return _bound(asset, betas, rotmats, True, ref)
+def bound_valu(asset, betas, rotmats, ref=None, E_R=None):
+    """The same for the VALU skinning kernel (B < 24, or an asset with more than four weights in a row).  Beside the outputs' bounds: .p, .J, .t, .J_shape -
+    the bounds of the blended rest vertex, the rest joints, the joint offsets and the regressed shape basis (tests/smpl_vjp_ref.py: the backward recomputes
+    them) - and .rest, their float64 values.  E_R [B, 24, 3, 3]: an error bound of the rotations themselves, for an entry that forms them on the device
+    (first order: `aP @ E_R` in the chain, `E_R |posedirs|` in the blend); None = the rotations are exact inputs."""
+    return _bound(asset, betas, rotmats, True, ref, E_R)
 
 
 def path_of(asset, B):
@@ -410,7 +417,8 @@ def _dot3(P, M):
 
 
 def emulate(asset, betas, rotmats, path, drop=None):
-    """The forward in numpy float32 / float16 in the device's order -> SimpleNamespace(vertices [B, V, 3], joints [B, 24 + n_extra, 3], A [B, 24, 3, 4]).
+    """The forward in numpy float32 / float16 in the device's order -> SimpleNamespace(vertices [B, V, 3], joints [B, 24 + n_extra, 3], A [B, 24, 3, 4];
+    and what the backward recomputes, for tests/smpl_vjp_ref.py: p [B, V, 3] the blended rest vertex, J [B, 24, 3], J_template, J_shape [24, 3, 10]).
     path = "mfma": skin_mfma_body (pd_scale, hi / lo split of both operands, per k-step of 16 the products c_lo . D_hi, c_hi . D_lo, c_hi . D_hi added
     to the float32 accumulator in that order, one rounding each);  path = "valu": skin_kernel's fmaf chains (sparse-4 or 24-joint transform as the
     asset's weights decide).  Sums of products are taken as the compiler contracts them (a * b + c -> fma).
@@ -506,7 +514,7 @@ def emulate(asset, betas, rotmats, path, drop=None):
     v = _fma(T[..., 2], p[:, :, None, 2], v)
     v = (v + T[..., 3]).astype(f)
     joints = np.concatenate([Gt, v[:, np.asarray(asset["extra_joints_idxs"], np.int64)]], 1)
-    return SimpleNamespace(vertices=v, joints=joints, A=A)
+    return SimpleNamespace(vertices=v, joints=joints, A=A, p=p, J=J, J_template=Jt, J_shape=Js)
 
 
 # ------------------------------------------------------------------------------------------------ cases
