@@ -18,6 +18,8 @@ _LAZY = {
     "rotmat_to_rot6d": ("geometry", "rotmat_to_rot6d"),
     "EgoHMRHipError": ("_lib", "EgoHMRHipError"),
     "ProHMRSceneTransl": ("stage1", "ProHMRSceneTransl"),
+    "ProHMRScene": ("stage1", "ProHMRScene"),
+    "GlowFlow": ("stage1", "GlowFlow"),
     "BatchBuilder": ("batch", "BatchBuilder"),
     "AugmentConfig": ("batch", "AugmentConfig"),
     "JpegDecoder": ("jpeg", "JpegDecoder"),

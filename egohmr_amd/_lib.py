@@ -29,7 +29,7 @@ _HERE = os.path.dirname(os.path.abspath(__file__))
 LIB_PATH = os.environ.get("EHM_LIB_PATH") or os.path.join(_HERE, "libegohmr_hip.so")   # EHM_LIB_PATH: A/B a second build (experiments)
 CSRC = os.path.join(_HERE, "csrc")
 INCLUDE = os.path.join(os.path.dirname(_HERE), "include")
-SOURCES = ["gcn.hip", "gcn_tile.hip", "linear.hip", "conv.hip", "stem.hip", "metrics.hip", "smpl.hip", "sampler.hip", "guidance.hip", "prep.hip", "step.hip", "eval.hip", "stage1.hip", "scene.hip", "loss.hip", "gcn_bwd.hip", "gcn_train.hip", "pointnet_bwd.hip", "train.hip", "conv_bwd.hip", "bn2d_train.hip", "nonlocal_bwd.hip", "batch.hip", "render.hip", "mesh_collision.hip", "jpeg.hip", "jpeg_enc.hip"]
+SOURCES = ["gcn.hip", "gcn_tile.hip", "linear.hip", "conv.hip", "stem.hip", "metrics.hip", "smpl.hip", "sampler.hip", "guidance.hip", "prep.hip", "step.hip", "eval.hip", "stage1.hip", "scene.hip", "loss.hip", "gcn_bwd.hip", "gcn_train.hip", "pointnet_bwd.hip", "train.hip", "conv_bwd.hip", "bn2d_train.hip", "nonlocal_bwd.hip", "batch.hip", "render.hip", "mesh_collision.hip", "jpeg.hip", "jpeg_enc.hip", "flow.hip"]
 
 
 class EgoHMRHipError(RuntimeError):
@@ -222,6 +222,24 @@ class Stage1Desc(C.Structure):
                 ("img_dim", C.c_int), ("scene_dim", C.c_int), ("hidden", C.c_int), ("B", C.c_int)]
 
 
+class FlowContextDesc(C.Structure):
+    """ehm_flow_context_desc"""
+    _fields_ = [("img_feats", C.c_void_p), ("scene_feats", C.c_void_p), ("fx", C.c_void_p), ("cam_cx", C.c_void_p), ("cam_cy", C.c_void_p),
+                ("box_center", C.c_void_p), ("box_size", C.c_void_p), ("out", C.c_void_p), ("fx_norm", C.c_float), ("with_cam_center", C.c_int),
+                ("with_bbox_info", C.c_int), ("with_focal_length", C.c_int), ("img_dim", C.c_int), ("scene_dim", C.c_int), ("ctx_pad", C.c_int), ("B", C.c_int)]
+
+
+class FlowGemmDesc(C.Structure):
+    """ehm_flow_gemm_desc"""
+    _fields_ = [("X", C.c_void_p), ("gather", C.c_void_p), ("W", C.c_void_p), ("bias", C.c_void_p), ("pro_scale", C.c_void_p), ("pro_shift", C.c_void_p),
+                ("item", C.c_void_p), ("scatter", C.c_void_p), ("Y", C.c_void_p), ("R", C.c_int), ("K", C.c_int), ("N", C.c_int), ("S", C.c_int),
+                ("ldx", C.c_int), ("ldw", C.c_int), ("ldy", C.c_int), ("ld_item", C.c_int), ("prologue", C.c_int), ("epilogue", C.c_int)]
+
+
+FLOW_PRO_NONE, FLOW_PRO_RELU, FLOW_PRO_BN_RELU, FLOW_PRO_SHIFT = 0, 1, 2, 3                                  # EHM_FLOW_PRO_* of the header
+FLOW_EPI_BIAS, FLOW_EPI_ITEM_ADD, FLOW_EPI_GLU_RES, FLOW_EPI_SCATTER_ADD, FLOW_EPI_SCATTER_SUB = 0, 1, 2, 3, 4   # EHM_FLOW_EPI_*
+
+
 class SceneDesc(C.Structure):
     """ehm_scene_desc"""
     _fields_ = [("verts", C.c_void_p), ("total_verts", C.c_int64), ("mesh_offsets", C.c_void_p), ("num_meshes", C.c_int), ("max_mesh_verts", C.c_int64),
@@ -383,6 +401,9 @@ PROTOTYPES = {
     "ehm_eval_procrustes_vis": (_I, [_P, _P, _P, _P, _P, _P, _P, _P, _I, _I, _I, _P]),
     "ehm_eval_diversity": (_I, [_P, _P, _I, _P, _P, _I, _I, _I, _P]),
     "ehm_stage1_head": (_I, [C.POINTER(Stage1Desc), _P]),
+    "ehm_flow_context": (_I, [C.POINTER(FlowContextDesc), _P]),
+    "ehm_flow_gemm": (_I, [C.POINTER(FlowGemmDesc), _P]),
+    "ehm_flow_finish": (_I, [_P, C.c_double, _P, _P, _P, _P, _P, _I, _P]),
     "ehm_scene_workspace_bytes": (_I, [C.POINTER(SceneDesc), C.POINTER(C.c_int64)]),
     "ehm_scene_select": (_I, [C.POINTER(SceneDesc), _P]),
     "ehm_image_patch": (_I, [C.POINTER(ImagePatchDesc), _P]),

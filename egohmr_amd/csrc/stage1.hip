@@ -1,7 +1,7 @@
 // Stage 1 (ProHMR-scene) translation on gfx950: the deterministic half of the reference's stage-1 model - context assembly
 // (models/prohmr/prohmr_scene.py:111-130), the camera / betas head FCHead (models/prohmr/fc_head.py:46-50) and the full-image camera conversion of
-// test_prohmr_scene.py:175-213 (utils/geometry.py:119-131) - in one launch.  The normalizing flow (pose samples, log-prob) is not here: pred_cam
-// does not read it.
+// test_prohmr_scene.py:175-213 (utils/geometry.py:119-131) - in one launch.  The normalizing flow (pose samples, log-prob) is csrc/flow.hip:
+// pred_cam does not read it.
 //
 // One 256-thread block per group of kItems items.  Layer 1 (K x 1024, K = 2560 + the switched leading features): thread t owns hidden units
 // t + 256 q (q < 4) of all kItems items, 32 f32 accumulators; the context is read IN PLACE from the two feature matrices and the per-item scalars,

@@ -8,8 +8,8 @@ What it stands in for (test_egohmr.py; argparse, the EgoBody dataloader, open3d 
     :374-505   G-MPJPE / MPJPE / PA-MPJPE / V2V with their visible / invisible splits, std / APD diversity, contact score
     :507-560   the running means the script prints (`error_dict`, `diversity_dict`)
     :672-695   ``results_seed_{seed}.pkl``
-``Stage1Driver`` is the counterpart for the stage-1 script (test_prohmr_scene.py:160-217, 417-426): the body translation of every image into
-``output_prohmr_scene_{model_id}/results.pkl``, which ``--two_stage`` stage-2 runs read.
+``Stage1Driver`` is the counterpart for the stage-1 script (test_prohmr_scene.py:160-217, 293-321, 417-426): the body translation of every image
+into ``output_prohmr_scene_{model_id}/results.pkl``, which ``--two_stage`` stage-2 runs read, and the six error figures of the mode.
 Everything stays on the device until ``summary()`` / ``results()``; the reference moves every metric to numpy per batch and runs
 the Procrustes alignment as a CPU loop of numpy SVDs (utils/pose_utils.py).  The S samples of a batch share one conditioning pass
 (``FusedSampler.prepare`` caches it per batch), the reference re-runs ResNet-50 and the PointNet in every denoising step.
@@ -24,6 +24,21 @@ import torch
 from . import io as eio
 from . import metrics as M
 from .geometry import perspective_projection
+
+
+@torch.no_grad()
+def ground_truth_bodies(smpl_male, smpl_female, batch, transl) -> dict:
+    """The ground-truth bodies of test_egohmr.py:306-318 / test_prohmr_scene.py:219-232: the male and the female model on the batch's annotations
+    at the translation ``transl``, the female one where ``gender == 1``; the first 24 joints, the vertices, the pelvis and both pelvis-aligned."""
+    sp = batch["smpl_params"]
+    kw = dict(global_orient=sp["global_orient"], transl=transl, body_pose=sp["body_pose"], betas=sp["betas"])
+    male, female = smpl_male(**kw), smpl_female(**kw)
+    fem = (batch["gender"] == 1).view(-1, 1, 1)
+    joints = torch.where(fem, female.joints, male.joints)
+    verts = torch.where(fem, female.vertices, male.vertices)
+    j24 = joints[:, :24, :]
+    pelvis = j24[:, [0], :].clone()
+    return dict(joints=j24, vertices=verts, pelvis=pelvis, joints_align=j24 - pelvis, vertices_align=verts - pelvis)
 
 
 class Stage2Driver:
@@ -95,15 +110,7 @@ class Stage2Driver:
     # ------------------------------------------------------------------ :306-318
     @torch.no_grad()
     def ground_truth(self, batch, gt_cam_full):
-        sp = batch["smpl_params"]
-        kw = dict(global_orient=sp["global_orient"], transl=gt_cam_full, body_pose=sp["body_pose"], betas=sp["betas"])
-        male, female = self.smpl_male(**kw), self.smpl_female(**kw)
-        fem = (batch["gender"] == 1).view(-1, 1, 1)
-        joints = torch.where(fem, female.joints, male.joints)
-        verts = torch.where(fem, female.vertices, male.vertices)
-        j24 = joints[:, :24, :]
-        pelvis = j24[:, [0], :].clone()
-        return dict(joints=j24, vertices=verts, pelvis=pelvis, joints_align=j24 - pelvis, vertices_align=verts - pelvis)
+        return ground_truth_bodies(self.smpl_male, self.smpl_female, batch, gt_cam_full)
 
     # ------------------------------------------------------------------ one batch: :230-505
     @torch.no_grad()
@@ -241,18 +248,59 @@ class Stage2Driver:
 
 
 class Stage1Driver:
-    """The translation half of test_prohmr_scene.py: run egohmr_amd.stage1.ProHMRSceneTransl over the stage-1 batches (whole-scene clouds),
-    collect pred_cam_full (:209-217) and write results.pkl (:417-426).  Stage-1 metrics and rendering are out of scope."""
+    """test_prohmr_scene.py as a harness.  ``Stage1Driver(model)`` with an egohmr_amd.stage1.ProHMRSceneTransl is the translation half: run it over
+    the stage-1 batches (whole-scene clouds), collect pred_cam_full (:209-217) and write results.pkl (:417-426).  With the three body models and an
+    egohmr_amd.stage1.ProHMRScene, ``step`` also draws ``num_samples`` bodies per image and computes the six error figures of the mode (z = 0,
+    :293-321): G-MPJPE, MPJPE, PA-MPJPE, G-V2V, V2V, PA-V2V, on the kernels of egohmr_amd.metrics; ``summary()`` returns their means in
+    millimetres.  Stage-1 rendering is egohmr_amd.render's (it draws any vertices)."""
 
-    def __init__(self, model):
+    METRICS = (("G-MPJPE", "g_mpjpe"), ("MPJPE", "mpjpe"), ("PA-MPJPE", "pa_mpjpe"), ("G-V2V", "g_v2v"), ("V2V", "v2v"), ("PA-V2V", "pa_v2v"))
+
+    def __init__(self, model, smpl_neutral=None, smpl_male=None, smpl_female=None, num_samples: int = 4):
         self.model = model
+        self.smpl_neutral, self.smpl_male, self.smpl_female = smpl_neutral, smpl_male, smpl_female
+        self.S = int(num_samples)
+        self.with_metrics = smpl_neutral is not None or smpl_male is not None or smpl_female is not None
+        if self.with_metrics and (smpl_neutral is None or smpl_male is None or smpl_female is None):
+            raise ValueError("Stage1Driver: the stage-1 metrics need all three body models (smpl_neutral, smpl_male, smpl_female)")
+        if self.with_metrics:
+            from .stage1 import ProHMRScene
+            if not isinstance(model, ProHMRScene):
+                raise TypeError(f"Stage1Driver: the stage-1 metrics need an egohmr_amd.stage1.ProHMRScene (pose samples), not {type(model).__name__}")
         self._cams = []
+        self._acc = {}
 
     @torch.no_grad()
-    def step(self, batch) -> dict:
-        out = self.model(batch)
+    def step(self, batch, z=None) -> dict:
+        if not self.with_metrics:
+            out = self.model(batch)
+            self._cams.append(out["pred_cam_full"])
+            return out
+        out = self.model(batch, num_samples=self.S, z=z)
         self._cams.append(out["pred_cam_full"])
-        return out
+        sp, cam = out["pred_smpl_params"], out["pred_cam_full"]
+        o = self.smpl_neutral(betas=sp["betas"][:, 0].contiguous(), body_pose=sp["body_pose"][:, 0].contiguous(),
+                              global_orient=sp["global_orient"][:, 0].contiguous(), pose2rot=False)          # :195-200: the script's own decode
+        # (with ITS neutral model, which need not be the one the network carries; the mode only)
+        j24, verts = o.joints[:, :24, :], o.vertices
+        pelvis = j24[:, [0], :].clone()                                                                       # :203-205
+        p = dict(joints_align=(j24 - pelvis).unsqueeze(1), vertices_align=(verts - pelvis).unsqueeze(1),
+                 joints_full=(j24 + cam.unsqueeze(1)).unsqueeze(1), vertices_full=(verts + cam.unsqueeze(1)).unsqueeze(1))   # :214-216
+        g = ground_truth_bodies(self.smpl_male, self.smpl_female, batch, batch["smpl_params"]["transl"])      # :219-232
+        res = {"g_mpjpe": M.point_errors(p["joints_full"], g["joints"], points=24)["mean"],                   # :293-295
+               "mpjpe": M.point_errors(p["joints_align"], g["joints_align"], points=24)["mean"],              # :298-300
+               "pa_mpjpe": M.procrustes(p["joints_align"].contiguous(), g["joints_align"].contiguous())["mean"],              # :303-306
+               "g_v2v": M.point_errors(p["vertices_full"], g["vertices"])["mean"],                            # :309-311
+               "v2v": M.point_errors(p["vertices_align"], g["vertices_align"])["mean"],                       # :314-316
+               "pa_v2v": M.procrustes(p["vertices_align"].contiguous(), g["vertices_align"].contiguous())["mean"]}            # :319-321
+        res = {k: v[:, 0] for k, v in res.items()}                                                            # [B] each
+        for k, v in res.items():
+            self._acc.setdefault(k, []).append(v)
+        return dict(out, decoded=p, gt=g, **res)
+
+    def summary(self) -> dict:
+        """The means test_prohmr_scene.py:324-329 prints, in millimetres, over the images stepped so far (empty without the body models)."""
+        return {name: 1000 * float(torch.cat(self._acc[key], 0).double().mean()) for name, key in self.METRICS if key in self._acc}
 
     def results(self) -> dict:
         """{'pred_cam_full_list': float32 numpy [n, 3]}, n = the images stepped so far, in order."""

@@ -4,7 +4,8 @@
   numpy arrays, exactly these keys) - what downstream visualisation / evaluation scripts of the reference read.
 * `load_stage1_cam`: `results.pkl['pred_cam_full_list']` written by the stage-1 script (test_prohmr_scene.py:417-426) and
   consumed by `--two_stage` runs; `save_stage1_results` writes that file from egohmr_amd.stage1's translations.
-* `load_stage1_checkpoint`: a ProHMR-scene checkpoint into egohmr_amd.stage1.ProHMRSceneTransl (test_prohmr_scene.py:81-85).
+* `load_stage1_checkpoint`: a ProHMR-scene checkpoint into egohmr_amd.stage1.ProHMRSceneTransl, or with `flow=True` - the pose flow's
+  `flow.flow.*` included - into egohmr_amd.stage1.ProHMRScene (test_prohmr_scene.py:81-85).
 * `read_obj_vertices`: the vertex array of a scene mesh OBJ (scene_mesh/{scene}/{scene}.obj), for egohmr_amd.scene.SceneClouds.
 * `read_obj_mesh`: the same file with its faces and vertex colours, for egohmr_amd.render (test_egohmr.py:595-597 loads it with trimesh).
 * `load_preprocess_stats`, `load_smpl_mean_params`, `load_checkpoint`: test_egohmr.py:109-111, models/egohmr/egohmr.py:669-671,
@@ -19,6 +20,8 @@ from typing import Mapping
 
 import numpy as np
 import torch
+
+from .synthetic import FLOW_DIM, FLOW_PREFIX
 
 RESULT_KEYS = ("pred_betas_list", "pred_global_orient_list", "pred_body_pose_list", "collision_ratio_list", "contact_ratio_list",
                "gt_cam_full_list")                  # + 'pred_cam_full_list' for --two_stage runs
@@ -92,15 +95,79 @@ def save_stage1_results(save_root: str, model_id: str, pred_cam_full) -> str:
 STAGE1_IGNORED_PREFIXES = ("flow.flow.", "discriminator.", "smpl")      # the flow, the GAN discriminator, the body models (smpl, smpl_male, ...)
 
 
-def load_stage1_checkpoint(model: torch.nn.Module, path_or_state):
+FLOW_TRANSFORM_PREFIX = FLOW_PREFIX
+FLOW_IGNORED_KEYS = ("flow.flow._distribution._log_z",)                 # the base distribution's constant: the kernels carry 72 log 2 pi themselves
+
+
+def _truth(v) -> bool:
+    """A scalar flag of a state dict as a bool: a tensor on any device (read on the host), a numpy or a Python value."""
+    return bool(v.detach().cpu()) if isinstance(v, torch.Tensor) else bool(np.asarray(v))
+
+
+def _shape(v) -> tuple:
+    return tuple(v.shape) if hasattr(v, "shape") else tuple(np.shape(v))
+
+
+def flow_transform_kinds(sd, prefix: str = FLOW_TRANSFORM_PREFIX) -> list:
+    """The kind of each transform of a checkpoint's pose flow, from its key set, in index order: 'actnorm' (``log_scale``), 'lulinear'
+    (``lower_entries``) or 'coupling' (``transform_net.*``).  Refused, each naming what was found and before any device call: an index that is
+    not a number or a gap in the indices, a key set of none of the three kinds, a coupling whose ``final_layer`` has 144 rows (the affine
+    coupling, not built), an ActNorm whose ``initialized`` is False (data-dependent initialisation belongs to training)."""
+    per = {}
+    for k, v in sd.items():
+        if k.startswith(prefix):
+            idx, _, name = k[len(prefix):].partition(".")
+            if not idx.isdigit() or not name:
+                raise KeyError(f"stage-1 checkpoint: {k} is not <index>.<name> below {prefix}")
+            per.setdefault(int(idx), {})[name] = v
+    if sorted(per) != list(range(len(per))):
+        raise KeyError(f"stage-1 checkpoint: the flow's transform indices {sorted(per)} are not 0 .. n-1")
+    kinds = []
+    for i in range(len(per)):
+        names = per[i]
+        if "log_scale" in names:
+            if "initialized" in names and not _truth(names["initialized"]):
+                raise ValueError(f"stage-1 checkpoint: ActNorm {prefix}{i} has initialized == False; its data-dependent initialisation belongs to "
+                                 "training and is not built")
+            kinds.append("actnorm")
+        elif "lower_entries" in names:
+            kinds.append("lulinear")
+        elif any(n.startswith("transform_net.") for n in names):
+            fw = names.get("transform_net.final_layer.weight")
+            if fw is None:
+                raise KeyError(f"stage-1 checkpoint: coupling {prefix}{i} has no transform_net.final_layer.weight (keys {sorted(names)[:6]} ...)")
+            if _shape(fw)[0] != FLOW_DIM // 2:
+                raise ValueError(f"stage-1 checkpoint: coupling {prefix}{i} has a final_layer of {_shape(fw)[0]} rows (an affine coupling has "
+                                 f"{FLOW_DIM}); only the additive coupling ({FLOW_DIM // 2} rows) is built")
+            kinds.append("coupling")
+        else:
+            raise KeyError(f"stage-1 checkpoint: unknown flow transform {prefix}{i} with keys {sorted(names)}")
+    return kinds
+
+
+def flow_has_batch_norm(sd) -> bool:
+    return any(k.startswith(FLOW_TRANSFORM_PREFIX) and ".batch_norm_layers." in k for k in sd)
+
+
+def load_stage1_checkpoint(model: torch.nn.Module, path_or_state, flow: bool = False):
     """A ProHMR-scene checkpoint (test_prohmr_scene.py:81-85) into egohmr_amd.stage1.ProHMRSceneTransl.  The keys the translation does not
     read - ``flow.flow.*`` (the normalizing flow), ``discriminator.*``, ``smpl*`` and ``initialized`` - are ignored; every other key must be one
     of the model's and every one of the model's must be present.  Stricter than the reference's ``strict=False`` on purpose: that would
-    silently keep random weights for a missing key, or for a head whose width (the context flags) does not match.  Returns the loaded keys."""
+    silently keep random weights for a missing key, or for a head whose width (the context flags) does not match.  Returns the loaded keys.
+
+    ``flow=True``: into egohmr_amd.stage1.ProHMRScene, ``flow.flow.*`` loaded as well (``flow.flow._distribution._log_z`` aside).  The flow's
+    names are those of published nflows; a checkpoint that differs - other names, another chain of transforms than the model's ActNorm, LULinear,
+    coupling per block, BatchNorm keys the model was not built for (``flow_batch_norm``) - is refused with the keys named
+    (:func:`flow_transform_kinds` lists the other refusals), never loaded in part."""
     w = torch.load(path_or_state, map_location="cpu") if isinstance(path_or_state, (str, os.PathLike)) else path_or_state
     sd = w["state_dict"] if isinstance(w, Mapping) and "state_dict" in w else w
-    sd = {k: v for k, v in sd.items() if k != "initialized" and not k.startswith(STAGE1_IGNORED_PREFIXES)}
+    ignored = tuple(p for p in STAGE1_IGNORED_PREFIXES if not (flow and p == "flow.flow."))
+    sd = {k: v for k, v in sd.items() if k != "initialized" and not k.startswith(ignored) and not (flow and k in FLOW_IGNORED_KEYS)}
     need = model.state_dict()
+    if flow:
+        kinds, want = flow_transform_kinds(sd), flow_transform_kinds(need)
+        if kinds != want:
+            raise KeyError(f"stage-1 checkpoint: the flow's transforms are {kinds}, the model's are {want}")
     missing, unexpected = sorted(set(need) - set(sd)), sorted(set(sd) - set(need))
     if missing or unexpected:
         raise KeyError(f"stage-1 checkpoint: missing {missing[:8]}{' ...' if len(missing) > 8 else ''} ({len(missing)}), "
@@ -109,6 +176,10 @@ def load_stage1_checkpoint(model: torch.nn.Module, path_or_state):
     if tuple(sd[k].shape) != tuple(need[k].shape):
         raise ValueError(f"stage-1 checkpoint: {k} is {tuple(sd[k].shape)}, the model's context flags (with_focal_length, with_bbox_info, "
                          f"with_cam_center) need {tuple(need[k].shape)}")
+    if flow:
+        for k in sorted(sd):
+            if k.startswith("flow.flow.") and _shape(sd[k]) != tuple(need[k].shape):
+                raise ValueError(f"stage-1 checkpoint: {k} is {_shape(sd[k])}, the model needs {tuple(need[k].shape)}")
     model.load_state_dict({kk: torch.as_tensor(np.asarray(v)) if not isinstance(v, torch.Tensor) else v for kk, v in sd.items()}, strict=True)
     return sorted(sd)
 

@@ -247,6 +247,84 @@ def make_stage1_state_dict(seed: int = 0, head_gain: float = 0.04, **flags) -> d
     return {k: sd[k] for k, _ in man}
 
 
+FLOW_DIM, FLOW_HIDDEN, FLOW_LAYERS, FLOW_DEPTH = 144, 1024, 4, 2      # configs/prohmr.yaml MODEL.FLOW: DIM, LAYER_HIDDEN_FEATURES, NUM_LAYERS, LAYER_DEPTH
+FLOW_PREFIX = "flow.flow._transform._transforms."
+
+
+def stage1_flow_manifest(with_focal_length: bool = True, with_bbox_info: bool = True, with_cam_center: bool = True, scene_feat_dim: int = 512,
+                         batch_norm: bool = False) -> list:
+    """(name, shape) of the stage-1 pose flow, ``flow.flow.*``: nflows' ConditionalGlow(144, 1024, 4, 2, context_features=ctx) of
+    models/prohmr/smpl_flow.py:24-26 as published nflows names it - per block an ActNorm (index 3l), an LULinear (3l + 1) and an additive
+    coupling (3l + 2) whose transform_net is a ResidualNet of two blocks; ``batch_norm``: with each block's two BatchNorm1d."""
+    ctx = stage1_context_dim(with_focal_length, with_bbox_info, with_cam_center, scene_feat_dim=scene_feat_dim)
+    D, H, tri = FLOW_DIM, FLOW_HIDDEN, FLOW_DIM * (FLOW_DIM - 1) // 2
+    m = []
+    for l in range(FLOW_LAYERS):
+        a, lu, cp = (f"{FLOW_PREFIX}{3 * l + j}." for j in range(3))
+        m += [(a + "log_scale", (D,)), (a + "shift", (D,)), (a + "initialized", ())]
+        m += [(lu + "lower_entries", (tri,)), (lu + "upper_entries", (tri,)), (lu + "unconstrained_upper_diag", (D,)), (lu + "bias", (D,))]
+        m += [(cp + "identity_features", (D // 2,)), (cp + "transform_features", (D // 2,))]
+        n = cp + "transform_net."
+        m += [(n + "initial_layer.weight", (H, D // 2 + ctx)), (n + "initial_layer.bias", (H,))]
+        for k in range(FLOW_DEPTH):
+            b = f"{n}blocks.{k}."
+            for j in range(2):
+                if batch_norm:
+                    m += [(f"{b}batch_norm_layers.{j}.{leaf}", () if leaf == "num_batches_tracked" else (H,))
+                          for leaf in ("weight", "bias", "running_mean", "running_var", "num_batches_tracked")]
+                m += [(f"{b}linear_layers.{j}.weight", (H, H)), (f"{b}linear_layers.{j}.bias", (H,))]
+            m += [(b + "context_layer.weight", (H, ctx)), (b + "context_layer.bias", (H,))]
+        m += [(n + "final_layer.weight", (D // 2, H)), (n + "final_layer.bias", (D // 2,))]
+    return m
+
+
+def make_stage1_flow_state_dict(seed: int = 0, **flags) -> dict:
+    """Seeded weights for every name of :func:`stage1_flow_manifest`, from a random stream of their own (``make_stage1_state_dict`` stays
+    bit-identical).  The scales keep the chain well conditioned: cond2(L U) stays under ~12 per block, a sampled pose has rms ~5.  The couplings'
+    index lists are the alternating masks of nflows in blocks 0 and 2, the swapped one in block 1 and a seeded split in block 3 (the lists are data,
+    not a rule)."""
+    D, H = FLOW_DIM, FLOW_HIDDEN
+    g = _rng(8000 + seed)
+    sd = {}
+    for name, shape in stage1_flow_manifest(**flags):
+        leaf, l = name.rsplit(".", 1)[-1], int(name[len(FLOW_PREFIX):].split(".", 1)[0]) // 3
+        normal = lambda scale, loc=0.0: g.normal(loc=loc, scale=scale, size=shape).astype(np.float32)
+        if leaf == "initialized":
+            sd[name] = np.array(True)
+        elif leaf == "num_batches_tracked":
+            sd[name] = np.array(100, dtype=np.int64)
+        elif leaf in ("identity_features", "transform_features"):
+            if leaf == "identity_features":                       # (drawn once per coupling, at its first list)
+                odd, even = np.arange(1, D, 2), np.arange(0, D, 2)
+                if l == 3:
+                    perm = g.permutation(D)
+                    split = (np.sort(perm[: D // 2]), np.sort(perm[D // 2:]))
+                else:
+                    split = (odd, even) if l % 2 == 0 else (even, odd)
+            sd[name] = split[0 if leaf == "identity_features" else 1].astype(np.int64)
+        elif leaf in ("log_scale", "shift"):
+            sd[name] = normal(0.3)
+        elif leaf in ("lower_entries", "upper_entries"):
+            sd[name] = normal(0.5 / np.sqrt(D))
+        elif leaf == "unconstrained_upper_diag":
+            sd[name] = normal(0.5, 0.5)
+        elif leaf == "running_mean":
+            sd[name] = normal(0.1)
+        elif leaf == "running_var":
+            sd[name] = g.uniform(0.6, 1.4, size=shape).astype(np.float32)
+        elif ".batch_norm_layers." in name:
+            sd[name] = normal(0.1, 1.0) if leaf == "weight" else normal(0.05)
+        elif leaf == "bias":
+            sd[name] = normal(0.1 if name.endswith(f"{3 * l + 1}.bias") else 0.05)
+        elif ".final_layer." in name:
+            sd[name] = normal(0.3 / np.sqrt(H))
+        elif ".linear_layers." in name:
+            sd[name] = normal(np.sqrt(2.0 / H))
+        else:                                                     # initial_layer, context_layer
+            sd[name] = normal(1.0 / np.sqrt(shape[1]))
+    return sd
+
+
 def positional_table(max_len: int = 5000, d_model: int = 512) -> np.ndarray:
     """sin/cos table of models/egohmr/egohmr.py:614-619, float32 arithmetic like torch's."""
     position = np.arange(max_len, dtype=np.float32)[:, None]

@@ -741,6 +741,61 @@ typedef struct ehm_stage1_desc {
 } ehm_stage1_desc;
 int ehm_stage1_head(const ehm_stage1_desc* d, void* stream);
 
+/* ------------------------------------------------------------------ stage 1: the conditional Glow flow (csrc/flow.hip) ---------- */
+/* The pose flow of models/prohmr/smpl_flow.py, nflows' ConditionalGlow(144, 1024, 4, 2, context_features = ctx), inference only: per block an
+ * ActNorm and an LULinear (folded on the host into one affine map) and an additive coupling whose net is a ResidualNet conditioned on the context
+ * by GLU gates.  The definition the kernels follow is restated in float64 in tests/flow_ref.py.  A direction is a chain of ehm_flow_gemm launches
+ * (one per product) between ehm_flow_context and ehm_flow_finish; nothing in it synchronises or reads back, nothing uses atomics. */
+
+/* The conditioning row of prohmr_scene.py:111-130, the columns of ehm_stage1_head's ctx, written out: out [B, ctx_pad], ctx_pad >= K (the live
+ * width), columns K .. ctx_pad - 1 zero. */
+typedef struct ehm_flow_context_desc {
+  const float* img_feats;    /* [B, img_dim]   */
+  const float* scene_feats;  /* [B, scene_dim] */
+  const float* fx; const float* cam_cx; const float* cam_cy; const float* box_center /* [B,2] */; const float* box_size;   /* [B] each */
+  float* out;                /* [B, ctx_pad]   */
+  float fx_norm;
+  int with_cam_center, with_bbox_info, with_focal_length;
+  int img_dim, scene_dim, ctx_pad, B;
+} ehm_flow_context_desc;
+int ehm_flow_context(const ehm_flow_context_desc* d, void* stream);
+
+/* Y = epi(pro(X)[R, K] . W[K, N]) in exact float32 (v_mfma_f32_32x32x2_f32), the numerics of ehm_skinny_gemm_f32: a 32 x 32 output tile per block,
+ * its waves (16 for K >= 1024, else 4) split K in 8-k groups, each wave one k-ordered chain, the waves' sums added in wave order.  The order along k
+ * depends on K alone.  Rows >= R of a tile are neither read nor written, columns >= N are not written.
+ *   X        [R, ldx]; with `gather` (K ints) column k is X[r][gather[k]] (an index outside [0, ldx) reads as 0), else column k itself
+ *            (ldx >= K, ldx % 4 == 0, X 16-byte aligned)
+ *   W        [K, ldw] row-major (nn.Linear's weight transposed), ldw % 32 == 0, ldw >= N, K % 8 == 0; bias [N] or NULL
+ *   prologue EHM_FLOW_PRO_NONE x | _RELU max(x, 0) | _BN_RELU max(pro_scale[k] x + pro_shift[k], 0) (an eval-mode BatchNorm1d) |
+ *            _SHIFT x - pro_shift[k]
+ *   epilogue with v = acc + bias[n], i = r / S (the item of row r; S >= 1):
+ *            EHM_FLOW_EPI_BIAS      Y[r][n] = v                                      (also the affine maps: state A^T + c, (state - c) Ainv^T by _SHIFT)
+ *            EHM_FLOW_EPI_ITEM_ADD  Y[r][n] = v + item[i][n]                         (a first layer plus its context term)
+ *            EHM_FLOW_EPI_GLU_RES   Y[r][n] = Y[r][n] + v sigmoid(item[i][n])        (F.glu of cat[v, context] plus the residual, in place)
+ *            EHM_FLOW_EPI_SCATTER_ADD / _SUB   Y[r][scatter[n]] +/-= v               (the coupling update, in place on the state; scatter: N ints,
+ *                                                                                     distinct; one outside [0, ldy) is skipped)
+ *   Y        [R, ldy], never X itself; item [ceil(R / S), ld_item]. */
+enum { EHM_FLOW_PRO_NONE = 0, EHM_FLOW_PRO_RELU = 1, EHM_FLOW_PRO_BN_RELU = 2, EHM_FLOW_PRO_SHIFT = 3 };
+enum { EHM_FLOW_EPI_BIAS = 0, EHM_FLOW_EPI_ITEM_ADD = 1, EHM_FLOW_EPI_GLU_RES = 2, EHM_FLOW_EPI_SCATTER_ADD = 3, EHM_FLOW_EPI_SCATTER_SUB = 4 };
+typedef struct ehm_flow_gemm_desc {
+  const float* X; const int32_t* gather; const float* W; const float* bias;
+  const float* pro_scale; const float* pro_shift;
+  const float* item; const int32_t* scatter;
+  float* Y;
+  int R, K, N, S;
+  int ldx, ldw, ldy, ld_item;
+  int prologue, epilogue;
+} ehm_flow_gemm_desc;
+int ehm_flow_gemm(const ehm_flow_gemm_desc* d, void* stream);
+
+/* The end of a direction, per row: log_prob[r] = -1/2 ||z_r||^2 + log_prob_const, the 144 squares added in index order by float32 fmaf and
+ * log_prob_const = -72 log 2 pi -/+ the chain's log|det| (data independent, summed on the host in float64) added in float64.  With `pose`
+ * (the sampling side: the chain's output x [R,144]) also pred_pose_6d = x and the 24 rotation matrices of utils/geometry.py:56-57 ('prohmr':
+ * mode 0 of ehm_rot6d_to_rotmat, the same device function): global_orient [R,1,3,3], body_pose [R,23,3,3].  pose, pose6d_out, global_orient,
+ * body_pose: all four or none. */
+int ehm_flow_finish(const float* z, double log_prob_const, float* log_prob, const float* pose, float* pose6d_out, float* global_orient,
+                    float* body_pose, int R, void* stream);
+
 /* ------------------------------------------------------------------ scene clouds -------------- */
 /* The scene point cloud each stage reads, per item, from scene meshes resident on the device (csrc/scene.hip).  It replaces the offline
  * preprocessing plus the loader's transform:

@@ -2,7 +2,7 @@
 """First thing to run when the licensed assets are at hand (they cannot ship; nothing here needs the network):
 
     python tools/verify_assets.py <smpl_dir | SMPL_NEUTRAL.pkl> <checkpoint.pt> [--stats preprocess_stats.npz] [--mean-params smpl_mean_params.npz]
-                                  [--timesteps 50] [--respacing ''] [--batch 32] [--json]
+                                  [--timesteps 50] [--respacing ''] [--batch 32] [--stage1-checkpoint prohmr_scene.pt] [--json]
 
 Loads the SMPL model through egohmr_amd.smpl (chumpy-free unpickler) and the checkpoint through egohmr_amd.io.load_checkpoint - the files
 the reference reads at models/egohmr/egohmr.py:105-107 and test_egohmr.py:109-111,125-127 - and checks what the synthetic stand-ins of
@@ -16,6 +16,10 @@ this repository could never tell:
   3. precision: on one synthetic batch (the images are noise - conditioning statistics will be off, the arithmetic is what is compared)
      the measured denoiser gain d x0 / d x_t per timestep, FusedSampler.calibrate_schedule's k for these weights, and max vertex distance
      of the 'f16x3', scheduled and 'f16' loops to the 'f32' (f32-input MFMA) loop on the same noise.
+
+  4. with --stage1-checkpoint (a ProHMR-scene checkpoint): the pose flow's transform kinds as egohmr_amd.io.flow_transform_kinds infers them
+     from the key sets, and whether BatchNorm keys were found - the flow is restated from published nflows, this is where a difference of
+     ProHMR's fork shows.
 
 Exit code 0 when every hard check passes.  The unit test (tests/test_verify_assets.py) runs it on a synthetic SMPL pkl + state dict.
 """
@@ -70,6 +74,7 @@ def main(argv=None) -> int:
     ap.add_argument("--hid", type=int, default=1024)
     ap.add_argument("--blocks", type=int, default=4)
     ap.add_argument("--skip-real-smpl-counts", action="store_true", help="do not insist on 6890 / 13776 (synthetic assets in the unit test keep them anyway)")
+    ap.add_argument("--stage1-checkpoint", default=None, help="a ProHMR-scene checkpoint: report its pose flow's transform kinds and BatchNorm keys")
     ap.add_argument("--json", action="store_true")
     a = ap.parse_args(argv)
 
@@ -117,6 +122,15 @@ def main(argv=None) -> int:
         f"{len(res.unexpected_keys)} unexpected: {list(res.unexpected_keys)[:6]}")
     put("checkpoint", "no_missing_keys_outside_smpl", not missing, f"{len(missing)} missing: {missing[:6]}")
     model.eval()
+    if a.stage1_checkpoint:
+        w1 = torch.load(a.stage1_checkpoint, map_location="cpu")
+        sd1 = w1["state_dict"] if "state_dict" in w1 else w1
+        try:
+            kinds, detail = eio.flow_transform_kinds(sd1), None
+        except (KeyError, ValueError) as e:
+            kinds, detail = None, str(e)
+        put("stage1_flow", "transform_kinds", kinds == ["actnorm", "lulinear", "coupling"] * 4,
+            detail or f"{kinds}; BatchNorm keys {'found (build ProHMRScene with flow_batch_norm=True)' if eio.flow_has_batch_norm(sd1) else 'not found'}")
 
     # ---- 3. precision on one batch
     d = create_gaussian_diffusion(num_diffusion_timesteps=a.timesteps, timestep_respacing=a.respacing)
