@@ -233,11 +233,29 @@ class FlowGemmDesc(C.Structure):
     """ehm_flow_gemm_desc"""
     _fields_ = [("X", C.c_void_p), ("gather", C.c_void_p), ("W", C.c_void_p), ("bias", C.c_void_p), ("pro_scale", C.c_void_p), ("pro_shift", C.c_void_p),
                 ("item", C.c_void_p), ("scatter", C.c_void_p), ("Y", C.c_void_p), ("R", C.c_int), ("K", C.c_int), ("N", C.c_int), ("S", C.c_int),
-                ("ldx", C.c_int), ("ldw", C.c_int), ("ldy", C.c_int), ("ld_item", C.c_int), ("prologue", C.c_int), ("epilogue", C.c_int)]
+                ("ldx", C.c_int), ("ldw", C.c_int), ("ldy", C.c_int), ("ld_item", C.c_int), ("prologue", C.c_int), ("epilogue", C.c_int),
+                ("mask", C.c_void_p), ("add", C.c_void_p), ("aux", C.c_void_p), ("ld_mask", C.c_int), ("ld_add", C.c_int),
+                ("w_window", C.c_int)]
 
 
-FLOW_PRO_NONE, FLOW_PRO_RELU, FLOW_PRO_BN_RELU, FLOW_PRO_SHIFT = 0, 1, 2, 3                                  # EHM_FLOW_PRO_* of the header
+class FlowWgradDesc(C.Structure):
+    """ehm_flow_wgrad_desc"""
+    _fields_ = [("G", C.c_void_p), ("gather_g", C.c_void_p), ("item", C.c_void_p), ("X", C.c_void_p), ("gather_x", C.c_void_p), ("x_shift", C.c_void_p),
+                ("out", C.c_void_p), ("R", C.c_int), ("Cg", C.c_int), ("Ca", C.c_int), ("S", C.c_int), ("ldg", C.c_int), ("ldx", C.c_int),
+                ("ld_item", C.c_int), ("ld_out", C.c_int), ("act", C.c_int), ("alpha", C.c_float), ("beta", C.c_float)]
+
+
+class FlowReduceDesc(C.Structure):
+    """ehm_flow_reduce_desc"""
+    _fields_ = [("G", C.c_void_p), ("gather", C.c_void_p), ("U2", C.c_void_p), ("item", C.c_void_p), ("out", C.c_void_p), ("R", C.c_int), ("N", C.c_int),
+                ("S", C.c_int), ("ldg", C.c_int), ("ldu", C.c_int), ("ld_item", C.c_int), ("ld_out", C.c_int), ("mode", C.c_int), ("scale", C.c_float)]
+
+
+FLOW_PRO_NONE, FLOW_PRO_RELU, FLOW_PRO_BN_RELU, FLOW_PRO_SHIFT, FLOW_PRO_GATE = 0, 1, 2, 3, 4                 # EHM_FLOW_PRO_* of the header
 FLOW_EPI_BIAS, FLOW_EPI_ITEM_ADD, FLOW_EPI_GLU_RES, FLOW_EPI_SCATTER_ADD, FLOW_EPI_SCATTER_SUB = 0, 1, 2, 3, 4   # EHM_FLOW_EPI_*
+FLOW_EPI_MASK, FLOW_EPI_MASK_ADD, FLOW_EPI_ADD = 5, 6, 7
+FLOW_ACT_NONE, FLOW_ACT_RELU = 0, 1                                                                          # EHM_FLOW_ACT_*
+FLOW_RED_COLS, FLOW_RED_ITEM, FLOW_RED_GATE = 0, 1, 2                                                        # EHM_FLOW_RED_*
 
 
 class SceneDesc(C.Structure):
@@ -404,6 +422,9 @@ PROTOTYPES = {
     "ehm_flow_context": (_I, [C.POINTER(FlowContextDesc), _P]),
     "ehm_flow_gemm": (_I, [C.POINTER(FlowGemmDesc), _P]),
     "ehm_flow_finish": (_I, [_P, C.c_double, _P, _P, _P, _P, _P, _I, _P]),
+    "ehm_flow_wgrad": (_I, [C.POINTER(FlowWgradDesc), _P]),
+    "ehm_flow_reduce": (_I, [C.POINTER(FlowReduceDesc), _P]),
+    "ehm_flow_finish_backward": (_I, [_P] * 10 + [_I, _P]),
     "ehm_scene_workspace_bytes": (_I, [C.POINTER(SceneDesc), C.POINTER(C.c_int64)]),
     "ehm_scene_select": (_I, [C.POINTER(SceneDesc), _P]),
     "ehm_image_patch": (_I, [C.POINTER(ImagePatchDesc), _P]),

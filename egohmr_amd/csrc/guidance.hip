@@ -694,49 +694,7 @@ __global__ void posefeat_sum_kernel(const float* __restrict__ part, float* __res
 }
 
 
-// VJP of R = rot6d_to_rotmat(a1, a2) (utils/geometry.py:59-66): gR [9] row-major -> (ga1, ga2)
-__device__ __forceinline__ void rot6d_bwd(float a1x, float a1y, float a1z, float a2x, float a2y, float a2z, const float (&gR)[9],
-                                          float (&ga1)[3], float (&ga2)[3]) {
-  const float n1r = sqrtf(a1x * a1x + a1y * a1y + a1z * a1z), n1 = fmaxf(n1r, 1e-12f);
-  const float b1[3] = {a1x / n1, a1y / n1, a1z / n1};
-  const float a2[3] = {a2x, a2y, a2z};
-  const float d = b1[0] * a2[0] + b1[1] * a2[1] + b1[2] * a2[2];
-  const float u[3] = {a2[0] - d * b1[0], a2[1] - d * b1[1], a2[2] - d * b1[2]};
-  const float n2r = sqrtf(u[0] * u[0] + u[1] * u[1] + u[2] * u[2]), n2 = fmaxf(n2r, 1e-12f);
-  const float b2[3] = {u[0] / n2, u[1] / n2, u[2] / n2};
-  float g1[3] = {gR[0], gR[3], gR[6]}, g2[3] = {gR[1], gR[4], gR[7]};
-  const float g3[3] = {gR[2], gR[5], gR[8]};
-  // b3 = b1 x b2
-  g1[0] += b2[1] * g3[2] - b2[2] * g3[1]; g1[1] += b2[2] * g3[0] - b2[0] * g3[2]; g1[2] += b2[0] * g3[1] - b2[1] * g3[0];
-  g2[0] += g3[1] * b1[2] - g3[2] * b1[1]; g2[1] += g3[2] * b1[0] - g3[0] * b1[2]; g2[2] += g3[0] * b1[1] - g3[1] * b1[0];
-  // b2 = u / max(|u|, eps); like clamp_min's backward, the gradient takes the |u| path where |u| >= eps (ties included)
-  float gu[3];
-  if (n2r >= 1e-12f) {
-    const float t = b2[0] * g2[0] + b2[1] * g2[1] + b2[2] * g2[2];
-#pragma unroll
-    for (int c = 0; c < 3; ++c) gu[c] = (g2[c] - b2[c] * t) / n2;
-  } else {
-#pragma unroll
-    for (int c = 0; c < 3; ++c) gu[c] = g2[c] / n2;
-  }
-  // u = a2 - (b1.a2) b1
-  const float gub1 = gu[0] * b1[0] + gu[1] * b1[1] + gu[2] * b1[2];
-#pragma unroll
-  for (int c = 0; c < 3; ++c) {
-    ga2[c] = gu[c] - gub1 * b1[c];
-    g1[c] += -d * gu[c] - gub1 * a2[c];
-  }
-  // b1 = a1 / max(|a1|, eps), the same tie rule
-  if (n1r >= 1e-12f) {
-    const float t = b1[0] * g1[0] + b1[1] * g1[1] + b1[2] * g1[2];
-#pragma unroll
-    for (int c = 0; c < 3; ++c) ga1[c] = (g1[c] - b1[c] * t) / n1;
-  } else {
-#pragma unroll
-    for (int c = 0; c < 3; ++c) ga1[c] = g1[c] / n1;
-  }
-}
-
+// (rot6d_bwd, the VJP of rot6d_to_R, lives beside it in smpl_dev.h: the flow's finish backward shares it)
 __global__ void rot6d_bwd_kernel(const float* __restrict__ x, const float* __restrict__ gR, float* __restrict__ gx, int64_t n, int mode) {
   int64_t i = (int64_t)blockIdx.x * blockDim.x + threadIdx.x;
   if (i >= n) return;

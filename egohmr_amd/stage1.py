@@ -192,7 +192,7 @@ class _Composite(nn.Module):
 
 
 class GlowFlow(nn.Module):
-    """nflows' ConditionalGlow(144, 1024, 4, 2, context_features=ctx_dim) of models/prohmr/smpl_flow.py:24-26, inference only, with the parameter
+    """nflows' ConditionalGlow(144, 1024, 4, 2, context_features=ctx_dim) of models/prohmr/smpl_flow.py:24-26 with the parameter
     names of published nflows (``_transform._transforms.{3l | 3l+1 | 3l+2}`` = ActNorm | LULinear | additive coupling with a ResidualNet), so a
     checkpoint's ``flow.flow.*`` loads with strict=True.  ``batch_norm``: the ResidualNet blocks carry their two eval-mode BatchNorm1d.
 
@@ -200,7 +200,13 @@ class GlowFlow(nn.Module):
     diag(exp(log_scale)), c = L U shift + bias, and A^-1 by two triangular solves), concatenates the twelve context-side weight slices (each
     coupling's first layer and two GLU gates) into one [ctx_pad, 12 * 1024] matrix, and transposes the per-row weights.  A direction is then
     ehm_skinny_gemm_f32 for the per-item terms and 7 ehm_flow_gemm launches per block (the affine map, the first layer, 2 x 2 hidden layers, the
-    last layer with the coupling update), then ehm_flow_finish.  No atomics: two calls give the same bits.  CPU tensors raise."""
+    last layer with the coupling update), then ehm_flow_finish.  No atomics: two calls give the same bits.  CPU tensors raise.
+
+    Both directions are differentiable (egohmr_amd/flow_grad.py, a HIP backward behind ``flow_grad.FlowFunction``): with grad mode on, a call whose
+    ``x`` / ``z`` / ``ctx`` requires grad - or, with ``grad_params = True`` (the meaning of ``ResnetPointnet.grad_params``), whose flow has a
+    parameter that does - returns results with a ``grad_fn``.  Every other call runs the no-graph route.  The ResidualNet's BatchNorm is not
+    differentiated: ``batch_norm=True`` raises on the autograd route."""
+    grad_params = False
 
     def __init__(self, ctx_dim: int, batch_norm: bool = False):
         super().__init__()
@@ -214,6 +220,23 @@ class GlowFlow(nn.Module):
         self.eval()
 
     # ------------------------------------------------------------------ host preparation
+    @staticmethod
+    def fold(an, lu):
+        """ActNorm + LULinear -> one affine map each way, float64 numpy: (A [144,144], c [144], A^-1, log|det A|) with s <- s A^T + c.
+        (flow_grad.fold is the same map as a torch function, for the gradients of the six parameters.)"""
+        D = FLOW_DIM
+        f64 = lambda t: t.detach().double().cpu().numpy()
+        Lm, U = np.eye(D), np.zeros((D, D))
+        Lm[np.tril_indices(D, -1)] = f64(lu.lower_entries)
+        U[np.triu_indices(D, 1)] = f64(lu.upper_entries)
+        diag = np.log1p(np.exp(f64(lu.unconstrained_upper_diag))) + 1e-3
+        U[np.diag_indices(D)] = diag
+        ls, LU = f64(an.log_scale), Lm @ U
+        A, c = LU * np.exp(ls)[None, :], LU @ f64(an.shift) + f64(lu.bias)
+        tri = lambda M, rhs, upper: torch.linalg.solve_triangular(torch.from_numpy(M), torch.from_numpy(rhs), upper=upper).numpy()
+        Ainv = np.exp(-ls)[:, None] * tri(U, tri(Lm, np.eye(D), False), True)                      # two float64 triangular solves, not inv(L U diag)
+        return A, c, Ainv, float(ls.sum() + np.log(diag).sum())
+
     def _weights(self, dev):
         if self._key_fn is None:
             self._key_fn = _lib.TensorKey(self)
@@ -231,19 +254,11 @@ class GlowFlow(nn.Module):
             an, lu, cp = tr[3 * l], tr[3 * l + 1], tr[3 * l + 2]
             if not bool(an.initialized):
                 raise ValueError(f"GlowFlow: ActNorm {3 * l} has initialized == False (data-dependent initialisation belongs to training)")
-            # ---- ActNorm + LULinear -> one affine map each way, float64
-            Lm, U = np.eye(D), np.zeros((D, D))
-            Lm[np.tril_indices(D, -1)] = f64(lu.lower_entries)
-            U[np.triu_indices(D, 1)] = f64(lu.upper_entries)
-            diag = np.log1p(np.exp(f64(lu.unconstrained_upper_diag))) + 1e-3
-            U[np.diag_indices(D)] = diag
-            ls, LU = f64(an.log_scale), Lm @ U
-            A, c = LU * np.exp(ls)[None, :], LU @ f64(an.shift) + f64(lu.bias)
-            tri = lambda M, rhs, upper: torch.linalg.solve_triangular(torch.from_numpy(M), torch.from_numpy(rhs), upper=upper).numpy()
-            Ainv = np.exp(-ls)[:, None] * tri(U, tri(Lm, np.eye(D), False), True)                  # two float64 triangular solves, not inv(L U diag)
-            logdet += float(ls.sum() + np.log(diag).sum())
+            A, c, Ainv, ld = self.fold(an, lu)
+            logdet += ld
             pad = lambda Wt: np.concatenate([Wt, np.zeros((D, 160 - D))], 1)                       # [K = 144, ldw = 160]
             w = dict(At=dev32(pad(A.T)), Ainvt=dev32(pad(Ainv.T)), c=dev32(c))
+            w["A"], w["Ainv"] = dev32(A), dev32(Ainv)                                              # the backward's operands: ds A, dx Ainv
             # ---- the coupling
             idf, trf = cp.identity_features.detach().cpu().numpy().astype(np.int64), cp.transform_features.detach().cpu().numpy().astype(np.int64)
             if idf.shape != (_HALF,) or trf.shape != (_HALF,) or sorted(np.concatenate([idf, trf]).tolist()) != list(range(D)):
@@ -255,6 +270,8 @@ class GlowFlow(nn.Module):
                 raise ValueError(f"GlowFlow: coupling {3 * l + 2}: initial_layer.weight is {tuple(W0.shape)}, final_layer.weight "
                                  f"{tuple(net.final_layer.weight.shape)}; the context width {ctx} needs ({H}, {_HALF + ctx}) and ({_HALF}, {H})")
             w["Wx"] = W0[:, :_HALF].t().contiguous()                                               # [72, 1024]
+            # (the backward reads the torch-layout weights themselves, [out, in] = the [K, N] operand of dY W^T: no copy when they are float32)
+            w["W0"], w["Wf_oi"], w["Wc"] = W0, _lib.f32(net.final_layer.weight, dev), []
             slot = 3 * l
             Wctx[:ctx, slot * H:(slot + 1) * H] = W0[:, _HALF:].t()
             bctx[slot * H:(slot + 1) * H] = _lib.f32(net.initial_layer.bias, dev)
@@ -264,9 +281,11 @@ class GlowFlow(nn.Module):
                 if tuple(Wc.shape) != (H, ctx):
                     raise ValueError(f"GlowFlow: coupling {3 * l + 2}: blocks.{k}.context_layer.weight is {tuple(Wc.shape)}, expected ({H}, {ctx})")
                 Wctx[:ctx, (slot + 1 + k) * H:(slot + 2 + k) * H] = Wc.t()
+                w["Wc"].append(Wc)
                 bctx[(slot + 1 + k) * H:(slot + 2 + k) * H] = _lib.f32(blk.context_layer.bias, dev)
                 for j in range(2):
-                    e = dict(Wt=_lib.f32(blk.linear_layers[j].weight, dev).t().contiguous(), b=_lib.f32(blk.linear_layers[j].bias, dev), s=None, o=None)
+                    Wl = _lib.f32(blk.linear_layers[j].weight, dev)
+                    e = dict(W=Wl, Wt=Wl.t().contiguous(), b=_lib.f32(blk.linear_layers[j].bias, dev), s=None, o=None)
                     if self.batch_norm:                                                            # eval-mode BatchNorm1d as x s + o, float64
                         bn = blk.batch_norm_layers[j]
                         s = f64(bn.weight) / np.sqrt(f64(bn.running_var) + _BN_EPS)
@@ -307,64 +326,108 @@ class GlowFlow(nn.Module):
 
     @staticmethod
     def _gemm(st, X, W, Y, R, K, N, ldx, ldw, ldy, S=1, bias=None, gather=None, pro=_lib.FLOW_PRO_NONE, pro_scale=None, pro_shift=None,
-              epi=_lib.FLOW_EPI_BIAS, item=None, ld_item=0, scatter=None):
-        P = _lib.ptr
+              epi=_lib.FLOW_EPI_BIAS, item=None, ld_item=0, scatter=None, mask=None, add=None, aux=None, ld_mask=0, ld_add=0, w_window=0):
+        P = lambda t: t if isinstance(t, int) else _lib.ptr(t)      # (an int: the address of a column window)
         d = _lib.FlowGemmDesc(X=P(X), gather=P(gather), W=P(W), bias=P(bias), pro_scale=P(pro_scale), pro_shift=P(pro_shift),
                               item=item, scatter=P(scatter), Y=P(Y), R=R, K=K, N=N, S=S, ldx=ldx, ldw=ldw, ldy=ldy, ld_item=ld_item,
-                              prologue=pro, epilogue=epi)
+                              prologue=pro, epilogue=epi, mask=P(mask), add=P(add), aux=P(aux), ld_mask=ld_mask, ld_add=ld_add,
+                              w_window=w_window)
         _lib.api().ehm_flow_gemm(C.byref(d), st)
 
-    def _coupling(self, st, w, l, state, T, U, P, R, S, subtract):
-        """state[:, tr] +/-= transform_net(state[:, id], context): six launches, in place on the state."""
+    def _coupling(self, st, w, l, state, T, U, P, R, S, subtract, keep=None):
+        """state[:, tr] +/-= transform_net(state[:, id], context): six launches, in place on the state.  keep (the autograd route): a dict that
+        receives what the backward reads - t_0, u1_0, u2_0, t_1, u1_1, u2_1, t_2 - from the same launches on the same operands; a GLU then writes
+        t_k+1 beside t_k (`add`) instead of over it, and its value half u2 goes out through `aux` (kept, not recomputed: 2 x [R,1024] per coupling
+        against one more GEMM per block in the backward)."""
         D, H, g = FLOW_DIM, HIDDEN, self._gemm
+        if keep is not None:
+            new = lambda: torch.empty(R, H, device=state.device)
+            keep["t"], keep["u1"], keep["u2"] = [new(), new(), new()], [new(), new()], [new(), new()]
+            T = keep["t"][0]
         item = lambda slot: P.data_ptr() + 4 * H * slot
         ldp = P.shape[1]
         g(st, state, w["Wx"], T, R, _HALF, H, D, H, H, S=S, gather=w["idf"], epi=_lib.FLOW_EPI_ITEM_ADD, item=item(3 * l), ld_item=ldp)
         for k in range(FLOW_DEPTH):
             e0, e1 = w["lin"][2 * k], w["lin"][2 * k + 1]
             pro = _lib.FLOW_PRO_BN_RELU if self.batch_norm else _lib.FLOW_PRO_RELU
+            if keep is not None:
+                U, Tn = keep["u1"][k], keep["t"][k + 1]
             g(st, T, e0["Wt"], U, R, H, H, H, H, H, bias=e0["b"], pro=pro, pro_scale=e0["s"], pro_shift=e0["o"])
-            g(st, U, e1["Wt"], T, R, H, H, H, H, H, S=S, bias=e1["b"], pro=pro, pro_scale=e1["s"], pro_shift=e1["o"], epi=_lib.FLOW_EPI_GLU_RES,
-              item=item(3 * l + 1 + k), ld_item=ldp)
+            if keep is None:
+                g(st, U, e1["Wt"], T, R, H, H, H, H, H, S=S, bias=e1["b"], pro=pro, pro_scale=e1["s"], pro_shift=e1["o"], epi=_lib.FLOW_EPI_GLU_RES,
+                  item=item(3 * l + 1 + k), ld_item=ldp)
+            else:
+                g(st, U, e1["Wt"], Tn, R, H, H, H, H, H, S=S, bias=e1["b"], pro=pro, pro_scale=e1["s"], pro_shift=e1["o"], epi=_lib.FLOW_EPI_GLU_RES,
+                  item=item(3 * l + 1 + k), ld_item=ldp, add=T, ld_add=H, aux=keep["u2"][k])
+                T = Tn
         g(st, T, w["Wf"], state, R, H, _HALF, H, 96, D, bias=w["bf"], scatter=w["trf"],
           epi=_lib.FLOW_EPI_SCATTER_SUB if subtract else _lib.FLOW_EPI_SCATTER_ADD)
 
-    def _run(self, ctxp, rows, S, sampling):
+    def _run(self, ctxp, rows, S, sampling, keep=None):
         """One direction on rows [R,144] (the noise when sampling, else the poses), R = B * S.  Sampling: (pose6d, log_prob, global_orient,
-        body_pose); else (log_prob, z)."""
+        body_pose); else (log_prob, z).  keep (the autograd route): a dict that receives the per-item terms `P`, per block the coupling's
+        activations (`blocks`) and the states (`states`): forward, states[l] enters affine map l and states[l + 1] leaves coupling l; sampling,
+        states[l] is the state between coupling l and its affine map (a coupling leaves its identity half alone, so either holds s[:, idf]).  The
+        route takes a fresh buffer per block where the no-graph route swaps two: same launches, same operands, same bits."""
         dev = rows.device
         w = self._weights(dev)
         R, D, H = rows.shape[0], FLOW_DIM, HIDDEN
         with _lib.on_device(dev):
             st = _lib.stream_ptr()
             P = self._item_terms(ctxp, w, st)
-            T, U = torch.empty(R, H, device=dev), torch.empty(R, H, device=dev)
+            T, U = (None, None) if keep is not None else (torch.empty(R, H, device=dev), torch.empty(R, H, device=dev))
             a, b = torch.empty(R, D, device=dev), torch.empty(R, D, device=dev)
             lp = torch.empty(R, device=dev)
+            if keep is not None:
+                keep.update(P=P, blocks=[{} for _ in range(FLOW_LAYERS)], states=[None] * (FLOW_LAYERS + (0 if sampling else 1)), w=w, rows=rows,
+                            ctxp=ctxp, S=S)
+            kept = lambda l: keep["blocks"][l] if keep is not None else None
             if sampling:
                 a.copy_(rows)                                  # (the coupling updates its state in place; the noise is kept for the norm)
                 for l in reversed(range(FLOW_LAYERS)):
                     wl = w["blocks"][l]
-                    self._coupling(st, wl, l, a, T, U, P, R, S, subtract=True)
+                    self._coupling(st, wl, l, a, T, U, P, R, S, subtract=True, keep=kept(l))
                     self._gemm(st, a, wl["Ainvt"], b, R, D, D, D, 160, D, pro=_lib.FLOW_PRO_SHIFT, pro_shift=wl["c"])   # (state - c) Ainv^T
-                    a, b = b, a
+                    if keep is not None:
+                        keep["states"][l] = a
+                        a, b = b, torch.empty(R, D, device=dev)
+                    else:
+                        a, b = b, a
                 p6, go, bp = torch.empty(R, D, device=dev), torch.empty(R, 1, 3, 3, device=dev), torch.empty(R, 23, 3, 3, device=dev)
                 _lib.api().ehm_flow_finish(rows, C.c_double(w["log_prob_const"]), lp, a, p6, go, bp, R, st)
+                if keep is not None:
+                    keep["x"] = a
                 return p6, lp, go, bp
             x = rows
             for l in range(FLOW_LAYERS):
                 wl = w["blocks"][l]
                 self._gemm(st, x, wl["At"], b, R, D, D, D, 160, D, bias=wl["c"])                                        # state A^T + c
-                self._coupling(st, wl, l, b, T, U, P, R, S, subtract=False)
-                x, b = b, (a if x is rows else x)
+                self._coupling(st, wl, l, b, T, U, P, R, S, subtract=False, keep=kept(l))
+                if keep is not None:
+                    keep["states"][l], keep["states"][l + 1] = x, b
+                    x, b = b, torch.empty(R, D, device=dev)
+                else:
+                    x, b = b, (a if x is rows else x)
             _lib.api().ehm_flow_finish(x, C.c_double(w["log_prob_const"]), lp, None, None, None, None, R, st)
+            if keep is not None:
+                keep["z"] = x
             return lp, x
 
-    @torch.no_grad()
+    def _wants_grad(self, *tensors) -> bool:
+        from .flow_grad import wants_grad
+        return wants_grad(self, *tensors)
+
     def sample_and_log_prob(self, ctx, num_samples=None, z=None, _padded=None) -> dict:
         """x = inverse(z) given the context ctx [B, ctx_dim]: z [B,S,144], or S = num_samples rows per item drawn from the global generator.
         -> ``pred_pose_6d`` [B,S,144], ``log_prob`` [B,S], ``z`` [B,S,144], ``global_orient`` [B,S,1,3,3], ``body_pose`` [B,S,23,3,3] (the
         'prohmr' rot6d rule on pred_pose_6d)."""
+        if self._wants_grad(ctx, z, _padded):
+            from .flow_grad import run_with_grad
+            return run_with_grad(self, ctx if _padded is None else _padded, z, num_samples, sampling=True)
+        with torch.no_grad():
+            return self._sample_and_log_prob(ctx, num_samples, z, _padded)
+
+    def _sample_and_log_prob(self, ctx, num_samples, z, _padded, keep=None):
         ctxp = _padded if _padded is not None else self._padded_context(ctx)
         B, dev = ctxp.shape[0], ctxp.device
         if z is None:
@@ -377,13 +440,19 @@ class GlowFlow(nn.Module):
         if z.dim() != 3 or z.shape[0] != B or z.shape[2] != FLOW_DIM:
             raise ValueError(f"z {tuple(z.shape)}, expected [{B}, S, {FLOW_DIM}]")
         S = z.shape[1]
-        p6, lp, go, bp = self._run(ctxp, z.reshape(B * S, FLOW_DIM), S, sampling=True)
+        p6, lp, go, bp = self._run(ctxp, z.reshape(B * S, FLOW_DIM), S, sampling=True, keep=keep)
         return {"pred_pose_6d": p6.reshape(B, S, FLOW_DIM), "log_prob": lp.reshape(B, S), "z": z, "global_orient": go.reshape(B, S, 1, 3, 3),
                 "body_pose": bp.reshape(B, S, 23, 3, 3)}
 
-    @torch.no_grad()
     def log_prob(self, x, ctx, _padded=None):
         """(log_prob [B,S], z [B,S,144]) of the poses x [B,S,144] given the context ctx [B, ctx_dim]."""
+        if self._wants_grad(ctx, x, _padded):
+            from .flow_grad import run_with_grad
+            return run_with_grad(self, ctx if _padded is None else _padded, x, None, sampling=False)
+        with torch.no_grad():
+            return self._log_prob(x, ctx, _padded)
+
+    def _log_prob(self, x, ctx, _padded, keep=None):
         ctxp = _padded if _padded is not None else self._padded_context(ctx)
         if not x.is_cuda:
             raise _lib.EgoHMRHipError("GlowFlow runs on the HIP kernels only (got a CPU tensor); there is no CPU path")
@@ -392,7 +461,7 @@ class GlowFlow(nn.Module):
         if x.dim() != 3 or x.shape[0] != B or x.shape[2] != FLOW_DIM:
             raise ValueError(f"x {tuple(x.shape)}, expected [{B}, S, {FLOW_DIM}]")
         S = x.shape[1]
-        lp, z = self._run(ctxp, x.reshape(B * S, FLOW_DIM), S, sampling=False)
+        lp, z = self._run(ctxp, x.reshape(B * S, FLOW_DIM), S, sampling=False, keep=keep)
         return lp.reshape(B, S), z.reshape(B, S, FLOW_DIM)
 
     def forward(self, ctx, num_samples=None, z=None):
@@ -488,9 +557,9 @@ class ProHMRScene(ProHMRSceneTransl):
         out["pred_keypoints_2d"] = k2.reshape(B, S, -1, 2)
         return out
 
-    @torch.no_grad()
     def log_prob(self, smpl_params, conditioning_feats):
         """models/prohmr/smpl_flow.py:31-50: (log_prob [B,N], z [B,N,144]) of ``smpl_params`` {global_orient [B,N,6], body_pose [B,N,138]} (the
-        6-D poses the flow models) given ``conditioning_feats`` [B,ctx]."""
+        6-D poses the flow models) given ``conditioning_feats`` [B,ctx].  Differentiable where ``GlowFlow.log_prob`` is (torch.cat carries the
+        gradient of the 6-D poses on)."""
         x = torch.cat((smpl_params["global_orient"], smpl_params["body_pose"]), dim=-1)
         return self.flow.flow.log_prob(x, conditioning_feats)

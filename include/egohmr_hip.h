@@ -742,7 +742,8 @@ typedef struct ehm_stage1_desc {
 int ehm_stage1_head(const ehm_stage1_desc* d, void* stream);
 
 /* ------------------------------------------------------------------ stage 1: the conditional Glow flow (csrc/flow.hip) ---------- */
-/* The pose flow of models/prohmr/smpl_flow.py, nflows' ConditionalGlow(144, 1024, 4, 2, context_features = ctx), inference only: per block an
+/* The pose flow of models/prohmr/smpl_flow.py, nflows' ConditionalGlow(144, 1024, 4, 2, context_features = ctx), both directions and their first
+ * derivatives (the entries from ehm_flow_wgrad on; eval-mode BatchNorm inside the ResidualNet is forward only): per block an
  * ActNorm and an LULinear (folded on the host into one affine map) and an additive coupling whose net is a ResidualNet conditioned on the context
  * by GLU gates.  The definition the kernels follow is restated in float64 in tests/flow_ref.py.  A direction is a chain of ehm_flow_gemm launches
  * (one per product) between ehm_flow_context and ehm_flow_finish; nothing in it synchronises or reads back, nothing uses atomics. */
@@ -765,18 +766,29 @@ int ehm_flow_context(const ehm_flow_context_desc* d, void* stream);
  * depends on K alone.  Rows >= R of a tile are neither read nor written, columns >= N are not written.
  *   X        [R, ldx]; with `gather` (K ints) column k is X[r][gather[k]] (an index outside [0, ldx) reads as 0), else column k itself
  *            (ldx >= K, ldx % 4 == 0, X 16-byte aligned)
- *   W        [K, ldw] row-major (nn.Linear's weight transposed), ldw % 32 == 0, ldw >= N, K % 8 == 0; bias [N] or NULL
+ *   W        [K, ldw] row-major (nn.Linear's weight transposed; in a backward product dY W^T the weight itself, [out, in] = [K, N]), ldw % 32 == 0,
+ *            ldw >= N, K % 8 == 0; bias [N] or NULL.  w_window != 0 lifts ldw % 32 == 0: columns >= N of W are never read, so any row-major
+ *            matrix with ldw >= N - a weight in torch layout, a column window of a wider one - is an operand as it lies, at no copy
  *   prologue EHM_FLOW_PRO_NONE x | _RELU max(x, 0) | _BN_RELU max(pro_scale[k] x + pro_shift[k], 0) (an eval-mode BatchNorm1d) |
- *            _SHIFT x - pro_shift[k]
+ *            _SHIFT x - pro_shift[k] | _GATE x sigmoid(item[i][k]) (the cotangent of a GLU's value half; item as below with ld_item >= K, and the
+ *            epilogue is then none of the two per-item ones)
  *   epilogue with v = acc + bias[n], i = r / S (the item of row r; S >= 1):
  *            EHM_FLOW_EPI_BIAS      Y[r][n] = v                                      (also the affine maps: state A^T + c, (state - c) Ainv^T by _SHIFT)
  *            EHM_FLOW_EPI_ITEM_ADD  Y[r][n] = v + item[i][n]                         (a first layer plus its context term)
  *            EHM_FLOW_EPI_GLU_RES   Y[r][n] = Y[r][n] + v sigmoid(item[i][n])        (F.glu of cat[v, context] plus the residual, in place)
  *            EHM_FLOW_EPI_SCATTER_ADD / _SUB   Y[r][scatter[n]] +/-= v               (the coupling update, in place on the state; scatter: N ints,
- *                                                                                     distinct; one outside [0, ldy) is skipped)
- *   Y        [R, ldy], never X itself; item [ceil(R / S), ld_item]. */
-enum { EHM_FLOW_PRO_NONE = 0, EHM_FLOW_PRO_RELU = 1, EHM_FLOW_PRO_BN_RELU = 2, EHM_FLOW_PRO_SHIFT = 3 };
-enum { EHM_FLOW_EPI_BIAS = 0, EHM_FLOW_EPI_ITEM_ADD = 1, EHM_FLOW_EPI_GLU_RES = 2, EHM_FLOW_EPI_SCATTER_ADD = 3, EHM_FLOW_EPI_SCATTER_SUB = 4 };
+ *                                                                                     distinct; one outside [0, ldy) is skipped; with
+ *                                                                                     gather = transform_features / scatter = identity_features the
+ *                                                                                     two ends of a coupling's backward, the sign being the coupling's)
+ *            EHM_FLOW_EPI_MASK      Y[r][n] = mask[r][n] > 0 ? v : 0                 (the backward of a ReLU on the saved pre-activation `mask`)
+ *            EHM_FLOW_EPI_MASK_ADD  Y[r][n] = add[r][n] + (mask[r][n] > 0 ? v : 0)   (the same plus the residual's cotangent; add may be Y)
+ *            EHM_FLOW_EPI_ADD       Y[r][n] = add[r][n] + v                          (a sum of products over several launches; add may be Y)
+ *            With _GLU_RES, a non-NULL `add` [R, ld_add] is read in place of Y (Y = add + v sigmoid(.): the input of the block survives, same bits)
+ *            and a non-NULL `aux` [R, ldy] receives v (the GLU's value half u2, kept for the backward).  Elsewhere add and aux are NULL.
+ *   Y        [R, ldy], never X itself; item [ceil(R / S), ld_item]; mask [R, ld_mask], never Y. */
+enum { EHM_FLOW_PRO_NONE = 0, EHM_FLOW_PRO_RELU = 1, EHM_FLOW_PRO_BN_RELU = 2, EHM_FLOW_PRO_SHIFT = 3, EHM_FLOW_PRO_GATE = 4 };
+enum { EHM_FLOW_EPI_BIAS = 0, EHM_FLOW_EPI_ITEM_ADD = 1, EHM_FLOW_EPI_GLU_RES = 2, EHM_FLOW_EPI_SCATTER_ADD = 3, EHM_FLOW_EPI_SCATTER_SUB = 4,
+       EHM_FLOW_EPI_MASK = 5, EHM_FLOW_EPI_MASK_ADD = 6, EHM_FLOW_EPI_ADD = 7 };
 typedef struct ehm_flow_gemm_desc {
   const float* X; const int32_t* gather; const float* W; const float* bias;
   const float* pro_scale; const float* pro_shift;
@@ -785,6 +797,9 @@ typedef struct ehm_flow_gemm_desc {
   int R, K, N, S;
   int ldx, ldw, ldy, ld_item;
   int prologue, epilogue;
+  const float* mask; const float* add; float* aux;    /* the backward's operands (above); NULL in a forward chain without saved activations */
+  int ld_mask, ld_add;
+  int w_window;
 } ehm_flow_gemm_desc;
 int ehm_flow_gemm(const ehm_flow_gemm_desc* d, void* stream);
 
@@ -795,6 +810,53 @@ int ehm_flow_gemm(const ehm_flow_gemm_desc* d, void* stream);
  * body_pose: all four or none. */
 int ehm_flow_finish(const float* z, double log_prob_const, float* log_prob, const float* pose, float* pose6d_out, float* global_orient,
                     float* body_pose, int R, void* stream);
+
+/* A weight gradient of the flow: out[n * ld_out + k] = alpha sum_r G'[r][n] X'[r][k] + beta out[n * ld_out + k], n < Cg, k < Ca, in nn.Linear's
+ * [out, in] layout, so it lands in a gradient buffer or in a column window of a wider one (ld_out >= Ca; other columns are left alone; beta == 0
+ * does not read out).  The contraction runs over the R rows straight from the row-major operands (no transpose, no packing), in exact float32
+ * (v_mfma_f32_32x32x2_f32): one wave per 32 x 32 tile of out and ONE chain in row order per tile, so the order of the sum depends on R alone; no
+ * atomics, no workspace, two calls give the same bits.  (ehm_pointnet_bwd_wgrad has the same numerics but a contract - rows in bodies of N_padded
+ * % 192, widths % 128 - that none of the flow's operands meets.)
+ *   G' [r][n] = G[r][gather_g ? gather_g[n] : n], times sigmoid(item[r / S][n]) when item is not NULL (a GLU's value-half cotangent)
+ *   X' [r][k] = act(X[r][gather_x ? gather_x[k] : k] - (x_shift ? x_shift[k] : 0)), act = EHM_FLOW_ACT_NONE | _RELU
+ * A gather index outside its row reads as 0.  G [R, ldg], X [R, ldx], item [ceil(R / S), ld_item >= Cg]; out is neither G nor X. */
+enum { EHM_FLOW_ACT_NONE = 0, EHM_FLOW_ACT_RELU = 1 };
+typedef struct ehm_flow_wgrad_desc {
+  const float* G; const int32_t* gather_g; const float* item;
+  const float* X; const int32_t* gather_x; const float* x_shift;
+  float* out;
+  int R, Cg, Ca, S;
+  int ldg, ldx, ld_item, ld_out;
+  int act;
+  float alpha, beta;
+} ehm_flow_wgrad_desc;
+int ehm_flow_wgrad(const ehm_flow_wgrad_desc* d, void* stream);
+
+/* The backward's sums, each in a fixed order (two calls give the same bits), i = r / S the item of row r:
+ *   EHM_FLOW_RED_COLS   out[n] = scale sum_r G'[r][n], n < N, G' as in ehm_flow_wgrad (gather, item gate): a bias gradient.  Sixteen runs of
+ *                       consecutive rows are summed in row order and the sixteen sums added in run order.
+ *   EHM_FLOW_RED_ITEM   out[i * ld_out + n] = scale sum_{r in item i} G[r][n]: the gradient of a first layer's per-item term
+ *   EHM_FLOW_RED_GATE   out[i * ld_out + n] = scale sum_{r in item i} G[r][n] U2[r][n] s (1 - s), s = sigmoid(item[i][n]): that of a GLU gate's
+ * G [R, ldg], U2 [R, ldu], item [ceil(R / S), ld_item >= N]; the two per-item modes take no gather list. */
+enum { EHM_FLOW_RED_COLS = 0, EHM_FLOW_RED_ITEM = 1, EHM_FLOW_RED_GATE = 2 };
+typedef struct ehm_flow_reduce_desc {
+  const float* G; const int32_t* gather; const float* U2; const float* item;
+  float* out;
+  int R, N, S;
+  int ldg, ldu, ld_item, ld_out;
+  int mode;
+  float scale;
+} ehm_flow_reduce_desc;
+int ehm_flow_reduce(const ehm_flow_reduce_desc* d, void* stream);
+
+/* The VJP of ehm_flow_finish.  Every group is optional (NULL outputs are not computed), at least one is asked for:
+ *   dz [R,144] = (dz_add ? dz_add : 0) - g_log_prob[r] z[r][.]   (one fmaf: exact to one rounding; g_log_prob == NULL: a copy of dz_add)
+ *   sum_g_log_prob [1] = sum_r g_log_prob[r], the cotangent of the chain's log|det| (lane l of one wave adds rows l, l + 64, ..., then the 64 sums
+ *                        are added in lane order)
+ *   dpose [R,144] = the 'prohmr' rot6d VJP (mode 0 of ehm_rot6d_to_rotmat_bwd, the same device function) of g_global_orient [R,1,3,3] and
+ *                   g_body_pose [R,23,3,3] at pose [R,144], plus g_pose6d [R,144]; each of the three cotangents may be NULL (zero). */
+int ehm_flow_finish_backward(const float* g_log_prob, const float* z, const float* dz_add, float* dz, float* sum_g_log_prob, const float* pose,
+                             const float* g_pose6d, const float* g_global_orient, const float* g_body_pose, float* dpose, int R, void* stream);
 
 /* ------------------------------------------------------------------ scene clouds -------------- */
 /* The scene point cloud each stage reads, per item, from scene meshes resident on the device (csrc/scene.hip).  It replaces the offline

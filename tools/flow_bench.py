@@ -1,14 +1,19 @@
 #!/usr/bin/env python
 """Time the stage-1 pose flow (egohmr_amd.stage1.GlowFlow, csrc/flow.hip) against the same chain in eager float32 torch, on one GPU.
 
-    python tools/flow_bench.py [--batch 256] [--samples 5 1] [--runs 30] [--warmup 5] [--once DIRECTION S]
+    python tools/flow_bench.py [--batch 256] [--samples 5 1] [--runs 30] [--warmup 5] [--once DIRECTION S] [--backward]
 
 For each S: one sampling direction and one log_prob direction on synthetic weights (all context flags on, ctx = 2566), the median of `--runs`
 timed calls after `--warmup`, timed on the device (hip events around the call).  The eager chain is the definition of tests/flow_ref.py written
 with torch ops: unfolded ActNorm and LULinear (triangular solves when sampling), torch.addmm for every layer, the context repeated per sample.
 Prints one JSON line per (S, direction).  `--once sample|log_prob S` runs one sampling call (host preparation, first launches) and then ten un-timed calls
 of that direction, nothing else: the command to put behind `rocprofv3 --kernel-trace --stats --` for the launch count and the kernels' time
-shares (docs/EXPERIMENTS.md)."""
+shares (docs/EXPERIMENTS.md).
+
+`--backward` times the training legs instead, forward plus backward with the parameter gradients on (GlowFlow.grad_params = True; every eager
+tensor a leaf that requires grad - L and U themselves, which spares eager the scatter of their entries): `log_prob` is -log_prob.mean() of the
+poses, `sample` the sum of pred_pose_6d and log_prob over the samples.  Same inputs, same event timing; with `--once` it is the profiled command
+of a backward direction."""
 import argparse
 import json
 import os
@@ -56,8 +61,27 @@ class EagerFlow:
             h = h + F.glu(torch.cat([u, F.linear(c, r["Wc"], r["bc"])], 1), dim=1)
         return F.linear(h, b["Wf"], b["bf"])
 
+    def require_grad(self):
+        for b in self.blocks:
+            for v in list(b.values()) + [t for r in b["res"] for t in r["W"] + r["b"] + [r["Wc"], r["bc"]]]:
+                if isinstance(v, torch.Tensor) and v.is_floating_point():
+                    v.requires_grad_(True)
+
+    def zero_grad(self):
+        for b in self.blocks:
+            for v in list(b.values()) + [t for r in b["res"] for t in r["W"] + r["b"] + [r["Wc"], r["bc"]]]:
+                if isinstance(v, torch.Tensor):
+                    v.grad = None
+
     @torch.no_grad()
     def sample(self, c, z):
+        return self.sample_graph(c, z)
+
+    @torch.no_grad()
+    def log_prob(self, c, x):
+        return self.log_prob_graph(c, x)
+
+    def sample_graph(self, c, z):
         S = z.shape[1]
         c, x = c.repeat_interleave(S, 0), z.reshape(-1, 144)
         lp = -0.5 * (x * x).sum(1)
@@ -68,8 +92,7 @@ class EagerFlow:
             x = (torch.linalg.solve_triangular(b["U"], y, upper=True).t() - b["shift"]) / b["scale"]
         return x, lp
 
-    @torch.no_grad()
-    def log_prob(self, c, x):
+    def log_prob_graph(self, c, x):
         S = x.shape[1]
         c, x = c.repeat_interleave(S, 0), x.reshape(-1, 144)
         for b in self.blocks:
@@ -97,11 +120,14 @@ def median_ms(fn, runs, warmup):
 def main():
     ap = argparse.ArgumentParser()
     ap.add_argument("--batch", type=int, default=256)
-    ap.add_argument("--samples", type=int, nargs="+", default=[5, 1])
+    ap.add_argument("--samples", type=int, nargs="+", default=None, help="default: 5 1, with --backward 1 2 5")
     ap.add_argument("--runs", type=int, default=30)
     ap.add_argument("--warmup", type=int, default=5)
     ap.add_argument("--once", nargs=2, metavar=("DIRECTION", "S"))
+    ap.add_argument("--backward", action="store_true")
     args = ap.parse_args()
+    if args.samples is None:
+        args.samples = [1, 2, 5] if args.backward else [5, 1]
     if args.runs < 20:
         ap.error("--runs must be at least 20")
     dev = torch.device("cuda:0")
@@ -113,21 +139,52 @@ def main():
     g = torch.Generator(device="cpu").manual_seed(0)
     B = args.batch
     c = torch.cat([0.3 * torch.randn(B, 6, generator=g), 2 * torch.rand(B, 2048, generator=g), torch.randn(B, 512, generator=g)], 1).to(dev)
+    def hip_step(direction, x, z):
+        flow.zero_grad(set_to_none=True)
+        if direction == "sample":
+            o = flow.sample_and_log_prob(c, z=z)
+            (o["pred_pose_6d"].sum() + o["log_prob"].sum()).backward()
+        else:
+            (-flow.log_prob(x, c)[0].mean()).backward()
+
+    def eager_step(direction, x, z):
+        eager.zero_grad()
+        if direction == "sample":
+            xe, lp = eager.sample_graph(c, z)
+            (xe.sum() + lp.sum()).backward()
+        else:
+            (-eager.log_prob_graph(c, x)[0].mean()).backward()
+
+    if args.backward:
+        flow.grad_params = True
+        eager.require_grad()
     if args.once:
         S = int(args.once[1])
         z = torch.randn(B, S, 144, generator=g).to(dev)
-        x = flow.sample_and_log_prob(c, z=z)["pred_pose_6d"]          # (the host preparation and the first launches)
+        with torch.no_grad():
+            x = flow.sample_and_log_prob(c, z=z)["pred_pose_6d"]      # (the host preparation and the first launches)
         fn = (lambda: flow.sample_and_log_prob(c, z=z)) if args.once[0] == "sample" else (lambda: flow.log_prob(x, c))
+        if args.backward:
+            fn = lambda: hip_step(args.once[0], x, z)
         for _ in range(10):
             fn()
         torch.cuda.synchronize()
         return
     for S in args.samples:
         z = torch.randn(B, S, 144, generator=g).to(dev)
-        out = flow.sample_and_log_prob(c, z=z)
+        with torch.no_grad():
+            out = flow.sample_and_log_prob(c, z=z)
         x = out["pred_pose_6d"]
         xe, _ = eager.sample(c, z)
         agree = float((xe.reshape(B, S, 144) - x).abs().max())
+        if args.backward:
+            for name in ("sample", "log_prob"):
+                h_med, h_min = median_ms(lambda: hip_step(name, x, z), args.runs, args.warmup)
+                e_med, e_min = median_ms(lambda: eager_step(name, x, z), args.runs, args.warmup)
+                print(json.dumps({"bench": "flow_backward", "direction": name, "B": B, "S": S, "rows": B * S, "runs": args.runs,
+                                  "hip_ms_median": round(h_med, 4), "hip_ms_min": round(h_min, 4), "eager_ms_median": round(e_med, 4),
+                                  "eager_ms_min": round(e_min, 4), "eager_over_hip": round(e_med / h_med, 3)}), flush=True)
+            continue
         for name, hip, ref in (("sample", lambda: flow.sample_and_log_prob(c, z=z), lambda: eager.sample(c, z)),
                                ("log_prob", lambda: flow.log_prob(x, c), lambda: eager.log_prob(c, x))):
             h_med, h_min = median_ms(hip, args.runs, args.warmup)
